@@ -14,7 +14,10 @@ N > 1, by the RCCL gather of the packed uchar4 rows to rank 0 and the
 de-interleave into the full framebuffer.  Seeding (setup_rng) and scene upload
 are outside the timed region, as in the reference (mort.cu:691-725).
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).  A plain run sets up, warms up, times the
+K steps and prints the headline fields; --full adds everything else this benchmark measures or checks (roofline
+and counter figures, calibration kernels, the non-parity throughput figure, the CPU baselines).
+--dump-outputs DIR writes the image of the last timed step (see dump_outputs).
 """
 import argparse
 import json
@@ -26,6 +29,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 60 * 10**6  # --dump-outputs: all files together stay under 64 MB
 MODE_NAMES = {"mega": "megakernel", "wave": "wavefront kernels", "throughput": "megakernel over (pixel, stratum row) streams [non-parity]"}
 SCENE_NAMES = {1: "random-spheres cover", 2: "two checker spheres", 3: "earth", 4: "two Perlin spheres", 5: "quads",
                6: "Cornell box, emissive light + MIS", 7: "Cornell smoke", 8: "book-2 final scene", 9: "book-2 final scene, low settings",
@@ -132,6 +136,25 @@ def profile_figures(tag, kernel_name, valu_cpi):
     return out
 
 
+def dump_outputs(path, frame):
+    """The framebuffer the last timed step produced, i.e. what a caller of the render path receives (uchar4 [H, W, 4]),
+    as DIR/rgba.npy in float32.  A frame larger than DUMP_BYTES is written as a fixed, seeded sample of its pixels:
+    rgba.npy [n, 4] and their flat indices y * W + x as rgba_pixels.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = frame.cpu().numpy()
+    H, W, C = img.shape
+    pixels = os.path.join(path, "rgba_pixels.npy")
+    if img.size * 4 <= DUMP_BYTES:
+        np.save(os.path.join(path, "rgba.npy"), img.astype(np.float32))
+        if os.path.exists(pixels):
+            os.remove(pixels)  # left by a larger frame: it would describe another layout
+        return
+    idx = np.sort(np.random.default_rng(0).choice(H * W, size=DUMP_BYTES // (C * 4 + 8), replace=False))
+    np.save(os.path.join(path, "rgba.npy"), img.reshape(H * W, C)[idx].astype(np.float32))
+    np.save(pixels, idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -152,6 +175,11 @@ def main():
                          "NON-PARITY mode (one stream per (pixel, stratum row) -- other random numbers than the reference's; never the headline)")
     ap.add_argument("--no-calib", action="store_true", help="skip the roofline calibration kernels (profiling runs: keeps the kernel list to the render's)")
     ap.add_argument("--no-throughput-line", action="store_true", help="skip the extra non-parity figure (profiling runs: keeps the kernel list to the headline's)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-launch kernel times, one blocking frame for the library's counters, the roofline and "
+                         "counter figures, the calibration kernels, the non-parity throughput figure and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step to DIR/rgba.npy (float32; a seeded pixel sample above 60 MB)")
     args = ap.parse_args()
 
     import torch
@@ -232,14 +260,17 @@ def main():
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        step(args.full)
     sync_all()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and rank == 0:  # before anything below renders into the same buffers
+        dump_outputs(args.dump_outputs, tile[:H] if world_size == 1 else (fg_host if rehearsal else fg).frame)
 
     kernel_ms = [a.elapsed_time(b) for a, b in ev_pairs]
     # the labelled non-parity mode, timed the same way beside the headline (worlds of the two LDS state-machine kernels); never `value`
     elapsed_tp = None
-    if args.mode == "mega" and args.scene in (1, 10, 8, 9) and not args.no_throughput_line:
+    if args.full and args.mode == "mega" and args.scene in (1, 10, 8, 9) and not args.no_throughput_line:
         step(False, hip.MODE_THROUGHPUT)  # seeds the sub-streams
         step(False, hip.MODE_THROUGHPUT)
         sync_all()
@@ -255,7 +286,7 @@ def main():
     elapsed_tp = float(t[1].item()) if elapsed_tp is not None else None
 
     # one more frame through the blocking entry to read the library's own counters/HIP-event time
-    st = ctx.render_device(cam, tile.data_ptr(), 0, stream.cuda_stream, mode=mode, sync=True)
+    st = ctx.render_device(cam, tile.data_ptr(), 0, stream.cuda_stream, mode=mode, sync=True) if args.full else None
 
     rehearsal_ok = None
     if rehearsal and world_size > 1:  # the composed frame must be the single-rank frame
@@ -266,40 +297,13 @@ def main():
             with hip.Context(0) as solo:
                 solo.upload_world(world)
                 solo.rng_seed(69420, W, H)
-                for _ in range(args.warmup + args.steps + 2 + (0 if elapsed_tp is None else 0)):
+                for _ in range(args.warmup + args.steps + 1 + (1 if st is not None else 0)):
                     ref = solo.render(cam, mode=mode, want_accum=False)["rgba"]
             rehearsal_ok = bool((composed.numpy() == ref).all())
 
     if rank == 0:
         samples_per_step = W * H * eff
         value = samples_per_step * args.steps / elapsed_max / 1e6
-        avg_kernel_s = (sum(kernel_ms) / max(len(kernel_ms), 1)) * 1e-3
-        pixels_launch = W * lr
-        algo_bytes = 100 * pixels_launch  # 48 B state in + 48 B out + 4 B uchar4 per pixel; 0 B per segment
-        if args.mode == "throughput":  # per (pixel, stratum row): 48 B state in + 48 B out + 12 B partial sum; the resolve kernel's 12 B in and 4 B per pixel out
-            algo_bytes = pixels_launch * (cam.sqrt_spp * (96 + 12 + 12) + 4)
-        if args.mode == "wave":
-            algo_bytes = int(st["algorithmic_hbm_bytes"])  # + 240 B per segment of front / hit / pixel / stack records (wave_bvh.h)
-        achieved = algo_bytes / avg_kernel_s / 1e9 if avg_kernel_s > 0 else 0.0
-        kernel_name = ("wf_trav + wf_shade (per front)" if args.mode == "wave" else st["kernel_name"])
-        # roofline calibration on THIS box, outside the timed region (include/mort_hip.h mort_hip_calib_*): the HBM rate a float4
-        # copy reaches, and the cycles a SIMD needs per wave64 VALU instruction at 1, 3 and 8 resident waves
-        calib = None
-        if world_size == 1 and not args.no_calib:
-            cv = {w: ctx.calib_valu(w, 0)["cycles_per_valu_per_simd"] for w in (1, 3, 4, 8)}
-            calib = {"hbm_copy_GBs": ctx.calib_hbm_copy(1 << 30, 3), "valu_cycles_per_inst_per_simd": {str(w): v for w, v in cv.items()},
-                     "note": "mort_hip_calib_valu (independent v_fma_f32, waves per SIMD -> cycles per instruction per SIMD) and "
-                             "mort_hip_calib_hbm_copy (float4 copy of 1 GiB per buffer, read + write)"}
-        valu_cpi = min(calib["valu_cycles_per_inst_per_simd"].values()) if calib else 2.0  # MI355X_MICROARCH.md: 2 cycles (SIMD-32)
-        # counter figures from the PMC passes committed under profiles/, quoted only when this run is the profiled configuration
-        pf = profile_figures(args.profile_tag, "wf_" if args.mode == "wave" else kernel_name, valu_cpi)
-        cfg = pf.get("config") or {}
-        same = (args.scene, W, H, args.spp, cam.bounce_limit, world_size, args.mode) == (
-            cfg.get("scene"), cfg.get("width"), cfg.get("height", H if args.aspect is None else None), cfg.get("spp"),
-            cfg.get("depth", cam.bounce_limit if args.depth is None else None), cfg.get("gpus"), cfg.get("mode", "mega"))
-        if not same:
-            pf = {"traffic": None}
-        traffic = pf.get("traffic")
         out = {
             "metric": f"Msamples/sec (width x height x spp/s), Scene {args.scene} {W}x{H}" +
                       (" -- NON-PARITY throughput mode (own RNG streams; not the reference's image)" if args.mode == "throughput" else ""),
@@ -310,28 +314,56 @@ def main():
                                    f"depth {cam.bounce_limit}, {MODE_NAMES[args.mode]}, seed 69420, host LCG scene",
                        "mode": args.mode, "partition": f"rows/{args.rows_per_block} interleaved over {world_size} rank(s)",
                        "nominal_msamples_per_s": W * H * args.spp * args.steps / elapsed_max / 1e6},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "peak_measured": calib["hbm_copy_GBs"] if calib else None,
-                         "kernel": kernel_name,
-                         "avg_kernel_ms": avg_kernel_s * 1e3,
-                         "algorithmic_bytes_per_launch": algo_bytes,
-                         "traffic_source": pf.get("traffic_source"),
-                         "note": ("megakernel keeps scene, RNG state and bounce stack on chip: 0 B/segment by construction, "
-                                  "so the HBM fraction is tiny; what binds it is instruction latency at the occupancy its registers allow -- "
-                                  "valu_issue_frac x valu_lane_occupancy is the share of the VALU lane throughput it uses (DESIGN.md 4.7)") if args.mode == "mega" else
-                                 ("NON-PARITY mode: one stream per (pixel, stratum row), so a pixel's sqrt_spp rows are independent work items; results are "
-                                  "this mode's own (tests/test_gpu_throughput.py), not the reference's -- reported beside the headline, never as it") if args.mode == "throughput" else
-                                 ("wavefront form: 100 B per pixel + 240 B per segment of front / hit / pixel / stack records; bound by "
-                                  "front granularity (one segment of every live pixel per launch pair), not by HBM (DESIGN.md 4)"),
-                         "valu_issue_frac": pf.get("valu_issue_frac"), "valu_lane_occupancy": pf.get("valu_lane_occupancy"),
-                         "valu_lane_throughput_frac": pf.get("valu_lane_throughput_frac"),
-                         "scalar_and_branch_share_of_insts": pf.get("scalar_and_branch_share_of_insts"), "wave_wait_share": pf.get("wave_wait_share"),
-                         "valu_insts_per_launch": pf.get("valu_insts_per_launch"), "valu_source": pf.get("valu_source")},
-            "calibration": calib,
-            "kernel": {"segments_per_frame": st["segments"], "segments_per_s": st["segments"] / st["seconds"],
-                       "hip_event_seconds": st["seconds"], "vgprs": st["kernel_vgprs"], "lds_bytes": st["kernel_lds_bytes"]},
         }
+        if args.full:
+            avg_kernel_s = (sum(kernel_ms) / max(len(kernel_ms), 1)) * 1e-3
+            pixels_launch = W * lr
+            algo_bytes = 100 * pixels_launch  # 48 B state in + 48 B out + 4 B uchar4 per pixel; 0 B per segment
+            if args.mode == "throughput":  # per (pixel, stratum row): 48 B state in + 48 B out + 12 B partial sum; the resolve kernel's 12 B in and 4 B per pixel out
+                algo_bytes = pixels_launch * (cam.sqrt_spp * (96 + 12 + 12) + 4)
+            if args.mode == "wave":
+                algo_bytes = int(st["algorithmic_hbm_bytes"])  # + 240 B per segment of front / hit / pixel / stack records (wave_bvh.h)
+            achieved = algo_bytes / avg_kernel_s / 1e9 if avg_kernel_s > 0 else 0.0
+            kernel_name = ("wf_trav + wf_shade (per front)" if args.mode == "wave" else st["kernel_name"])
+            # roofline calibration on THIS box, outside the timed region (include/mort_hip.h mort_hip_calib_*): the HBM rate a float4
+            # copy reaches, and the cycles a SIMD needs per wave64 VALU instruction at 1, 3 and 8 resident waves
+            calib = None
+            if world_size == 1 and not args.no_calib:
+                cv = {w: ctx.calib_valu(w, 0)["cycles_per_valu_per_simd"] for w in (1, 3, 4, 8)}
+                calib = {"hbm_copy_GBs": ctx.calib_hbm_copy(1 << 30, 3), "valu_cycles_per_inst_per_simd": {str(w): v for w, v in cv.items()},
+                         "note": "mort_hip_calib_valu (independent v_fma_f32, waves per SIMD -> cycles per instruction per SIMD) and "
+                                 "mort_hip_calib_hbm_copy (float4 copy of 1 GiB per buffer, read + write)"}
+            valu_cpi = min(calib["valu_cycles_per_inst_per_simd"].values()) if calib else 2.0  # MI355X_MICROARCH.md: 2 cycles (SIMD-32)
+            # counter figures from the PMC passes committed under profiles/, quoted only when this run is the profiled configuration
+            pf = profile_figures(args.profile_tag, "wf_" if args.mode == "wave" else kernel_name, valu_cpi)
+            cfg = pf.get("config") or {}
+            same = (args.scene, W, H, args.spp, cam.bounce_limit, world_size, args.mode) == (
+                cfg.get("scene"), cfg.get("width"), cfg.get("height", H if args.aspect is None else None), cfg.get("spp"),
+                cfg.get("depth", cam.bounce_limit if args.depth is None else None), cfg.get("gpus"), cfg.get("mode", "mega"))
+            if not same:
+                pf = {"traffic": None}
+            traffic = pf.get("traffic")
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "peak_measured": calib["hbm_copy_GBs"] if calib else None,
+                               "kernel": kernel_name,
+                               "avg_kernel_ms": avg_kernel_s * 1e3,
+                               "algorithmic_bytes_per_launch": algo_bytes,
+                               "traffic_source": pf.get("traffic_source"),
+                               "note": ("megakernel keeps scene, RNG state and bounce stack on chip: 0 B/segment by construction, "
+                                        "so the HBM fraction is tiny; what binds it is instruction latency at the occupancy its registers allow -- "
+                                        "valu_issue_frac x valu_lane_occupancy is the share of the VALU lane throughput it uses (DESIGN.md 4.7)") if args.mode == "mega" else
+                                       ("NON-PARITY mode: one stream per (pixel, stratum row), so a pixel's sqrt_spp rows are independent work items; results are "
+                                        "this mode's own (tests/test_gpu_throughput.py), not the reference's -- reported beside the headline, never as it") if args.mode == "throughput" else
+                                       ("wavefront form: 100 B per pixel + 240 B per segment of front / hit / pixel / stack records; bound by "
+                                        "front granularity (one segment of every live pixel per launch pair), not by HBM (DESIGN.md 4)"),
+                               "valu_issue_frac": pf.get("valu_issue_frac"), "valu_lane_occupancy": pf.get("valu_lane_occupancy"),
+                               "valu_lane_throughput_frac": pf.get("valu_lane_throughput_frac"),
+                               "scalar_and_branch_share_of_insts": pf.get("scalar_and_branch_share_of_insts"), "wave_wait_share": pf.get("wave_wait_share"),
+                               "valu_insts_per_launch": pf.get("valu_insts_per_launch"), "valu_source": pf.get("valu_source")}
+            out["calibration"] = calib
+            out["kernel"] = {"segments_per_frame": st["segments"], "segments_per_s": st["segments"] / st["seconds"],
+                             "hip_event_seconds": st["seconds"], "vgprs": st["kernel_vgprs"], "lds_bytes": st["kernel_lds_bytes"]}
         if rehearsal:
             out["rehearsal"] = {"note": "MORT_BENCH_REHEARSAL=1: all ranks on GPU 0, gather through gloo -- control-flow rehearsal, timings meaningless",
                                 "composed_frame_equals_single_rank": rehearsal_ok}
@@ -340,7 +372,7 @@ def main():
                 "value": samples_per_step * args.steps / elapsed_tp / 1e6, "unit": "Msamples/s", "ms_per_step": elapsed_tp / args.steps * 1e3,
                 "note": "MORT_MODE_THROUGHPUT: one XORWOW stream per (pixel, stratum row) instead of the reference's one per pixel -- same estimator and "
                         "per-sample arithmetic, other random numbers, so NOT the reference's image; an extra figure, not the headline (DESIGN.md 4.8)"}
-        if world_size == 1 and args.cpu_spp > 0:
+        if args.full and world_size == 1 and args.cpu_spp > 0:
             threads = args.cpu_threads or min(len(os.sched_getaffinity(0)), 16)  # 16 = one GPU's CPU share
             out["cpu_baseline"] = cpu_baseline(args, threads)
             out["host_loop"] = host_loop(args, threads)

@@ -5,9 +5,9 @@ set -o pipefail
 TAG=${1:-vX}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out
-timeout -k 10 400 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -5 $O/${TAG}_bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -5 $O/${TAG}_bench.err; exit 1; }
 tail -1 $O/${TAG}_bench.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -- python3 bench.py --steps 5 --warmup 1 --cpu-spp 0 > $O/${TAG}_stats.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -- python3 bench.py --steps 5 --warmup 1 --full --cpu-spp 0 > $O/${TAG}_stats.log 2>&1 || exit 1
 cp $(find $O/${TAG}_stats -name "*kernel_stats.csv" | head -1) $O/${TAG}_bench_kernel_stats.csv && head -3 $O/${TAG}_bench_kernel_stats.csv
 rm -rf $O/${TAG}_stats
 for c in FETCH_SIZE WRITE_SIZE; do

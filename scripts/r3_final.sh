@@ -24,16 +24,16 @@ exit 0
 fi
 # ---- lines: the counter sets of the first half must be in profiles/r3 (committed, or copied from gpurun_out/) ----
 for k in headline c3 s8 wave_s1 c5geom_wave c5geom_mega; do [ -f $P/${k}_pmc_hbm.json ] || { [ -f $O/r3f_${k}_pmc_hbm.json ] && cp $O/r3f_${k}_pmc_hbm.json $P/${k}_pmc_hbm.json && cp $O/r3f_${k}_pmc_sq_summary.csv $P/${k}_pmc_sq_summary.csv; }; done
-timeout -k 10 600 python bench.py > $O/r3f_headline_bench.json 2> $O/r3f_headline_bench.err || exit 1
-timeout -k 10 600 python bench.py --mode throughput --cpu-spp 0 > $O/r3f_throughput_bench.json 2> $O/r3f_throughput_bench.err || exit 1
-timeout -k 10 600 python bench.py --scene 6 --width 800 --spp 1000 --profile-tag r3/c3 --steps 5 --warmup 1 > $O/r3f_c3_bench.json 2> $O/r3f_c3_bench.err || exit 1
-timeout -k 10 600 python bench.py --scene 8 --width 800 --spp 1000 --profile-tag r3/s8 --steps 2 --warmup 1 > $O/r3f_s8_bench.json 2> $O/r3f_s8_bench.err || exit 1
-timeout -k 10 600 python bench.py --mode wave --profile-tag r3/wave_s1 --steps 3 --warmup 1 --cpu-spp 0 > $O/r3f_wave_s1_bench.json 2> $O/r3f_wave_s1_bench.err || exit 1
-timeout -k 10 300 python bench.py --scene 8 --width 4096 --aspect 1 --spp 4 --profile-tag r3/c5geom_mega --steps 2 --warmup 1 --cpu-spp 0 > $O/r3f_c5geom_mega_bench.json 2> $O/r3f_c5geom.err || exit 1
-timeout -k 10 300 python bench.py --scene 8 --width 4096 --aspect 1 --spp 4 --mode wave --profile-tag r3/c5geom_wave --steps 2 --warmup 1 --cpu-spp 0 > $O/r3f_c5geom_wave_bench.json 2>> $O/r3f_c5geom.err || exit 1
-timeout -k 10 600 python bench.py --scene 8 --width 800 --spp 100 --mode wave --steps 2 --warmup 1 --cpu-spp 0 > $O/r3f_wave_s8_bench.json 2> $O/r3f_wave_s8_bench.err || exit 1
+timeout -k 10 600 python bench.py --full > $O/r3f_headline_bench.json 2> $O/r3f_headline_bench.err || exit 1
+timeout -k 10 600 python bench.py --full --mode throughput --cpu-spp 0 > $O/r3f_throughput_bench.json 2> $O/r3f_throughput_bench.err || exit 1
+timeout -k 10 600 python bench.py --full --scene 6 --width 800 --spp 1000 --profile-tag r3/c3 --steps 5 --warmup 1 > $O/r3f_c3_bench.json 2> $O/r3f_c3_bench.err || exit 1
+timeout -k 10 600 python bench.py --full --scene 8 --width 800 --spp 1000 --profile-tag r3/s8 --steps 2 --warmup 1 > $O/r3f_s8_bench.json 2> $O/r3f_s8_bench.err || exit 1
+timeout -k 10 600 python bench.py --full --mode wave --profile-tag r3/wave_s1 --steps 3 --warmup 1 --cpu-spp 0 > $O/r3f_wave_s1_bench.json 2> $O/r3f_wave_s1_bench.err || exit 1
+timeout -k 10 300 python bench.py --full --scene 8 --width 4096 --aspect 1 --spp 4 --profile-tag r3/c5geom_mega --steps 2 --warmup 1 --cpu-spp 0 > $O/r3f_c5geom_mega_bench.json 2> $O/r3f_c5geom.err || exit 1
+timeout -k 10 300 python bench.py --full --scene 8 --width 4096 --aspect 1 --spp 4 --mode wave --profile-tag r3/c5geom_wave --steps 2 --warmup 1 --cpu-spp 0 > $O/r3f_c5geom_wave_bench.json 2>> $O/r3f_c5geom.err || exit 1
+timeout -k 10 600 python bench.py --full --scene 8 --width 800 --spp 100 --mode wave --steps 2 --warmup 1 --cpu-spp 0 > $O/r3f_wave_s8_bench.json 2> $O/r3f_wave_s8_bench.err || exit 1
 # config 4's frame at its own spp on one GPU (one step: 4 900 effective spp), and config 5's frame at 49 spp in wavefront mode
-timeout -k 10 600 python bench.py --scene 8 --width 1920 --aspect 1.7777778 --spp 5000 --steps 1 --warmup 1 --cpu-spp 0 --no-calib --no-throughput-line > $O/r3f_c4_5000spp_bench.json 2> $O/r3f_c4.err || exit 1
+timeout -k 10 600 python bench.py --full --scene 8 --width 1920 --aspect 1.7777778 --spp 5000 --steps 1 --warmup 1 --cpu-spp 0 --no-calib --no-throughput-line > $O/r3f_c4_5000spp_bench.json 2> $O/r3f_c4.err || exit 1
 timeout -k 10 300 python scripts/time_partition.py 1 1200 500 mega > $O/r3f_time_partition_s1.json 2> $O/r3f_tp.err || exit 1
 timeout -k 10 300 python scripts/time_partition.py 1 1200 500 throughput > $O/r3f_time_partition_s1_throughput.json 2>> $O/r3f_tp.err || exit 1
 timeout -k 10 300 python scripts/time_partition.py 8 1920 49 mega 1.7777778 > $O/r3f_time_partition_c4geom_49spp.json 2>> $O/r3f_tp.err || exit 1

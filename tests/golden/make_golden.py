@@ -6,7 +6,10 @@
 1. earthmap_rgb.npz -- texels of the reference's imgs/earthmap.jpg decoded with the reference's
    vendored stb_image.h (oracle/_ref/stb_decode, compiled from /root/reference where it lies).
    Needs /root/reference; skipped (existing file kept) when it is absent.
-2. oracle_golden.npz -- outputs of the CPU oracle (oracle/mort_oracle.c) for small configurations
+2. earthmap_damaged.npz -- damaged copies of earthmap.jpg (truncations, bytes changed inside the scan: the recipe) and what
+   the same stb_decode makes of each (SHA-256 and shape of the RGB bytes, or "" where it refuses the file).  Needs
+   oracle/_ref like (1); skipped (existing file kept) when it is absent.
+3. oracle_golden.npz -- outputs of the CPU oracle (oracle/mort_oracle.c) for small configurations
    of every scene family: uchar4 image, fp32 accumulators, per-pixel segment counts, and the final
    RNG words of a few pixels.  BASELINE config 1 (Scene 1, 200x112, 4 spp) is case "s1_c1".
 
@@ -54,6 +57,54 @@ def make_earth():
     print("earthmap", w, h)
 
 
+def damaged_cases(data, recipe):
+    """The damaged files of earthmap_damaged.npz's recipe, in order."""
+    cases = [data[:int(n)] for n in recipe["trunc"]]
+    for n, pos, val in zip(recipe["flip_n"], recipe["flip_pos"], recipe["flip_val"]):
+        d = bytearray(data)
+        for i, v in zip(pos[:n], val[:n]):
+            d[int(i)] = int(v)
+        cases.append(bytes(d))
+    return cases
+
+
+def make_damaged():
+    import hashlib
+    import tempfile
+    exe = os.path.join(ROOT, "oracle", "_ref", "stb_decode")
+    if not os.path.exists(exe):
+        print("oracle/_ref/stb_decode absent: keeping existing damaged-file fixture")
+        return
+    data = open(os.path.join(HERE, "earthmap.jpg"), "rb").read()
+    rng = np.random.default_rng(11)
+    trunc = [600, 2000, 20000, len(data) - 1000, len(data) - 3]
+    flip_n = np.zeros(60, np.int64)
+    flip_pos = np.zeros((60, 5), np.int64)
+    flip_val = np.zeros((60, 5), np.uint8)
+    for k in range(60):  # damage inside the entropy-coded scan (headers stay valid)
+        pos = rng.integers(1000, len(data) - 2, size=int(rng.integers(1, 6)))
+        flip_n[k] = len(pos)
+        for j, i in enumerate(pos):
+            flip_pos[k, j], flip_val[k, j] = i, rng.integers(0, 255)  # never 0xff: no new markers
+    recipe = dict(trunc=np.array(trunc, np.int64), flip_n=flip_n, flip_pos=flip_pos, flip_val=flip_val)
+    digests, shapes = [], []
+    with tempfile.TemporaryDirectory() as tmp:
+        for k, blob in enumerate(damaged_cases(data, recipe)):
+            jpg, ppm = os.path.join(tmp, f"case{k}.jpg"), os.path.join(tmp, f"case{k}.ppm")
+            open(jpg, "wb").write(blob)
+            p = subprocess.run([exe, jpg, ppm], capture_output=True)
+            if p.returncode != 0 or not os.path.exists(ppm):
+                digests.append(""); shapes.append((0, 0, 0))
+                continue
+            raw = open(ppm, "rb").read()
+            hdr = raw[:32].split()
+            w, h = int(hdr[1]), int(hdr[2])
+            off = raw.index(b"255") + 4
+            digests.append(hashlib.sha256(raw[off:off + w * h * 3]).hexdigest()); shapes.append((h, w, 3))
+    np.savez_compressed(os.path.join(HERE, "earthmap_damaged.npz"), sha256=np.array(digests), shape=np.array(shapes, np.int64), **recipe)
+    print("damaged", len(digests), "cases,", sum(1 for d in digests if d), "decoded")
+
+
 def make_oracle():
     from mort_amd import host
     from tests import oracle_lib as O
@@ -72,4 +123,5 @@ def make_oracle():
 
 if __name__ == "__main__":
     make_earth()
+    make_damaged()
     make_oracle()

@@ -86,28 +86,33 @@ def _stb(exe, path, tmp_path):
 
 def test_damaged_files_decode_like_the_reference_decoder(tmp_path):
     """Truncated scans and flipped bytes: whatever the reference's stb_image makes of the file (it pads a short scan with zeros), the
-    product decoder makes the same bytes of it, or both refuse it."""
-    import pytest
+    product decoder makes the same bytes of it, or both refuse it.  The damaged files (their recipe) and stb_image's result for each
+    (SHA-256 of the RGB bytes) are stored in tests/golden/earthmap_damaged.npz (make_golden.py); where oracle/_ref is built, the live
+    decoder is compared as well."""
+    import hashlib
+    from tests.golden.make_golden import damaged_cases
+    gold = np.load(os.path.join(HERE, "golden", "earthmap_damaged.npz"))
     exe = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "stb_decode")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref not built here (no /root/reference)")
+    live = os.path.exists(exe)
     data = open(os.path.join(HERE, "golden", "earthmap.jpg"), "rb").read()
-    rng = np.random.default_rng(11)
-    cases = [data[:n] for n in (600, 2000, 20000, len(data) - 1000, len(data) - 3)]
-    for _ in range(60):  # damage inside the entropy-coded scan (headers stay valid)
-        d = bytearray(data)
-        for i in rng.integers(1000, len(d) - 2, size=int(rng.integers(1, 6))):
-            d[int(i)] = int(rng.integers(0, 255))  # never 0xff: no new markers
-        cases.append(bytes(d))
+    cases = damaged_cases(data, gold)
+    assert len(cases) == len(gold["sha256"]) == 65
     compared = 0
     for k, blob in enumerate(cases):
         f = tmp_path / f"case{k}.jpg"
         f.write_bytes(blob)
-        ours, ref = _decode(str(f)), _stb(exe, f, tmp_path)
-        if ref is None:
+        ours, want = _decode(str(f)), str(gold["sha256"][k])
+        if live:
+            ref = _stb(exe, f, tmp_path)
+            assert (ref is None) == (want == ""), f"case {k}: the stored result is not the live decoder's"
+            if ref is not None:
+                assert hashlib.sha256(ref.tobytes()).hexdigest() == want, f"case {k}: the stored result is not the live decoder's"
+                assert ours is not None and ours.shape == ref.shape
+                assert (ours == ref).all(), f"case {k}: {int((ours != ref).sum())} bytes differ"
+        if want == "":
             assert ours is None
             continue
-        assert ours is not None and ours.shape == ref.shape
-        assert (ours == ref).all(), f"case {k}: {int((ours != ref).sum())} bytes differ"
+        assert ours is not None and ours.shape == tuple(gold["shape"][k])
+        assert hashlib.sha256(ours.tobytes()).hexdigest() == want, f"case {k}: not the reference decoder's bytes"
         compared += 1
     assert compared >= 5
