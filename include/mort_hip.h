@@ -162,6 +162,43 @@ typedef struct mort_calib_valu {
 int mort_hip_calib_valu(mort_ctx *ctx, int waves_per_simd, int kind, mort_calib_valu *out);
 int mort_hip_calib_hbm_copy(mort_ctx *ctx, size_t bytes, int reps, double *gbs_out);
 
+/* ---- first-hit feature buffers and an edge-aware a-trous denoiser (Dammertz et al., HPG 2010).  NOT parity: an extra on
+ * top of the render for a viewable image at low sample counts.  None of these calls draws a random number or touches what the render keeps
+ * across frames (RNG states, tile-cost cache).  All buffers are full-image f32, row 0 = bottom row.  `seconds` may be NULL; when given it
+ * receives the HIP-event device time of the kernels (host forms: wall time of the loop).
+ *
+ * Features: one ray per pixel from the lens centre through the pixel centre (time 0.5), closest solid hit (t_min = 0.001), then the
+ * constant media in scan order entered before it (no random distance).  albedo W*H*3: lambertian / isotropic = texture at the hit,
+ * metal = its colour, dielectric / diffuse_light = 1; normal W*H*3: world space, front-face oriented (medium: -unit(dir)); depth W*H:
+ * t * |dir|.  A miss: albedo = camera background, normal = 0, depth = 0 (the "no hit" sentinel).
+ *
+ * Denoise: C' = remodulate(a-trous^n(C / max(A, 1e-3))) with the weights of DESIGN.md 4.9, then the render's NaN guard and gamma tail
+ * for rgba (uchar4 W*H).  iterations == 0 returns C unchanged and the render's own rgba.  accum_out (W*H*3) or rgba_out may be NULL;
+ * outputs must not alias inputs.  Whole image, whatever the context's partition. ---- */
+typedef struct mort_denoise_params {
+    int iterations;          /* 0..8; iteration i filters at step 2^i */
+    float sigma_color;       /* demodulated colour; halves every iteration */
+    float sigma_depth;       /* relative depth difference per step */
+    float sigma_albedo;      /* albedo difference */
+    int normal_log2_power;   /* normal weight max(0, Np.Nq)^(2^k), k squarings; 0..16 */
+} mort_denoise_params;
+int mort_hip_denoise_defaults(mort_denoise_params *params);
+/* full-size host buffers; under a partition only the owned rows are written.  Needs an uploaded world, no RNG. */
+int mort_hip_render_features(mort_ctx *ctx, const mort_camera *cam, float *albedo_out, float *normal_out, float *depth_out, double *seconds);
+/* packed owned rows in DEVICE buffers (local_rows * W pixels), on `stream` (NULL = the context's); asynchronous when seconds is NULL */
+int mort_hip_render_features_device(mort_ctx *ctx, const mort_camera *cam, void *d_albedo, void *d_normal, void *d_depth, void *stream,
+                                    double *seconds);
+int mort_hip_denoise(mort_ctx *ctx, const mort_denoise_params *params, int width, int height, const float *accum, const float *albedo,
+                     const float *normal, const float *depth, float *accum_out, uint8_t *rgba_out, double *seconds);
+/* the same on DEVICE buffers of the whole image, on `stream` (NULL = the context's); asynchronous when seconds is NULL */
+int mort_hip_denoise_device(mort_ctx *ctx, const mort_denoise_params *params, int width, int height, const void *d_accum, const void *d_albedo,
+                            const void *d_normal, const void *d_depth, void *d_accum_out, void *d_rgba_out, void *stream, double *seconds);
+/* host loops of the same bodies: no GPU, no HIP runtime call.  flags: MORT_HOST_TREE as for mort_hip_render_host */
+int mort_hip_render_features_host(const mort_world *world, const mort_camera *cam, int nthreads, int flags, float *albedo_out, float *normal_out,
+                                  float *depth_out, double *seconds);
+int mort_hip_denoise_host(const mort_denoise_params *params, int width, int height, int nthreads, const float *accum, const float *albedo,
+                          const float *normal, const float *depth, float *accum_out, uint8_t *rgba_out, double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

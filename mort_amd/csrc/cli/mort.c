@@ -9,10 +9,14 @@
  *                   [--gpus N] [--devices a,b,..] [--gather rccl|shm]     one process per GPU, rows partitioned, one gather
  *                   [--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth img] [--rtl] [--device K]
  *                   [--keys WASD..] [--mouse dx,dy]        the reference's interactive loop, scripted: one idle tick per frame
+ *                   [--denoise] [--features-out PREFIX]   first-hit features + a-trous denoiser on the last frame (single GPU / host)
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
  * --mouse delta dragged with the left button.  --out / --dump-f32 hold the last frame.
+ * --denoise: after the last frame, the feature pass for its camera and the a-trous denoiser (default parameters) over its
+ * accumulators; --out then holds the denoised image (--dump-f32 stays the raw render) and the JSON line gains "denoise_seconds".
+ * --features-out P writes P.albedo.f32, P.normal.f32, P.depth.f32 (W*H*3 / *3 / *1 floats, row 0 = bottom row).
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -55,7 +59,8 @@ static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &
 static int usage(void) {
     printf("Usage: mort <number_between_1_and_10> [--width W] [--aspect A] [--spp N] [--depth D] [--seed S] [--frames N] "
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
-           "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy]\n");
+           "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
+           "[--denoise] [--features-out PREFIX]\n");
     return -1;
 }
 
@@ -96,7 +101,8 @@ int main(int argc, char **argv) {
     int gpus = 1, gather_shm = 0, devices[64], n_devices = 0;
     double aspect = 0;
     unsigned long long seed = MORT_DEFAULT_SEED;
-    const char *out = NULL, *dump = NULL, *sin = NULL, *sout = NULL, *earth = NULL, *keys = NULL;
+    const char *out = NULL, *dump = NULL, *sin = NULL, *sout = NULL, *earth = NULL, *keys = NULL, *feat_out = NULL;
+    int denoise = 0;
     int mouse_dx = 0, mouse_dy = 0;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
@@ -130,11 +136,14 @@ int main(int argc, char **argv) {
         }
         else if (strcmp(argv[i], "--rtl") == 0) rtl = 1;
         else if (strcmp(argv[i], "--tree") == 0) tree = 1;
+        else if (strcmp(argv[i], "--denoise") == 0) denoise = 1;
+        else if (ARG("--features-out")) feat_out = argv[++i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
     if (host_mode && gpus != 1) { fprintf(stderr, "--mode host runs on the host: --gpus does not apply\n"); return -1; }
     if (gpus > 1 && (dump || sin || sout)) { fprintf(stderr, "--dump-f32 / --states-in / --states-out are single-GPU options\n"); return -1; }
+    if (gpus > 1 && (denoise || feat_out)) { fprintf(stderr, "--denoise / --features-out are single-GPU options\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;
@@ -198,8 +207,8 @@ int main(int argc, char **argv) {
     }
 
     uint8_t *rgba = calloc(npx, 4);
-    float *accum = dump ? calloc(npx * 3, sizeof(float)) : NULL;
-    if (!rgba || (dump && !accum)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    float *accum = (dump || denoise) ? calloc(npx * 3, sizeof(float)) : NULL;
+    if (!rgba || ((dump || denoise) && !accum)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
     mort_stats stats;
     memset(&stats, 0, sizeof stats);
     double total_ms = 0, frame_wall = 0;
@@ -265,6 +274,36 @@ int main(int argc, char **argv) {
         }
     }
 
+    /* ---- --denoise / --features-out (single GPU or host mode): the last frame's camera; the PPM becomes the denoised image ---- */
+    double denoise_sec = 0;
+    if (denoise || feat_out) {
+        float *alb = malloc(npx * 3 * sizeof(float)), *nrm = malloc(npx * 3 * sizeof(float)), *dep = malloc(npx * sizeof(float));
+        if (!alb || !nrm || !dep) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+        double fs = 0, ds = 0;
+        if (host_mode) { if ((st = mort_hip_render_features_host(&world, &cam, threads, tree ? MORT_HOST_TREE : 0, alb, nrm, dep, &fs)) != MORT_OK) die(NULL, st, "mort_hip_render_features_host"); }
+        else if ((st = mort_hip_render_features(ctx, &cam, alb, nrm, dep, &fs)) != MORT_OK) die(ctx, st, "mort_hip_render_features");
+        if (denoise) {
+            mort_denoise_params dp;
+            mort_hip_denoise_defaults(&dp);
+            if (host_mode) { if ((st = mort_hip_denoise_host(&dp, W, H, threads, accum, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_denoise_host"); }
+            else if ((st = mort_hip_denoise(ctx, &dp, W, H, accum, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(ctx, st, "mort_hip_denoise");
+            denoise_sec = fs + ds;
+        }
+        if (feat_out) {
+            const char *suffix[3] = {"albedo", "normal", "depth"};
+            const float *buf[3] = {alb, nrm, dep};
+            const size_t cnt[3] = {npx * 3, npx * 3, npx};
+            for (int k = 0; k < 3; k++) {
+                char path[4096];
+                snprintf(path, sizeof path, "%s.%s.f32", feat_out, suffix[k]);
+                FILE *f = fopen(path, "wb");
+                if (!f || fwrite(buf[k], sizeof(float), cnt[k], f) != cnt[k]) { fprintf(stderr, "cannot write %s\n", path); return EXIT_FAILURE; }
+                fclose(f);
+            }
+        }
+        free(alb); free(nrm); free(dep);
+    }
+
     /* ---- ranks other than 0 are done; rank 0 waits for them (their rows are in shm / were gathered) ---- */
     if (rank != 0) {
         if (ctx) mort_hip_shutdown(ctx);
@@ -285,11 +324,13 @@ int main(int argc, char **argv) {
     const double sec = (gpus > 1) ? frame_wall : stats.seconds; /* multi-GPU: wall clock of the frame on rank 0, gather included */
     printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp_nominal\": %d, \"spp_effective\": %d, \"depth\": %d, \"mode\": \"%s\", \"gpus\": %d, "
            "\"seconds\": %.6f, \"msamples_per_s\": %.3f, \"kernel_seconds\": %.6f, \"gather_seconds\": %.6f, \"segments\": %llu, "
-           "\"algorithmic_hbm_bytes\": %llu, \"hbm_GBps\": %.4g, \"hbm_frac_of_8TBps\": %.3g, \"reference_walks\": %llu, \"kernel\": \"%s\"}\n",
+           "\"algorithmic_hbm_bytes\": %llu, \"hbm_GBps\": %.4g, \"hbm_frac_of_8TBps\": %.3g, \"reference_walks\": %llu, \"kernel\": \"%s\"",
            scene, W, H, cam.samples_per_pixel, eff, cam.bounce_limit, host_mode ? "host" : mode == MORT_MODE_WAVE ? "wave" : mode == MORT_MODE_THROUGHPUT ? "throughput (non-parity)" : "mega", gpus, sec,
            (double)npx * eff / sec / 1e6, stats.seconds, stats.gather_seconds, (unsigned long long)stats.segments,
            (unsigned long long)stats.algorithmic_hbm_bytes, stats.algorithmic_hbm_bytes / stats.seconds / 1e9,
            stats.algorithmic_hbm_bytes / stats.seconds / 8e12, (unsigned long long)stats.reference_walks, stats.kernel_name);
+    if (denoise) printf(", \"denoise_seconds\": %.6f", denoise_sec); /* feature pass + denoise, device time (host loops: wall time) */
+    printf("}\n");
     if (out && mort_write_ppm(out, rgba, W, H) != 0) { fprintf(stderr, "cannot write %s\n", out); return EXIT_FAILURE; }
     if (dump) {
         FILE *f = fopen(dump, "wb");

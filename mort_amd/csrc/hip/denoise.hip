@@ -1,0 +1,370 @@
+/*
+ * denoise.hip -- first-hit feature buffers and the edge-aware a-trous denoiser: a non-parity extra on top
+ * of the untouched render path, for a viewable image at the sample counts an interactive frame can afford.
+ *
+ * Kernels (gfx950, wave64, 64x4-pixel workgroups: every wave covers 64 contiguous pixels of one row):
+ *   feat_kernel<TREE>             one primary ray per pixel (lens centre -> pixel centre, tm = 0.5), no random numbers:
+ *                                 albedo, normal, depth of the first hit.  TREE: the unified-tree walk with its pending
+ *                                 children in LDS (16 x 256 x 2 B), else the item scan.  Reads the scene in HBM.
+ *   atrous_kernel<FIRST, LAST>    one a-trous iteration, 5x5 taps at step 2^i; iteration 0 demodulates the caller's buffers,
+ *                                 the last remodulates and writes the accumulators and the rgba: n launches for n iterations
+ *   atrous_passthrough_kernel     iterations == 0: the accumulators and the render's own rgba
+ *
+ * The host forms (mort_hip_render_features_host, mort_hip_denoise_host) run the same per-pixel bodies (dev_features.h)
+ * on host threads and make no HIP runtime call.  Nothing here touches the render's RNG states, tile-cost cache or counters.
+ */
+#include <hip/hip_runtime.h>
+
+#include <pthread.h>
+#include <time.h>
+
+#include <atomic>
+#include <cstring>
+#include <vector>
+
+#include "mort_hip.h"
+#include "dev_features.h"
+#include "scene_blob.h"
+#include "mort_ctx.h"
+
+#pragma clang fp contract(off)
+
+#define FEAT_BX 64
+#define FEAT_BY 4
+
+/* ====================================================================== device */
+
+template <bool TREE>
+__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) feat_kernel(const FeatArgs a) {
+    __shared__ unsigned short feat_stack[MORT_OWN_STACK * FEAT_BX * FEAT_BY];
+    const int tid = threadIdx.x + threadIdx.y * FEAT_BX;
+    const int x = blockIdx.x * FEAT_BX + threadIdx.x, ly = blockIdx.y * FEAT_BY + threadIdx.y;
+    if (x >= a.width || ly >= a.local_rows) return;
+    feat_pixel<TREE>(a, x, ly, &feat_stack[tid], FEAT_BX * FEAT_BY);
+}
+
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) atrous_kernel(const AtrousArgs a) {
+    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    dn_pixel<FIRST, LAST>(a, x, y);
+}
+
+__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) atrous_passthrough_kernel(const AtrousArgs a) {
+    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    dn_passthrough(a, x, y);
+}
+
+/* ====================================================================== host */
+
+namespace {
+
+double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+
+/* tuned on scenes 1, 3 and 6 at 4 spp */
+const mort_denoise_params kDefaults = {5, 2.0f, 0.1f, 0.05f, 3};
+
+bool params_ok(const mort_denoise_params *p) {
+    if (!p) return false;
+    if (p->iterations < 0 || p->iterations > 8) return false;
+    if (p->normal_log2_power < 0 || p->normal_log2_power > 16) return false;
+    const float s[3] = {p->sigma_color, p->sigma_depth, p->sigma_albedo};
+    for (float v : s) if (!(v > 0.0f && v < 1e30f)) return false;
+    return true;
+}
+
+/* the arguments of iteration i of n (buffers filled in by the caller) */
+AtrousArgs atrous_args(const mort_denoise_params *p, int W, int H, int i) {
+    AtrousArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.width = W; a.height = H;
+    a.step = 1 << i;
+    a.npow = p->normal_log2_power;
+    a.inv_c = (float)(1 << (2 * i)) / (p->sigma_color * p->sigma_color); /* the colour sigma halves every iteration */
+    a.sd = p->sigma_depth * (float)a.step;
+    a.inv_a = 1.0f / (p->sigma_albedo * p->sigma_albedo);
+    return a;
+}
+
+/* run `fn(row)` for rows [0, rows) on `nthreads` host threads */
+struct RowJob {
+    std::atomic<int> next{0};
+    int rows = 0;
+    void (*fn)(void *, int) = nullptr;
+    void *arg = nullptr;
+};
+void *row_worker(void *p) {
+    RowJob *j = (RowJob *)p;
+    for (;;) {
+        const int r = j->next.fetch_add(1);
+        if (r >= j->rows) break;
+        j->fn(j->arg, r);
+    }
+    return nullptr;
+}
+void run_rows(int rows, int nthreads, void (*fn)(void *, int), void *arg) {
+    RowJob job;
+    job.rows = rows; job.fn = fn; job.arg = arg;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    std::vector<pthread_t> th((size_t)nthreads - 1);
+    size_t started = 0;
+    for (; started < th.size(); started++)
+        if (pthread_create(&th[started], nullptr, row_worker, &job) != 0) break;
+    row_worker(&job);
+    for (size_t i = 0; i < started; i++) pthread_join(th[i], nullptr);
+}
+
+struct FeatHostJob { FeatArgs a; bool tree; };
+void feat_host_row(void *p, int ly) {
+    const FeatHostJob *j = (const FeatHostJob *)p;
+    unsigned short stack[MORT_OWN_STACK];
+    for (int x = 0; x < j->a.width; x++) {
+        if (j->tree) feat_pixel<true>(j->a, x, ly, stack, 1);
+        else feat_pixel<false>(j->a, x, ly, stack, 1);
+    }
+}
+
+struct DnHostJob { AtrousArgs a; int first, last, pass; };
+void dn_host_row(void *p, int y) {
+    const DnHostJob *j = (const DnHostJob *)p;
+    for (int x = 0; x < j->a.width; x++) {
+        if (j->pass) dn_passthrough(j->a, x, y);
+        else if (j->first && j->last) dn_pixel<true, true>(j->a, x, y);
+        else if (j->first) dn_pixel<true, false>(j->a, x, y);
+        else if (j->last) dn_pixel<false, true>(j->a, x, y);
+        else dn_pixel<false, false>(j->a, x, y);
+    }
+}
+
+void feat_camera(FeatArgs &a, const mort_camera *cam) {
+    a.width = cam->image_width; a.height = cam->image_height;
+    a.background = to_v3(cam->background); a.center = to_v3(cam->center); a.pixel00 = to_v3(cam->pixel00_loc);
+    a.du = to_v3(cam->pixel_delta_u); a.dv = to_v3(cam->pixel_delta_v);
+}
+
+/* the camera must lie where the unified tree's pads were sized for (the test of mort_hip_render_host, origin = lens centre) */
+bool camera_in_reach(const mort_camera *cam, const float lo[3], const float hi[3], float reach) {
+    for (int k = 0; k < 3; k++) {
+        const float v = cam->center.e[k];
+        if (!(v >= lo[k] - reach && v <= hi[k] + reach)) return false;
+    }
+    return true;
+}
+
+int grow(mort_ctx *c, void **p, size_t *cap, size_t need) {
+    if (*p && *cap >= need) return MORT_OK;
+    if (*p) { HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
+    HIPCHK(c, hipMalloc(p, need ? need : 16));
+    *cap = need;
+    return MORT_OK;
+}
+
+/* a call on another stream than the previous one: that one may still read the scratch buffers */
+hipError_t dn_switch_stream(mort_ctx *c, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (c->dn_stream && c->dn_stream != s) e = hipStreamSynchronize(c->dn_stream);
+    c->dn_stream = s;
+    return e;
+}
+
+} // namespace
+
+extern "C" int mort_hip_denoise_defaults(mort_denoise_params *p) {
+    if (!p) return MORT_ERR_INVALID;
+    *p = kDefaults;
+    return MORT_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------- feature pass */
+
+extern "C" int mort_hip_render_features_device(mort_ctx *c, const mort_camera *cam, void *d_albedo, void *d_normal, void *d_depth,
+                                               void *stream, double *seconds) {
+    if (!c || !cam || !d_albedo || !d_normal || !d_depth) return MORT_ERR_INVALID;
+    if (!c->have_world) return MORT_ERR_NO_WORLD;
+    const int W = cam->image_width, H = cam->image_height;
+    if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, dn_switch_stream(c, s));
+
+    FeatArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.sc = c->sc;
+    feat_camera(a, cam);
+    a.rank = c->part.rank; a.nranks = c->part.nranks; a.rows_per_block = c->part.rows_per_block;
+    a.local_rows = mort_hip_local_rows(c, H);
+    a.albedo = (float *)d_albedo; a.normal = (float *)d_normal; a.depth = (float *)d_depth;
+    const bool tree = c->gen_ok && camera_in_reach(cam, c->gen_lo, c->gen_hi, c->gen_reach);
+    if (tree) {
+        const unsigned char *g = (const unsigned char *)c->d_gen;
+        a.gw.nodes = (const DNodeQ *)(g + c->gen.o_nodes); a.gw.entries = (const uint32_t *)(g + c->gen.o_entries);
+        a.gw.chains = (const int *)(g + c->gen.o_chains); a.gw.ranks = c->gen.ranks; a.gw.n_spheres = c->gen.n_spheres;
+        a.gw.n_chains = c->gen.n_chains; a.gw.root = c->gen.root; a.gw.first_medium = c->gen.first_medium;
+        a.gw.gx = c->gen.gx; a.gw.gy = c->gen.gy; a.gw.gz = c->gen.gz; a.gw.gR = c->gen.gR; a.gw.mnear = c->gen.mnear; a.gw.kmin = c->gen.kmin;
+    }
+    if (seconds) HIPCHK(c, hipEventRecord(c->ev0, s));
+    if (a.local_rows > 0) {
+        const dim3 grid((W + FEAT_BX - 1) / FEAT_BX, (a.local_rows + FEAT_BY - 1) / FEAT_BY), block(FEAT_BX, FEAT_BY);
+        if (tree) hipLaunchKernelGGL(feat_kernel<true>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(feat_kernel<false>, grid, block, 0, s, a);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (seconds) {
+        HIPCHK(c, hipEventRecord(c->ev1, s));
+        HIPCHK(c, hipEventSynchronize(c->ev1));
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *seconds = ms * 1e-3;
+    }
+    return MORT_OK;
+}
+
+extern "C" int mort_hip_render_features(mort_ctx *c, const mort_camera *cam, float *albedo_out, float *normal_out, float *depth_out,
+                                        double *seconds) {
+    if (!c || !cam || !albedo_out || !normal_out || !depth_out) return MORT_ERR_INVALID;
+    if (!c->have_world) return MORT_ERR_NO_WORLD;
+    const int W = cam->image_width, H = cam->image_height;
+    if (W <= 0 || H <= 0) return MORT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int lr = mort_hip_local_rows(c, H);
+    const size_t npx = (size_t)W * (size_t)lr;
+    HIPCHK(c, dn_switch_stream(c, c->stream));
+    int st = grow(c, &c->d_feat, &c->feat_cap, npx * 7 * sizeof(float));
+    if (st != MORT_OK) return st;
+    float *d_alb = (float *)c->d_feat, *d_nrm = d_alb + 3 * npx, *d_dep = d_nrm + 3 * npx;
+    double sec = 0;
+    if ((st = mort_hip_render_features_device(c, cam, d_alb, d_nrm, d_dep, c->stream, &sec)) != MORT_OK) return st;
+    if (seconds) *seconds = sec;
+    if (c->part.nranks == 1) {
+        HIPCHK(c, hipMemcpy(albedo_out, d_alb, npx * 12, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(normal_out, d_nrm, npx * 12, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(depth_out, d_dep, npx * 4, hipMemcpyDeviceToHost));
+        return MORT_OK;
+    }
+    for (int ly = 0; ly < lr; ly++) {
+        const size_t y = (size_t)mort_hip_global_row(c, ly), W3 = (size_t)W * 3;
+        HIPCHK(c, hipMemcpy(albedo_out + y * W3, d_alb + (size_t)ly * W3, W3 * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(normal_out + y * W3, d_nrm + (size_t)ly * W3, W3 * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(depth_out + y * W, d_dep + (size_t)ly * W, (size_t)W * 4, hipMemcpyDeviceToHost));
+    }
+    return MORT_OK;
+}
+
+extern "C" int mort_hip_render_features_host(const mort_world *world, const mort_camera *cam, int nthreads, int flags, float *albedo_out,
+                                             float *normal_out, float *depth_out, double *seconds) {
+    if (!world || !cam || !albedo_out || !normal_out || !depth_out) return MORT_ERR_INVALID;
+    const int W = cam->image_width, H = cam->image_height;
+    if (W <= 0 || H <= 0) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(world, sb);
+    if (st != MORT_OK) return st;
+    FeatHostJob job;
+    std::memset(&job.a, 0, sizeof job.a);
+    scene_view(sb, sb.bytes.data(), job.a.sc);
+    feat_camera(job.a, cam);
+    job.a.rank = 0; job.a.nranks = 1; job.a.rows_per_block = 8; job.a.local_rows = H;
+    job.a.albedo = albedo_out; job.a.normal = normal_out; job.a.depth = depth_out;
+    const mortc::Compiled &o = sb.comp;
+    job.tree = (flags & MORT_HOST_TREE) && o.g_ok && camera_in_reach(cam, o.g_lo, o.g_hi, o.g_reach);
+    if (job.tree) {
+        GenWalk &gw = job.a.gw;
+        gw.nodes = o.g_nodes.data(); gw.entries = o.g_entries.data(); gw.chains = o.g_chains.data();
+        gw.ranks = o.g_ranks.data(); gw.n_spheres = (int)o.spheres.size();
+        gw.n_chains = (int)(o.g_chains.size() / 2); gw.root = o.g_root; gw.first_medium = o.g_first_medium;
+        gw.gx = o.g_c[0]; gw.gy = o.g_c[1]; gw.gz = o.g_c[2]; gw.gR = o.g_R; gw.mnear = o.g_mnear; gw.kmin = o.g_kmin;
+    }
+    const double t0 = now_s();
+    run_rows(H, nthreads, feat_host_row, &job);
+    if (seconds) *seconds = now_s() - t0;
+    return MORT_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------- denoiser */
+
+extern "C" int mort_hip_denoise_device(mort_ctx *c, const mort_denoise_params *p, int W, int H, const void *d_accum, const void *d_albedo,
+                                       const void *d_normal, const void *d_depth, void *d_accum_out, void *d_rgba_out, void *stream,
+                                       double *seconds) {
+    if (!c || !params_ok(p) || !d_accum || !d_albedo || !d_normal || !d_depth) return MORT_ERR_INVALID;
+    if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, dn_switch_stream(c, s));
+    const size_t npx = (size_t)W * (size_t)H;
+    const int n = p->iterations;
+    if (n > 1) { /* e ping-pong, g0, g1 */
+        const int st = grow(c, &c->d_dn, &c->dn_cap, npx * 4 * sizeof(float4));
+        if (st != MORT_OK) return st;
+    }
+    float4 *e0 = (float4 *)c->d_dn, *e1 = e0 + npx, *g0 = e1 + npx, *g1 = g0 + npx;
+    const dim3 grid((W + FEAT_BX - 1) / FEAT_BX, (H + FEAT_BY - 1) / FEAT_BY), block(FEAT_BX, FEAT_BY);
+    if (seconds) HIPCHK(c, hipEventRecord(c->ev0, s));
+    for (int i = 0; i < (n > 0 ? n : 1); i++) {
+        AtrousArgs a = atrous_args(p, W, H, i);
+        a.C = (const float *)d_accum; a.A = (const float *)d_albedo; a.N = (const float *)d_normal; a.D = (const float *)d_depth;
+        a.e_in = (i & 1) ? e1 : e0; a.e_out = (i & 1) ? e0 : e1; a.g0 = g0; a.g1 = g1;
+        a.accum_out = (float *)d_accum_out; a.rgba_out = (uchar4 *)d_rgba_out;
+        const bool first = i == 0, last = i == n - 1;
+        if (n == 0) hipLaunchKernelGGL(atrous_passthrough_kernel, grid, block, 0, s, a);
+        else if (first && last) hipLaunchKernelGGL((atrous_kernel<true, true>), grid, block, 0, s, a);
+        else if (first) hipLaunchKernelGGL((atrous_kernel<true, false>), grid, block, 0, s, a);
+        else if (last) hipLaunchKernelGGL((atrous_kernel<false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((atrous_kernel<false, false>), grid, block, 0, s, a);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (seconds) {
+        HIPCHK(c, hipEventRecord(c->ev1, s));
+        HIPCHK(c, hipEventSynchronize(c->ev1));
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *seconds = ms * 1e-3;
+    }
+    return MORT_OK;
+}
+
+extern "C" int mort_hip_denoise(mort_ctx *c, const mort_denoise_params *p, int W, int H, const float *accum, const float *albedo,
+                                const float *normal, const float *depth, float *accum_out, uint8_t *rgba_out, double *seconds) {
+    if (!c || !params_ok(p) || !accum || !albedo || !normal || !depth) return MORT_ERR_INVALID;
+    if (W <= 0 || H <= 0) return MORT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, dn_switch_stream(c, c->stream));
+    const size_t npx = (size_t)W * (size_t)H;
+    /* C, A, N (3 floats each), D, accum_out (3 floats), rgba (4 bytes) */
+    int st = grow(c, &c->d_dnio, &c->dnio_cap, npx * 15 * sizeof(float));
+    if (st != MORT_OK) return st;
+    float *dC = (float *)c->d_dnio, *dA = dC + 3 * npx, *dN = dA + 3 * npx, *dD = dN + 3 * npx, *dO = dD + npx;
+    uint8_t *dR = (uint8_t *)(dO + 3 * npx);
+    HIPCHK(c, hipMemcpy(dC, accum, npx * 12, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dA, albedo, npx * 12, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dN, normal, npx * 12, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dD, depth, npx * 4, hipMemcpyHostToDevice));
+    double sec = 0;
+    if ((st = mort_hip_denoise_device(c, p, W, H, dC, dA, dN, dD, dO, dR, c->stream, &sec)) != MORT_OK) return st;
+    if (seconds) *seconds = sec;
+    if (accum_out) HIPCHK(c, hipMemcpy(accum_out, dO, npx * 12, hipMemcpyDeviceToHost));
+    if (rgba_out) HIPCHK(c, hipMemcpy(rgba_out, dR, npx * 4, hipMemcpyDeviceToHost));
+    return MORT_OK;
+}
+
+extern "C" int mort_hip_denoise_host(const mort_denoise_params *p, int W, int H, int nthreads, const float *accum, const float *albedo,
+                                     const float *normal, const float *depth, float *accum_out, uint8_t *rgba_out, double *seconds) {
+    if (!params_ok(p) || !accum || !albedo || !normal || !depth) return MORT_ERR_INVALID;
+    if (W <= 0 || H <= 0) return MORT_ERR_INVALID;
+    const size_t npx = (size_t)W * (size_t)H;
+    const int n = p->iterations;
+    std::vector<float4> buf(n > 1 ? npx * 4 : 0);
+    float4 *e0 = buf.data(), *e1 = e0 ? e0 + npx : nullptr, *g0 = e1 ? e1 + npx : nullptr, *g1 = g0 ? g0 + npx : nullptr;
+    const double t0 = now_s();
+    for (int i = 0; i < (n > 0 ? n : 1); i++) {
+        DnHostJob job;
+        job.a = atrous_args(p, W, H, i);
+        job.a.C = accum; job.a.A = albedo; job.a.N = normal; job.a.D = depth;
+        job.a.e_in = (i & 1) ? e1 : e0; job.a.e_out = (i & 1) ? e0 : e1; job.a.g0 = g0; job.a.g1 = g1;
+        job.a.accum_out = accum_out; job.a.rgba_out = (uchar4 *)rgba_out;
+        job.pass = n == 0; job.first = i == 0; job.last = i == n - 1;
+        run_rows(H, nthreads, dn_host_row, &job);
+    }
+    if (seconds) *seconds = now_s() - t0;
+    return MORT_OK;
+}

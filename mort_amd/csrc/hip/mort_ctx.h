@@ -89,6 +89,12 @@ struct mort_ctx {
     /* mort_hip_render_gather: the render's statistics are collected after the gather's one host wait */
     bool defer_stats = false;
     std::function<int(mort_stats *)> pending_stats;
+    /* feature pass and denoiser (denoise.hip): their own scratch, nothing the render keeps across frames */
+    void *d_feat = nullptr;          /* mort_hip_render_features: packed albedo / normal / depth of the owned rows */
+    void *d_dn = nullptr;            /* the filter's float4 buffers: colour ping-pong, (normal, depth), albedo */
+    void *d_dnio = nullptr;          /* mort_hip_denoise: the host buffers' device copies */
+    size_t feat_cap = 0, dn_cap = 0, dnio_cap = 0;
+    hipStream_t dn_stream = nullptr; /* stream of the last feature / denoise launch */
 };
 
 static inline int hip_fail(mort_ctx *c, hipError_t e, const char *what) {

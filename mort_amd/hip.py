@@ -27,6 +27,8 @@ EXPORTS = [
     "mort_hip_render_device", "mort_hip_local_rows", "mort_hip_global_row", "mort_hip_rng_seed_host", "mort_hip_render_host",
     "mort_hip_comm_id", "mort_hip_comm_init", "mort_hip_comm_destroy", "mort_hip_render_gather", "mort_hip_comm_selftest",
     "mort_hip_calib_valu", "mort_hip_calib_hbm_copy",
+    "mort_hip_denoise_defaults", "mort_hip_render_features", "mort_hip_render_features_device", "mort_hip_denoise",
+    "mort_hip_denoise_device", "mort_hip_render_features_host", "mort_hip_denoise_host",
 ]
 HOST_TREE = 1
 
@@ -51,6 +53,21 @@ class CalibValu(C.Structure):
     _fields_ = [("waves_per_simd", C.c_int), ("kind", C.c_int), ("seconds", C.c_double), ("cycles_per_wave", C.c_double),
                 ("clock_ghz", C.c_double), ("valu_per_wave", C.c_double), ("simds_seen", C.c_int), ("resident_waves_per_simd", C.c_double),
                 ("cycles_per_valu_per_wave", C.c_double), ("cycles_per_valu_per_simd", C.c_double)]
+
+
+class DenoiseParams(C.Structure):
+    """mort_denoise_params: DenoiseParams() holds the tuned defaults (mort_hip_denoise_defaults); keyword arguments override them."""
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
+                ("normal_log2_power", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mort_hip_denoise_defaults(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class MortHipError(RuntimeError):
@@ -90,6 +107,16 @@ def lib():
         L.mort_hip_render_host.restype = C.c_int
         L.mort_hip_calib_valu.argtypes = [ctx, C.c_int, C.c_int, C.POINTER(CalibValu)]; L.mort_hip_calib_valu.restype = C.c_int
         L.mort_hip_calib_hbm_copy.argtypes = [ctx, C.c_size_t, C.c_int, C.POINTER(C.c_double)]; L.mort_hip_calib_hbm_copy.restype = C.c_int
+        vp, dp, fp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(DenoiseParams)
+        L.mort_hip_denoise_defaults.argtypes = [fp]; L.mort_hip_denoise_defaults.restype = C.c_int
+        L.mort_hip_render_features.argtypes = [ctx, C.POINTER(S.Camera), vp, vp, vp, dp]; L.mort_hip_render_features.restype = C.c_int
+        L.mort_hip_render_features_device.argtypes = [ctx, C.POINTER(S.Camera), vp, vp, vp, vp, dp]
+        L.mort_hip_render_features_device.restype = C.c_int
+        L.mort_hip_denoise.argtypes = [ctx, fp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_denoise.restype = C.c_int
+        L.mort_hip_denoise_device.argtypes = [ctx, fp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_denoise_device.restype = C.c_int
+        L.mort_hip_render_features_host.argtypes = [C.POINTER(S.World), C.POINTER(S.Camera), C.c_int, C.c_int, vp, vp, vp, dp]
+        L.mort_hip_render_features_host.restype = C.c_int
+        L.mort_hip_denoise_host.argtypes = [fp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_denoise_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -163,6 +190,61 @@ class Context:
                                                C.byref(st) if sync else None), "mort_hip_render_device")
         return st.asdict() if sync else None
 
+    def render_features(self, cam):
+        """First-hit feature buffers of the owned rows (full-size arrays, other rows stay zero): albedo (H, W, 3), normal (H, W, 3),
+        depth (H, W) -- depth 0 = no hit.  Needs an uploaded world, no RNG."""
+        W, H = cam.image_width, cam.image_height
+        f = _feature_arrays(W, H)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_render_features(self._h, C.byref(cam), f["albedo"].ctypes.data, f["normal"].ctypes.data,
+                                                 f["depth"].ctypes.data, C.byref(sec)), "mort_hip_render_features")
+        f["seconds"] = sec.value
+        return f
+
+    def render_features_device(self, cam, albedo, normal, depth, sync=False):
+        """Feature pass into torch tensors on this context's device (packed owned rows: local_rows * W * 3 / * 3 / * 1 float32),
+        on the current torch stream.  Asynchronous unless sync (then returns the device seconds) or torch runs on its legacy default stream."""
+        import torch
+        lr = self.local_rows(cam.image_height)
+        _check_tensors(torch, ((albedo, 3), (normal, 3), (depth, 1)), lr * cam.image_width)
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, albedo.device, sync)
+        self._chk(lib().mort_hip_render_features_device(self._h, C.byref(cam), albedo.data_ptr(), normal.data_ptr(), depth.data_ptr(),
+                                                        stream, C.byref(sec) if sync else None), "mort_hip_render_features_device")
+        return sec.value if sync else None
+
+    def denoise(self, accum, albedo, normal, depth, params=None):
+        """A-trous denoise of full-image host arrays on the GPU: dict(accum (H, W, 3) f32, rgba (H, W, 4) u8, seconds)."""
+        params = params if params is not None else DenoiseParams()
+        H, W = np.asarray(depth).shape[:2]
+        ins = [np.ascontiguousarray(a, dtype=np.float32) for a in (accum, albedo, normal, depth)]
+        out_acc = np.zeros((H, W, 3), dtype=np.float32)
+        rgba = np.zeros((H, W, 4), dtype=np.uint8)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_denoise(self._h, C.byref(params), W, H, *[a.ctypes.data for a in ins], out_acc.ctypes.data,
+                                         rgba.ctypes.data, C.byref(sec)), "mort_hip_denoise")
+        return dict(accum=out_acc, rgba=rgba, seconds=sec.value)
+
+    def denoise_device(self, width, height, accum, albedo, normal, depth, accum_out=None, rgba_out=None, params=None, sync=False):
+        """The denoiser on torch tensors of the whole image (float32: W*H*3, *3, *3, *1; rgba_out uint8 W*H*4), on the current torch
+        stream.  Outputs may be None.  Asynchronous unless sync (then returns
+        the device seconds) or torch runs on its legacy default stream."""
+        import torch
+        params = params if params is not None else DenoiseParams()
+        n = width * height
+        _check_tensors(torch, ((accum, 3), (albedo, 3), (normal, 3), (depth, 1)), n)
+        if accum_out is not None:
+            _check_tensors(torch, ((accum_out, 3),), n)
+        if rgba_out is not None:
+            assert rgba_out.dtype == torch.uint8 and rgba_out.is_contiguous() and rgba_out.numel() == 4 * n and rgba_out.device == accum.device
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, accum.device, sync)
+        self._chk(lib().mort_hip_denoise_device(self._h, C.byref(params), width, height, accum.data_ptr(), albedo.data_ptr(), normal.data_ptr(),
+                                                depth.data_ptr(), accum_out.data_ptr() if accum_out is not None else None,
+                                                rgba_out.data_ptr() if rgba_out is not None else None,
+                                                stream, C.byref(sec) if sync else None), "mort_hip_denoise_device")
+        return sec.value if sync else None
+
     def calib_valu(self, waves_per_simd, kind=0):
         """Shader cycles one SIMD needs per wave64 VALU instruction at `waves_per_simd` resident waves (include/mort_hip.h)."""
         r = CalibValu()
@@ -200,3 +282,55 @@ def render_host(world, cam, states=None, seed=S.DEFAULT_SEED, nthreads=1, tree=F
     if rc != 0:
         raise MortHipError(rc, "mort_hip_render_host")
     return dict(rgba=rgba, accum=accum, segments_px=seg, stats=stt.asdict(), states=st8)
+
+
+def _feature_arrays(W, H):
+    return dict(albedo=np.zeros((H, W, 3), dtype=np.float32), normal=np.zeros((H, W, 3), dtype=np.float32),
+                depth=np.zeros((H, W), dtype=np.float32))
+
+
+def _torch_stream(torch, device, sync):
+    """(stream handle for the C ABI, sync).  torch's legacy default stream has handle 0, which the ABI reads as "the context's
+    stream" (a non-blocking one): the call then waits for torch's queued work first and is made blocking."""
+    s = torch.cuda.current_stream(device).cuda_stream
+    if s:
+        return s, sync
+    torch.cuda.current_stream(device).synchronize()
+    return None, True
+
+
+def _check_tensors(torch, pairs, npx):
+    dev = pairs[0][0].device
+    for t, ch in pairs:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != ch * npx or t.device != dev or t.device.type != "cuda":
+            raise ValueError(f"expected a contiguous float32 tensor of {ch * npx} elements on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def render_features_host(world, cam, nthreads=1, tree=False):
+    """The feature pass as a host loop (mort_hip_render_features_host), no GPU: dict(albedo, normal, depth, seconds)."""
+    W, H = cam.image_width, cam.image_height
+    f = _feature_arrays(W, H)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_render_features_host(world.ptr, C.byref(cam), nthreads, HOST_TREE if tree else 0, f["albedo"].ctypes.data,
+                                             f["normal"].ctypes.data, f["depth"].ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_render_features_host")
+    f["seconds"] = sec.value
+    return f
+
+
+def denoise_host(accum, albedo, normal, depth, params=None, nthreads=1):
+    """The a-trous denoiser as a host loop (mort_hip_denoise_host), no GPU: dict(accum (H, W, 3) f32, rgba (H, W, 4) u8, seconds)."""
+    params = params if params is not None else DenoiseParams()
+    H, W = np.asarray(depth).shape[:2]
+    ins = [np.ascontiguousarray(a, dtype=np.float32) for a in (accum, albedo, normal, depth)]
+    for a, ch in zip(ins, (3, 3, 3, 1)):
+        assert a.size == W * H * ch
+    out_acc = np.zeros((H, W, 3), dtype=np.float32)
+    rgba = np.zeros((H, W, 4), dtype=np.uint8)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_denoise_host(C.byref(params), W, H, nthreads, *[a.ctypes.data for a in ins], out_acc.ctypes.data, rgba.ctypes.data,
+                                     C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_denoise_host")
+    return dict(accum=out_acc, rgba=rgba, seconds=sec.value)
