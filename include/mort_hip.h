@@ -199,6 +199,39 @@ int mort_hip_render_features_host(const mort_world *world, const mort_camera *ca
 int mort_hip_denoise_host(const mort_denoise_params *params, int width, int height, int nthreads, const float *accum, const float *albedo,
                           const float *normal, const float *depth, float *accum_out, uint8_t *rgba_out, double *seconds);
 
+/* ---- temporal accumulation across frames with camera reprojection (the reprojection / accumulation half of SVGF, Schied et al.,
+ * HPG 2017).  NOT parity.  Between the render and the denoiser: the frame's accumulators (W*H*3) and its features
+ * (normal W*H*3, depth W*H from mort_hip_render_features*) are blended with a caller-owned history of the frames before, seen from
+ * prev_cam (NULL = no history: a reset).  The frame weighs cam->sqrt_spp^2 effective samples.  A still camera (centre, viewport and
+ * size bit-identical to prev_cam's) reads each pixel's own history, misses included; a moved one reprojects the hit point into the
+ * previous frame and gathers the accepted bilinear taps (hit, depth within depth_tolerance, normal dot >= normal_min); a miss under
+ * motion starts over.  History: MORT_TEMPORAL_HISTORY_FLOATS floats per pixel as three float4 planes (16-byte aligned) of W*H,
+ * plane k at k*W*H*4 floats, row 0 = bottom: (mu.rgb, n), (mean L, mean L^2, frames, depth), (normal, 0).  hist_in and hist_out
+ * must not alias.  Outputs: accum_out = the accumulated colour (what mort_hip_denoise* takes as accum), rgba_out = its gamma tail,
+ * variance_out (W*H) = the estimated variance of the accumulated luminance mean, -1 with fewer than 2 frames.  accum_out,
+ * variance_out and rgba_out may be NULL; outputs must not alias inputs.  Whole image, whatever the context's partition.  None of
+ * these calls draws a random number or touches what the render keeps across frames. ---- */
+#define MORT_TEMPORAL_HISTORY_FLOATS 12
+typedef struct mort_temporal_params {
+    int max_samples;         /* cap on the accumulated effective samples, still camera; 0 = unbounded */
+    int motion_max_samples;  /* the same after a reprojection; 0 = unbounded */
+    float depth_tolerance;   /* a history tap counts if |D_q - |X - c'|| <= depth_tolerance * |X - c'|; 0..1 */
+    float normal_min;        /* ... and N_p . N_q >= normal_min; -1..1 */
+} mort_temporal_params;
+int mort_hip_temporal_defaults(mort_temporal_params *params);
+/* host buffers; the kernel's HIP-event time in *seconds */
+int mort_hip_temporal(mort_ctx *ctx, const mort_temporal_params *params, const mort_camera *prev_cam, const mort_camera *cam, int width,
+                      int height, const float *accum, const float *normal, const float *depth, const float *hist_in, float *hist_out,
+                      float *accum_out, float *variance_out, uint8_t *rgba_out, double *seconds);
+/* the same on DEVICE buffers, on `stream` (NULL = the context's); asynchronous when seconds is NULL */
+int mort_hip_temporal_device(mort_ctx *ctx, const mort_temporal_params *params, const mort_camera *prev_cam, const mort_camera *cam,
+                             int width, int height, const void *d_accum, const void *d_normal, const void *d_depth, const void *d_hist_in,
+                             void *d_hist_out, void *d_accum_out, void *d_variance_out, void *d_rgba_out, void *stream, double *seconds);
+/* host loop of the same body: no GPU, no HIP runtime call */
+int mort_hip_temporal_host(const mort_temporal_params *params, const mort_camera *prev_cam, const mort_camera *cam, int width, int height,
+                           int nthreads, const float *accum, const float *normal, const float *depth, const float *hist_in, float *hist_out,
+                           float *accum_out, float *variance_out, uint8_t *rgba_out, double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

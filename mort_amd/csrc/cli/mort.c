@@ -10,6 +10,7 @@
  *                   [--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth img] [--rtl] [--device K]
  *                   [--keys WASD..] [--mouse dx,dy]        the reference's interactive loop, scripted: one idle tick per frame
  *                   [--denoise] [--features-out PREFIX]   first-hit features + a-trous denoiser on the last frame (single GPU / host)
+ *                   [--temporal] [--variance-out F]       temporal accumulation across frames with reprojection (single GPU / host)
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -17,6 +18,10 @@
  * --denoise: after the last frame, the feature pass for its camera and the a-trous denoiser (default parameters) over its
  * accumulators; --out then holds the denoised image (--dump-f32 stays the raw render) and the JSON line gains "denoise_seconds".
  * --features-out P writes P.albedo.f32, P.normal.f32, P.depth.f32 (W*H*3 / *3 / *1 floats, row 0 = bottom row).
+ * --temporal: after every frame, the feature pass for its camera and one temporal step (default parameters; the previous frame's
+ * camera, none for frame 0); --out then holds the accumulated image of the last frame, --denoise filters the accumulated colour
+ * with the last frame's features, --dump-f32 stays the raw render, and the JSON line gains "temporal_seconds" (features + temporal,
+ * summed over frames).  --variance-out F writes the last step's variance estimate (W*H floats, -1 = unknown).
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -60,7 +65,7 @@ static int usage(void) {
     printf("Usage: mort <number_between_1_and_10> [--width W] [--aspect A] [--spp N] [--depth D] [--seed S] [--frames N] "
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
-           "[--denoise] [--features-out PREFIX]\n");
+           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F]\n");
     return -1;
 }
 
@@ -101,8 +106,8 @@ int main(int argc, char **argv) {
     int gpus = 1, gather_shm = 0, devices[64], n_devices = 0;
     double aspect = 0;
     unsigned long long seed = MORT_DEFAULT_SEED;
-    const char *out = NULL, *dump = NULL, *sin = NULL, *sout = NULL, *earth = NULL, *keys = NULL, *feat_out = NULL;
-    int denoise = 0;
+    const char *out = NULL, *dump = NULL, *sin = NULL, *sout = NULL, *earth = NULL, *keys = NULL, *feat_out = NULL, *var_out = NULL;
+    int denoise = 0, temporal = 0;
     int mouse_dx = 0, mouse_dy = 0;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
@@ -138,12 +143,16 @@ int main(int argc, char **argv) {
         else if (strcmp(argv[i], "--tree") == 0) tree = 1;
         else if (strcmp(argv[i], "--denoise") == 0) denoise = 1;
         else if (ARG("--features-out")) feat_out = argv[++i];
+        else if (strcmp(argv[i], "--temporal") == 0) temporal = 1;
+        else if (ARG("--variance-out")) var_out = argv[++i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
     if (host_mode && gpus != 1) { fprintf(stderr, "--mode host runs on the host: --gpus does not apply\n"); return -1; }
     if (gpus > 1 && (dump || sin || sout)) { fprintf(stderr, "--dump-f32 / --states-in / --states-out are single-GPU options\n"); return -1; }
     if (gpus > 1 && (denoise || feat_out)) { fprintf(stderr, "--denoise / --features-out are single-GPU options\n"); return -1; }
+    if (gpus > 1 && (temporal || var_out)) { fprintf(stderr, "--temporal / --variance-out are single-GPU options\n"); return -1; }
+    if (var_out && !temporal) { fprintf(stderr, "--variance-out needs --temporal\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;
@@ -207,8 +216,21 @@ int main(int argc, char **argv) {
     }
 
     uint8_t *rgba = calloc(npx, 4);
-    float *accum = (dump || denoise) ? calloc(npx * 3, sizeof(float)) : NULL;
-    if (!rgba || ((dump || denoise) && !accum)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    const int want_accum = dump || denoise || temporal;
+    float *accum = want_accum ? calloc(npx * 3, sizeof(float)) : NULL;
+    if (!rgba || (want_accum && !accum)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    /* --temporal: this frame's features (albedo unused), the ping-ponged history, the accumulated colour and the variance */
+    float *alb = NULL, *nrm = NULL, *dep = NULL, *hist[2] = {NULL, NULL}, *tacc = NULL, *tvar = NULL;
+    mort_camera prev_cam;
+    mort_temporal_params tp;
+    mort_hip_temporal_defaults(&tp);
+    double temporal_sec = 0;
+    if (temporal) {
+        alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
+        tacc = malloc(npx * 3 * sizeof(float)); tvar = malloc(npx * sizeof(float));
+        for (int k = 0; k < 2; k++) hist[k] = aligned_alloc(16, npx * MORT_TEMPORAL_HISTORY_FLOATS * sizeof(float));
+        if (!alb || !nrm || !dep || !tacc || !tvar || !hist[0] || !hist[1]) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    }
     mort_stats stats;
     memset(&stats, 0, sizeof stats);
     double total_ms = 0, frame_wall = 0;
@@ -229,6 +251,14 @@ int main(int argc, char **argv) {
             if ((st = mort_hip_render_host(&world, &cam, hstates, threads, tree ? MORT_HOST_TREE : 0, rgba, accum, NULL, &stats)) != MORT_OK) die(NULL, st, "mort_hip_render_host");
             total_ms += stats.seconds * 1e3;
             printf("Avg. time per frame: %3.1f ms\n", total_ms / (f + 1)); /* mort.cu:119 */
+            if (temporal) {
+                double fs = 0, ts = 0;
+                if ((st = mort_hip_render_features_host(&world, &cam, threads, tree ? MORT_HOST_TREE : 0, alb, nrm, dep, &fs)) != MORT_OK) die(NULL, st, "mort_hip_render_features_host");
+                if ((st = mort_hip_temporal_host(&tp, f ? &prev_cam : NULL, &cam, W, H, threads, accum, nrm, dep, f ? hist[(f + 1) & 1] : NULL, hist[f & 1],
+                                                 tacc, tvar, rgba, &ts)) != MORT_OK) die(NULL, st, "mort_hip_temporal_host");
+                temporal_sec += fs + ts;
+                prev_cam = cam;
+            }
         }
         frame_wall = stats.seconds;
     } else {
@@ -271,22 +301,36 @@ int main(int argc, char **argv) {
             frame_wall = now_s() - t0;
             total_ms += stats.seconds * 1e3;
             if (rank == 0) printf("Avg. time per frame: %3.1f ms\n", total_ms / (f + 1)); /* mort.cu:119 */
+            if (temporal) {
+                double fs = 0, ts = 0;
+                if ((st = mort_hip_render_features(ctx, &cam, alb, nrm, dep, &fs)) != MORT_OK) die(ctx, st, "mort_hip_render_features");
+                if ((st = mort_hip_temporal(ctx, &tp, f ? &prev_cam : NULL, &cam, W, H, accum, nrm, dep, f ? hist[(f + 1) & 1] : NULL, hist[f & 1],
+                                            tacc, tvar, rgba, &ts)) != MORT_OK) die(ctx, st, "mort_hip_temporal");
+                temporal_sec += fs + ts;
+                prev_cam = cam;
+            }
         }
     }
 
-    /* ---- --denoise / --features-out (single GPU or host mode): the last frame's camera; the PPM becomes the denoised image ---- */
+    /* ---- --denoise / --features-out (single GPU or host mode): the last frame's camera; the PPM becomes the denoised image.  With
+     * --temporal the features are the last step's and the denoiser filters the accumulated colour ---- */
     double denoise_sec = 0;
     if (denoise || feat_out) {
-        float *alb = malloc(npx * 3 * sizeof(float)), *nrm = malloc(npx * 3 * sizeof(float)), *dep = malloc(npx * sizeof(float));
-        if (!alb || !nrm || !dep) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+        if (!temporal) {
+            alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
+            if (!alb || !nrm || !dep) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+        }
         double fs = 0, ds = 0;
-        if (host_mode) { if ((st = mort_hip_render_features_host(&world, &cam, threads, tree ? MORT_HOST_TREE : 0, alb, nrm, dep, &fs)) != MORT_OK) die(NULL, st, "mort_hip_render_features_host"); }
-        else if ((st = mort_hip_render_features(ctx, &cam, alb, nrm, dep, &fs)) != MORT_OK) die(ctx, st, "mort_hip_render_features");
+        if (!temporal) { /* with --temporal: the last step's */
+            if (host_mode) { if ((st = mort_hip_render_features_host(&world, &cam, threads, tree ? MORT_HOST_TREE : 0, alb, nrm, dep, &fs)) != MORT_OK) die(NULL, st, "mort_hip_render_features_host"); }
+            else if ((st = mort_hip_render_features(ctx, &cam, alb, nrm, dep, &fs)) != MORT_OK) die(ctx, st, "mort_hip_render_features");
+        }
         if (denoise) {
+            const float *col = temporal ? tacc : accum;
             mort_denoise_params dp;
             mort_hip_denoise_defaults(&dp);
-            if (host_mode) { if ((st = mort_hip_denoise_host(&dp, W, H, threads, accum, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_denoise_host"); }
-            else if ((st = mort_hip_denoise(ctx, &dp, W, H, accum, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(ctx, st, "mort_hip_denoise");
+            if (host_mode) { if ((st = mort_hip_denoise_host(&dp, W, H, threads, col, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_denoise_host"); }
+            else if ((st = mort_hip_denoise(ctx, &dp, W, H, col, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(ctx, st, "mort_hip_denoise");
             denoise_sec = fs + ds;
         }
         if (feat_out) {
@@ -301,8 +345,13 @@ int main(int argc, char **argv) {
                 fclose(f);
             }
         }
-        free(alb); free(nrm); free(dep);
     }
+    if (var_out) {
+        FILE *f = fopen(var_out, "wb");
+        if (!f || fwrite(tvar, sizeof(float), npx, f) != npx) { fprintf(stderr, "cannot write %s\n", var_out); return EXIT_FAILURE; }
+        fclose(f);
+    }
+    free(alb); free(nrm); free(dep); free(tacc); free(tvar); free(hist[0]); free(hist[1]);
 
     /* ---- ranks other than 0 are done; rank 0 waits for them (their rows are in shm / were gathered) ---- */
     if (rank != 0) {
@@ -330,6 +379,7 @@ int main(int argc, char **argv) {
            (unsigned long long)stats.algorithmic_hbm_bytes, stats.algorithmic_hbm_bytes / stats.seconds / 1e9,
            stats.algorithmic_hbm_bytes / stats.seconds / 8e12, (unsigned long long)stats.reference_walks, stats.kernel_name);
     if (denoise) printf(", \"denoise_seconds\": %.6f", denoise_sec); /* feature pass + denoise, device time (host loops: wall time) */
+    if (temporal) printf(", \"temporal_seconds\": %.6f", temporal_sec); /* feature passes + temporal steps over all frames, likewise */
     printf("}\n");
     if (out && mort_write_ppm(out, rgba, W, H) != 0) { fprintf(stderr, "cannot write %s\n", out); return EXIT_FAILURE; }
     if (dump) {

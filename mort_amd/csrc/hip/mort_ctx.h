@@ -94,7 +94,10 @@ struct mort_ctx {
     void *d_dn = nullptr;            /* the filter's float4 buffers: colour ping-pong, (normal, depth), albedo */
     void *d_dnio = nullptr;          /* mort_hip_denoise: the host buffers' device copies */
     size_t feat_cap = 0, dn_cap = 0, dnio_cap = 0;
-    hipStream_t dn_stream = nullptr; /* stream of the last feature / denoise launch */
+    hipStream_t dn_stream = nullptr; /* stream of the last feature / denoise / temporal launch */
+    /* temporal accumulation (temporal.hip): mort_hip_temporal's device copies of the host buffers */
+    void *d_tio = nullptr;
+    size_t tio_cap = 0;
 };
 
 static inline int hip_fail(mort_ctx *c, hipError_t e, const char *what) {

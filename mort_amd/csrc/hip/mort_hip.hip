@@ -222,7 +222,7 @@ extern "C" void mort_hip_shutdown(mort_ctx *c) {
     hipFree(c->d_substates); hipFree(c->d_vaccum);
     hipFree(c->d_rgba); hipFree(c->d_accum); hipFree(c->d_segpx); hipFree(c->d_counters); hipFree(c->d_wf);
     hipFree(c->d_tile_cost); hipFree(c->d_tile_order); hipFree(c->d_probe_states); hipFree(c->d_deep); hipFree(c->d_wave_log);
-    hipFree(c->d_feat); hipFree(c->d_dn); hipFree(c->d_dnio);
+    hipFree(c->d_feat); hipFree(c->d_dn); hipFree(c->d_dnio); hipFree(c->d_tio);
     if (c->h_live) hipHostFree(c->h_live);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);

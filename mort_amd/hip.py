@@ -29,7 +29,9 @@ EXPORTS = [
     "mort_hip_calib_valu", "mort_hip_calib_hbm_copy",
     "mort_hip_denoise_defaults", "mort_hip_render_features", "mort_hip_render_features_device", "mort_hip_denoise",
     "mort_hip_denoise_device", "mort_hip_render_features_host", "mort_hip_denoise_host",
+    "mort_hip_temporal_defaults", "mort_hip_temporal", "mort_hip_temporal_device", "mort_hip_temporal_host",
 ]
+TEMPORAL_HISTORY_FLOATS = 12
 HOST_TREE = 1
 
 
@@ -63,6 +65,20 @@ class DenoiseParams(C.Structure):
     def __init__(self, **kw):
         super().__init__()
         lib().mort_hip_denoise_defaults(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TemporalParams(C.Structure):
+    """mort_temporal_params: TemporalParams() holds the tuned defaults (mort_hip_temporal_defaults); keyword arguments override them."""
+    _fields_ = [("max_samples", C.c_int), ("motion_max_samples", C.c_int), ("depth_tolerance", C.c_float), ("normal_min", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mort_hip_temporal_defaults(C.byref(self))
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -117,6 +133,11 @@ def lib():
         L.mort_hip_render_features_host.argtypes = [C.POINTER(S.World), C.POINTER(S.Camera), C.c_int, C.c_int, vp, vp, vp, dp]
         L.mort_hip_render_features_host.restype = C.c_int
         L.mort_hip_denoise_host.argtypes = [fp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_denoise_host.restype = C.c_int
+        tp, cp = C.POINTER(TemporalParams), C.POINTER(S.Camera)
+        L.mort_hip_temporal_defaults.argtypes = [tp]; L.mort_hip_temporal_defaults.restype = C.c_int
+        L.mort_hip_temporal.argtypes = [ctx, tp, cp, cp, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_temporal.restype = C.c_int
+        L.mort_hip_temporal_device.argtypes = [ctx, tp, cp, cp, C.c_int, C.c_int] + [vp] * 9 + [dp]; L.mort_hip_temporal_device.restype = C.c_int
+        L.mort_hip_temporal_host.argtypes = [tp, cp, cp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_temporal_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -245,6 +266,40 @@ class Context:
                                                 stream, C.byref(sec) if sync else None), "mort_hip_denoise_device")
         return sec.value if sync else None
 
+    def temporal(self, prev_cam, cam, accum, normal, depth, hist_in, hist_out=None, params=None):
+        """One temporal step of full-image host arrays on the GPU (include/mort_hip.h): prev_cam None = reset (then hist_in must be
+        None).  hist_out (3, H, W, 4) f32 is filled in (allocated when None).  dict(accum (H, W, 3) f32, rgba (H, W, 4) u8,
+        variance (H, W) f32, history, seconds)."""
+        params = params if params is not None else TemporalParams()
+        ins, outs = _temporal_arrays(cam, accum, normal, depth, hist_in, hist_out)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_temporal(self._h, C.byref(params), C.byref(prev_cam) if prev_cam is not None else None, C.byref(cam),
+                                          cam.image_width, cam.image_height, *[_ptr(a) for a in ins], *[_ptr(a) for a in outs],
+                                          C.byref(sec)), "mort_hip_temporal")
+        return dict(history=outs[0], accum=outs[1], variance=outs[2], rgba=outs[3], seconds=sec.value)
+
+    def temporal_device(self, prev_cam, cam, accum, normal, depth, hist_in, hist_out, accum_out=None, variance_out=None, rgba_out=None,
+                        params=None, sync=False):
+        """One temporal step on torch tensors of the whole image (float32: W*H*3, *3, *1; history 12*W*H each; variance_out W*H;
+        rgba_out uint8 W*H*4), on the current torch stream.  Outputs other than hist_out may be None; hist_in None iff prev_cam None.
+        Asynchronous unless sync (then returns the device seconds) or torch runs on its legacy default stream."""
+        import torch
+        params = params if params is not None else TemporalParams()
+        n = cam.image_width * cam.image_height
+        pairs = ((accum, 3), (normal, 3), (depth, 1), (hist_in, TEMPORAL_HISTORY_FLOATS), (hist_out, TEMPORAL_HISTORY_FLOATS), (accum_out, 3),
+                 (variance_out, 1))
+        _check_tensors(torch, [(t, ch) for t, ch in pairs if t is not None], n)
+        if rgba_out is not None:
+            assert rgba_out.dtype == torch.uint8 and rgba_out.is_contiguous() and rgba_out.numel() == 4 * n and rgba_out.device == accum.device
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, accum.device, sync)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._chk(lib().mort_hip_temporal_device(self._h, C.byref(params), C.byref(prev_cam) if prev_cam is not None else None, C.byref(cam),
+                                                 cam.image_width, cam.image_height, ptr(accum), ptr(normal), ptr(depth), ptr(hist_in),
+                                                 ptr(hist_out), ptr(accum_out), ptr(variance_out), ptr(rgba_out), stream,
+                                                 C.byref(sec) if sync else None), "mort_hip_temporal_device")
+        return sec.value if sync else None
+
     def calib_valu(self, waves_per_simd, kind=0):
         """Shader cycles one SIMD needs per wave64 VALU instruction at `waves_per_simd` resident waves (include/mort_hip.h)."""
         r = CalibValu()
@@ -334,3 +389,100 @@ def denoise_host(accum, albedo, normal, depth, params=None, nthreads=1):
     if rc != 0:
         raise MortHipError(rc, "mort_hip_denoise_host")
     return dict(accum=out_acc, rgba=rgba, seconds=sec.value)
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def history_array(width, height):
+    """An empty temporal history: three float4 planes, (3, H, W, 4) float32."""
+    return np.zeros((3, height, width, 4), dtype=np.float32)
+
+
+def _temporal_arrays(cam, accum, normal, depth, hist_in, hist_out):
+    W, H = cam.image_width, cam.image_height
+    ins = [np.ascontiguousarray(a, dtype=np.float32) for a in (accum, normal, depth)]
+    for a, ch in zip(ins, (3, 3, 1)):
+        if a.size != W * H * ch:
+            raise ValueError(f"expected {W * H * ch} floats, got {a.size}")
+    if hist_in is not None:
+        hist_in = np.ascontiguousarray(hist_in, dtype=np.float32)
+        if hist_in.size != W * H * TEMPORAL_HISTORY_FLOATS:
+            raise ValueError("history of the wrong size")
+    if hist_out is None:
+        hist_out = history_array(W, H)
+    assert hist_out.dtype == np.float32 and hist_out.flags.c_contiguous and hist_out.size == W * H * TEMPORAL_HISTORY_FLOATS
+    outs = [hist_out, np.zeros((H, W, 3), dtype=np.float32), np.zeros((H, W), dtype=np.float32), np.zeros((H, W, 4), dtype=np.uint8)]
+    return ins + [hist_in], outs
+
+
+def temporal_host(prev_cam, cam, accum, normal, depth, hist_in, hist_out=None, params=None, nthreads=1):
+    """One temporal step as a host loop (mort_hip_temporal_host), no GPU: dict(accum, rgba, variance, history, seconds) as
+    Context.temporal."""
+    params = params if params is not None else TemporalParams()
+    ins, outs = _temporal_arrays(cam, accum, normal, depth, hist_in, hist_out)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_temporal_host(C.byref(params), C.byref(prev_cam) if prev_cam is not None else None, C.byref(cam), cam.image_width,
+                                      cam.image_height, nthreads, *[_ptr(a) for a in ins], *[_ptr(a) for a in outs], C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_temporal_host")
+    return dict(history=outs[0], accum=outs[1], variance=outs[2], rgba=outs[3], seconds=sec.value)
+
+
+class TemporalHistory:
+    """Frame-to-frame state of temporal accumulation: the two ping-ponged history buffers and the previous camera.
+
+    backend: None = the host loop (numpy arrays), a Context = its GPU (numpy arrays through mort_hip_temporal), or
+    ("device", ctx) = torch tensors on ctx's device (mort_hip_temporal_device on the current torch stream).  step() takes one
+    frame's accumulators and features and returns dict(accum, rgba, variance, samples) -- samples = the effective sample count
+    per pixel (H, W) -- as arrays / tensors of the backend; the returned buffers are reused by the next step."""
+
+    def __init__(self, width, height, params=None, backend=None, nthreads=1):
+        self.width, self.height = width, height
+        self.params = params if params is not None else TemporalParams()
+        self.backend, self.nthreads = backend, nthreads
+        self.device = isinstance(backend, tuple) and backend[0] == "device"
+        n = width * height
+        if self.device:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            z = lambda k, dt=torch.float32: torch.zeros(k, dtype=dt, device=dev)  # noqa: E731
+            self._hist = [z(TEMPORAL_HISTORY_FLOATS * n), z(TEMPORAL_HISTORY_FLOATS * n)]
+            self._out = dict(accum=z(3 * n), variance=z(n), rgba=z(4 * n, torch.uint8))
+        else:
+            self._hist = [history_array(width, height), history_array(width, height)]
+        self.prev_cam = None
+        self.frames = 0
+
+    def reset(self):
+        """Forget the history: the next step starts over."""
+        self.prev_cam = None
+        self.frames = 0
+
+    @property
+    def history(self):
+        """The history the last step wrote (three float4 planes)."""
+        return self._hist[0]
+
+    def step(self, accum, normal, depth, cam, sync=False):
+        """One frame; "seconds" in the result is the kernel's device time (host loop: wall time; device backend: None unless sync)."""
+        assert cam.image_width == self.width and cam.image_height == self.height
+        prev = self.prev_cam
+        hin, hout = (self._hist[0] if prev is not None else None), self._hist[1]
+        if self.device:
+            o = self._out
+            sec = self.backend[1].temporal_device(prev, cam, accum, normal, depth, hin, hout, accum_out=o["accum"], variance_out=o["variance"],
+                                                  rgba_out=o["rgba"], params=self.params, sync=sync)
+            r = dict(o, seconds=sec)
+            samples = hout.view(3, self.height, self.width, 4)[0, ..., 3]
+        else:
+            if self.backend is None:
+                r = temporal_host(prev, cam, accum, normal, depth, hin, hout, params=self.params, nthreads=self.nthreads)
+            else:
+                r = self.backend.temporal(prev, cam, accum, normal, depth, hin, hout, params=self.params)
+            samples = hout[0, ..., 3]
+        self._hist.reverse()
+        self.prev_cam = S.Camera.from_buffer_copy(cam)
+        self.frames += 1
+        return dict(accum=r["accum"], rgba=r["rgba"], variance=r["variance"], samples=samples, seconds=r["seconds"])

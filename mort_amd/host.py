@@ -58,6 +58,7 @@ def lib():
         L.mort_box.argtypes = [W, V, V, i, i]; L.mort_box.restype = None
         L.mort_rotated_box.argtypes = [W, V, V, f, i, i]; L.mort_rotated_box.restype = None
         L.mort_rotated_smoke_box.argtypes = [W, V, V, f, f, i, i]; L.mort_rotated_smoke_box.restype = None
+        L.mort_camera_input.argtypes = [Cam, C.c_int, C.c_int, C.c_int, C.c_int]; L.mort_camera_input.restype = None
         L.mort_write_ppm.argtypes = [C.c_char_p, C.c_void_p, i, i]; L.mort_write_ppm.restype = C.c_int
         _lib = L
     return _lib
@@ -170,6 +171,19 @@ def build_scene(scene_id, width=None, spp=None, depth=None, aspect=None, args_rt
         cam.aspect_ratio = float(aspect)
     lib().mort_camera_initialize(C.byref(cam))
     return w, cam
+
+
+KEYS = {"W": 1, "S": 2, "A": 4, "D": 8}
+
+
+def camera_input(cam, key=None, mouse=(0, 0)):
+    """One idle tick of the reference's input() on `cam` in place (mort_camera_input): `key` one of W / A / S / D held down (None or
+    '.' = none), `mouse` the (dx, dy) dragged with the left button -- what `mort --frames` does before each frame after the first."""
+    k = KEYS.get((key or ".").upper(), 0)
+    dx, dy = mouse
+    if k or dx or dy:
+        lib().mort_camera_input(C.byref(cam), k, int(dx), int(dy), 1 if (dx or dy) else 0)
+    return cam
 
 
 def effective_spp(cam):

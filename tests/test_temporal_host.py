@@ -1,0 +1,500 @@
+"""Temporal accumulation with camera reprojection through its host form -- the same per-pixel body the gfx950
+kernel runs (dev_temporal.h) -- on the CPU: an independent float64 numpy restatement of the contract on still, moved and
+rotated cameras, exact accumulation under a still camera, closed-form reprojections, the cap, parameter checks, the quality
+it reaches over a few frames, the variance estimate's calibration, the CLI flags and the new kernels' resources."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from mort_amd import hip, host
+from mort_amd import structs as S
+from tests.worlds import flat_camera, flat_world
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MORT = os.path.join(ROOT, "mort_amd", "bin", "mort")
+NT = min(16, os.cpu_count() or 1)
+
+
+def _v(v):
+    return np.array([v.e[0], v.e[1], v.e[2]], dtype=np.float64)
+
+
+def _copy(cam):
+    return S.Camera.from_buffer_copy(cam)
+
+
+def _moved(cam, key=None, mouse=(0, 0)):
+    return host.camera_input(_copy(cam), key, mouse)
+
+
+def _still(prev, cam):
+    f = ("center", "pixel00_loc", "pixel_delta_u", "pixel_delta_v")
+    return all((_v(getattr(prev, k)).astype(np.float32) == _v(getattr(cam, k)).astype(np.float32)).all() for k in f) and \
+        (prev.image_width, prev.image_height) == (cam.image_width, cam.image_height)
+
+
+# ---- the contract, restated in float64 (include/mort_hip.h) ----
+def ref_temporal(prev, cam, C, N, D, hin, p):
+    """(history (3, H, W, 4), accum (H, W, 3), variance (H, W), ambiguous (H, W)): `ambiguous` marks the pixels where a decision
+    (a tap's acceptance, the image border, the disocclusion threshold) lies within rounding of its boundary, so float32 and
+    float64 may take different branches there.  Which pixel a coordinate floors to is not one: a tap it adds or drops has a weight
+    within rounding of 0."""
+    C, N, D = (np.asarray(a, dtype=np.float64) for a in (C, N, D))
+    H, W = D.shape
+    C = np.where(np.isnan(C), 0.0, C)
+    L = 0.2126 * C[..., 0] + 0.7152 * C[..., 1] + 0.0722 * C[..., 2]
+    nc = float(cam.sqrt_spp ** 2)
+    h = np.zeros((H, W, 7))  # mu.rgb, n, m1, m2, f
+    spread = np.zeros((H, W, 7))  # max - min of the accepted taps' fields over their summed weight (moved camera)
+    amb = np.zeros((H, W), dtype=bool)
+    hit = D > 0
+    eps = 1e-5
+    still = prev is None or _still(prev, cam)
+    if prev is not None:
+        hin = np.asarray(hin, dtype=np.float64).reshape(3, H, W, 4)
+        fields = np.concatenate([hin[0], hin[1][..., :3]], axis=-1)
+        if still:
+            # the tests on the pixel's own float32 values, evaluated in float32 as the contract writes them: no rounding ambiguity
+            h32, N32, D32, f32 = hin.astype(np.float32), N.astype(np.float32), D.astype(np.float32), np.float32
+            Dq, Nq = h32[1][..., 3], h32[2][..., :3]
+            dot = N32[..., 0] * Nq[..., 0] + N32[..., 1] * Nq[..., 1] + N32[..., 2] * Nq[..., 2]
+            ok = (hit == (Dq > 0)) & (~hit | ((np.abs(Dq - D32) <= f32(p.depth_tolerance) * D32) & (dot >= f32(p.normal_min))))
+            h = np.where(ok[..., None], fields, 0.0)
+        else:
+            ys, xs = np.mgrid[0:H, 0:W]
+            # the feature pass's primary ray, whose direction is a float32 expression (get_ray: pixel00 + x du + y dv - centre)
+            c, p00, du, dv = (_v(getattr(cam, k)).astype(np.float32) for k in ("center", "pixel00_loc", "pixel_delta_u", "pixel_delta_v"))
+            f32 = np.float32
+            d = ((p00 + xs[..., None].astype(f32) * du) + ys[..., None].astype(f32) * dv - c).astype(np.float64)
+            X = c + D[..., None] * d / np.linalg.norm(d, axis=-1, keepdims=True)
+            pc, pp00, pdu, pdv = (_v(getattr(prev, k)) for k in ("center", "pixel00_loc", "pixel_delta_u", "pixel_delta_v"))
+            r = X - pc
+            dist = np.linalg.norm(r, axis=-1)
+            nrm = np.cross(pdu, pdv)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                t = (nrm @ (pp00 - pc)) / (r @ nrm)
+                front = hit & (t > 0)
+                e = t[..., None] * r + pc - pp00
+            G = np.array([[pdu @ pdu, pdu @ pdv], [pdu @ pdv, pdv @ pdv]])
+            ab = np.linalg.solve(G, np.stack([e @ pdu, e @ pdv], axis=-1)[..., None])[..., 0]
+            a, b = ab[..., 0], ab[..., 1]
+            inside = front & (a > -1) & (a < W) & (b > -1) & (b < H)
+            with np.errstate(invalid="ignore"):
+                amb |= front & ((np.abs(a + 1) < 1e-4) | (np.abs(a - W) < 1e-4) | (np.abs(b + 1) < 1e-4) | (np.abs(b - H) < 1e-4))
+            a, b = np.where(inside, a, 0.0), np.where(inside, b, 0.0)
+            x0, y0 = np.floor(a), np.floor(b)
+            fx, fy = a - x0, b - y0
+            s = np.zeros((H, W, 7))
+            sw = np.zeros((H, W))
+            lo, hi = np.full((H, W, 7), np.inf), np.full((H, W, 7), -np.inf)
+            for j in (0, 1):
+                for i in (0, 1):
+                    qx, qy = x0.astype(int) + i, y0.astype(int) + j
+                    inb = inside & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                    qx, qy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+                    Dq, Nq = hin[1][qy, qx, 3], hin[2][qy, qx, :3]
+                    dm = np.abs(Dq - dist) - p.depth_tolerance * dist
+                    nm = (N * Nq).sum(-1) - p.normal_min
+                    ok = inb & (Dq > 0) & (dm <= 0) & (nm >= 0)
+                    amb |= inb & (Dq > 0) & ((np.abs(dm) < eps * dist) | (np.abs(nm) < eps))
+                    w = (fx if i else 1 - fx) * (fy if j else 1 - fy)
+                    w = np.where(ok, w, 0.0)
+                    s += w[..., None] * fields[qy, qx]
+                    sw += w
+            amb |= np.abs(sw - 1e-3) < 1e-5
+            # the accepted taps within 1 + 1e-4 px of (a, b): those a rounding of the coordinate can give a weight
+            for j in range(-1, 3):
+                for i in range(-1, 3):
+                    qx, qy = x0.astype(int) + i, y0.astype(int) + j
+                    near = inside & (np.abs(qx - a) < 1 + 1e-4) & (np.abs(qy - b) < 1 + 1e-4) & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                    qx, qy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+                    Dq, Nq = hin[1][qy, qx, 3], hin[2][qy, qx, :3]
+                    ok = near & (Dq > 0) & (np.abs(Dq - dist) <= p.depth_tolerance * dist) & ((N * Nq).sum(-1) >= p.normal_min)
+                    lo = np.where(ok[..., None], np.minimum(lo, fields[qy, qx]), lo)
+                    hi = np.where(ok[..., None], np.maximum(hi, fields[qy, qx]), hi)
+            h = np.where((sw > 1e-3)[..., None], s / np.where(sw > 1e-3, sw, 1.0)[..., None], 0.0)
+            spread = np.where((sw > 1e-3)[..., None], (hi - lo) / np.where(sw > 1e-3, sw, 1.0)[..., None], 0.0)
+    cap = float(p.max_samples if still else p.motion_max_samples)
+    n, f = h[..., 3], h[..., 6]
+    if cap > 0:
+        over = (n > 0) & (n + nc > cap)
+        sc = np.where(over, np.maximum(0.0, cap - nc) / np.where(n > 0, n, 1.0), 1.0)
+        n, f = n * sc, f * sc
+    n1 = n + nc
+    mu = (n[..., None] * h[..., :3] + nc * C) / n1[..., None]
+    m1 = (n * h[..., 4] + nc * L) / n1
+    m2 = (n * h[..., 5] + nc * L * L) / n1
+    f1 = f + 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = np.where(f1 >= 2, np.maximum(0.0, m2 - m1 * m1) / (f1 - 1), -1.0)
+    hist = np.zeros((3, H, W, 4))
+    hist[0, ..., :3], hist[0, ..., 3] = mu, n1
+    hist[1, ..., 0], hist[1, ..., 1], hist[1, ..., 2], hist[1, ..., 3] = m1, m2, f1, D
+    hist[2, ..., :3] = N
+    return hist, mu, var, amb, spread
+
+
+def gamma_tail(acc):
+    v = np.clip(np.sqrt(acc.astype(np.float32)), np.float32(0), np.float32(0.999))
+    return (np.float32(256) * v).astype(np.int32).astype(np.uint8)
+
+
+def _history_for(cam, feats, seed):
+    """A plausible history seen from `cam`: random colours and moments, the camera's own features."""
+    g = np.random.default_rng(seed)
+    H, W = cam.image_height, cam.image_width
+    h = np.zeros((3, H, W, 4), dtype=np.float32)
+    h[0, ..., :3] = g.uniform(0, 2, (H, W, 3))
+    h[0, ..., 3] = g.choice([1.0, 4.0, 9.0, 16.0, 40.0], (H, W))
+    m1 = g.uniform(0, 1.5, (H, W))
+    h[1, ..., 0], h[1, ..., 1] = m1, m1 * m1 + g.uniform(0, 0.5, (H, W))
+    h[1, ..., 2] = g.integers(1, 6, (H, W))
+    h[1, ..., 3] = feats["depth"]
+    h[2, ..., :3] = feats["normal"]
+    return h
+
+
+def _check(prev, cam, C, N, D, hin, p, max_amb=0.05):
+    """The host loop against ref_temporal to 1e-5 relative.  After a move, a resampled value also carries the float32 rounding of
+    the reprojected coordinate (the ray's direction is rounded at world scale, and the pixel coordinate is a difference of
+    viewport-sized terms): up to ~2e-4 px, allowed as 5e-4 x the spread of the accepted taps' values over their summed weight."""
+    out = hip.temporal_host(prev, cam, C, N, D, hin, params=p, nthreads=NT)
+    hist, mu, var, amb, spread = ref_temporal(prev, cam, C, N, D, hin, p)
+    assert amb.mean() <= max_amb, amb.mean()
+    ok = ~amb
+    got = out["history"].astype(np.float64)
+    sp0, sp1 = spread[..., :4], np.concatenate([spread[..., 4:], np.zeros(spread.shape[:2] + (1,))], axis=-1)
+    # the cap scales f by cap' / n_h: a relative error of n_h carries over
+    capr = (5e-4 * spread[..., 3] / np.maximum(hist[0, ..., 3] - cam.sqrt_spp ** 2, 1.0))[..., None]
+    for k, sp in ((0, sp0), (1, sp1), (2, 0.0 * sp0)):
+        tol = 1e-5 * np.abs(hist[k]) + 5e-4 * sp + capr * np.abs(hist[k]) + 1e-6
+        assert (np.abs(got[k] - hist[k]) <= tol)[ok].all(), (k, np.abs(got[k] - hist[k])[ok].max())
+    assert (out["accum"] == out["history"][0, ..., :3]).all(), "accum_out is the history's colour"
+    m1, m2, f1 = hist[1, ..., 0], hist[1, ..., 1], hist[1, ..., 2]
+    vtol = 1e-4 * np.abs(var) + 1e-5 * np.abs(m2).max() + 5e-4 * (spread[..., 5] + 2 * np.abs(m1) * spread[..., 4] + np.abs(var) * spread[..., 6]) / np.maximum(f1 - 1, 1) + capr[..., 0] * np.abs(var)
+    assert (np.abs(out["variance"] - var) <= vtol)[ok].all()
+    assert ((out["variance"] == -1) == (var == -1))[ok].all()
+    assert (out["rgba"][..., :3] == gamma_tail(out["accum"])).all() and (out["rgba"][..., 3] == 255).all()
+    return out, hist, amb
+
+
+MOVES = {"still": (None, (0, 0)), "W": ("W", (0, 0)), "A": ("A", (0, 0)), "S": ("S", (0, 0)), "D": ("D", (0, 0)),
+         "drag": (None, (9, -5)), "D+drag": ("D", (-4, 3))}
+
+
+@pytest.mark.parametrize("move", sorted(MOVES))
+@pytest.mark.parametrize("sid", [1, 6])
+def test_temporal_matches_numpy(sid, move):
+    world, prev = host.build_scene(sid, width=64, spp=4)
+    key, mouse = MOVES[move]
+    cam = _moved(prev, key, mouse)
+    assert _still(prev, cam) == (move == "still")
+    fp = hip.render_features_host(world, prev, nthreads=NT)
+    fc = hip.render_features_host(world, cam, nthreads=NT)
+    hin = _history_for(prev, fp, sid)
+    g = np.random.default_rng(sid + 17)
+    C = g.uniform(0, 3, (cam.image_height, cam.image_width, 3)).astype(np.float32)
+    C[0, 0, 1] = np.nan  # the render's NaN guard
+    for p in (hip.TemporalParams(), hip.TemporalParams(max_samples=20, motion_max_samples=10, depth_tolerance=0.2, normal_min=0.5),
+              hip.TemporalParams(motion_max_samples=0, depth_tolerance=0.01, normal_min=-1.0)):
+        out, hist, amb = _check(prev, cam, C, fc["normal"], fc["depth"], hin, p)
+        if move != "still" and p.depth_tolerance > 0:
+            kept = (hist[0, ..., 3] > cam.sqrt_spp ** 2)[~amb]
+            assert kept.mean() > 0.2, f"almost no history survived the move ({kept.mean():.3f})"
+    # reset: no history at all
+    out, hist, amb = _check(None, cam, C, fc["normal"], fc["depth"], None, hip.TemporalParams())
+    assert (out["history"][0, ..., 3] == cam.sqrt_spp ** 2).all() and (out["history"][1, ..., 2] == 1).all() and (out["variance"] == -1).all()
+
+
+# ---- a still camera accumulates exactly: the sample-weighted mean of the frames ----
+def _frames(sid, cams, width=64, nthreads=NT):
+    world, _ = host.build_scene(sid, width=width, spp=4)
+    W, H = cams[0].image_width, cams[0].image_height
+    st = hip.seed_states_host(S.DEFAULT_SEED, W, H)
+    out = []
+    for c in cams:
+        r = hip.render_host(world, c, states=st, nthreads=nthreads)
+        st = r["states"]
+        out.append((r["accum"], hip.render_features_host(world, c, nthreads=nthreads)))
+    return world, out
+
+
+def _with_spp(cam, spp):
+    c = _copy(cam)
+    c.samples_per_pixel = spp
+    host.lib().mort_camera_initialize(__import__("ctypes").byref(c))
+    return c
+
+
+def test_still_camera_gives_the_sample_weighted_mean():
+    _, cam = host.build_scene(6, width=64, spp=4)
+    cams = [_with_spp(cam, (4, 4, 9, 4, 1, 4, 16, 4)[k]) for k in range(8)]
+    _, frames = _frames(6, cams)
+    th = hip.TemporalHistory(cam.image_width, cam.image_height, nthreads=NT)
+    num, den = 0.0, 0.0
+    for k, ((acc, f), c) in enumerate(zip(frames, cams)):
+        out = th.step(acc, f["normal"], f["depth"], c)
+        w = c.sqrt_spp ** 2
+        num, den = num + w * acc.astype(np.float64), den + w
+        np.testing.assert_allclose(out["accum"], num / den, rtol=1e-6, atol=1e-7)
+        assert (out["samples"] == den).all() and (th.history[1, ..., 2] == k + 1).all()
+    assert th.frames == 8
+
+
+# ---- closed-form reprojections ----
+def _view(cam, frm, at, vfov=40):
+    from tests.worlds import set_view
+    c = _copy(cam)
+    set_view(c, frm, at, vfov=vfov, defocus=0.0)
+    return c
+
+
+def _history_const(feats, n=4.0, colour=None):
+    H, W = feats["depth"].shape
+    h = np.zeros((3, H, W, 4), dtype=np.float32)
+    h[0, ..., :3] = 0.5 if colour is None else colour
+    h[0, ..., 3] = n
+    h[1, ..., 2] = 1
+    h[1, ..., 3] = feats["depth"]
+    h[2, ..., :3] = feats["normal"]
+    return h
+
+
+def test_fronto_parallel_quad_takes_the_predicted_pixel():
+    world, _ = flat_world([("quad", (-50, -50, -2), (100, 0, 0), (0, 100, 0), ("lamb", (.5, .5, .5)))])
+    prev = _view(flat_camera(width=64, spp=4), (0, 0, 2), (0, 0, -1))
+    cam = _moved(prev, "D")
+    assert np.allclose(_v(cam.center) - _v(prev.center), (1, 0, 0), atol=1e-6), "D moves one unit along u = +x"
+    fp = hip.render_features_host(world, prev, nthreads=NT)
+    fc = hip.render_features_host(world, cam, nthreads=NT)
+    H, W = fp["depth"].shape
+    assert (fp["depth"] > 0).all() and (fc["depth"] > 0).all()
+    xs = np.arange(W, dtype=np.float32)
+    hin = _history_const(fp, colour=0.0)
+    hin[0, ..., 0] = 0.01 * xs[None, :]                # red ramps linearly in x: bilinear interpolation is exact
+    hin[0, ..., 1] = 0.01 * np.arange(H)[:, None]      # green in y: the rows are bottom-first on both sides
+    C = np.zeros((H, W, 3), dtype=np.float32)
+    out = hip.temporal_host(prev, cam, C, fc["normal"], fc["depth"], hin, nthreads=NT)
+    # the point seen at pixel (x, y) is c + t d on z = -2; seen from the previous centre it projects to pixel x + shift
+    shift = (_v(cam.center)[0] - _v(prev.center)[0]) * (2 - _v(prev.pixel00_loc)[2]) / 4 / _v(prev.pixel_delta_u)[0]
+    a = xs + shift
+    inside = (a >= 0) & (a <= W - 1)
+    assert 5 < shift < W - 10 and inside.sum() > 10
+    nc = cam.sqrt_spp ** 2
+    got = out["history"]
+    h0 = got[0]
+    np.testing.assert_allclose(h0[:, inside, 3], np.full((H, inside.sum()), 4.0 + nc))
+    np.testing.assert_allclose(h0[:, inside, 0], np.broadcast_to(4 * 0.01 * a[inside] / (4 + nc), (H, inside.sum())), rtol=1e-4)
+    np.testing.assert_allclose(h0[:, inside, 1], np.broadcast_to((4 * 0.01 * np.arange(H) / (4 + nc))[:, None], (H, inside.sum())),
+                               rtol=1e-4, atol=1e-7)
+    assert (a >= W).any() and (h0[:, a >= W, 3] == nc).all(), "pixels that were outside the previous image start over"
+
+
+def test_sphere_in_front_of_a_wall_disoccludes():
+    world, _ = flat_world([("quad", (-50, -50, -3), (100, 0, 0), (0, 100, 0), ("lamb", (.5, .5, .5))),
+                           ("sphere", (0, 0, -1.5), 0.5, ("lamb", (.7, .3, .3)))])
+    prev = _view(flat_camera(width=96, spp=4), (0, 0, 2), (0, 0, -1))
+    cam = _moved(prev, "D")
+    fp = hip.render_features_host(world, prev, nthreads=NT)
+    fc = hip.render_features_host(world, cam, nthreads=NT)
+    H, W = fp["depth"].shape
+    out = hip.temporal_host(prev, cam, np.zeros((H, W, 3), np.float32), fc["normal"], fc["depth"], _history_const(fp), nthreads=NT)
+    n, nc = out["history"][0, ..., 3], cam.sqrt_spp ** 2
+    # where a wall pixel came from in the previous frame (the wall is z = -5 from the eye: a fixed shift)
+    ys, xs = np.mgrid[0:H, 0:W]
+    shift = (2 - _v(prev.pixel00_loc)[2]) / 5 / _v(prev.pixel_delta_u)[0]
+    a = xs + shift
+    wall_now = fc["albedo"][..., 0] == np.float32(.5)
+    on_sphere_before = fp["albedo"][..., 0] == np.float32(.7)
+    x0 = np.clip(np.floor(a).astype(int), 0, W - 2)
+    taps = np.stack([on_sphere_before[ys, x0], on_sphere_before[ys, x0 + 1]])
+    ok_a = (a >= 0) & (a <= W - 1)
+    uncovered = wall_now & ok_a & taps.all(0)
+    kept = wall_now & ok_a & ~taps.any(0)
+    assert uncovered.sum() > 5 and kept.sum() > 100
+    assert (n[uncovered] == nc).all(), "newly uncovered wall: no history"
+    assert (n[kept] == 4 + nc).all(), "wall away from the sphere keeps its history"
+
+
+def test_misses_under_motion_reset_and_the_cap_scales():
+    world, prev = host.build_scene(1, width=64, spp=4)
+    fp = hip.render_features_host(world, prev, nthreads=NT)
+    hin = _history_const(fp, n=16.0)
+    hin[1, ..., 2] = 4.0
+    H, W = fp["depth"].shape
+    C = np.ones((H, W, 3), np.float32)
+    cam = _moved(prev, None, (5, 0))
+    fc = hip.render_features_host(world, cam, nthreads=NT)
+    out = hip.temporal_host(prev, cam, C, fc["normal"], fc["depth"], hin, params=hip.TemporalParams(motion_max_samples=0), nthreads=NT)
+    miss = fc["depth"] == 0
+    assert miss.any() and (out["history"][0, ..., 3][miss] == 4).all() and (out["history"][1, ..., 2][miss] == 1).all()
+    assert (out["variance"][miss] == -1).all()
+    # still camera, cap 10: n_h = 16 scaled to 10 - 4 = 6, f_h = 4 by the same 6 / 16
+    out = hip.temporal_host(prev, prev, C, fp["normal"], fp["depth"], hin, params=hip.TemporalParams(max_samples=10), nthreads=NT)
+    np.testing.assert_allclose(out["history"][0, ..., 3], 10.0)
+    np.testing.assert_allclose(out["history"][1, ..., 2], 4.0 * 6 / 16 + 1, rtol=1e-6)
+    np.testing.assert_allclose(out["accum"], (6 * 0.5 + 4 * 1.0) / 10, rtol=1e-6)
+    # a cap below one frame keeps only the frame
+    out = hip.temporal_host(prev, prev, C, fp["normal"], fp["depth"], hin, params=hip.TemporalParams(max_samples=3), nthreads=NT)
+    assert (out["history"][0, ..., 3] == 4).all() and (out["accum"] == 1).all()
+    # moved: motion_max_samples applies
+    out = hip.temporal_host(prev, cam, C, fc["normal"], fc["depth"], hin, params=hip.TemporalParams(motion_max_samples=12), nthreads=NT)
+    assert out["history"][0, ..., 3].max() <= 12 + 1e-5 and (out["history"][0, ..., 3] > 4).any()
+
+
+def test_thread_counts_reset_and_parameter_checks():
+    import ctypes as C_
+    world, prev = host.build_scene(6, width=48, spp=4)
+    cam = _moved(prev, "W")
+    fp, fc = (hip.render_features_host(world, c, nthreads=NT) for c in (prev, cam))
+    hin = _history_for(prev, fp, 3)
+    g = np.random.default_rng(5)
+    acc = g.uniform(0, 2, fc["normal"].shape).astype(np.float32)
+    a = hip.temporal_host(prev, cam, acc, fc["normal"], fc["depth"], hin, nthreads=1)
+    b = hip.temporal_host(prev, cam, acc, fc["normal"], fc["depth"], hin, nthreads=NT)
+    for k in ("history", "accum", "variance", "rgba"):
+        assert (np.ascontiguousarray(a[k]).view(np.uint8) == np.ascontiguousarray(b[k]).view(np.uint8)).all(), k
+    r = hip.temporal_host(None, cam, acc, fc["normal"], fc["depth"], None, nthreads=NT)
+    assert (r["accum"] == acc).all() and (r["history"][0, ..., 3] == 4).all() and (r["variance"] == -1).all()
+    p = hip.TemporalParams()
+    assert (p.max_samples, p.motion_max_samples) == (0, 32) and abs(p.depth_tolerance - 0.02) < 1e-7 and abs(p.normal_min - 0.8) < 1e-7
+    for bad in (dict(max_samples=-1), dict(motion_max_samples=-5), dict(depth_tolerance=-0.1), dict(depth_tolerance=float("nan")),
+                dict(depth_tolerance=2.0), dict(normal_min=1.5), dict(normal_min=float("nan"))):
+        with pytest.raises(hip.MortHipError) as e:
+            hip.temporal_host(prev, cam, acc, fc["normal"], fc["depth"], hin, params=hip.TemporalParams(**bad))
+        assert e.value.status == -1
+    L, H, W = hip.lib(), cam.image_height, cam.image_width
+    hout = hip.history_array(W, H)
+    ptr = lambda x: x.ctypes.data  # noqa: E731
+    args = lambda pc, c, w, h, hi, ho: (C_.byref(p), pc, C_.byref(c), w, h, 4, ptr(acc), ptr(fc["normal"]), ptr(fc["depth"]), hi, ho,  # noqa: E731
+                                        None, None, None, None)
+    assert L.mort_hip_temporal_host(*args(C_.byref(prev), cam, W, H, ptr(hin), ptr(hout))) == 0
+    assert L.mort_hip_temporal_host(*args(C_.byref(prev), cam, W + 1, H, ptr(hin), ptr(hout))) == -1, "size differs from the camera"
+    small = _with_spp(prev, 4)
+    small.image_width = W - 8
+    host.lib().mort_camera_initialize(C_.byref(small))
+    assert L.mort_hip_temporal_host(*args(C_.byref(small), cam, W, H, ptr(hin), ptr(hout))) == -1, "previous camera of another size"
+    assert L.mort_hip_temporal_host(*args(None, cam, W, H, ptr(hin), ptr(hout))) == -1, "history without a previous camera"
+    assert L.mort_hip_temporal_host(*args(C_.byref(prev), cam, W, H, None, ptr(hout))) == -1, "previous camera without history"
+    assert L.mort_hip_temporal_host(*args(C_.byref(prev), cam, W, H, ptr(hin), ptr(hin))) == -1, "hist_in aliases hist_out"
+    assert L.mort_hip_temporal_host(*args(C_.byref(prev), cam, W, H, ptr(hin), ptr(hout) + 4)) == -1, "unaligned history"
+    assert L.mort_hip_temporal_defaults(None) == -1
+
+
+# ---- quality over 8 frames at 4 spp against 400 spp at the final camera (DESIGN.md 4.10 records the ratios) ----
+def _g(a):
+    return np.sqrt(np.clip(a, 0, 0.999 ** 2))
+
+
+def _sequence(sid, kind, frames=8, width=96, spp=4):
+    _, cam = host.build_scene(sid, width=width, spp=spp)
+    cams = [cam]
+    for _ in range(frames - 1):
+        cams.append(_moved(cams[-1], "D" if kind == "keys" else None, (3, 0) if kind == "mouse" else (0, 0)))
+    world, frames_ = _frames(sid, cams, width=width)
+    w2, _ = host.build_scene(sid, width=width, spp=400)
+    ref = hip.render_host(w2, _with_spp(cams[-1], 400), nthreads=NT)["accum"]
+    return world, cams, frames_, ref
+
+
+QUALITY = [(1, "still", 0.45), (3, "still", 0.45), (6, "still", 0.45),
+           (1, "keys", 0.82), (1, "mouse", 0.46), (3, "keys", 1.0), (3, "mouse", 0.96), (6, "keys", 0.37), (6, "mouse", 0.38)]
+
+
+@pytest.mark.parametrize("sid,kind,limit", QUALITY)
+def test_temporal_quality(sid, kind, limit):
+    world, cams, frames, ref = _sequence(sid, kind)
+    th = hip.TemporalHistory(cams[0].image_width, cams[0].image_height, nthreads=NT)
+    for (acc, f), c in zip(frames, cams):
+        out = th.step(acc, f["normal"], f["depth"], c)
+    e0 = np.sqrt(np.mean((_g(frames[-1][0]) - _g(ref)) ** 2))
+    e1 = np.sqrt(np.mean((_g(out["accum"]) - _g(ref)) ** 2))
+    assert e1 <= limit * e0, f"scene {sid} {kind}: accumulated RMSE {e1:.4f} vs one frame {e0:.4f} (ratio {e1 / e0:.3f})"
+    if sid == 6 and kind == "still":
+        f = frames[-1][1]
+        den_one = hip.denoise_host(frames[-1][0], f["albedo"], f["normal"], f["depth"], nthreads=NT)["accum"]
+        den_acc = hip.denoise_host(out["accum"], f["albedo"], f["normal"], f["depth"], nthreads=NT)["accum"]
+        e2 = np.sqrt(np.mean((_g(den_one) - _g(ref)) ** 2))
+        e3 = np.sqrt(np.mean((_g(den_acc) - _g(ref)) ** 2))
+        assert e3 < e2, f"temporal + denoise {e3:.4f} vs denoise alone {e2:.4f}"
+
+
+def test_variance_estimate_is_calibrated():
+    _, cam = host.build_scene(6, width=96, spp=1)
+    cams = [cam] * 16
+    world, frames = _frames(6, cams, width=96)
+    w2, _ = host.build_scene(6, width=96, spp=400)
+    ref = hip.render_host(w2, _with_spp(cam, 400), nthreads=NT)["accum"].astype(np.float64)
+    th = hip.TemporalHistory(cam.image_width, cam.image_height, nthreads=NT)
+    for acc, f in frames:
+        out = th.step(acc, f["normal"], f["depth"], cam)
+    lum = lambda c: 0.2126 * c[..., 0] + 0.7152 * c[..., 1] + 0.0722 * c[..., 2]  # noqa: E731
+    err = np.mean((lum(out["accum"].astype(np.float64)) - lum(ref)) ** 2)
+    est = float(out["variance"].mean())
+    assert (out["variance"] >= 0).all()
+    assert 0.5 * err <= est <= 2.0 * err, f"mean variance estimate {est:.3e} vs mean squared luminance error {err:.3e}"
+
+
+# ---- CLI ----
+def _run(*args, cwd):
+    return subprocess.run([MORT, *map(str, args)], cwd=cwd, capture_output=True, text=True, timeout=600)
+
+
+def test_cli_temporal_matches_the_python_chain(tmp_path):
+    p = _run(6, "--mode", "host", "--width", 64, "--spp", 4, "--frames", 4, "--keys", ".D.D", "--temporal", "--denoise", "--variance-out", "V",
+             "--out", "x.ppm", "--dump-f32", "raw.f32", "--threads", NT, cwd=tmp_path)
+    assert p.returncode == 0, p.stderr
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["temporal_seconds"] > 0 and line["denoise_seconds"] > 0
+    _, cam = host.build_scene(6, width=64, spp=4)
+    cams = [cam]
+    for k in ".D.":
+        cams.append(_moved(cams[-1], None if k == "." else k))
+    _, frames = _frames(6, cams)
+    th = hip.TemporalHistory(cam.image_width, cam.image_height, nthreads=NT)
+    for (acc, f), c in zip(frames, cams):
+        out = th.step(acc, f["normal"], f["depth"], c)
+    f = frames[-1][1]
+    den = hip.denoise_host(out["accum"], f["albedo"], f["normal"], f["depth"], nthreads=NT)
+    W, H = line["width"], line["height"]
+    data = open(tmp_path / "x.ppm", "rb").read()
+    img = np.frombuffer(data[len(data) - W * H * 3:], dtype=np.uint8).reshape(H, W, 3)
+    assert (img[::-1] == den["rgba"][..., :3]).all() or (img == den["rgba"][..., :3]).all()
+    assert (np.fromfile(tmp_path / "V", dtype=np.float32).view(np.uint32) == out["variance"].reshape(-1).view(np.uint32)).all()
+    raw = np.fromfile(tmp_path / "raw.f32", dtype=np.float32)
+    assert (raw.view(np.uint32) == frames[-1][0].reshape(-1).view(np.uint32)).all(), "--dump-f32 is the raw render"
+
+
+def test_cli_temporal_without_denoise_writes_the_accumulated_image(tmp_path):
+    p = _run(1, "--mode", "host", "--width", 48, "--spp", 4, "--frames", 3, "--temporal", "--out", "x.ppm", "--threads", NT, cwd=tmp_path)
+    assert p.returncode == 0, p.stderr
+    _, cam = host.build_scene(1, width=48, spp=4)
+    _, frames = _frames(1, [cam] * 3, width=48)
+    th = hip.TemporalHistory(cam.image_width, cam.image_height, nthreads=NT)
+    for acc, f in frames:
+        out = th.step(acc, f["normal"], f["depth"], cam)
+    W, H = cam.image_width, cam.image_height
+    data = open(tmp_path / "x.ppm", "rb").read()
+    img = np.frombuffer(data[len(data) - W * H * 3:], dtype=np.uint8).reshape(H, W, 3)
+    assert (img[::-1] == out["rgba"][..., :3]).all() or (img == out["rgba"][..., :3]).all()
+
+
+@pytest.mark.parametrize("flag", [["--temporal"], ["--temporal", "--variance-out", "V"]])
+def test_cli_rejects_temporal_with_several_gpus(tmp_path, flag):
+    p = _run(1, "--gpus", 2, "--gather", "shm", *flag, cwd=tmp_path)
+    assert p.returncode != 0 and "single-GPU" in p.stderr
+    assert not list(tmp_path.iterdir())
+
+
+def test_new_kernels_use_no_private_memory():
+    lib = os.path.join(ROOT, "mort_amd", "lib", "libmort_hip.so")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "kernel_resources.py"), lib], capture_output=True, text=True, check=True).stdout
+    rows = [l.split() for l in out.splitlines() if l.startswith("tacc_")]
+    assert {" ".join(r[:-7]) for r in rows} == {"tacc_kernel<false>", "tacc_kernel<true>"}
+    for r in rows:
+        vspill, sspill, private = int(r[-4]), int(r[-3]), int(r[-2])
+        assert vspill == 0 and sspill == 0 and private == 0, r
