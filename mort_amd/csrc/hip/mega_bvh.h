@@ -320,6 +320,10 @@ __device__ __attribute__((noinline)) void pixel_write(const FastArgs *fap, float
         const unsigned slot = 32u + 2u * (blockIdx.x & 31u);
         atomicAdd(&a.counters[slot], (unsigned long long)segments);
         atomicAdd(&a.counters[slot + 1u], (unsigned long long)draws);
+    } else { /* the probe's totals in the same slots: a cold frame's heavy-wave head is decided from them (tile_sort.hip heavy_count_kernel) */
+        const unsigned slot = 32u + 2u * (blockIdx.x & 31u);
+        atomicAdd(&a.counters[slot], (unsigned long long)segments);
+        atomicAdd(&a.counters[slot + 1u], (unsigned long long)draws);
     }
 }
 struct PixelFetch { int got; /* 0, or 1 + the stratum row (SUB) */ int xy /* x | y << 16 | priority pixel << 31 */, lofs; uint32_t d, v0, v1, v2, v3, v4; };

@@ -546,7 +546,7 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
         pa.tile_order = nullptr; pa.tile_cost = c->d_tile_cost;
         { const char *tk = std::getenv("MORT_TILE_KEY"); pa.tile_key_sum = (tk && std::strcmp(tk, "sum") == 0) ? 1 : 0; }
         HIPCHK(c, launch_probe(pa));
-        if (c->d_prio_count) HIPCHK(c, hipMemcpyAsync(c->d_prio_count + 4, c->d_counters, 96 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s)); /* the probe's counters (its segment total), beside its tile costs */
+        if (c->d_prio_count) HIPCHK(c, hipMemcpyAsync(c->d_prio_count + 4, c->d_counters, 96 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s)); /* the probe's counters (pixel_write<true> adds its segments to the per-workgroup slots), beside its tile costs */
         HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 96 * sizeof(unsigned long long), s)); /* probe totals and work cursor */
         c->cost_key = key;
     }
@@ -700,10 +700,11 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
         ga.f.hot_src = (const unsigned char *)c->d_gen; ga.f.hot_bytes = c->gen_bytes;
         ga.f.th_s = 32; ga.f.th_l = 24; ga.f.t_keep = 16; /* wf_trav_gen's retire+refill / leaf / box-run thresholds */
         { const char *th = std::getenv("MORT_WAVE_THRESHOLDS"); /* "f,l,k" */
-          if (th) { int f_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &f_, &l_, &k_) == 3) { ga.f.th_s = f_; ga.f.th_l = l_; ga.f.t_keep = k_; } } }
+          if (th) { int f_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &f_, &l_, &k_) == 3 && f_ >= 1 && l_ >= 1 && k_ >= 1) { ga.f.th_s = f_; ga.f.th_l = l_; ga.f.t_keep = k_; } } }
         if (!c->h_live) HIPCHK(c, hipHostMalloc((void **)&c->h_live, 64));
         WfGenHost hb;
-        hb.d_wf = &c->d_wf; hb.wf_bytes = &c->wf_bytes; hb.h_live = &c->h_live; hb.fronts = &c->wf_fronts; hb.num_cus = c->num_cus;
+        int trav_block = 0;
+        hb.d_wf = &c->d_wf; hb.wf_bytes = &c->wf_bytes; hb.h_live = &c->h_live; hb.fronts = &c->wf_fronts; hb.num_cus = c->num_cus; hb.trav_block = &trav_block;
         unsigned live_left = 0;
         hipError_t e_w = mort_wave_gen_render(ga, hb, cam->bounce_limit, cam->sqrt_spp, s, &live_left);
         if (e_w != hipSuccess) {
@@ -711,7 +712,7 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
             return hip_fail(c, e_w, "mort_wave_gen_render");
         }
         lds_bytes_used = (int)c->gen_bytes;
-        std::snprintf(kname, sizeof kname, "wf_trav_gen<%s>", ga.prims_in_lds ? "true" : "false");
+        std::snprintf(kname, sizeof kname, "wf_trav_gen<%d, %s>", trav_block, ga.prims_in_lds ? "true" : "false"); /* <BLOCK, PRIMS_LDS> */
     } else if (blocks > 0 && mode == MORT_MODE_WAVE) {
         int st_w = render_wavefront(c, a, cam, s);
         if (st_w != MORT_OK) return st_w;
@@ -776,7 +777,7 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
         {
             fa.th_s = MORT_TH_S; fa.th_l = MORT_TH_L; fa.t_keep = MORT_T_KEEP;
             const char *th = std::getenv("MORT_THRESHOLDS"); /* "s,l,k" */
-            if (th) { int s_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &s_, &l_, &k_) == 3) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; } }
+            if (th) { int s_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &s_, &l_, &k_) == 3 && s_ >= 1 && l_ >= 1 && k_ >= 1) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; } }
         }
         /* LDS: hot blob + as many bounce-stack levels per lane as fit next to it (768 threads: one workgroup per CU) */
         const uint32_t tstack_off = (fa.hot_bytes + 15u) & ~15u; /* traversal stacks: [levels][thread] u16 (four-wide: the world's own bound, at most MORT_OWN4_STACK) */
@@ -876,9 +877,10 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
           if (hv && !substream && std::sscanf(hv, "%d,%d,%d,%d", &m_, &n_, &k_, &p_) == 4 && m_ >= 1 && n_ >= 1 && n_ <= m_ && k_ >= 1 && k_ <= 64 && p_ >= 1 && p_ <= 100) {
               fa.heavy_mod = m_; fa.heavy_num = n_; fa.heavy_cap = k_; c->heavy_percent = p_; } }
         ga.drain_mode = 3; /* thresholds as shares of the live lanes; measured alternatives: 0 = fixed counts, 1 = follow one lane, 2 = rounds */
-        { const char *dm = std::getenv("MORT_GEN_DRAIN"); if (dm) ga.drain_mode = std::atoi(dm); }
+        { const char *dm = std::getenv("MORT_GEN_DRAIN"); if (dm && std::atoi(dm) >= 0 && std::atoi(dm) <= 3) ga.drain_mode = std::atoi(dm); } /* other values: the default */
+        /* thresholds below 1 are refused: with t_keep < 1 a box-step loop whose lanes have all left the tree would never end */
         { const char *th = std::getenv("MORT_GEN_THRESHOLDS"); /* "s,l,k,m" */
-          if (th) { int s_ = 0, l_ = 0, k_ = 0, m_ = 0; if (std::sscanf(th, "%d,%d,%d,%d", &s_, &l_, &k_, &m_) == 4) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; ga.th_m = m_; } } }
+          if (th) { int s_ = 0, l_ = 0, k_ = 0, m_ = 0; if (std::sscanf(th, "%d,%d,%d,%d", &s_, &l_, &k_, &m_) == 4 && s_ >= 1 && l_ >= 1 && k_ >= 1 && m_ >= 1) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; ga.th_m = m_; } } }
         const uint32_t tstack_off = (c->gen_bytes + 15u) & ~15u;
         const uint32_t stack_off = tstack_off + (uint32_t)MORT_OWN_STACK * (uint32_t)FB * 2u;
         fa.off_tstack = tstack_off;
@@ -891,7 +893,7 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
         if (room < 0) { c->last_error = "unified-tree image does not fit one CU's LDS"; return MORT_ERR_CAPACITY; }
         int dl = (int)(room / ((long long)FB * 16));
         if (dl > 12) dl = 12;
-        { const char *de = std::getenv("MORT_GEN_DL"); if (de && std::atoi(de) < dl) dl = std::atoi(de); }
+        { const char *de = std::getenv("MORT_GEN_DL"); if (de && std::atoi(de) < dl) dl = std::atoi(de) > 0 ? std::atoi(de) : 0; } /* a negative count would shrink the LDS below the traversal stacks */
         fa.off_stack = stack_off; fa.stack_lds_depth = dl;
         const size_t lds_bytes = (size_t)stack_off + (size_t)dl * FB * 16;
         int per_cu = mort_gen_blocks_per_cu(FB, ga.prims_in_lds != 0, lds_bytes, substream);

@@ -9,6 +9,7 @@
 
 struct WfGenHost { /* scratch owned by the context */
     void **d_wf; size_t *wf_bytes; unsigned **h_live; int *fronts; int num_cus;
+    int *trav_block; /* out: workgroup size of wf_trav_gen for this render, or null */
 };
 
 /* Renders the owned rows through fronts of (path id, ray) records: wf_init, then one wf_trav_gen + wf_shade_gen launch

@@ -516,6 +516,7 @@ hipError_t mort_wave_gen_render(const GenArgs &ga, const WfGenHost &hb, int boun
     w.cnt = (WfCounters *)(base + o_cnt);
 
     const int TB = trav_block_for(ga);
+    if (hb.trav_block) *hb.trav_block = TB;
     trav_kernel_t trav = pick_trav(TB, ga.prims_in_lds != 0);
     /* LDS of wf_trav_gen: image | traversal stacks | class staging */
     w.g.f.off_tstack = (ga.f.hot_bytes + 15u) & ~15u;

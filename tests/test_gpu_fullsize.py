@@ -4,6 +4,8 @@ properties instead -- different kernels (different traversals of different trees
 must agree BIT FOR BIT on image, fp32 accumulators, per-pixel segment counts and final XORWOW words, and a render must repeat
 itself.  The same kernels are compared with the oracle at small sizes in test_gpu_gen.py / test_gpu_parity.py; round 1's wrong ray
 showed up at 800x800 x 100 spp and at no test size, which is what these cases are for.  About 40 s of GPU time in all."""
+import re
+
 import numpy as np
 import pytest
 
@@ -107,23 +109,33 @@ def test_final_scene_workgroup_shapes_fill_the_chip(oracle, monkeypatch, block):
 
 
 @pytest.mark.parametrize("heavy", ["3,2,12,50", "1,1,4,100", "4,1,8,75", "2,1,1,30"])
-def test_final_scene_heavy_waves_do_not_reach_the_pixels(oracle, monkeypatch, heavy):
+def test_final_scene_heavy_waves_do_not_reach_the_pixels(oracle, monkeypatch, capfd, heavy):
     """Heavy waves (mega_bvh.h FastArgs.heavy_*: some waves take a few lanes' worth of pixels from the head of the cost order, the others start
     behind it; which tiles form the head is decided on the device) are scheduling only: the final scene 800x800 x 16 spp with them forced in
-    four shapes -- and a second frame, whose head comes from the first frame's costs instead of the probe's -- equals the launch without them."""
+    four shapes -- and a second frame, whose head comes from the first frame's costs instead of the probe's -- equals the launch without them.
+    MORT_GEN_HEAVY_DEBUG=1 prints the head the device chose ("[heavy] head tiles N of T"): it must be non-empty for the single frame
+    (costs from the probe) and for both frames below, else the comparison would check nothing."""
+    heads = lambda: [int(m.group(1)) for m in re.finditer(r"\[heavy\] head tiles (\d+) of ", capfd.readouterr().err)]
     world, cam = host.build_scene(8, width=800, spp=16)
     a = _render(world, cam, oracle, monkeypatch, env={"MORT_GEN_NO_HEAVY": "1"})
-    b = _render(world, cam, oracle, monkeypatch, env={"MORT_GEN_HEAVY": heavy, "MORT_GEN_BLOCK_SIZE": "1024"})
+    capfd.readouterr()
+    b = _render(world, cam, oracle, monkeypatch, env={"MORT_GEN_HEAVY": heavy, "MORT_GEN_BLOCK_SIZE": "1024", "MORT_GEN_HEAVY_DEBUG": "1"})
+    h = heads()
+    assert len(h) == 1 and h[0] > 0, f"single frame: heavy-wave head {h}"
     assert b["name"].startswith("mega_gen_kernel<1024"), b["name"]
     _same(a, b)
     W, H = cam.image_width, cam.image_height
-    for k, v in {"MORT_GEN_HEAVY": heavy, "MORT_GEN_BLOCK_SIZE": "1024"}.items():
+    for k, v in {"MORT_GEN_HEAVY": heavy, "MORT_GEN_BLOCK_SIZE": "1024", "MORT_GEN_HEAVY_DEBUG": "1"}.items():
         monkeypatch.setenv(k, v)
     with hip.Context(0) as ctx:  # two frames on one context: the streams continue, the second frame's order and head come from the first one's costs
         ctx.upload_world(world); ctx.rng_seed(S.DEFAULT_SEED, W, H)
+        capfd.readouterr()
         f1 = ctx.render(cam, want_accum=False, want_segments=True)
+        h1 = heads()
         f2 = ctx.render(cam, want_accum=False, want_segments=True)
-    monkeypatch.delenv("MORT_GEN_HEAVY"); monkeypatch.delenv("MORT_GEN_BLOCK_SIZE")
+        h2 = heads()
+    assert len(h1) == 1 and h1[0] > 0 and len(h2) == 1 and h2[0] > 0, f"heavy-wave heads of frames 1 and 2: {h1} {h2}"
+    monkeypatch.delenv("MORT_GEN_HEAVY"); monkeypatch.delenv("MORT_GEN_BLOCK_SIZE"); monkeypatch.delenv("MORT_GEN_HEAVY_DEBUG")
     monkeypatch.setenv("MORT_GEN_NO_HEAVY", "1")
     with hip.Context(0) as ctx:
         ctx.upload_world(world); ctx.rng_seed(S.DEFAULT_SEED, W, H)
