@@ -58,13 +58,6 @@ int rccl_fail(mort_ctx *c, ncclResult_t e, const char *what) {
 }
 #define RCHK(ctx, call) do { ncclResult_t e_ = (call); if (e_ != ncclSuccess) return rccl_fail(ctx, e_, #call); } while (0)
 
-int rows_of(int rank, int nranks, int rpb, int height) {
-    int n = 0;
-    const int nblocks = (height + rpb - 1) / rpb;
-    for (int b = rank; b < nblocks; b += nranks) { int r0 = b * rpb, r1 = r0 + rpb; if (r1 > height) r1 = height; n += r1 - r0; }
-    return n;
-}
-
 } // namespace
 
 /* gathered[r][local row][x] -> frame[global row][x]: one thread per pixel of the frame */
@@ -119,7 +112,7 @@ extern "C" int mort_hip_render_gather(mort_ctx *c, const mort_camera *cam, int m
     if (N > 1 && !c->comm) return MORT_ERR_INVALID;
     if (R == 0 && !rgba_out) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    const int lr = rows_of(R, N, rpb, H);
+    const int lr = local_rows_for(c->part, H);
     const size_t max_rows = (size_t)(((H + rpb - 1) / rpb + N - 1) / N) * (size_t)rpb; /* every rank's tile fits */
     const size_t tile_px = max_rows * (size_t)W;
     /* ---- every allocation first ---- */
@@ -160,7 +153,7 @@ extern "C" int mort_hip_render_gather(mort_ctx *c, const mort_camera *cam, int m
         if (e_x == ncclSuccess) {
             if (R == 0) {
                 for (int r = 1; r < N && e_x == ncclSuccess; r++) {
-                    const size_t bytes = (size_t)rows_of(r, N, rpb, H) * (size_t)W * 4;
+                    const size_t bytes = (size_t)local_rows_for(mort_partition{r, N, rpb}, H) * (size_t)W * 4;
                     if (bytes) e_x = rccl().Recv((unsigned char *)c->d_gather + (size_t)r * tile_px * 4, bytes, ncclUint8, r, (ncclComm_t)c->comm, c->stream);
                 }
             } else if (lr > 0) {

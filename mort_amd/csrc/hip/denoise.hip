@@ -15,10 +15,6 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <pthread.h>
-#include <time.h>
-
-#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -60,8 +56,6 @@ __global__ void __launch_bounds__(FEAT_BX * FEAT_BY) atrous_passthrough_kernel(c
 
 namespace {
 
-double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-
 /* tuned on scenes 1, 3 and 6 at 4 spp */
 const mort_denoise_params kDefaults = {5, 2.0f, 0.1f, 0.05f, 3};
 
@@ -85,35 +79,6 @@ AtrousArgs atrous_args(const mort_denoise_params *p, int W, int H, int i) {
     a.sd = p->sigma_depth * (float)a.step;
     a.inv_a = 1.0f / (p->sigma_albedo * p->sigma_albedo);
     return a;
-}
-
-/* run `fn(row)` for rows [0, rows) on `nthreads` host threads */
-struct RowJob {
-    std::atomic<int> next{0};
-    int rows = 0;
-    void (*fn)(void *, int) = nullptr;
-    void *arg = nullptr;
-};
-void *row_worker(void *p) {
-    RowJob *j = (RowJob *)p;
-    for (;;) {
-        const int r = j->next.fetch_add(1);
-        if (r >= j->rows) break;
-        j->fn(j->arg, r);
-    }
-    return nullptr;
-}
-void run_rows(int rows, int nthreads, void (*fn)(void *, int), void *arg) {
-    RowJob job;
-    job.rows = rows; job.fn = fn; job.arg = arg;
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > 256) nthreads = 256;
-    std::vector<pthread_t> th((size_t)nthreads - 1);
-    size_t started = 0;
-    for (; started < th.size(); started++)
-        if (pthread_create(&th[started], nullptr, row_worker, &job) != 0) break;
-    row_worker(&job);
-    for (size_t i = 0; i < started; i++) pthread_join(th[i], nullptr);
 }
 
 struct FeatHostJob { FeatArgs a; bool tree; };
@@ -144,31 +109,6 @@ void feat_camera(FeatArgs &a, const mort_camera *cam) {
     a.du = to_v3(cam->pixel_delta_u); a.dv = to_v3(cam->pixel_delta_v);
 }
 
-/* the camera must lie where the unified tree's pads were sized for (the test of mort_hip_render_host, origin = lens centre) */
-bool camera_in_reach(const mort_camera *cam, const float lo[3], const float hi[3], float reach) {
-    for (int k = 0; k < 3; k++) {
-        const float v = cam->center.e[k];
-        if (!(v >= lo[k] - reach && v <= hi[k] + reach)) return false;
-    }
-    return true;
-}
-
-int grow(mort_ctx *c, void **p, size_t *cap, size_t need) {
-    if (*p && *cap >= need) return MORT_OK;
-    if (*p) { HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
-    HIPCHK(c, hipMalloc(p, need ? need : 16));
-    *cap = need;
-    return MORT_OK;
-}
-
-/* a call on another stream than the previous one: that one may still read the scratch buffers */
-hipError_t dn_switch_stream(mort_ctx *c, hipStream_t s) {
-    hipError_t e = hipSuccess;
-    if (c->dn_stream && c->dn_stream != s) e = hipStreamSynchronize(c->dn_stream);
-    c->dn_stream = s;
-    return e;
-}
-
 } // namespace
 
 extern "C" int mort_hip_denoise_defaults(mort_denoise_params *p) {
@@ -187,7 +127,7 @@ extern "C" int mort_hip_render_features_device(mort_ctx *c, const mort_camera *c
     if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, dn_switch_stream(c, s));
+    HIPCHK(c, switch_stream(c, s));
 
     FeatArgs a;
     std::memset(&a, 0, sizeof a);
@@ -196,7 +136,7 @@ extern "C" int mort_hip_render_features_device(mort_ctx *c, const mort_camera *c
     a.rank = c->part.rank; a.nranks = c->part.nranks; a.rows_per_block = c->part.rows_per_block;
     a.local_rows = mort_hip_local_rows(c, H);
     a.albedo = (float *)d_albedo; a.normal = (float *)d_normal; a.depth = (float *)d_depth;
-    const bool tree = c->gen_ok && camera_in_reach(cam, c->gen_lo, c->gen_hi, c->gen_reach);
+    const bool tree = c->gen_ok && camera_in_reach(cam, c->gen_lo, c->gen_hi, c->gen_reach, 0.0f);
     if (tree) {
         const unsigned char *g = (const unsigned char *)c->d_gen;
         a.gw.nodes = (const DNodeQ *)(g + c->gen.o_nodes); a.gw.entries = (const uint32_t *)(g + c->gen.o_entries);
@@ -230,8 +170,8 @@ extern "C" int mort_hip_render_features(mort_ctx *c, const mort_camera *cam, flo
     HIPCHK(c, hipSetDevice(c->device));
     const int lr = mort_hip_local_rows(c, H);
     const size_t npx = (size_t)W * (size_t)lr;
-    HIPCHK(c, dn_switch_stream(c, c->stream));
-    int st = grow(c, &c->d_feat, &c->feat_cap, npx * 7 * sizeof(float));
+    HIPCHK(c, switch_stream(c, c->stream));
+    int st = ensure_buf(c, &c->d_feat, &c->feat_cap, npx * 7 * sizeof(float));
     if (st != MORT_OK) return st;
     float *d_alb = (float *)c->d_feat, *d_nrm = d_alb + 3 * npx, *d_dep = d_nrm + 3 * npx;
     double sec = 0;
@@ -267,7 +207,7 @@ extern "C" int mort_hip_render_features_host(const mort_world *world, const mort
     job.a.rank = 0; job.a.nranks = 1; job.a.rows_per_block = 8; job.a.local_rows = H;
     job.a.albedo = albedo_out; job.a.normal = normal_out; job.a.depth = depth_out;
     const mortc::Compiled &o = sb.comp;
-    job.tree = (flags & MORT_HOST_TREE) && o.g_ok && camera_in_reach(cam, o.g_lo, o.g_hi, o.g_reach);
+    job.tree = (flags & MORT_HOST_TREE) && o.g_ok && camera_in_reach(cam, o.g_lo, o.g_hi, o.g_reach, 0.0f);
     if (job.tree) {
         GenWalk &gw = job.a.gw;
         gw.nodes = o.g_nodes.data(); gw.entries = o.g_entries.data(); gw.chains = o.g_chains.data();
@@ -290,11 +230,11 @@ extern "C" int mort_hip_denoise_device(mort_ctx *c, const mort_denoise_params *p
     if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, dn_switch_stream(c, s));
+    HIPCHK(c, switch_stream(c, s));
     const size_t npx = (size_t)W * (size_t)H;
     const int n = p->iterations;
     if (n > 1) { /* e ping-pong, g0, g1 */
-        const int st = grow(c, &c->d_dn, &c->dn_cap, npx * 4 * sizeof(float4));
+        const int st = ensure_buf(c, &c->d_dn, &c->dn_cap, npx * 4 * sizeof(float4));
         if (st != MORT_OK) return st;
     }
     float4 *e0 = (float4 *)c->d_dn, *e1 = e0 + npx, *g0 = e1 + npx, *g1 = g0 + npx;
@@ -328,10 +268,10 @@ extern "C" int mort_hip_denoise(mort_ctx *c, const mort_denoise_params *p, int W
     if (!c || !params_ok(p) || !accum || !albedo || !normal || !depth) return MORT_ERR_INVALID;
     if (W <= 0 || H <= 0) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, dn_switch_stream(c, c->stream));
+    HIPCHK(c, switch_stream(c, c->stream));
     const size_t npx = (size_t)W * (size_t)H;
     /* C, A, N (3 floats each), D, accum_out (3 floats), rgba (4 bytes) */
-    int st = grow(c, &c->d_dnio, &c->dnio_cap, npx * 15 * sizeof(float));
+    int st = ensure_buf(c, &c->d_dnio, &c->dnio_cap, npx * 15 * sizeof(float));
     if (st != MORT_OK) return st;
     float *dC = (float *)c->d_dnio, *dA = dC + 3 * npx, *dN = dA + 3 * npx, *dD = dN + 3 * npx, *dO = dD + npx;
     uint8_t *dR = (uint8_t *)(dO + 3 * npx);

@@ -13,7 +13,6 @@
 #include <hip/hip_runtime.h>
 
 #include <pthread.h>
-#include <time.h>
 
 #include <atomic>
 #include <cstdio>
@@ -25,6 +24,7 @@
 #include "dev_pixel.h"
 #include "scene_blob.h"
 #include "seed_host.h"
+#include "mort_ctx.h"
 
 #pragma clang fp contract(off)
 
@@ -54,8 +54,6 @@ void *host_worker(void *p) {
     if (std::getenv("MORT_HOST_DEBUG")) std::fprintf(stderr, "[host worker %lu] %llu segments\n", (unsigned long)pthread_self(), seg);
     return nullptr;
 }
-
-double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 } // namespace
 
@@ -99,13 +97,7 @@ extern "C" int mort_hip_render_host(const mort_world *world, const mort_camera *
     job.a.counters = nullptr;
     /* the unified tree walked by one lane (dev_gen.h gen_world_hit), when the world has one and the caller asks for it */
     const mortc::Compiled &o = sb.comp;
-    job.tree = (flags & MORT_HOST_TREE) && o.g_ok;
-    if (job.tree) {
-        for (int k = 0; k < 3; k++) {
-            const float v = cam->center.e[k];
-            if (!(v >= o.g_lo[k] - o.g_reach && v <= o.g_hi[k] + o.g_reach)) job.tree = false;
-        }
-    }
+    job.tree = (flags & MORT_HOST_TREE) && o.g_ok && camera_in_reach(cam, o.g_lo, o.g_hi, o.g_reach, 0.0f);
     std::memset(&job.gw, 0, sizeof job.gw);
     if (job.tree) {
         job.gw.nodes = o.g_nodes.data(); job.gw.entries = o.g_entries.data(); job.gw.chains = o.g_chains.data();

@@ -63,9 +63,8 @@ __device__ __forceinline__ DQuad rec_quad(const PrimRec &r) {
     return q;
 }
 
-/* host side (mega_gen.hip) */
-int mort_gen_blocks_per_cu(int block, bool prims_in_lds, size_t lds_bytes, bool sub = false);
-hipError_t mort_gen_launch(const GenArgs &ga, int block, int grid, size_t lds_bytes, hipStream_t s);
-hipError_t mort_gen_attributes(int block, bool prims_in_lds, hipFuncAttributes *out, bool sub = false);
+/* host side (mega_gen.hip): mega_gen_kernel<block, prims_in_lds, sub>, or null where that shape is not instantiated */
+typedef void (*gen_kernel_t)(const GenArgs);
+gen_kernel_t mort_gen_kernel(int block, bool prims_in_lds, bool sub);
 
 #endif

@@ -495,8 +495,7 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 1024 ? 4 : BLOCK == 512 ? MOR
 }
 
 /* ---- host side ---- */
-typedef void (*gen_kernel_t)(const GenArgs);
-static gen_kernel_t pick_kernel(int block, bool prims_in_lds, bool sub = false) {
+gen_kernel_t mort_gen_kernel(int block, bool prims_in_lds, bool sub) {
     if (sub) { /* the non-parity launch: 512- and 256-thread workgroups only */
         if (block == 512) return prims_in_lds ? mega_gen_kernel<512, true, true> : mega_gen_kernel<512, false, true>;
         if (block == 256) return prims_in_lds ? mega_gen_kernel<256, true, true> : mega_gen_kernel<256, false, true>;
@@ -509,25 +508,4 @@ static gen_kernel_t pick_kernel(int block, bool prims_in_lds, bool sub = false) 
     case 256: return prims_in_lds ? mega_gen_kernel<256, true> : mega_gen_kernel<256, false>;
     }
     return nullptr;
-}
-int mort_gen_blocks_per_cu(int block, bool prims_in_lds, size_t lds_bytes, bool sub) {
-    gen_kernel_t k = pick_kernel(block, prims_in_lds, sub);
-    if (!k) return 0;
-    if (hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return 0;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, block, lds_bytes) != hipSuccess) return 0;
-    return per_cu;
-}
-hipError_t mort_gen_launch(const GenArgs &ga, int block, int grid, size_t lds_bytes, hipStream_t s) {
-    gen_kernel_t k = pick_kernel(block, ga.prims_in_lds != 0, ga.f.sub > 0);
-    if (!k) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds_bytes, s, ga);
-    return hipGetLastError();
-}
-hipError_t mort_gen_attributes(int block, bool prims_in_lds, hipFuncAttributes *out, bool sub) {
-    gen_kernel_t k = pick_kernel(block, prims_in_lds, sub);
-    if (!k) return hipErrorInvalidValue;
-    return hipFuncGetAttributes(out, (const void *)k);
 }

@@ -6,12 +6,28 @@
 
 #include <hip/hip_runtime.h>
 
+#include <pthread.h>
+#include <time.h>
+
+#include <atomic>
 #include <functional>
 #include <string>
 #include <vector>
 
 #include "mort_hip.h"
 #include "mega_gen.h"
+
+/* the kernel families of a render (mort_hip.hip choose_family) */
+enum RenderFamily { FAM_MEGA, FAM_BVH, FAM_GEN, FAM_WAVE, FAM_WAVE_GEN };
+
+/* what a render launched: filled by its family's launcher, read by its statistics */
+struct LaunchPlan {
+    RenderFamily fam;
+    const void *kernel; /* the main kernel that ran: its registers (and static LDS) are reported */
+    int block;
+    int lds_bytes;      /* LDS reported: the launch's own figure, or -1 for the kernel's static LDS */
+    char name[64];      /* as rocprofv3 prints it */
+};
 
 struct mort_ctx {
     int device = 0;
@@ -105,6 +121,79 @@ static inline int hip_fail(mort_ctx *c, hipError_t e, const char *what) {
     return MORT_ERR_HIP;
 }
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); } while (0)
+
+/* ---- host helpers of the translation units ---- */
+
+/* a device buffer of at least `need` bytes in *p (capacity *cap); a smaller one is freed first */
+static inline int ensure_buf(mort_ctx *c, void **p, size_t *cap, size_t need) {
+    if (*p && *cap >= need) return MORT_OK;
+    if (*p) { HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
+    HIPCHK(c, hipMalloc(p, need ? need : 16));
+    *cap = need;
+    return MORT_OK;
+}
+
+/* a feature / denoise / temporal call on another stream than the previous one: that one may still read the scratch buffers */
+static inline hipError_t switch_stream(mort_ctx *c, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (c->dn_stream && c->dn_stream != s) e = hipStreamSynchronize(c->dn_stream);
+    c->dn_stream = s;
+    return e;
+}
+
+/* rows of `height` that partition p owns: blocks rank, rank + nranks, ... of rows_per_block rows */
+static inline int local_rows_for(const mort_partition &p, int height) {
+    int n = 0;
+    const int rpb = p.rows_per_block;
+    const int nblocks = (height + rpb - 1) / rpb;
+    for (int b = p.rank; b < nblocks; b += p.nranks) {
+        int r0 = b * rpb, r1 = r0 + rpb;
+        if (r1 > height) r1 = height;
+        n += r1 - r0;
+    }
+    return n;
+}
+
+/* the camera must lie where the unified tree's pads were sized for (scene_compile.h build_unified): its centre, widened by
+ * the lens radius `rad` for rays that start on the lens */
+static inline bool camera_in_reach(const mort_camera *cam, const float lo[3], const float hi[3], float reach, float rad) {
+    for (int k = 0; k < 3; k++) {
+        const float v = cam->center.e[k];
+        if (!(v - rad >= lo[k] - reach && v + rad <= hi[k] + reach)) return false;
+    }
+    return true;
+}
+
+static inline double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+
+/* run `fn(arg, row)` for rows [0, rows) on `nthreads` host threads (1..256), rows handed out one at a time */
+struct RowJob {
+    std::atomic<int> next{0};
+    int rows = 0;
+    void (*fn)(void *, int) = nullptr;
+    void *arg = nullptr;
+};
+static inline void *row_worker(void *p) {
+    RowJob *j = (RowJob *)p;
+    for (;;) {
+        const int r = j->next.fetch_add(1);
+        if (r >= j->rows) break;
+        j->fn(j->arg, r);
+    }
+    return nullptr;
+}
+static inline void run_rows(int rows, int nthreads, void (*fn)(void *, int), void *arg) {
+    RowJob job;
+    job.rows = rows; job.fn = fn; job.arg = arg;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    std::vector<pthread_t> th((size_t)nthreads - 1);
+    size_t started = 0;
+    for (; started < th.size(); started++)
+        if (pthread_create(&th[started], nullptr, row_worker, &job) != 0) break;
+    row_worker(&job);
+    for (size_t i = 0; i < started; i++) pthread_join(th[i], nullptr);
+}
 
 
 #endif

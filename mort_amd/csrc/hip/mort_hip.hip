@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -170,17 +171,6 @@ extern "C" const char *mort_hip_strerror(int st) {
 }
 extern "C" const char *mort_hip_last_error(const mort_ctx *c) { return c ? c->last_error.c_str() : ""; }
 
-static int local_rows_for(const mort_partition &p, int height) {
-    int n = 0;
-    const int rpb = p.rows_per_block;
-    const int nblocks = (height + rpb - 1) / rpb;
-    for (int b = p.rank; b < nblocks; b += p.nranks) {
-        int r0 = b * rpb, r1 = r0 + rpb;
-        if (r1 > height) r1 = height;
-        n += r1 - r0;
-    }
-    return n;
-}
 static int global_row_host(const mort_partition &p, int ly) {
     const int lb = ly / p.rows_per_block, within = ly % p.rows_per_block;
     return (lb * p.nranks + p.rank) * p.rows_per_block + within;
@@ -425,41 +415,12 @@ static int check_light(const mort_ctx *c, int type, int idx) {
     return MORT_OK; /* any other tag samples nothing: pdf 0, direction (1,0,0) (objects.cuh:961,978) */
 }
 
-/* ---- wavefront mode: one wf_trav + one wf_shade launch per front until no pixel is live ---- */
-static int render_wavefront(mort_ctx *c, const RenderArgs &a, const mort_camera *cam, hipStream_t s) {
-    const size_t N = (size_t)a.width * (size_t)a.local_rows;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    const size_t o_ray0 = take(N * sizeof(WfRay)), o_ray1 = take(N * sizeof(WfRay));
-    const size_t o_id0 = take(N * sizeof(unsigned)), o_id1 = take(N * sizeof(unsigned));
-    const size_t o_hits = take(N * sizeof(WfHit)), o_pix = take(N * sizeof(WfPix));
-    const size_t o_stack = take(N * (size_t)cam->bounce_limit * sizeof(float4));
-    const size_t o_c0 = take(N * sizeof(unsigned)), o_c1 = take(N * sizeof(unsigned)), o_c2 = take(N * sizeof(unsigned));
-    const size_t o_cnt = take(sizeof(WfCounters));
-    const size_t total = off;
-    if (c->wf_bytes < total) {
-        if (c->d_wf) { hipFree(c->d_wf); c->d_wf = nullptr; c->wf_bytes = 0; }
-        HIPCHK(c, hipMalloc(&c->d_wf, total));
-        c->wf_bytes = total;
-    }
-    if (!c->h_live) HIPCHK(c, hipHostMalloc((void **)&c->h_live, 64));
-    unsigned char *base = (unsigned char *)c->d_wf;
+/* ---- wavefront mode over one reference BVH of spheres: one wf_trav + one wf_shade launch per front (wave_common.h wf_render) ---- */
+static int launch_wave(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, hipStream_t s, LaunchPlan &plan) {
     WfArgs w;
     std::memset(&w, 0, sizeof w);
     w.r = a;
     w.node_first = 0; w.node_count = c->sc.n_nodes;
-    w.n_paths = (int)N;
-    w.q_ray[0] = (WfRay *)(base + o_ray0); w.q_ray[1] = (WfRay *)(base + o_ray1);
-    w.q_id[0] = (unsigned *)(base + o_id0); w.q_id[1] = (unsigned *)(base + o_id1);
-    w.hits = (WfHit *)(base + o_hits); w.pix = (WfPix *)(base + o_pix);
-    w.stack = (float4 *)(base + o_stack);
-    w.q_cls[0] = (unsigned *)(base + o_c0); w.q_cls[1] = (unsigned *)(base + o_c1); w.q_cls[2] = (unsigned *)(base + o_c2);
-    w.cnt = (WfCounters *)(base + o_cnt);
-
-    const int nb256 = (int)((N + 255) / 256);
-    hipLaunchKernelGGL(wf_init, dim3(nb256), dim3(256), 0, s, w);
-    HIPCHK(c, hipGetLastError());
     auto trav = wf_trav<MORT_WF_BLOCK>;
     const size_t stage_bytes = (size_t)(MORT_WF_BLOCK / 64) * 3 * MORT_WF_STAGE * sizeof(unsigned);
     /* wf_trav's LDS: its image (binary own tree, leaf nodes, spheres) | traversal stacks | class staging | prefetch rings */
@@ -470,42 +431,23 @@ static int render_wavefront(mort_ctx *c, const RenderArgs &a, const mort_camera 
     const size_t ring_off = (((size_t)w.t_stage + stage_bytes) + 1023) & ~(size_t)1023;
     const size_t trav_lds = ring_off + (size_t)(MORT_WF_BLOCK / 64) * 4096;
     w.off_ring = (uint32_t)ring_off;
-    HIPCHK(c, hipFuncSetAttribute((const void *)trav, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trav_lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trav, MORT_WF_BLOCK, trav_lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int max_trav_grid = c->num_cus * per_cu;
     size_t wf_share = 1; /* 64-record batches per wave at least (MORT_WAVE_SHARE; 2 was 4 % slower: a front's time is its slowest wave's) */
     { const char *sh = std::getenv("MORT_WAVE_SHARE"); if (sh && std::atoi(sh) >= 1) wf_share = (size_t)std::atoi(sh); }
-    const long long max_fronts = (long long)cam->sqrt_spp * cam->sqrt_spp * ((long long)cam->bounce_limit + 1) + 8;
-    size_t live = N;
-    long long front = 0;
-    const int chunk = 32;
-    while (live > 0 && front < max_fronts) {
-        int tg = (int)((live + (size_t)(MORT_WF_BLOCK / 64) * 64 * wf_share - 1) / ((size_t)(MORT_WF_BLOCK / 64) * 64 * wf_share));
-        if (tg > max_trav_grid) tg = max_trav_grid;
-        if (tg < 1) tg = 1;
-        const int sg = (int)((live + 255) / 256) + 3;
-        for (int k = 0; k < chunk; k++, front++) {
-            w.parity = (int)(front & 1);
-            hipLaunchKernelGGL(trav, dim3(tg), dim3(MORT_WF_BLOCK), trav_lds, s, w);
-            hipLaunchKernelGGL(wf_shade, dim3(sg), dim3(256), 0, s, w);
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_live, &w.cnt->live, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        live = *c->h_live;
-    }
-    c->wf_fronts = (int)front;
-    if (live != 0) { c->last_error = "wavefront: front limit reached with live pixels"; return MORT_ERR_HIP; }
-    return MORT_OK;
+    plan.kernel = (const void *)trav; plan.block = MORT_WF_BLOCK; plan.lds_bytes = (int)c->trav_bytes;
+    std::snprintf(plan.name, sizeof plan.name, "wf_trav<%d>", MORT_WF_BLOCK);
+    return wf_render(c, cam, (size_t)a.width * (size_t)a.local_rows, w, wf_init, trav, wf_shade, MORT_WF_BLOCK, trav_lds,
+                     (size_t)(MORT_WF_BLOCK / 64) * 64 * wf_share, s);
 }
 
 /* ---- tile order of the state-machine megakernels: most expensive 8x8 tiles first (cost = segments per tile in the
  * previous frame of this world / view / partition, or in a one-sample probe on a scratch copy of the streams), so a frame
- * does not end on its longest pixel chains.  Everything is queued on `s`; nothing waits on the host. ---- */
+ * does not end on its longest pixel chains.  Sub-stream launches are not ordered: their work items are a stratum row,
+ * 1/sqrt_spp of a pixel -- no long tail to order away.  Everything is queued on `s`; nothing waits on the host.  Leaves
+ * fa.tile_order null when it orders nothing. ---- */
 template <typename ProbeFn>
 static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, FastArgs &fa, int tiles, int grid, int FB,
-                              bool chain_bound, hipStream_t s, ProbeFn launch_probe) {
+                              bool chain_bound, bool sub, bool timed, hipStream_t s, ProbeFn launch_probe) {
+    if (sub || std::getenv("MORT_NO_TILE_ORDER") || tiles < 4 * grid) return MORT_OK;
     const int W = a.width, H = a.height;
     if (c->tile_cap < (size_t)tiles) {
         hipFree(c->d_tile_cost); hipFree(c->d_tile_order); hipFree(c->d_tile_keys); hipFree(c->d_tile_iota); hipFree(c->d_sort_tmp);
@@ -524,6 +466,8 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
         HIPCHK(c, hipMalloc((void **)&c->d_prio_count, 16 + 96 * sizeof(unsigned long long)));
         HIPCHK(c, hipMemsetAsync(c->d_prio_count, 0, 16 + 96 * sizeof(unsigned long long), s));
     }
+    const char *tk = std::getenv("MORT_TILE_KEY");
+    const int key_sum = (tk && std::strcmp(tk, "sum") == 0) ? 1 : 0;
     /* the costs belong to one (world, image geometry, partition, view): FNV-1a over all of it */
     unsigned long long key = 1469598103934665603ull;
     auto mix = [&key](const void *p, size_t n) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < n; i++) { key ^= b[i]; key *= 1099511628211ull; } };
@@ -544,7 +488,7 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
         pa.r.states = c->d_probe_states; pa.r.sqrt_spp = 1; pa.r.recip_sqrt_spp = 1.0f; pa.r.pixel_samples_scale = 1.0f;
         pa.r.accum = nullptr; pa.r.seg_px = nullptr;
         pa.tile_order = nullptr; pa.tile_cost = c->d_tile_cost;
-        { const char *tk = std::getenv("MORT_TILE_KEY"); pa.tile_key_sum = (tk && std::strcmp(tk, "sum") == 0) ? 1 : 0; }
+        pa.tile_key_sum = key_sum;
         HIPCHK(c, launch_probe(pa));
         if (c->d_prio_count) HIPCHK(c, hipMemcpyAsync(c->d_prio_count + 4, c->d_counters, 96 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s)); /* the probe's counters (pixel_write<true> adds its segments to the per-workgroup slots), beside its tile costs */
         HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 96 * sizeof(unsigned long long), s)); /* probe totals and work cursor */
@@ -562,11 +506,12 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
     }
     HIPCHK(c, hipMemsetAsync(c->d_tile_cost, 0, (size_t)tiles * sizeof(unsigned), s));
     fa.tile_order = c->d_tile_order; fa.tile_cost = c->d_tile_cost;
-    { const char *tk = std::getenv("MORT_TILE_KEY"); fa.tile_key_sum = (tk && std::strcmp(tk, "sum") == 0) ? 1 : 0; }
+    fa.tile_key_sum = key_sum;
     fa.gen_tiles = grid * (FB / 64); /* one tile's worth of slots per wave in flight */
     fa.spread_shift = chain_bound ? 0 : 6; /* measured: whole tiles while lanes refill several times, single pixels otherwise */
     { const char *sp = std::getenv("MORT_SPREAD_SHIFT"); if (sp) fa.spread_shift = std::atoi(sp); }
     if (fa.spread_shift >= 6 || fa.spread_shift < 0) fa.gen_tiles = 0;
+    if (timed) HIPCHK(c, hipEventRecord(c->ev0, s)); /* time the frame itself; ordering upkeep is reported by wall-clock benches */
     return MORT_OK;
 }
 
@@ -604,10 +549,355 @@ static int ensure_substates(mort_ctx *c, int W, int H, int S, hipStream_t s) {
     return MORT_OK;
 }
 
+/* ---- the two state-machine megakernels (mega_bvh_kernel, mega_gen_kernel): what their launches share ---- */
+
+/* the FastArgs fields both fill alike: camera / buffers, LDS image source, work cursor, tiles, sub-streams, lane cap */
+static void fast_args_base(const mort_ctx *c, const mort_camera *cam, const RenderArgs &a, FastArgs &fa, const void *image, uint32_t image_bytes,
+                           int tiles, bool sub) {
+    fa.r = a;
+    fa.hot_src = (const unsigned char *)image; fa.hot_bytes = image_bytes;
+    fa.next_q = (unsigned int *)(c->d_counters + 2);
+    fa.tiles_x = (a.width + 7) / 8; fa.tiles_total = tiles;
+    if (sub) { fa.sub = cam->sqrt_spp; fa.vaccum = c->d_vaccum; fa.r.states = c->d_substates; }
+    fa.lane_cap = 64;
+    { const char *lc = std::getenv("MORT_LANE_CAP"); if (lc && std::atoi(lc) >= 1 && std::atoi(lc) <= 64) fa.lane_cap = std::atoi(lc); }
+}
+
+/* LDS, grid and HBM scratch of a launch of `kern` in FB-thread groups.  LDS: the image (fa.hot_bytes) | traversal stacks
+ * [tstack_levels][FB] u16 | as many bounce-stack levels [dl][FB] float4 as fit next to them, at most 12 and dl_cap, with as many
+ * groups per CU as keep 12 waves per CU (fewer when their LDS does not fit 160 KB) and at most per_cu_cap.  The levels below dl
+ * go to c->d_deep; MORT_WAVE_LINES (profile builds) sizes the per-wave log. */
+static int state_setup(mort_ctx *c, const mort_camera *cam, FastArgs &fa, const void *kern, int FB, uint32_t tstack_levels, int dl_cap,
+                       int per_cu_cap, const char *too_big, hipStream_t s, size_t &lds_bytes, int &grid) {
+    const uint32_t tstack_off = (fa.hot_bytes + 15u) & ~15u;
+    const uint32_t stack_off = tstack_off + tstack_levels * (uint32_t)FB * 2u;
+    fa.off_tstack = tstack_off;
+    uint32_t static_lds = 1024; /* the kernel's own __shared__ objects come out of the same 160 KB */
+    { hipFuncAttributes fattr; if (hipFuncGetAttributes(&fattr, kern) == hipSuccess) static_lds = (uint32_t)((fattr.sharedSizeBytes + 1023) & ~(size_t)1023); }
+    int groups_per_cu = FB >= 768 ? 1 : 768 / FB;
+    while (groups_per_cu > 1 && (long long)(stack_off + static_lds) * groups_per_cu > 160ll * 1024) groups_per_cu--;
+    const long long room = (160ll * 1024 - (long long)static_lds * groups_per_cu) / groups_per_cu - (long long)stack_off;
+    if (room < 0) { c->last_error = too_big; return MORT_ERR_CAPACITY; }
+    int dl = (int)(room / ((long long)FB * 16));
+    if (dl > 12) dl = 12;
+    if (dl > dl_cap) dl = dl_cap;
+    fa.off_stack = stack_off; fa.stack_lds_depth = dl;
+    lds_bytes = (size_t)stack_off + (size_t)dl * FB * 16;
+    HIPCHK(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, FB, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (per_cu > per_cu_cap) per_cu = per_cu_cap;
+    grid = c->num_cus * per_cu;
+    const int want_blocks = (int)(((long long)fa.tiles_total * 64 + FB - 1) / FB);
+    if (grid > want_blocks) grid = want_blocks;
+    if (grid < 1) grid = 1;
+    /* bounce-stack levels that do not fit in LDS: [level - dl][lane of the launch] in HBM */
+    const int deep_levels = cam->bounce_limit > dl ? cam->bounce_limit - dl : 0;
+    const int st = ensure_buf(c, &c->d_deep, &c->deep_cap, (size_t)(deep_levels > 0 ? deep_levels : 1) * (size_t)grid * (size_t)FB * sizeof(float4));
+    if (st != MORT_OK) return st;
+    fa.deep = (float4 *)c->d_deep;
+    fa.wave_log = nullptr;
+    if (std::getenv("MORT_WAVE_LINES")) { /* profile builds: 16 words per wave, read back by mort_hip_debug_wave_log */
+        c->wave_log_waves = (size_t)grid * (size_t)(FB / 64);
+        if (ensure_buf(c, &c->d_wave_log, &c->wave_log_cap, c->wave_log_waves * 16 * sizeof(unsigned long long)) == MORT_OK) {
+            hipMemsetAsync(c->d_wave_log, 0, c->wave_log_waves * 16 * sizeof(unsigned long long), s);
+            fa.wave_log = (unsigned long long *)c->d_wave_log;
+        }
+    }
+    return MORT_OK;
+}
+
+/* mega_bvh_kernel<BLOCK, PROBE, DRAIN, SUB> for a launch shape (1024-thread groups have no DRAIN variant; a probe is neither DRAIN
+ * nor SUB).  Written so that the device code object lists the variants in the order it always has. */
+typedef void (*bvh_kernel_t)(const FastArgs);
+static bvh_kernel_t bvh_kernel(int FB, bool probe, bool drain, bool sub) {
+    if (!sub) switch (FB) {
+        case 1024: return !probe ? mega_bvh_kernel<1024, false, false> : mega_bvh_kernel<1024, true, false>;
+        case 768: return probe ? mega_bvh_kernel<768, true, false> : drain ? mega_bvh_kernel<768, false, true> : mega_bvh_kernel<768, false, false>;
+        case 512: return probe ? mega_bvh_kernel<512, true, false> : drain ? mega_bvh_kernel<512, false, true> : mega_bvh_kernel<512, false, false>;
+        case 384: return probe ? mega_bvh_kernel<384, true, false> : drain ? mega_bvh_kernel<384, false, true> : mega_bvh_kernel<384, false, false>;
+        default: return probe ? mega_bvh_kernel<256, true, false> : drain ? mega_bvh_kernel<256, false, true> : mega_bvh_kernel<256, false, false>;
+    }
+    return FB == 1024 ? mega_bvh_kernel<1024, false, false, true> : FB == 768 ? mega_bvh_kernel<768, false, false, true> : FB == 512 ? mega_bvh_kernel<512, false, false, true>
+           : FB == 384 ? mega_bvh_kernel<384, false, false, true> : mega_bvh_kernel<256, false, false, true>;
+}
+
+/* ---- the BVH megakernel (mega_bvh.h): one reference BVH as the world, its own four-wide tree in LDS ---- */
+static int launch_bvh(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, int tiles, bool sub, bool timed, hipStream_t s, LaunchPlan &plan) {
+    FastArgs fa;
+    std::memset(&fa, 0, sizeof fa);
+    fast_args_base(c, cam, a, fa, c->d_fast, c->fast_bytes, tiles, sub);
+    fa.off_nodes4 = c->f_nodes4; fa.off_leafrecs = c->f_leafrecs; fa.off_lambert = c->f_lambert; fa.off_metal = c->f_metal;
+    fa.off_diel = c->f_diel; fa.off_dlight = c->f_dlight; fa.off_iso = c->f_iso; fa.off_solid = c->f_solid; fa.off_checker = c->f_checker;
+    fa.node_first = 0; fa.node_count = c->sc.n_nodes; /* the reference's threaded nodes (HBM): fallback walk */
+    const long long lanes_wanted = (long long)tiles * 64;
+    const double px_per_lane = (double)lanes_wanted / ((double)c->num_cus * 768.0);
+    /* workgroup size.  Two pixels per lane or more: 1024 threads, compiled for 128 registers = 16 waves per CU.  A wave issues a
+     * dependent vector instruction every ~8 cycles and an independent one every ~5 (calibration), a SIMD can issue one
+     * every ~1.2: a fourth wave per SIMD is worth more than the 24 registers the 1024-thread build keeps in private memory, all of
+     * them touched in the shade step only (Scene 1: 103.7 ms against 111.9 ms with 768 threads at 153 registers).
+     * Otherwise the largest of {768, 512, 384, 256} that still gives every CU a workgroup
+     * (a rank of an 8-way partition owns ~100 k pixels: 768-thread groups would leave half the CUs idle) */
+    int FB = MORT_FAST_BLOCK;
+    const char *fb_env = std::getenv("MORT_FAST_BLOCK_SIZE");
+    if (fb_env) FB = std::atoi(fb_env);
+    else {
+        const int cand[4] = {768, 512, 384, 256};
+        FB = 256;
+        const bool wide_ok = lanes_wanted >= 2ll * 1024 * c->num_cus;
+        /* about one pixel per lane or fewer: the frame is as long as its longest pixel chain, so take the drain kernels that are
+         * compiled without spills (<= 512 threads; one rank of 4 at 1200x675: 81 ms vs 90 ms with 768) */
+        for (int k = (px_per_lane < 1.5 && !sub) ? 1 : 0; k < 4; k++) if (lanes_wanted >= (long long)cand[k] * c->num_cus) { FB = cand[k]; break; }
+        if (wide_ok) FB = 1024;
+    }
+    /* 1024 threads: image + traversal stacks + one bounce-stack level per lane must fit one CU's LDS, else the widest shape that does */
+    if (FB == 1024 && (size_t)((fa.hot_bytes + 15u) & ~15u) + (size_t)c->own4_stack * 1024u * 2u + 2048u + 1024u * 16u > 160u * 1024u) FB = 768;
+    if (FB != 1024 && FB != 768 && FB != 512 && FB != 384) FB = 256;
+    fa.drain_rounds = 3; /* batch thresholds as shares of the wave's LIVE lanes (they differ from fixed counts only once lanes have run out of pixels: the tail of a frame;
+                          * three runs each, one box: N = 1 100.1-100.5 vs 100.3-102.9 ms, a rank of 2 75.6-78.6 vs 77.6-82.2 ms, ranks of 4 / 8 unchanged); DRAIN kernels
+                          * also follow the lane furthest behind (round 2).  MORT_BVH_DRAIN: 0 / 1 = fixed counts, 2 = rounds, 3 = this */
+    { const char *dm = std::getenv("MORT_BVH_DRAIN"); if (dm) fa.drain_rounds = std::atoi(dm) == 2 ? 1 : std::atoi(dm) == 3 ? 3 : 0; }
+    /* chain-bound partition (about one pixel per lane or fewer): drain mode + spread fetches (mega_bvh.h); no drain variant at 1024
+     * threads: chain-bound partitions take <= 512 */
+    bool chain_bound = px_per_lane < 1.5 && !sub;
+    { const char *cb = std::getenv("MORT_CHAIN_BOUND"); if (cb && !sub) chain_bound = cb[0] == '1'; }
+    if (FB == 1024) chain_bound = false;
+    const bvh_kernel_t kern = bvh_kernel(FB, false, chain_bound, sub), kern_probe = bvh_kernel(FB, true, false, false);
+    /* scheduling thresholds (mega_bvh.h).  Smaller batches do not help a chain-bound partition: measured on
+     * one rank of 8, (32,24,16) 100 ms, (12,12,8) 126 ms, (2,2,2) 192 ms -- a lane waits through every step
+     * its wave runs for other lanes, and small batches mean more of those */
+    fa.th_s = MORT_TH_S; fa.th_l = MORT_TH_L; fa.t_keep = MORT_T_KEEP;
+    { const char *th = std::getenv("MORT_THRESHOLDS"); /* "s,l,k" */
+      if (th) { int s_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &s_, &l_, &k_) == 3 && s_ >= 1 && l_ >= 1 && k_ >= 1) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; } } }
+    int per_cu_cap = INT_MAX;
+    { const char *pc = std::getenv("MORT_FAST_BLOCKS_PER_CU"); if (pc && std::atoi(pc) >= 1) per_cu_cap = std::atoi(pc); }
+    /* traversal stacks: the world's own four-wide bound (at most MORT_OWN4_STACK) */
+    size_t lds_bytes = 0;
+    int grid = 0;
+    int st = state_setup(c, cam, fa, (const void *)kern, FB, (uint32_t)c->own4_stack, 12, per_cu_cap, "BVH image does not fit one CU's LDS", s, lds_bytes, grid);
+    if (st != MORT_OK) return st;
+    st = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, chain_bound, sub, timed, s, [&](const FastArgs &pa) {
+        hipError_t e_ = hipFuncSetAttribute((const void *)kern_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e_ != hipSuccess) return e_;
+        hipLaunchKernelGGL(kern_probe, dim3(grid), dim3(FB), lds_bytes, s, pa);
+        return hipGetLastError();
+    });
+    if (st != MORT_OK) return st;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(FB), lds_bytes, s, fa);
+    HIPCHK(c, hipGetLastError());
+    plan.kernel = (const void *)kern; plan.block = FB; plan.lds_bytes = (int)lds_bytes;
+    std::snprintf(plan.name, sizeof plan.name, "mega_bvh_kernel<%d, false, %s, %s>", FB, chain_bound ? "true" : "false", sub ? "true" : "false");
+    return MORT_OK;
+}
+
+/* ---- the unified-tree megakernel (mega_gen.hip): every world without reference BVHs ---- */
+static int launch_gen(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, int tiles, bool sub, bool timed, hipStream_t s, LaunchPlan &plan) {
+    GenArgs ga = c->gen; /* LDS image offsets, root, far-ray constants (upload_world) */
+    FastArgs &fa = ga.f;
+    fast_args_base(c, cam, a, fa, c->d_gen, c->gen_bytes, tiles, sub);
+    const long long lanes_wanted = (long long)tiles * 64;
+    int FB = 768;
+    bool heavy_default = false;
+    { const char *fb_env = std::getenv("MORT_GEN_BLOCK_SIZE");
+      if (fb_env && !sub) FB = std::atoi(fb_env);
+      else { /* many pixels per lane: 1024 threads compiled for 128 registers = four waves per SIMD, which pays for its spills as in the BVH
+              * kernel (4096 x 4096 x 4: 126.6 ms, 768 threads at 160 registers 137.5 ms, 512 threads 181 ms; 1920 x 1080 x 49: 173 vs 175 ms).
+              * With a handful of pixels per lane the frame ends with its longest pixel chains, whose rounds are faster with two waves per
+              * SIMD and no spills (final scene 800 x 800 x 961: 3.07 s with 512 threads, 3.21 s with 1024); fewer pixels than lanes:
+              * 256-thread groups so every CU has work */
+             const double ppl = (double)lanes_wanted / ((double)c->num_cus * 768.0);
+             FB = ppl >= 8.0 ? 1024 : (lanes_wanted >= 512ll * c->num_cus) ? 512 : 256;
+             /* fewer pixels per lane: the frame may be bound by its longest pixel chains, and then HEAVY WAVES pay (below): 1024 threads, the launch decides on the device */
+             if (ppl < 8.0 && lanes_wanted >= 32ll * 1024 && !std::getenv("MORT_GEN_NO_HEAVY")) { FB = 1024; heavy_default = true; } } }
+    if (FB != 1024 && FB != 768 && FB != 512 && FB != 256) FB = 256;
+    if (FB == 1024 && (size_t)c->gen_bytes + 16u + (size_t)MORT_OWN_STACK * 1024u * 2u + 2048u > 160u * 1024u) FB = 768; /* image + traversal stacks of 1024 threads must fit */
+    if (sub && FB > 512) FB = 512; /* the non-parity launch is instantiated for 512- and 256-thread workgroups */
+    /* swept on the final scene, 800x800x100 (scripts/th_sweep.py, 180 settings): 373 ms here vs 449 ms with the BVH kernel's (40,24,12) and m = 24 */
+    fa.th_s = 28; fa.th_l = 20; fa.t_keep = 4; ga.th_m = 56;
+    /* heavy waves (mega_bvh.h FastArgs.heavy_*): "mod,num,cap,percent" */
+    fa.heavy_mod = 0; fa.heavy_num = 0; fa.heavy_cap = 64; c->heavy_percent = 50;
+    /* default where the frame has fewer than 8 pixels per lane: two waves of three take 12 lanes each from the tiles whose longest pixel reaches half of the frame's
+     * longest -- IF the device finds the frame chain-bound (tile_sort.hip heavy_count_kernel); final scene 800x800x961: 3.04 -> 2.55 s, x100: 318 -> 270 ms */
+    if (heavy_default && FB == 1024 && !sub) { fa.heavy_mod = 3; fa.heavy_num = 2; fa.heavy_cap = 12; }
+    { const char *hv = std::getenv("MORT_GEN_HEAVY"); int m_ = 0, n_ = 0, k_ = 0, p_ = 0;
+      if (hv && !sub && std::sscanf(hv, "%d,%d,%d,%d", &m_, &n_, &k_, &p_) == 4 && m_ >= 1 && n_ >= 1 && n_ <= m_ && k_ >= 1 && k_ <= 64 && p_ >= 1 && p_ <= 100) {
+          fa.heavy_mod = m_; fa.heavy_num = n_; fa.heavy_cap = k_; c->heavy_percent = p_; } }
+    ga.drain_mode = 3; /* thresholds as shares of the live lanes; measured alternatives: 0 = fixed counts, 1 = follow one lane, 2 = rounds */
+    { const char *dm = std::getenv("MORT_GEN_DRAIN"); if (dm && std::atoi(dm) >= 0 && std::atoi(dm) <= 3) ga.drain_mode = std::atoi(dm); } /* other values: the default */
+    /* thresholds below 1 are refused: with t_keep < 1 a box-step loop whose lanes have all left the tree would never end */
+    { const char *th = std::getenv("MORT_GEN_THRESHOLDS"); /* "s,l,k,m" */
+      if (th) { int s_ = 0, l_ = 0, k_ = 0, m_ = 0; if (std::sscanf(th, "%d,%d,%d,%d", &s_, &l_, &k_, &m_) == 4 && s_ >= 1 && l_ >= 1 && k_ >= 1 && m_ >= 1) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; ga.th_m = m_; } } }
+    const gen_kernel_t kern = mort_gen_kernel(FB, ga.prims_in_lds != 0, sub);
+    int dl_cap = 12;
+    { const char *de = std::getenv("MORT_GEN_DL"); if (de) dl_cap = std::atoi(de) > 0 ? std::atoi(de) : 0; } /* a negative count would shrink the LDS below the traversal stacks */
+    size_t lds_bytes = 0;
+    int grid = 0;
+    int st = state_setup(c, cam, fa, (const void *)kern, FB, MORT_OWN_STACK, dl_cap, INT_MAX, "unified-tree image does not fit one CU's LDS", s, lds_bytes, grid);
+    if (st != MORT_OK) return st;
+    st = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, false, sub, timed, s, [&](const FastArgs &pa) {
+        GenArgs pg = ga;
+        pg.f = pa;
+        pg.probe = 1;
+        hipError_t e_ = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e_ != hipSuccess) return e_;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(FB), lds_bytes, s, pg);
+        return hipGetLastError();
+    });
+    if (st != MORT_OK) return st;
+    /* priority pixels (mega_bvh.h FastArgs), with a tile order only: the head of the cost order, a few per wave.  A frame with a handful
+     * of pixels per lane ends when its longest pixel chain does (final scene 800x800: the fog ball's pixels run 8 x the mean), and a chain
+     * advances one segment per round of its wave: such a pixel must not share its wave with 63 others of its kind, and its wave must follow it */
+    if (fa.tile_order) {
+        int k_prio = 0; /* measured, not the default: following one lane starves the other 63 of a tile whose pixels are all long */
+        { const char *kp = std::getenv("MORT_GEN_PRIO_LANES"); if (kp) k_prio = std::atoi(kp); }
+        if (k_prio > 0 && ga.drain_mode == 1) {
+            const long long waves = (long long)grid * (FB / 64);
+            long long pt = (waves * k_prio + 63) / 64;
+            if (pt > tiles / 4) pt = tiles / 4;
+            fa.prio_tiles = (int)pt; fa.prio_lanes = k_prio;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(FB), lds_bytes, s, ga);
+    HIPCHK(c, hipGetLastError());
+    if (fa.heavy_mod > 0 && c->d_prio_count && std::getenv("MORT_GEN_HEAVY_DEBUG")) { /* diagnostic: what the device decided for this launch */
+        unsigned h[4] = {0, 0, 0, 0};
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipMemcpy(h, c->d_prio_count, 16, hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "[heavy] head tiles %u of %d, lanes %d\n", h[0], tiles, grid * FB);
+    }
+    if (fa.heavy_mod > 0 && c->d_prio_count) /* this frame's segment total, beside the tile costs it leaves for the next frame's order */
+        HIPCHK(c, hipMemcpyAsync(c->d_prio_count + 4, c->d_counters, 96 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    plan.kernel = (const void *)kern; plan.block = FB; plan.lds_bytes = (int)lds_bytes;
+    std::snprintf(plan.name, sizeof plan.name, "mega_gen_kernel<%d, %s, %s>", FB, ga.prims_in_lds ? "true" : "false", sub ? "true" : "false"); /* as rocprofv3 prints it: <BLOCK, PRIMS_LDS, SUB> */
+    return MORT_OK;
+}
+
+/* the kernel family that renders this call, or the status the call fails with (arguments, world and RNG already checked) */
+static int choose_family(const mort_ctx *c, const mort_camera *cam, int mode, bool seg_px, RenderFamily &fam) {
+    const int W = cam->image_width, H = cam->image_height;
+    const char *force = std::getenv("MORT_FORCE_GENERIC");
+    const bool state_ok = cam->sqrt_spp >= 1 && cam->sqrt_spp < 32768 && cam->bounce_limit >= 1 && W < 65536 && H < 32768 && !(force && force[0] == '1');
+    /* rays start on the lens: the unified tree serves cameras within its reach widened by the lens radius */
+    const float rad = std::fabs(cam->defocus_disk_u.e[0]) + std::fabs(cam->defocus_disk_u.e[1]) + std::fabs(cam->defocus_disk_u.e[2]) +
+                      std::fabs(cam->defocus_disk_v.e[0]) + std::fabs(cam->defocus_disk_v.e[1]) + std::fabs(cam->defocus_disk_v.e[2]);
+    const bool gen_reach = c->gen_ok && camera_in_reach(cam, c->gen_lo, c->gen_hi, c->gen_reach, rad);
+    if (mode == MORT_MODE_WAVE) {
+        /* the wavefront pipeline: wave_bvh.h for one reference BVH of spheres as the world (no light object), wave_gen.hip for
+         * every world with a unified tree (lights, quads, instances, media); anything else is not supported in this mode */
+        if (!(cam->sqrt_spp >= 1 && cam->sqrt_spp < 4096 && cam->bounce_limit >= 1)) return MORT_ERR_UNSUPPORTED;
+        if (c->wave_ok && c->fast_ok && cam->light_obj_type == -1) fam = FAM_WAVE;
+        else if (gen_reach) fam = FAM_WAVE_GEN;
+        else return MORT_ERR_UNSUPPORTED;
+        return MORT_OK;
+    }
+    const bool use_fast = c->fast_ok && cam->light_obj_type == -1 && state_ok;
+    /* the unified-tree megakernel: worlds without reference BVHs.  Small worlds stay on the one-lane-per-pixel kernel: scanning a
+     * dozen primitives in lockstep keeps every lane busy, a tree walk scheduled by state does not (Cornell box 800x800x100: 53 ms
+     * vs 83 ms) */
+    bool use_gen = !use_fast && state_ok && gen_reach;
+    if (use_gen) {
+        int min_prims = 48;
+        if (const char *mp = std::getenv("MORT_GEN_MIN_PRIMS")) min_prims = std::atoi(mp);
+        if (c->gen_prims < min_prims) use_gen = false;
+    }
+    if (mode == MORT_MODE_THROUGHPUT) {
+        if (!(use_fast || use_gen) || seg_px) return MORT_ERR_UNSUPPORTED; /* the two LDS state-machine kernels only */
+        if (!c->seed_known) return MORT_ERR_NO_RNG;
+        if ((long long)c->rng_local_rows * cam->sqrt_spp >= 32768ll * 64) return MORT_ERR_CAPACITY;
+    }
+    fam = use_fast ? FAM_BVH : use_gen ? FAM_GEN : FAM_MEGA;
+    return MORT_OK;
+}
+
+#ifdef MORT_PROFILE_STATES
+/* profile builds: the state counters of the launch (mega_bvh.h, mega_gen.hip, wave_bvh.h PROF_*) */
+static void print_profile(const mort_ctx *c, RenderFamily fam, const unsigned long long *cnt) {
+    if (fam == FAM_WAVE || fam == FAM_WAVE_GEN) {
+        const char *nm[3] = {"T", "L", "F"};
+        const double tot = (double)(cnt[12] + cnt[13] + cnt[14] + cnt[15]);
+        for (int k = 0; k < 3; k++)
+            std::fprintf(stderr, "[wf_trav %s] %10llu wave-steps  util %5.1f%%  cycles %5.1f%% (%.0f/step)\n", nm[k], cnt[4 + k],
+                         cnt[4 + k] ? 100.0 * (double)cnt[8 + k] / (64.0 * (double)cnt[4 + k]) : 0.0, 100.0 * (double)cnt[12 + k] / tot,
+                         cnt[4 + k] ? (double)cnt[12 + k] / (double)cnt[4 + k] : 0.0);
+        std::fprintf(stderr, "[wf_trav sched] cycles %5.1f%%   fronts %d\n", 100.0 * (double)cnt[15] / tot, c->wf_fronts);
+        std::fprintf(stderr, "[wf_trav waves] %llu waves, mean lifetime %.1f us, in-loop cycles per wave %.0f\n", cnt[21],
+                     cnt[21] ? (double)cnt[20] / (double)cnt[21] * 0.01 : 0.0, cnt[21] ? tot / (double)cnt[21] : 0.0);
+    } else if (fam == FAM_GEN) {
+        const char *nm[4] = {"T", "L", "M", "S"};
+        unsigned long long segs = cnt[0];
+        for (int k = 0; k < 32; k++) segs += cnt[32 + 2 * k];
+        const double tot = (double)(cnt[12] + cnt[13] + cnt[14] + cnt[15] + cnt[16]);
+        for (int k = 0; k < 4; k++)
+            std::fprintf(stderr, "[gen %s] %12llu wave-steps  lanes %5.1f%%  cycles %5.1f%% (%.0f/step)\n", nm[k], cnt[4 + 2 * k],
+                         cnt[4 + 2 * k] ? 100.0 * (double)cnt[5 + 2 * k] / (64.0 * (double)cnt[4 + 2 * k]) : 0.0, 100.0 * (double)cnt[12 + k] / tot,
+                         cnt[4 + 2 * k] ? (double)cnt[12 + k] / (double)cnt[4 + 2 * k] : 0.0);
+        std::fprintf(stderr, "[gen S parts, cycles per S step] scan+decode %.0f  shade call %.0f  stack store %.0f  finish %.0f  newpix %.0f  newray %.0f\n", (double)cnt[24] / (double)cnt[10],
+                     (double)cnt[25] / (double)cnt[10], (double)cnt[20] / (double)cnt[10], (double)cnt[21] / (double)cnt[10], (double)cnt[22] / (double)cnt[10], (double)cnt[23] / (double)cnt[10]);
+        std::fprintf(stderr, "[gen sched] cycles %5.1f%%; leaf loop: %.2f iterations per L step, %.1f lanes per iteration; scans %llu; steps per segment: T %.2f L %.2f M %.2f S %.2f\n",
+                     100.0 * (double)cnt[16] / tot, cnt[6] ? (double)cnt[17] / (double)cnt[6] : 0.0, cnt[17] ? (double)cnt[18] / (double)cnt[17] : 0.0, cnt[3],
+                     (double)cnt[5] / (double)(segs + 1), (double)cnt[7] / (double)(segs + 1), (double)cnt[9] / (double)(segs + 1), (double)cnt[11] / (double)(segs + 1));
+    } else if (fam == FAM_BVH) {
+        const char *nm[3] = {"T", "L", "S"};
+        for (int k = 0; k < 3; k++)
+            std::fprintf(stderr, "[states] %s: %llu wave-steps, %llu lane-steps, utilisation %.1f%%\n", nm[k], cnt[4 + 2 * k], cnt[5 + 2 * k],
+                         cnt[4 + 2 * k] ? 100.0 * (double)cnt[5 + 2 * k] / (64.0 * (double)cnt[4 + 2 * k]) : 0.0);
+        std::fprintf(stderr, "[states] box-step runs: %llu (%.1f steps per run)\n", cnt[30], cnt[30] ? (double)cnt[4] / (double)cnt[30] : 0.0);
+        const double tot = (double)(cnt[10] + cnt[11] + cnt[12] + cnt[13]);
+        std::fprintf(stderr, "[cycles] T %.1f%% (%.0f/step)  L %.1f%% (%.0f/step)  S %.1f%% (%.0f/step)  sched %.1f%%  total wave-cycles %.3g\n",
+                     100.0 * cnt[10] / tot, (double)cnt[10] / (double)cnt[4], 100.0 * cnt[11] / tot, (double)cnt[11] / (double)cnt[6],
+                     100.0 * cnt[12] / tot, (double)cnt[12] / (double)cnt[8], 100.0 * cnt[13] / tot, tot);
+#ifdef MORT_PROFILE_FINE
+        std::fprintf(stderr, "[S shade parts, cycles/step] verify %.0f  hit record %.0f  metal %.0f  dielectric %.0f  lambert texture %.0f  lambert scatter %.0f  light %.0f  (rest of 'shade' below: stack store)\n",
+                     (double)cnt[18] / (double)cnt[8], (double)cnt[19] / (double)cnt[8], (double)cnt[20] / (double)cnt[8], (double)cnt[21] / (double)cnt[8],
+                     (double)cnt[22] / (double)cnt[8], (double)cnt[23] / (double)cnt[8], (double)cnt[24] / (double)cnt[8]);
+#else
+        const char *bn[6] = {"metal", "dielectric", "lambertian", "finish", "get_ray", "unwind iteration"};
+        for (int k = 0; k < 6; k++)
+            std::fprintf(stderr, "[S branch] %-16s entered in %5.1f%% of S steps (x%.2f), %4.1f lanes when entered\n", bn[k],
+                         100.0 * (double)cnt[18 + 2 * k] / (double)cnt[8], (double)cnt[18 + 2 * k] / (double)cnt[8],
+                         cnt[18 + 2 * k] ? (double)cnt[19 + 2 * k] / (double)cnt[18 + 2 * k] : 0.0);
+#endif
+        std::fprintf(stderr, "[S parts, cycles/step] shade %.0f  finish %.0f  newpix %.0f  newsample+setup %.0f\n", (double)cnt[14] / (double)cnt[8],
+                     (double)cnt[15] / (double)cnt[8], (double)cnt[16] / (double)cnt[8], (double)cnt[17] / (double)cnt[8]);
+    }
+}
+#endif
+
+/* the statistics of a render, once its stop event has been recorded */
+static int collect_stats(mort_ctx *c, const LaunchPlan &plan, int W, int local_rows, int sqrt_spp, bool has_accum, mort_stats *stats) {
+    HIPCHK(c, hipEventSynchronize(c->ev1));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    unsigned long long cnt[96] = {0};
+    HIPCHK(c, hipMemcpy(cnt, c->d_counters, sizeof cnt, hipMemcpyDeviceToHost));
+#ifdef MORT_PROFILE_STATES
+    print_profile(c, plan.fam, cnt);
+#endif
+    const bool wave = plan.fam == FAM_WAVE || plan.fam == FAM_WAVE_GEN;
+    std::memset(stats, 0, sizeof *stats);
+    stats->seconds = ms * 1e-3;
+    for (int k = 0; k < 32; k++) { cnt[0] += cnt[32 + 2 * k]; cnt[1] += cnt[33 + 2 * k]; } /* BVH megakernel: per-workgroup slots */
+    stats->segments = cnt[0];
+    stats->rng_draws = cnt[1];
+    stats->reference_walks = (plan.fam == FAM_BVH || plan.fam == FAM_GEN) ? cnt[3] : 0;
+    stats->pixels = (uint64_t)W * (uint64_t)local_rows;
+    stats->eff_samples = stats->pixels * (uint64_t)(sqrt_spp * sqrt_spp);
+    stats->algorithmic_hbm_bytes = stats->pixels * (uint64_t)(100 + (has_accum ? 12 : 0));
+    stats->scene_in_lds = plan.fam != FAM_MEGA ? 1 : 0;
+    if (wave) stats->algorithmic_hbm_bytes += 240ull * stats->segments; /* wave_bvh.h: per-segment record traffic */
+    stats->local_rows = local_rows;
+    std::snprintf(stats->kernel_name, sizeof stats->kernel_name, "%s", plan.name);
+    hipFuncAttributes fattr;
+    if (hipFuncGetAttributes(&fattr, plan.kernel) == hipSuccess) {
+        stats->kernel_vgprs = fattr.numRegs;
+        stats->kernel_lds_bytes = plan.lds_bytes >= 0 ? plan.lds_bytes : (int)fattr.sharedSizeBytes;
+    }
+    return MORT_OK;
+}
+
 /* d_segpx: per-pixel segment counts for the packed owned rows, or null.  Only mort_hip_render passes one (sized for
  * THIS image and partition); the public device entry never does, so a buffer left over from an earlier, smaller
  * render can not be written past its end. */
-static int ensure_buf(mort_ctx *c, void **p, size_t *cap, size_t need);
 static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, void *d_rgba, void *d_accum, uint32_t *d_segpx,
                               void *stream, mort_stats *stats) {
     if (!c || !cam || !d_rgba) return MORT_ERR_INVALID;
@@ -619,6 +909,8 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
     if (!c->d_states || c->rng_w != W || c->rng_h != H) return MORT_ERR_NO_RNG;
     int st = check_light(c, cam->light_obj_type, cam->light_obj_idx);
     if (st != MORT_OK) return st;
+    LaunchPlan plan = {FAM_MEGA, (const void *)mega_kernel, 256, -1, "mega_kernel"};
+    if ((st = choose_family(c, cam, mode, d_segpx != nullptr, plan.fam)) != MORT_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     /* a render still running on another stream uses the same states and counters */
@@ -639,419 +931,35 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
 
     HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 96 * sizeof(unsigned long long), s));
     /* MORT_MODE_THROUGHPUT: the launch covers a virtual image of local_rows * sqrt_spp rows (mega_bvh.h FastArgs.sub) */
-    const bool substream = mode == MORT_MODE_THROUGHPUT;
-    const int tiles = ((W + 7) / 8) * (((substream ? a.local_rows * (cam->sqrt_spp > 0 ? cam->sqrt_spp : 1) : a.local_rows) + 7) / 8);
-    const int waves_per_block = 4;
-    const int blocks = (tiles + waves_per_block - 1) / waves_per_block;
-    const char *force = std::getenv("MORT_FORCE_GENERIC");
-    const bool use_fast = c->fast_ok && cam->light_obj_type == -1 && cam->sqrt_spp >= 1 && cam->sqrt_spp < 32768 && cam->bounce_limit >= 1 &&
-                          W < 65536 && H < 32768 &&
-                          !(force && force[0] == '1');
-    /* the unified-tree megakernel (mega_gen.hip): worlds without reference BVHs; the camera must lie where the tree's
-     * pads were sized for (scene_compile.h build_unified) */
-    bool use_gen = c->gen_ok && !use_fast && cam->sqrt_spp >= 1 && cam->sqrt_spp < 32768 && cam->bounce_limit >= 1 && W < 65536 && H < 32768 &&
-                   !(force && force[0] == '1');
-    /* small worlds stay on the one-lane-per-pixel kernel: scanning a dozen primitives in lockstep keeps every lane busy,
-     * a tree walk scheduled by state does not (Cornell box 800x800x100: 53 ms vs 83 ms) */
-    if (use_gen) {
-        int min_prims = 48;
-        if (const char *mp = std::getenv("MORT_GEN_MIN_PRIMS")) min_prims = std::atoi(mp);
-        if (c->gen_prims < min_prims) use_gen = false;
-    }
-    if (use_gen) {
-        const float rad = std::fabs(cam->defocus_disk_u.e[0]) + std::fabs(cam->defocus_disk_u.e[1]) + std::fabs(cam->defocus_disk_u.e[2]) +
-                          std::fabs(cam->defocus_disk_v.e[0]) + std::fabs(cam->defocus_disk_v.e[1]) + std::fabs(cam->defocus_disk_v.e[2]);
-        for (int k = 0; k < 3; k++) {
-            const float v = cam->center.e[k];
-            if (!(v - rad >= c->gen_lo[k] - c->gen_reach && v + rad <= c->gen_hi[k] + c->gen_reach)) use_gen = false;
-        }
-    }
-    int lds_bytes_used = 0, gen_block_used = 0;
-    const void *fast_kernel_used = nullptr;
-    char kname[64] = "mega_kernel";
-    /* the wavefront pipeline: wave_bvh.h for one reference BVH of spheres as the world (no light object), wave_gen.hip for
-     * every world with a unified tree (lights, quads, instances, media); anything else is not supported in this mode */
-    const bool wave_bvh = c->wave_ok && c->fast_ok && cam->light_obj_type == -1;
-    bool wave_gen = false;
-    if (mode == MORT_MODE_WAVE) {
-        if (!(cam->sqrt_spp >= 1 && cam->sqrt_spp < 4096 && cam->bounce_limit >= 1)) return MORT_ERR_UNSUPPORTED;
-        if (!wave_bvh) {
-            wave_gen = c->gen_ok;
-            const float rad = std::fabs(cam->defocus_disk_u.e[0]) + std::fabs(cam->defocus_disk_u.e[1]) + std::fabs(cam->defocus_disk_u.e[2]) +
-                              std::fabs(cam->defocus_disk_v.e[0]) + std::fabs(cam->defocus_disk_v.e[1]) + std::fabs(cam->defocus_disk_v.e[2]);
-            for (int k = 0; k < 3 && wave_gen; k++) {
-                const float v = cam->center.e[k];
-                if (!(v - rad >= c->gen_lo[k] - c->gen_reach && v + rad <= c->gen_hi[k] + c->gen_reach)) wave_gen = false;
-            }
-            if (!wave_gen) return MORT_ERR_UNSUPPORTED;
-        }
-    }
-    if (substream) {
-        if (!(use_fast || use_gen) || d_segpx) return MORT_ERR_UNSUPPORTED; /* the two LDS state-machine kernels only */
-        if (!c->seed_known) return MORT_ERR_NO_RNG;
-        if ((long long)a.local_rows * cam->sqrt_spp >= 32768ll * 64) return MORT_ERR_CAPACITY;
-        int st_s = ensure_substates(c, W, H, cam->sqrt_spp, s);
-        if (st_s != MORT_OK) return st_s;
-    }
+    const bool sub = mode == MORT_MODE_THROUGHPUT;
+    const int tiles = ((W + 7) / 8) * (((sub ? a.local_rows * cam->sqrt_spp : a.local_rows) + 7) / 8);
+    if (sub && (st = ensure_substates(c, W, H, cam->sqrt_spp, s)) != MORT_OK) return st;
     if (stats) HIPCHK(c, hipEventRecord(c->ev0, s));
-    if (blocks > 0 && mode == MORT_MODE_WAVE && wave_gen) {
-        GenArgs ga = c->gen;
-        ga.f.r = a;
-        ga.f.hot_src = (const unsigned char *)c->d_gen; ga.f.hot_bytes = c->gen_bytes;
-        ga.f.th_s = 32; ga.f.th_l = 24; ga.f.t_keep = 16; /* wf_trav_gen's retire+refill / leaf / box-run thresholds */
-        { const char *th = std::getenv("MORT_WAVE_THRESHOLDS"); /* "f,l,k" */
-          if (th) { int f_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &f_, &l_, &k_) == 3 && f_ >= 1 && l_ >= 1 && k_ >= 1) { ga.f.th_s = f_; ga.f.th_l = l_; ga.f.t_keep = k_; } } }
-        if (!c->h_live) HIPCHK(c, hipHostMalloc((void **)&c->h_live, 64));
-        WfGenHost hb;
-        int trav_block = 0;
-        hb.d_wf = &c->d_wf; hb.wf_bytes = &c->wf_bytes; hb.h_live = &c->h_live; hb.fronts = &c->wf_fronts; hb.num_cus = c->num_cus; hb.trav_block = &trav_block;
-        unsigned live_left = 0;
-        hipError_t e_w = mort_wave_gen_render(ga, hb, cam->bounce_limit, cam->sqrt_spp, s, &live_left);
-        if (e_w != hipSuccess) {
-            if (live_left) { c->last_error = "wavefront: front limit reached with live pixels"; return MORT_ERR_HIP; }
-            return hip_fail(c, e_w, "mort_wave_gen_render");
+    /* a rank that owns no rows launches nothing (and reports mega_kernel) */
+    if (tiles > 0) {
+        switch (plan.fam) {
+        case FAM_MEGA: hipLaunchKernelGGL(mega_kernel, dim3((tiles + 3) / 4), dim3(256), 0, s, a); HIPCHK(c, hipGetLastError()); break; /* four 8x8 tiles per group */
+        case FAM_BVH: st = launch_bvh(c, cam, a, tiles, sub, stats != nullptr, s, plan); break;
+        case FAM_GEN: st = launch_gen(c, cam, a, tiles, sub, stats != nullptr, s, plan); break;
+        case FAM_WAVE: st = launch_wave(c, cam, a, s, plan); break;
+        case FAM_WAVE_GEN: st = mort_wave_gen_render(c, cam, a, s, plan); break;
         }
-        lds_bytes_used = (int)c->gen_bytes;
-        std::snprintf(kname, sizeof kname, "wf_trav_gen<%d, %s>", trav_block, ga.prims_in_lds ? "true" : "false"); /* <BLOCK, PRIMS_LDS> */
-    } else if (blocks > 0 && mode == MORT_MODE_WAVE) {
-        int st_w = render_wavefront(c, a, cam, s);
-        if (st_w != MORT_OK) return st_w;
-        lds_bytes_used = (int)c->trav_bytes;
-        std::snprintf(kname, sizeof kname, "wf_trav<%d>", MORT_WF_BLOCK);
-    } else if (blocks > 0 && use_fast) {
-        FastArgs fa;
-        std::memset(&fa, 0, sizeof fa);
-        fa.r = a;
-        fa.hot_src = (const unsigned char *)c->d_fast; fa.hot_bytes = c->fast_bytes;
-        fa.off_nodes4 = c->f_nodes4; fa.off_leafrecs = c->f_leafrecs; fa.off_lambert = c->f_lambert; fa.off_metal = c->f_metal;
-        fa.off_diel = c->f_diel; fa.off_dlight = c->f_dlight; fa.off_iso = c->f_iso; fa.off_solid = c->f_solid; fa.off_checker = c->f_checker;
-        fa.node_first = 0; fa.node_count = c->sc.n_nodes; /* the reference's threaded nodes (HBM): fallback walk */
-        fa.next_q = (unsigned int *)(c->d_counters + 2);
-        fa.tiles_x = (W + 7) / 8; fa.tiles_total = tiles;
-        if (substream) { fa.sub = cam->sqrt_spp; fa.vaccum = c->d_vaccum; fa.r.states = c->d_substates; }
-        const long long lanes_wanted = (long long)tiles * 64;
-        const double px_per_lane = (double)lanes_wanted / ((double)c->num_cus * 768.0);
-        /* workgroup size.  Two pixels per lane or more: 1024 threads, compiled for 128 registers = 16 waves per CU.  A wave issues a
-         * dependent vector instruction every ~8 cycles and an independent one every ~5 (calibration), a SIMD can issue one
-         * every ~1.2: a fourth wave per SIMD is worth more than the 24 registers the 1024-thread build keeps in private memory, all of
-         * them touched in the shade step only (Scene 1: 103.7 ms against 111.9 ms with 768 threads at 153 registers).
-         * Otherwise the largest of {768, 512, 384, 256} that still gives every CU a workgroup
-         * (a rank of an 8-way partition owns ~100 k pixels: 768-thread groups would leave half the CUs idle) */
-        int FB = MORT_FAST_BLOCK;
-        const char *fb_env = std::getenv("MORT_FAST_BLOCK_SIZE");
-        if (fb_env) FB = std::atoi(fb_env);
-        else {
-            const int cand[4] = {768, 512, 384, 256};
-            FB = 256;
-            const bool wide_ok = lanes_wanted >= 2ll * 1024 * c->num_cus;
-            /* about one pixel per lane or fewer: the frame is as long as its longest pixel chain, so take the drain kernels that are
-             * compiled without spills (<= 512 threads; one rank of 4 at 1200x675: 81 ms vs 90 ms with 768) */
-            for (int k = (px_per_lane < 1.5 && !substream) ? 1 : 0; k < 4; k++) if (lanes_wanted >= (long long)cand[k] * c->num_cus) { FB = cand[k]; break; }
-            if (wide_ok) FB = 1024;
-        }
-        /* 1024 threads: image + traversal stacks + one bounce-stack level per lane must fit one CU's LDS, else the widest shape that does */
-        if (FB == 1024 && (size_t)((fa.hot_bytes + 15u) & ~15u) + (size_t)c->own4_stack * 1024u * 2u + 2048u + 1024u * 16u > 160u * 1024u) FB = 768;
-        fa.lane_cap = 64;
-        { const char *lc = std::getenv("MORT_LANE_CAP"); if (lc && std::atoi(lc) >= 1 && std::atoi(lc) <= 64) fa.lane_cap = std::atoi(lc); }
-        fa.drain_rounds = 3; /* batch thresholds as shares of the wave's LIVE lanes (they differ from fixed counts only once lanes have run out of pixels: the tail of a frame;
-                              * three runs each, one box: N = 1 100.1-100.5 vs 100.3-102.9 ms, a rank of 2 75.6-78.6 vs 77.6-82.2 ms, ranks of 4 / 8 unchanged); DRAIN kernels
-                              * also follow the lane furthest behind (round 2).  MORT_BVH_DRAIN: 0 / 1 = fixed counts, 2 = rounds, 3 = this */
-        { const char *dm = std::getenv("MORT_BVH_DRAIN"); if (dm) fa.drain_rounds = std::atoi(dm) == 2 ? 1 : std::atoi(dm) == 3 ? 3 : 0; }
-        void (*kern)(const FastArgs) = nullptr, (*kern_probe)(const FastArgs) = nullptr;
-        /* chain-bound partition (about one pixel per lane or fewer): drain mode + spread fetches (mega_bvh.h) */
-        bool chain_bound = px_per_lane < 1.5 && !substream;
-        { const char *cb = std::getenv("MORT_CHAIN_BOUND"); if (cb && !substream) chain_bound = cb[0] == '1'; }
-        switch (FB) {
-        case 1024: kern = mega_bvh_kernel<1024, false, false>; kern_probe = mega_bvh_kernel<1024, true, false>; chain_bound = false; break; /* no drain variant: chain-bound partitions take <= 512 threads */
-        case 768: kern = chain_bound ? mega_bvh_kernel<768, false, true> : mega_bvh_kernel<768, false, false>; kern_probe = mega_bvh_kernel<768, true, false>; break;
-        case 512: kern = chain_bound ? mega_bvh_kernel<512, false, true> : mega_bvh_kernel<512, false, false>; kern_probe = mega_bvh_kernel<512, true, false>; break;
-        case 384: kern = chain_bound ? mega_bvh_kernel<384, false, true> : mega_bvh_kernel<384, false, false>; kern_probe = mega_bvh_kernel<384, true, false>; break;
-        default: FB = 256; kern = chain_bound ? mega_bvh_kernel<256, false, true> : mega_bvh_kernel<256, false, false>; kern_probe = mega_bvh_kernel<256, true, false>; break;
-        }
-        if (substream) /* <BLOCK, PROBE, DRAIN, SUB> */
-            kern = FB == 1024 ? mega_bvh_kernel<1024, false, false, true> : FB == 768 ? mega_bvh_kernel<768, false, false, true> : FB == 512 ? mega_bvh_kernel<512, false, false, true>
-                   : FB == 384 ? mega_bvh_kernel<384, false, false, true> : mega_bvh_kernel<256, false, false, true>;
-        /* scheduling thresholds (mega_bvh.h).  Smaller batches do not help a chain-bound partition: measured on
-         * one rank of 8, (32,24,16) 100 ms, (12,12,8) 126 ms, (2,2,2) 192 ms -- a lane waits through every step
-         * its wave runs for other lanes, and small batches mean more of those */
-        {
-            fa.th_s = MORT_TH_S; fa.th_l = MORT_TH_L; fa.t_keep = MORT_T_KEEP;
-            const char *th = std::getenv("MORT_THRESHOLDS"); /* "s,l,k" */
-            if (th) { int s_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &s_, &l_, &k_) == 3 && s_ >= 1 && l_ >= 1 && k_ >= 1) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; } }
-        }
-        /* LDS: hot blob + as many bounce-stack levels per lane as fit next to it (768 threads: one workgroup per CU) */
-        const uint32_t tstack_off = (fa.hot_bytes + 15u) & ~15u; /* traversal stacks: [levels][thread] u16 (four-wide: the world's own bound, at most MORT_OWN4_STACK) */
-        const uint32_t stack_off = tstack_off + (uint32_t)c->own4_stack * (uint32_t)FB * 2u; /* as many levels as this world's tree can have pending */
-        fa.off_tstack = tstack_off;
-        uint32_t static_lds = 1024; /* the kernel's own __shared__ objects come out of the same 160 KB */
-        { hipFuncAttributes fattr; if (hipFuncGetAttributes(&fattr, (const void *)kern) == hipSuccess) static_lds = (uint32_t)((fattr.sharedSizeBytes + 1023) & ~(size_t)1023); }
-        int groups_per_cu = FB >= 768 ? 1 : 768 / FB; /* keep 12 waves per CU */
-        while (groups_per_cu > 1 && (long long)(stack_off + static_lds) * groups_per_cu > 160ll * 1024) groups_per_cu--;
-        long long room = (160ll * 1024 - (long long)static_lds * groups_per_cu) / groups_per_cu - (long long)stack_off;
-        if (room < 0) { c->last_error = "BVH image does not fit one CU's LDS"; return MORT_ERR_CAPACITY; }
-        int dl = (int)(room / ((long long)FB * 16));
-        if (dl > 12) dl = 12;
-        fa.off_stack = stack_off; fa.stack_lds_depth = dl;
-        const size_t lds_bytes = (size_t)stack_off + (size_t)dl * FB * 16;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, FB, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
-        { const char *pc = std::getenv("MORT_FAST_BLOCKS_PER_CU"); if (pc && std::atoi(pc) >= 1 && std::atoi(pc) < per_cu) per_cu = std::atoi(pc); }
-        int grid = c->num_cus * per_cu;
-        const int want_blocks = (int)((lanes_wanted + FB - 1) / FB);
-        if (grid > want_blocks) grid = want_blocks;
-        if (grid < 1) grid = 1;
-        lds_bytes_used = (int)lds_bytes;
-        fast_kernel_used = (const void *)kern;
-        { /* bounce-stack levels that do not fit in LDS: [level - dl][lane of the launch] in HBM */
-            const int deep_levels = cam->bounce_limit > dl ? cam->bounce_limit - dl : 0;
-            int st_d = ensure_buf(c, &c->d_deep, &c->deep_cap, (size_t)(deep_levels > 0 ? deep_levels : 1) * (size_t)grid * (size_t)FB * sizeof(float4));
-            if (st_d != MORT_OK) return st_d;
-            fa.deep = (float4 *)c->d_deep;
-            fa.wave_log = nullptr;
-            if (std::getenv("MORT_WAVE_LINES")) { /* profile builds: 16 words per wave, read back by mort_hip_debug_wave_log */
-                c->wave_log_waves = (size_t)grid * (size_t)(FB / 64);
-                if (ensure_buf(c, &c->d_wave_log, &c->wave_log_cap, c->wave_log_waves * 16 * sizeof(unsigned long long)) == MORT_OK) {
-                    hipMemsetAsync(c->d_wave_log, 0, c->wave_log_waves * 16 * sizeof(unsigned long long), s);
-                    fa.wave_log = (unsigned long long *)c->d_wave_log;
-                }
-            }
-        }
-        std::snprintf(kname, sizeof kname, "mega_bvh_kernel<%d, false, %s, %s>", FB, chain_bound ? "true" : "false", substream ? "true" : "false");
-        /* ---- tile order: expensive tiles first (sub-stream launches: work items are a stratum row, 1/sqrt_spp of a pixel -- no long tail to order away) ---- */
-        if (!substream && !std::getenv("MORT_NO_TILE_ORDER") && tiles >= 4 * grid) {
-            int st_o = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, chain_bound, s, [&](const FastArgs &pa) {
-                hipError_t e_ = hipFuncSetAttribute((const void *)kern_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                if (e_ != hipSuccess) return e_;
-                hipLaunchKernelGGL(kern_probe, dim3(grid), dim3(FB), lds_bytes, s, pa);
-                return hipGetLastError();
-            });
-            if (st_o != MORT_OK) return st_o;
-            if (stats) HIPCHK(c, hipEventRecord(c->ev0, s)); /* time the frame itself; ordering upkeep is reported by wall-clock benches */
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(FB), lds_bytes, s, fa);
-        HIPCHK(c, hipGetLastError());
-        if (substream) {
-            const int npx = W * a.local_rows;
-            hipLaunchKernelGGL(substream_resolve_kernel, dim3((npx + 255) / 256), dim3(256), 0, s, (const float *)c->d_vaccum, W, a.local_rows, cam->sqrt_spp,
-                               a.pixel_samples_scale, (uchar4 *)d_rgba, (float *)d_accum);
+        if (st != MORT_OK) return st;
+        if (sub) { /* the stratum rows of each pixel summed in order, then Camera::render's tail */
+            hipLaunchKernelGGL(substream_resolve_kernel, dim3((W * a.local_rows + 255) / 256), dim3(256), 0, s, (const float *)c->d_vaccum, W, a.local_rows,
+                               cam->sqrt_spp, a.pixel_samples_scale, a.rgba, a.accum);
             HIPCHK(c, hipGetLastError());
         }
-    } else if (blocks > 0 && use_gen) {
-        GenArgs ga;
-        std::memset(&ga, 0, sizeof ga);
-        ga = c->gen; /* LDS image offsets, root, far-ray constants (upload_world) */
-        FastArgs &fa = ga.f;
-        fa.r = a;
-        fa.hot_src = (const unsigned char *)c->d_gen; fa.hot_bytes = c->gen_bytes;
-        fa.next_q = (unsigned int *)(c->d_counters + 2);
-        fa.tiles_x = (W + 7) / 8; fa.tiles_total = tiles;
-        if (substream) { fa.sub = cam->sqrt_spp; fa.vaccum = c->d_vaccum; fa.r.states = c->d_substates; }
-        const long long lanes_wanted = (long long)tiles * 64;
-        int FB = 768;
-        bool heavy_default = false;
-        { const char *fb_env = std::getenv("MORT_GEN_BLOCK_SIZE");
-          if (fb_env && !substream) FB = std::atoi(fb_env);
-          else { /* many pixels per lane: 1024 threads compiled for 128 registers = four waves per SIMD, which pays for its spills as in the BVH
-                  * kernel (4096 x 4096 x 4: 126.6 ms, 768 threads at 160 registers 137.5 ms, 512 threads 181 ms; 1920 x 1080 x 49: 173 vs 175 ms).
-                  * With a handful of pixels per lane the frame ends with its longest pixel chains, whose rounds are faster with two waves per
-                  * SIMD and no spills (final scene 800 x 800 x 961: 3.07 s with 512 threads, 3.21 s with 1024); fewer pixels than lanes:
-                  * 256-thread groups so every CU has work */
-                 const double ppl = (double)lanes_wanted / ((double)c->num_cus * 768.0);
-                 FB = ppl >= 8.0 ? 1024 : (lanes_wanted >= 512ll * c->num_cus) ? 512 : 256;
-                 /* fewer pixels per lane: the frame may be bound by its longest pixel chains, and then HEAVY WAVES pay (below): 1024 threads, the launch decides on the device */
-                 if (ppl < 8.0 && lanes_wanted >= 32ll * 1024 && !std::getenv("MORT_GEN_NO_HEAVY")) { FB = 1024; heavy_default = true; } } }
-        if (FB != 1024 && FB != 768 && FB != 512 && FB != 256) FB = 256;
-        if (FB == 1024 && (size_t)c->gen_bytes + 16u + (size_t)MORT_OWN_STACK * 1024u * 2u + 2048u > 160u * 1024u) FB = 768; /* image + traversal stacks of 1024 threads must fit */
-        if (substream && FB > 512) FB = 512; /* the non-parity launch is instantiated for 512- and 256-thread workgroups */
-        /* swept on the final scene, 800x800x100 (scripts/th_sweep.py, 180 settings): 373 ms here vs 449 ms with the BVH kernel's (40,24,12) and m = 24 */
-        fa.th_s = 28; fa.th_l = 20; fa.t_keep = 4; ga.th_m = 56;
-        fa.lane_cap = 64;
-        { const char *lc = std::getenv("MORT_LANE_CAP"); if (lc && std::atoi(lc) >= 1 && std::atoi(lc) <= 64) fa.lane_cap = std::atoi(lc); }
-        /* heavy waves (mega_bvh.h FastArgs.heavy_*): "mod,num,cap,percent" */
-        fa.heavy_mod = 0; fa.heavy_num = 0; fa.heavy_cap = 64; c->heavy_percent = 50;
-        /* default where the frame has fewer than 8 pixels per lane: two waves of three take 12 lanes each from the tiles whose longest pixel reaches half of the frame's
-         * longest -- IF the device finds the frame chain-bound (tile_sort.hip heavy_count_kernel); final scene 800x800x961: 3.04 -> 2.55 s, x100: 318 -> 270 ms */
-        if (heavy_default && FB == 1024 && !substream) { fa.heavy_mod = 3; fa.heavy_num = 2; fa.heavy_cap = 12; }
-        { const char *hv = std::getenv("MORT_GEN_HEAVY"); int m_ = 0, n_ = 0, k_ = 0, p_ = 0;
-          if (hv && !substream && std::sscanf(hv, "%d,%d,%d,%d", &m_, &n_, &k_, &p_) == 4 && m_ >= 1 && n_ >= 1 && n_ <= m_ && k_ >= 1 && k_ <= 64 && p_ >= 1 && p_ <= 100) {
-              fa.heavy_mod = m_; fa.heavy_num = n_; fa.heavy_cap = k_; c->heavy_percent = p_; } }
-        ga.drain_mode = 3; /* thresholds as shares of the live lanes; measured alternatives: 0 = fixed counts, 1 = follow one lane, 2 = rounds */
-        { const char *dm = std::getenv("MORT_GEN_DRAIN"); if (dm && std::atoi(dm) >= 0 && std::atoi(dm) <= 3) ga.drain_mode = std::atoi(dm); } /* other values: the default */
-        /* thresholds below 1 are refused: with t_keep < 1 a box-step loop whose lanes have all left the tree would never end */
-        { const char *th = std::getenv("MORT_GEN_THRESHOLDS"); /* "s,l,k,m" */
-          if (th) { int s_ = 0, l_ = 0, k_ = 0, m_ = 0; if (std::sscanf(th, "%d,%d,%d,%d", &s_, &l_, &k_, &m_) == 4 && s_ >= 1 && l_ >= 1 && k_ >= 1 && m_ >= 1) { fa.th_s = s_; fa.th_l = l_; fa.t_keep = k_; ga.th_m = m_; } } }
-        const uint32_t tstack_off = (c->gen_bytes + 15u) & ~15u;
-        const uint32_t stack_off = tstack_off + (uint32_t)MORT_OWN_STACK * (uint32_t)FB * 2u;
-        fa.off_tstack = tstack_off;
-        uint32_t static_lds = 1024; /* the kernel's own __shared__ objects come out of the same 160 KB */
-        { hipFuncAttributes fattr; if (mort_gen_attributes(FB, ga.prims_in_lds != 0, &fattr, substream) == hipSuccess) static_lds = (uint32_t)((fattr.sharedSizeBytes + 1023) & ~(size_t)1023); }
-        /* workgroups per CU: as many as keep 12 waves per CU, but a big image (the final scene's 120 KB) admits one */
-        int groups_per_cu = (FB == 512 || FB == 1024) ? 1 : 768 / FB;
-        while (groups_per_cu > 1 && (long long)(stack_off + static_lds) * groups_per_cu > 160ll * 1024) groups_per_cu--;
-        long long room = (160ll * 1024 - (long long)static_lds * groups_per_cu) / groups_per_cu - (long long)stack_off;
-        if (room < 0) { c->last_error = "unified-tree image does not fit one CU's LDS"; return MORT_ERR_CAPACITY; }
-        int dl = (int)(room / ((long long)FB * 16));
-        if (dl > 12) dl = 12;
-        { const char *de = std::getenv("MORT_GEN_DL"); if (de && std::atoi(de) < dl) dl = std::atoi(de) > 0 ? std::atoi(de) : 0; } /* a negative count would shrink the LDS below the traversal stacks */
-        fa.off_stack = stack_off; fa.stack_lds_depth = dl;
-        const size_t lds_bytes = (size_t)stack_off + (size_t)dl * FB * 16;
-        int per_cu = mort_gen_blocks_per_cu(FB, ga.prims_in_lds != 0, lds_bytes, substream);
-        if (per_cu < 1) per_cu = 1;
-        int grid = c->num_cus * per_cu;
-        const int want_blocks = (int)((lanes_wanted + FB - 1) / FB);
-        if (grid > want_blocks) grid = want_blocks;
-        if (grid < 1) grid = 1;
-        lds_bytes_used = (int)lds_bytes;
-        gen_block_used = FB;
-        { /* bounce-stack levels that do not fit in LDS: [level - dl][lane of the launch] in HBM */
-            const int deep_levels = cam->bounce_limit > dl ? cam->bounce_limit - dl : 0;
-            int st_d = ensure_buf(c, &c->d_deep, &c->deep_cap, (size_t)(deep_levels > 0 ? deep_levels : 1) * (size_t)grid * (size_t)FB * sizeof(float4));
-            if (st_d != MORT_OK) return st_d;
-            fa.deep = (float4 *)c->d_deep;
-            fa.wave_log = nullptr;
-            if (std::getenv("MORT_WAVE_LINES")) { /* profile builds: 16 words per wave, read back by mort_hip_debug_wave_log */
-                c->wave_log_waves = (size_t)grid * (size_t)(FB / 64);
-                if (ensure_buf(c, &c->d_wave_log, &c->wave_log_cap, c->wave_log_waves * 16 * sizeof(unsigned long long)) == MORT_OK) {
-                    hipMemsetAsync(c->d_wave_log, 0, c->wave_log_waves * 16 * sizeof(unsigned long long), s);
-                    fa.wave_log = (unsigned long long *)c->d_wave_log;
-                }
-            }
-        }
-        std::snprintf(kname, sizeof kname, substream ? "mega_gen_kernel<%d, %s, true>" : "mega_gen_kernel<%d, %s, false>", FB, ga.prims_in_lds ? "true" : "false"); /* as rocprofv3 prints it: <BLOCK, PRIMS_LDS, SUB> */
-        if (!substream && !std::getenv("MORT_NO_TILE_ORDER") && tiles >= 4 * grid) {
-            int st_o = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, false, s, [&](const FastArgs &pa) {
-                GenArgs pg = ga;
-                pg.f = pa;
-                pg.probe = 1;
-                return mort_gen_launch(pg, FB, grid, lds_bytes, s);
-            });
-            if (st_o != MORT_OK) return st_o;
-            if (stats) HIPCHK(c, hipEventRecord(c->ev0, s));
-            /* priority pixels (mega_bvh.h FastArgs): the head of the cost order, a few per wave.  A frame with a handful of pixels per lane
-             * ends when its longest pixel chain does (final scene 800x800: the fog ball's pixels run 8 x the mean), and a chain advances one
-             * segment per round of its wave: such a pixel must not share its wave with 63 others of its kind, and its wave must follow it */
-            int k_prio = 0; /* measured, not the default: following one lane starves the other 63 of a tile whose pixels are all long */
-            { const char *kp = std::getenv("MORT_GEN_PRIO_LANES"); if (kp) k_prio = std::atoi(kp); }
-            if (k_prio > 0 && ga.drain_mode == 1 && !substream) {
-                const long long waves = (long long)grid * (FB / 64);
-                long long pt = (waves * k_prio + 63) / 64;
-                if (pt > tiles / 4) pt = tiles / 4;
-                fa.prio_tiles = (int)pt; fa.prio_lanes = k_prio;
-            }
-        }
-        HIPCHK(c, mort_gen_launch(ga, FB, grid, lds_bytes, s));
-        if (fa.heavy_mod > 0 && c->d_prio_count && std::getenv("MORT_GEN_HEAVY_DEBUG")) { /* diagnostic: what the device decided for this launch */
-            unsigned h[4] = {0, 0, 0, 0};
-            HIPCHK(c, hipStreamSynchronize(s));
-            HIPCHK(c, hipMemcpy(h, c->d_prio_count, 16, hipMemcpyDeviceToHost));
-            std::fprintf(stderr, "[heavy] head tiles %u of %d, lanes %d\n", h[0], tiles, grid * FB);
-        }
-        if (fa.heavy_mod > 0 && c->d_prio_count) /* this frame's segment total, beside the tile costs it leaves for the next frame's order */
-            HIPCHK(c, hipMemcpyAsync(c->d_prio_count + 4, c->d_counters, 96 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
-        if (substream) {
-            const int npx = W * a.local_rows;
-            hipLaunchKernelGGL(substream_resolve_kernel, dim3((npx + 255) / 256), dim3(256), 0, s, (const float *)c->d_vaccum, W, a.local_rows, cam->sqrt_spp,
-                               a.pixel_samples_scale, (uchar4 *)d_rgba, (float *)d_accum);
-            HIPCHK(c, hipGetLastError());
-        }
-    } else if (blocks > 0) {
-        hipLaunchKernelGGL(mega_kernel, dim3(blocks), dim3(64 * waves_per_block), 0, s, a);
-        HIPCHK(c, hipGetLastError());
     }
-    if (stats) {
-        HIPCHK(c, hipEventRecord(c->ev1, s));
-        /* what the statistics need, by value: mort_hip_render_gather lets the frame gather follow the render on the stream
-         * and collects them after its one wait (c->defer_stats) */
-        const int sqrt_spp_ = cam->sqrt_spp, local_rows_ = a.local_rows;
-        const bool has_accum_ = d_accum != nullptr;
-        const std::string kname_ = kname;
-        auto fill = [=](mort_stats *stats) -> int {
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        unsigned long long cnt[96] = {0};
-        HIPCHK(c, hipMemcpy(cnt, c->d_counters, sizeof cnt, hipMemcpyDeviceToHost));
-#ifdef MORT_PROFILE_STATES
-        if (mode == MORT_MODE_WAVE) {
-            const char *nm[3] = {"T", "L", "F"};
-            const double tot = (double)(cnt[12] + cnt[13] + cnt[14] + cnt[15]);
-            for (int k = 0; k < 3; k++)
-                std::fprintf(stderr, "[wf_trav %s] %10llu wave-steps  util %5.1f%%  cycles %5.1f%% (%.0f/step)\n", nm[k], cnt[4 + k],
-                             cnt[4 + k] ? 100.0 * (double)cnt[8 + k] / (64.0 * (double)cnt[4 + k]) : 0.0, 100.0 * (double)cnt[12 + k] / tot,
-                             cnt[4 + k] ? (double)cnt[12 + k] / (double)cnt[4 + k] : 0.0);
-            std::fprintf(stderr, "[wf_trav sched] cycles %5.1f%%   fronts %d\n", 100.0 * (double)cnt[15] / tot, c->wf_fronts);
-            std::fprintf(stderr, "[wf_trav waves] %llu waves, mean lifetime %.1f us, in-loop cycles per wave %.0f\n", cnt[21],
-                         cnt[21] ? (double)cnt[20] / (double)cnt[21] * 0.01 : 0.0, cnt[21] ? tot / (double)cnt[21] : 0.0);
-        } else if (use_gen) {
-            const char *nm[4] = {"T", "L", "M", "S"};
-            unsigned long long segs = cnt[0];
-            for (int k = 0; k < 32; k++) segs += cnt[32 + 2 * k];
-            const double tot = (double)(cnt[12] + cnt[13] + cnt[14] + cnt[15] + cnt[16]);
-            for (int k = 0; k < 4; k++)
-                std::fprintf(stderr, "[gen %s] %12llu wave-steps  lanes %5.1f%%  cycles %5.1f%% (%.0f/step)\n", nm[k], cnt[4 + 2 * k],
-                             cnt[4 + 2 * k] ? 100.0 * (double)cnt[5 + 2 * k] / (64.0 * (double)cnt[4 + 2 * k]) : 0.0, 100.0 * (double)cnt[12 + k] / tot,
-                             cnt[4 + 2 * k] ? (double)cnt[12 + k] / (double)cnt[4 + 2 * k] : 0.0);
-            std::fprintf(stderr, "[gen S parts, cycles per S step] scan+decode %.0f  shade call %.0f  stack store %.0f  finish %.0f  newpix %.0f  newray %.0f\n", (double)cnt[24] / (double)cnt[10],
-                         (double)cnt[25] / (double)cnt[10], (double)cnt[20] / (double)cnt[10], (double)cnt[21] / (double)cnt[10], (double)cnt[22] / (double)cnt[10], (double)cnt[23] / (double)cnt[10]);
-            std::fprintf(stderr, "[gen sched] cycles %5.1f%%; leaf loop: %.2f iterations per L step, %.1f lanes per iteration; scans %llu; steps per segment: T %.2f L %.2f M %.2f S %.2f\n",
-                         100.0 * (double)cnt[16] / tot, cnt[6] ? (double)cnt[17] / (double)cnt[6] : 0.0, cnt[17] ? (double)cnt[18] / (double)cnt[17] : 0.0, cnt[3],
-                         (double)cnt[5] / (double)(segs + 1), (double)cnt[7] / (double)(segs + 1), (double)cnt[9] / (double)(segs + 1), (double)cnt[11] / (double)(segs + 1));
-        } else if (use_fast) {
-            const char *nm[3] = {"T", "L", "S"};
-            for (int k = 0; k < 3; k++)
-                std::fprintf(stderr, "[states] %s: %llu wave-steps, %llu lane-steps, utilisation %.1f%%\n", nm[k], cnt[4 + 2 * k], cnt[5 + 2 * k],
-                             cnt[4 + 2 * k] ? 100.0 * (double)cnt[5 + 2 * k] / (64.0 * (double)cnt[4 + 2 * k]) : 0.0);
-            std::fprintf(stderr, "[states] box-step runs: %llu (%.1f steps per run)\n", cnt[30], cnt[30] ? (double)cnt[4] / (double)cnt[30] : 0.0);
-            const double tot = (double)(cnt[10] + cnt[11] + cnt[12] + cnt[13]);
-            std::fprintf(stderr, "[cycles] T %.1f%% (%.0f/step)  L %.1f%% (%.0f/step)  S %.1f%% (%.0f/step)  sched %.1f%%  total wave-cycles %.3g\n",
-                         100.0 * cnt[10] / tot, (double)cnt[10] / (double)cnt[4], 100.0 * cnt[11] / tot, (double)cnt[11] / (double)cnt[6],
-                         100.0 * cnt[12] / tot, (double)cnt[12] / (double)cnt[8], 100.0 * cnt[13] / tot, tot);
-#ifdef MORT_PROFILE_FINE
-            std::fprintf(stderr, "[S shade parts, cycles/step] verify %.0f  hit record %.0f  metal %.0f  dielectric %.0f  lambert texture %.0f  lambert scatter %.0f  light %.0f  (rest of 'shade' below: stack store)\n",
-                         (double)cnt[18] / (double)cnt[8], (double)cnt[19] / (double)cnt[8], (double)cnt[20] / (double)cnt[8], (double)cnt[21] / (double)cnt[8],
-                         (double)cnt[22] / (double)cnt[8], (double)cnt[23] / (double)cnt[8], (double)cnt[24] / (double)cnt[8]);
-#else
-            {
-                const char *bn[6] = {"metal", "dielectric", "lambertian", "finish", "get_ray", "unwind iteration"};
-                for (int k = 0; k < 6; k++)
-                    std::fprintf(stderr, "[S branch] %-16s entered in %5.1f%% of S steps (x%.2f), %4.1f lanes when entered\n", bn[k],
-                                 100.0 * (double)cnt[18 + 2 * k] / (double)cnt[8], (double)cnt[18 + 2 * k] / (double)cnt[8],
-                                 cnt[18 + 2 * k] ? (double)cnt[19 + 2 * k] / (double)cnt[18 + 2 * k] : 0.0);
-            }
-#endif
-            std::fprintf(stderr, "[S parts, cycles/step] shade %.0f  finish %.0f  newpix %.0f  newsample+setup %.0f\n", (double)cnt[14] / (double)cnt[8],
-                         (double)cnt[15] / (double)cnt[8], (double)cnt[16] / (double)cnt[8], (double)cnt[17] / (double)cnt[8]);
-        }
-#endif
-        std::memset(stats, 0, sizeof *stats);
-        stats->seconds = ms * 1e-3;
-        for (int k = 0; k < 32; k++) { cnt[0] += cnt[32 + 2 * k]; cnt[1] += cnt[33 + 2 * k]; } /* BVH megakernel: per-workgroup slots */
-        stats->segments = cnt[0];
-        stats->rng_draws = cnt[1];
-        stats->reference_walks = ((use_fast || use_gen) && mode != MORT_MODE_WAVE) ? cnt[3] : 0;
-        stats->pixels = (uint64_t)W * (uint64_t)local_rows_;
-        stats->eff_samples = stats->pixels * (uint64_t)(sqrt_spp_ * sqrt_spp_);
-        stats->algorithmic_hbm_bytes = stats->pixels * (uint64_t)(100 + (has_accum_ ? 12 : 0));
-        stats->scene_in_lds = (use_fast || use_gen || mode == MORT_MODE_WAVE) ? 1 : 0;
-        if (mode == MORT_MODE_WAVE) stats->algorithmic_hbm_bytes += 240ull * stats->segments; /* wave_bvh.h: per-segment record traffic */
-        stats->local_rows = local_rows_;
-        std::snprintf(stats->kernel_name, sizeof stats->kernel_name, "%s", kname_.c_str());
-        hipFuncAttributes fattr;
-        const void *kf = (mode == MORT_MODE_WAVE && wave_gen) ? mort_wave_gen_trav_kernel(c->gen.prims_in_lds != 0, nullptr)
-                         : mode == MORT_MODE_WAVE ? (const void *)wf_trav<MORT_WF_BLOCK> : !use_fast ? (const void *)mega_kernel
-                         : fast_kernel_used;
-        const bool gen_ran = use_gen && mode != MORT_MODE_WAVE && gen_block_used > 0;
-        if ((gen_ran ? mort_gen_attributes(gen_block_used, c->gen.prims_in_lds != 0, &fattr, substream) : hipFuncGetAttributes(&fattr, kf)) == hipSuccess) {
-            stats->kernel_vgprs = fattr.numRegs;
-            stats->kernel_lds_bytes = (use_fast || gen_ran) ? lds_bytes_used : (int)fattr.sharedSizeBytes;
-        }
-            return MORT_OK;
-        };
-        if (c->defer_stats) { c->pending_stats = fill; return MORT_OK; }
-        return fill(stats);
-    }
-    return MORT_OK;
+    if (!stats) return MORT_OK;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    /* what the statistics need, by value: mort_hip_render_gather lets the frame gather follow the render on the stream
+     * and collects them after its one wait (c->defer_stats) */
+    const int local_rows = a.local_rows, sqrt_spp = cam->sqrt_spp;
+    const bool has_accum = d_accum != nullptr;
+    auto fill = [=](mort_stats *out) { return collect_stats(c, plan, W, local_rows, sqrt_spp, has_accum, out); };
+    if (c->defer_stats) { c->pending_stats = fill; return MORT_OK; }
+    return fill(stats);
 }
 
 /* diagnostic (not in include/mort_hip.h): the per-wave records of the last frame of a profile build run with MORT_WAVE_LINES=1 */
@@ -1120,14 +1028,6 @@ extern "C" int mort_hip_debug_own_tree(const mort_world *w, int *out) {
 extern "C" int mort_hip_render_device(mort_ctx *c, const mort_camera *cam, int mode, void *d_rgba, void *d_accum,
                                       void *stream, mort_stats *stats) {
     return render_device_impl(c, cam, mode, d_rgba, d_accum, nullptr, stream, stats);
-}
-
-static int ensure_buf(mort_ctx *c, void **p, size_t *cap, size_t need) {
-    if (*cap >= need && *p) return MORT_OK;
-    if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
-    HIPCHK(c, hipMalloc(p, need ? need : 16));
-    *cap = need;
-    return MORT_OK;
 }
 
 extern "C" int mort_hip_render(mort_ctx *c, const mort_camera *cam, int mode, uint8_t *rgba_out, float *accum_out,

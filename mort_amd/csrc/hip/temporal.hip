@@ -13,10 +13,6 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <pthread.h>
-#include <time.h>
-
-#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -42,8 +38,6 @@ __global__ void __launch_bounds__(FEAT_BX * FEAT_BY) tacc_kernel(const TaccArgs 
 /* ====================================================================== host */
 
 namespace {
-
-double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 /* tuned on scenes 1, 3 and 6, still and moving cameras */
 const mort_temporal_params kDefaults = {0, 32, 0.02f, 0.8f};
@@ -128,40 +122,14 @@ int temporal_args(const mort_temporal_params *p, const mort_camera *prev, const 
     return MORT_OK;
 }
 
-/* the host loop: rows handed out one at a time to `nthreads` host threads */
-struct RowJob {
-    std::atomic<int> next{0};
-    int rows = 0;
-    const TaccArgs *a = nullptr;
-    bool still = false;
-};
-void *row_worker(void *p) {
-    RowJob *j = (RowJob *)p;
-    for (;;) {
-        const int y = j->next.fetch_add(1);
-        if (y >= j->rows) break;
-        for (int x = 0; x < j->a->width; x++) {
-            if (j->still) tacc_pixel<true>(*j->a, x, y);
-            else tacc_pixel<false>(*j->a, x, y);
-        }
+/* the host loop: one row of tacc_pixel (run_rows) */
+struct TaccHostJob { const TaccArgs *a; bool still; };
+void tacc_host_row(void *p, int y) {
+    const TaccHostJob *j = (const TaccHostJob *)p;
+    for (int x = 0; x < j->a->width; x++) {
+        if (j->still) tacc_pixel<true>(*j->a, x, y);
+        else tacc_pixel<false>(*j->a, x, y);
     }
-    return nullptr;
-}
-
-int grow(mort_ctx *c, void **p, size_t *cap, size_t need) {
-    if (*p && *cap >= need) return MORT_OK;
-    if (*p) { HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
-    HIPCHK(c, hipMalloc(p, need ? need : 16));
-    *cap = need;
-    return MORT_OK;
-}
-
-/* a call on another stream than the previous feature / denoise / temporal one: that one may still read the scratch buffers */
-hipError_t switch_stream(mort_ctx *c, hipStream_t s) {
-    hipError_t e = hipSuccess;
-    if (c->dn_stream && c->dn_stream != s) e = hipStreamSynchronize(c->dn_stream);
-    c->dn_stream = s;
-    return e;
 }
 
 } // namespace
@@ -211,7 +179,7 @@ extern "C" int mort_hip_temporal(mort_ctx *c, const mort_temporal_params *p, con
     HIPCHK(c, switch_stream(c, c->stream));
     const size_t npx = (size_t)W * (size_t)H, hf = npx * MORT_TEMPORAL_HISTORY_FLOATS;
     /* history in, history out (float4 planes first), C, N (3 floats each), D, accum_out (3 floats), variance, rgba (4 bytes) */
-    st = grow(c, &c->d_tio, &c->tio_cap, (2 * hf + 12 * npx) * sizeof(float));
+    st = ensure_buf(c, &c->d_tio, &c->tio_cap, (2 * hf + 12 * npx) * sizeof(float));
     if (st != MORT_OK) return st;
     float *dHi = (float *)c->d_tio, *dHo = dHi + hf, *dC = dHo + hf, *dN = dC + 3 * npx, *dD = dN + 3 * npx, *dO = dD + npx, *dV = dO + 3 * npx;
     uint8_t *dR = (uint8_t *)(dV + npx);
@@ -239,16 +207,8 @@ extern "C" int mort_hip_temporal_host(const mort_temporal_params *p, const mort_
     const int st = temporal_args(p, prev_cam, cam, W, H, accum, normal, depth, hist_in, hist_out, accum_out, variance_out, rgba_out, a, still);
     if (st != MORT_OK) return st;
     const double t0 = now_s();
-    RowJob job;
-    job.rows = H; job.a = &a; job.still = still;
-    if (nthreads < 1) nthreads = 1;
-    if (nthreads > 256) nthreads = 256;
-    std::vector<pthread_t> th((size_t)nthreads - 1);
-    size_t started = 0;
-    for (; started < th.size(); started++)
-        if (pthread_create(&th[started], nullptr, row_worker, &job) != 0) break;
-    row_worker(&job);
-    for (size_t i = 0; i < started; i++) pthread_join(th[i], nullptr);
+    TaccHostJob job = {&a, still};
+    run_rows(H, nthreads, tacc_host_row, &job);
     if (seconds) *seconds = now_s() - t0;
     return MORT_OK;
 }

@@ -23,6 +23,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -475,87 +476,29 @@ static int trav_block_for(const GenArgs &ga) { /* the LDS image + per-wave stagi
     if (const char *e = std::getenv("MORT_WAVE_TRAV_BLOCK")) { const int v = std::atoi(e); if (v == 256 || v == 512 || (v == 1024 && need1024 <= 158 * 1024)) tb = v; }
     return tb;
 }
-const void *mort_wave_gen_trav_kernel(bool prims_in_lds, int *block) {
-    if (block) *block = 512;
-    return (const void *)pick_trav(512, prims_in_lds);
-}
-
-#define WCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
-
-hipError_t mort_wave_gen_render(const GenArgs &ga, const WfGenHost &hb, int bounce_limit, int sqrt_spp, hipStream_t s, unsigned *live_left) {
-    const RenderArgs &a = ga.f.r;
-    const size_t N = (size_t)a.width * (size_t)a.local_rows;
-    if (live_left) *live_left = 0;
-    if (N == 0) return hipSuccess;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    const size_t o_ray0 = take(N * sizeof(WfRay)), o_ray1 = take(N * sizeof(WfRay));
-    const size_t o_id0 = take(N * sizeof(unsigned)), o_id1 = take(N * sizeof(unsigned));
-    const size_t o_hits = take(N * sizeof(WfHit)), o_pix = take(N * sizeof(WfPix));
-    const size_t o_stack = take(N * (size_t)(bounce_limit > 0 ? bounce_limit : 1) * sizeof(float4));
-    const size_t o_c0 = take(N * sizeof(unsigned)), o_c1 = take(N * sizeof(unsigned)), o_c2 = take(N * sizeof(unsigned));
-    const size_t o_cnt = take(sizeof(WfCounters));
-    const size_t total = off;
-    if (*hb.wf_bytes < total) {
-        if (*hb.d_wf) { hipFree(*hb.d_wf); *hb.d_wf = nullptr; *hb.wf_bytes = 0; }
-        WCHK(hipMalloc(hb.d_wf, total));
-        *hb.wf_bytes = total;
-    }
-    if (!*hb.h_live) WCHK(hipHostMalloc((void **)hb.h_live, 64));
-    unsigned char *base = (unsigned char *)*hb.d_wf;
+int mort_wave_gen_render(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, hipStream_t s, LaunchPlan &plan) {
     WfGenArgs w;
     std::memset(&w, 0, sizeof w);
-    w.g = ga;
-    w.n_paths = (int)N;
-    w.q_ray[0] = (WfRay *)(base + o_ray0); w.q_ray[1] = (WfRay *)(base + o_ray1);
-    w.q_id[0] = (unsigned *)(base + o_id0); w.q_id[1] = (unsigned *)(base + o_id1);
-    w.hits = (WfHit *)(base + o_hits); w.pix = (WfPix *)(base + o_pix);
-    w.stack = (float4 *)(base + o_stack);
-    w.q_cls[0] = (unsigned *)(base + o_c0); w.q_cls[1] = (unsigned *)(base + o_c1); w.q_cls[2] = (unsigned *)(base + o_c2);
-    w.cnt = (WfCounters *)(base + o_cnt);
-
+    GenArgs &ga = w.g;
+    ga = c->gen; /* LDS image offsets, root, far-ray constants (upload_world) */
+    ga.f.r = a;
+    ga.f.hot_src = (const unsigned char *)c->d_gen; ga.f.hot_bytes = c->gen_bytes;
+    ga.f.th_s = 32; ga.f.th_l = 24; ga.f.t_keep = 16; /* wf_trav_gen's retire+refill / leaf / box-run thresholds */
+    { const char *th = std::getenv("MORT_WAVE_THRESHOLDS"); /* "f,l,k" */
+      if (th) { int f_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &f_, &l_, &k_) == 3 && f_ >= 1 && l_ >= 1 && k_ >= 1) { ga.f.th_s = f_; ga.f.th_l = l_; ga.f.t_keep = k_; } } }
     const int TB = trav_block_for(ga);
-    if (hb.trav_block) *hb.trav_block = TB;
     trav_kernel_t trav = pick_trav(TB, ga.prims_in_lds != 0);
     /* LDS of wf_trav_gen: image | traversal stacks | class staging */
-    w.g.f.off_tstack = (ga.f.hot_bytes + 15u) & ~15u;
-    w.t_stage = w.g.f.off_tstack + (uint32_t)MORT_OWN_STACK * (uint32_t)TB * 2u;
+    ga.f.off_tstack = (ga.f.hot_bytes + 15u) & ~15u;
+    w.t_stage = ga.f.off_tstack + (uint32_t)MORT_OWN_STACK * (uint32_t)TB * 2u;
     const size_t trav_lds = (size_t)w.t_stage + (size_t)(TB / 64) * 3 * WG_STAGE * sizeof(unsigned);
     { /* dynamic + the kernel's own __shared__ objects must fit the CU's 160 KB: refuse here rather than fail at the first launch */
         hipFuncAttributes fattr;
-        WCHK(hipFuncGetAttributes(&fattr, (const void *)trav));
-        if (trav_lds + fattr.sharedSizeBytes > (size_t)160 * 1024) return hipErrorInvalidValue;
+        HIPCHK(c, hipFuncGetAttributes(&fattr, (const void *)trav));
+        if (trav_lds + fattr.sharedSizeBytes > (size_t)160 * 1024) return hip_fail(c, hipErrorInvalidValue, "wf_trav_gen LDS");
     }
-    WCHK(hipFuncSetAttribute((const void *)trav, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trav_lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trav, TB, trav_lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int max_trav_grid = hb.num_cus * per_cu;
-
-    const int nb256 = (int)((N + 255) / 256);
-    hipLaunchKernelGGL(wf_init_gen, dim3(nb256), dim3(256), 0, s, w);
-    WCHK(hipGetLastError());
-    const long long max_fronts = (long long)sqrt_spp * sqrt_spp * ((long long)bounce_limit + 1) + 8;
-    size_t live = N;
-    long long front = 0;
-    const int chunk = 32; /* fronts per host round trip (the live count is read back in between) */
-    while (live > 0 && front < max_fronts) {
-        /* a wave's share of a front: one 64-record batch at least (two were 4 % slower on small fronts: the front's time is its slowest wave's) */
-        int tg = (int)((live + (size_t)(TB / 64) * 64 - 1) / ((size_t)(TB / 64) * 64));
-        if (tg > max_trav_grid) tg = max_trav_grid;
-        if (tg < 1) tg = 1;
-        const int sg = (int)((live + 255) / 256) + 3;
-        for (int k = 0; k < chunk; k++, front++) {
-            w.parity = (int)(front & 1);
-            hipLaunchKernelGGL(trav, dim3(tg), dim3(TB), trav_lds, s, w);
-            hipLaunchKernelGGL(wf_shade_gen, dim3(sg), dim3(256), 0, s, w);
-        }
-        WCHK(hipGetLastError());
-        WCHK(hipMemcpyAsync(*hb.h_live, &w.cnt->live, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        WCHK(hipStreamSynchronize(s));
-        live = **hb.h_live;
-    }
-    *hb.fronts = (int)front;
-    if (live_left) *live_left = (unsigned)live;
-    return live == 0 ? hipSuccess : hipErrorUnknown;
+    plan.kernel = (const void *)trav; plan.block = TB; plan.lds_bytes = -1;
+    std::snprintf(plan.name, sizeof plan.name, "wf_trav_gen<%d, %s>", TB, ga.prims_in_lds ? "true" : "false"); /* <BLOCK, PRIMS_LDS> */
+    /* a wave's share of a front: one 64-record batch at least (two were 4 % slower on small fronts: the front's time is its slowest wave's) */
+    return wf_render(c, cam, (size_t)a.width * (size_t)a.local_rows, w, wf_init_gen, trav, wf_shade_gen, TB, trav_lds, (size_t)(TB / 64) * 64, s);
 }

@@ -277,7 +277,7 @@ def test_wavefront_unified_tree_knobs(gpu_ctx, oracle, monkeypatch, env, block):
 @pytest.mark.parametrize("env", [{"MORT_WAVE_SHARE": "2"}, {"MORT_WAVE_SHARE": "8"}],
                          ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
 def test_wavefront_bvh_knobs(gpu_ctx, oracle, monkeypatch, env):
-    """Scene 1 through the wavefront pipeline of BVH worlds (mort_hip.hip render_wavefront), which reads MORT_WAVE_SHARE: the 64-record
+    """Scene 1 through the wavefront pipeline of BVH worlds (mort_hip.hip launch_wave), which reads MORT_WAVE_SHARE: the 64-record
     batches per wave of a traversal front."""
     _setenv(monkeypatch, env)
     out1, _, _, _ = _two_frames(gpu_ctx, oracle, "s1", mode=hip.MODE_WAVE)
