@@ -8,13 +8,15 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this; the
  * product (libmort_hip.so, the CLI) never links or calls it.
  *
- * PARITY STATUS: "parity unpinned" against the CUDA reference.  The reference
- * ships no tests, golden images, state dumps or known-answer vectors
- *  and cannot be built here (nvcc, cuRAND, Windows.h, GLUT), so
- * this restatement is pinned only by (a) cross-checks of its XORWOW
- * recurrence and 2^67 sequence skip against rocRAND's independent
- * implementation, (b) closed-form known answers for the geometric functions
- * and (c) golden vectors generated by itself (tests/golden/, script committed).
+ * PARITY STATUS: pinned to the reference's own device code.  The reference's
+ * .cuh headers, compiled for the CPU through the shim in refshim/ (ref_render.cpp,
+ * oracle/_ref/libmort_ref.so), agree with this file bit for bit on renders,
+ * per-ray known answers and the BVH build (tests/test_reference_pin.py); the
+ * recorded digests (tests/golden/ref_pin.npz) hold that where the reference is
+ * absent.  Shared with that build and so not pinned by it: cuRAND's seed-scramble
+ * constants, mort_math.h in place of CUDA's libm, no FMA contraction, MSVC's
+ * host tan and the host scene builders.  Also pinned: the XORWOW recurrence and
+ * 2^67 skip against rocRAND's engine, closed-form known answers, goldens.
  * Third-party pieces restated from their published definitions:
  *   cuRAND XORWOW (CUDA 11.3/13.2, curand_kernel.h: curand_init, curand,
  *   curand_uniform) -- call sites rng.cuh:14,20,34.

@@ -12,10 +12,14 @@
 3. oracle_golden.npz -- outputs of the CPU oracle (oracle/mort_oracle.c) for small configurations
    of every scene family: uchar4 image, fp32 accumulators, per-pixel segment counts, and the final
    RNG words of a few pixels.  BASELINE config 1 (Scene 1, 200x112, 4 spp) is case "s1_c1".
+4. ref_pin.npz -- SHA-256 of what the reference's own device code, compiled for the CPU (oracle/_ref/libmort_ref.so,
+   tests/ref_lib.py), renders for REF_PIN_CASES (two frames each: uchar4 image, fp32 accumulators, XORWOW words), and of
+   the world bytes the reference's BVH builder leaves for REF_PIN_BVH.  Needs the reference; skipped (existing file
+   kept) when it is absent.  The GPU kernels and the oracle are compared with these where the reference is absent.
 
-The reference ships no golden data of its own, so these vectors pin the oracle against
-regressions and give the GPU tests a fixed target; they do not pin it against the CUDA render
-("parity unpinned", DESIGN.md).
+The reference ships no golden data of its own.  (3) pins the oracle against its own regressions; (4) records
+the reference's own arithmetic, so the oracle and the kernels stay pinned to it where the reference is absent (what
+that cannot see: DESIGN.md 2).
 """
 import os
 import subprocess
@@ -39,6 +43,52 @@ CASES = {  # name: (scene, width, spp, depth)
     "s10": (10, 160, 1, None),
     "s1_depth3": (1, 96, 4, 3),
 }
+
+
+# name: (scene, width, spp, depth); each kernel family renders at least one (tests/test_gpu_reference_pin.py)
+REF_PIN_CASES = {
+    "s1": (1, 64, 4, None),     # reference BVH: mega_bvh_kernel
+    "s10": (10, 48, 4, 3),      # reference BVH: mega_bvh_kernel
+    "s9": (9, 32, 4, None),     # final scene: mega_gen_kernel
+    "s6": (6, 32, 4, None),     # Cornell box: mega_kernel
+    "s3": (3, 48, 4, None),     # the earth image texture: mega_kernel
+}
+REF_PIN_FRAMES = 2
+REF_PIN_BVH = ("scene1_reversed", "scene10_shuffled", "mixed_instances")
+
+
+def digest(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def state_words(states):
+    """d and v[5] of 48-byte XORWOW records (a structured STATE_DTYPE array or raw bytes) as uint32 (N, 6)"""
+    from tests import oracle_lib as O
+    st = np.ascontiguousarray(states).view(O.STATE_DTYPE).reshape(-1)
+    return np.concatenate([st["d"][:, None], st["v"]], axis=1).astype("<u4")
+
+
+def make_ref_pin():
+    from mort_amd import host
+    from tests import ref_lib as R
+    from tests.worlds import BVH_BUILDS, world_object_bytes
+    if not R.ensure_built():
+        print("reference absent: keeping existing ref_pin fixture")
+        return
+    out = {}
+    for name, (sid, width, spp, depth) in REF_PIN_CASES.items():
+        world, cam = host.build_scene(sid, width=width, spp=spp, depth=depth)
+        st = R.seed_states(69420, cam.image_width, cam.image_height)
+        for f in range(REF_PIN_FRAMES):
+            r = R.render(world, cam, states=st)
+            out[f"{name}_f{f}"] = np.array([digest(r["rgba"]), digest(r["accum"]), digest(state_words(r["states"]))])
+        print(name, cam.image_width, cam.image_height)
+    for name in REF_PIN_BVH:
+        w, li = BVH_BUILDS[name]()
+        assert R.lib().mort_ref_add_bvh(w.ptr, li, False, 0) == 0
+        out["bvh_" + name] = np.array([digest(np.frombuffer(world_object_bytes(w), np.uint8))])
+    np.savez_compressed(os.path.join(HERE, "ref_pin.npz"), **out)
 
 
 def make_earth():
@@ -125,3 +175,4 @@ if __name__ == "__main__":
     make_earth()
     make_damaged()
     make_oracle()
+    make_ref_pin()

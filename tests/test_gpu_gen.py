@@ -1,8 +1,8 @@
 """Parity tests of the unified-tree megakernel (mort_amd/csrc/hip/mega_gen.hip): worlds WITHOUT reference BVHs
 -- reference scenes 2..9 and hand-built worlds -- through the C ABI, against the CPU oracle, BIT-EXACT (uchar4
 image, fp32 accumulator bits, per-pixel segment counts, final XORWOW words), plus cross-checks against the
-one-lane-per-pixel kernel (mega_kernel) at sizes the oracle cannot reach in a test.  Parity against the CUDA
-reference itself is unpinned."""
+one-lane-per-pixel kernel (mega_kernel) at sizes the oracle cannot reach in a test (parity against the CUDA
+reference's own device code: tests/test_gpu_reference_pin.py)."""
 import ctypes as C
 import os
 

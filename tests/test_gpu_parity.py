@@ -3,7 +3,7 @@ the CPU oracle on the same seeded inputs.  Bar: BIT-EXACT -- uchar4 image, fp32 
 (compared as raw bits), per-pixel segment counts and final XORWOW words.  Every kernel is
 compiled with -ffp-contract=off and uses include/mort_math.h, as the oracle does, so there is no
 tolerance to state (the north_star's "stated ULP tolerance" is 0 ULP against the oracle; against
-the CUDA reference parity is unpinned)."""
+the CUDA reference: tests/test_gpu_reference_pin.py and DESIGN.md 2)."""
 import os
 
 import numpy as np

@@ -2,6 +2,8 @@
 CPU tests of the host loop (tests/test_host_mode.py): the awkward cases the built-in scenes do not contain."""
 import ctypes as C
 
+import numpy as np
+
 from mort_amd import host, structs as S
 
 
@@ -151,4 +153,99 @@ BVH_WORLDS = {
                          ((-1.1, 0, -1), 0.5, ("lamb", (.8, .8, 0))), ((1.1, 0, -1), 0.5, ("metal", (.8, .6, .2), 1.0))],
     "every_material": [_BVH_GROUND] + [((-3 + 1.0 * k, 0.0, -1.5 - 0.2 * k), 0.45, m) for k, m in enumerate(
         [("lamb", (.7, .3, .3)), ("noise",), ("image",), ("metal", (.7, .6, .5), 0.2), ("glass", 1.5), ("light", (4, 4, 4)), ("iso", (.3, .6, .9))])],
+}
+
+
+# ---- pre-build worlds for the BVH builder (tests/test_reference_pin.py, tests/golden/make_golden.py) ----
+
+def _raw(ptr, n, T):
+    return C.string_at(C.cast(ptr, C.c_void_p).value, n * C.sizeof(T)) if n else b""
+
+
+def world_object_bytes(w):
+    """sphere / quad / translate / rotate_y / medium arrays and every BVH, byte for byte (the lists are left out: the
+    reference's scenes sort a local copy, mort_add_bvh the world's own)"""
+    o = w.c.objs
+    return b"".join([_raw(o.host_sphere, o.num_spheres, S.Sphere), _raw(o.host_quad, o.num_quads, S.Quad),
+                     _raw(o.host_translate, o.num_translates, S.Translate), _raw(o.host_rotate_y, o.num_rotate_y, S.RotateY),
+                     _raw(o.host_constant_medium, o.num_constant_medium, S.ConstantMedium), _raw(o.host_bvh, o.num_bvh, S.Bvh),
+                     bytes([o.num_bvh, int(w.c.bvh_mode)])])
+
+
+def _list_world(items):
+    """a pre-build world: one skip list over `items` = ("s", centre, radius) | ("q", Q, u, v) | ("t", item, offset) |
+    ("r", item, degrees) | ("b", size, translation, degrees) (a rotated box: list -> rotate_y -> translate)"""
+    L = host.lib()
+    w = host.World()
+    m = L.mort_add_lambertian(w.ptr, S.TEXTURE_SOLID, L.mort_add_solid_color(w.ptr, host.vec3(.5, .5, .5)))
+    lam = S.MAT_LAMBERTIAN
+
+    def add(it):
+        if it[0] == "s":
+            return S.OBJ_SPHERE, L.mort_add_sphere(w.ptr, host.vec3(*it[1]), it[2], lam, m, True)
+        if it[0] == "q":
+            return S.OBJ_QUAD, L.mort_add_quad(w.ptr, host.vec3(*it[1]), host.vec3(*it[2]), host.vec3(*it[3]), lam, m, True)
+        if it[0] == "t":
+            t, i = add(it[1])
+            return S.OBJ_TRANSLATE, L.mort_add_translate(w.ptr, t, i, host.vec3(*it[2]), True)
+        t, i = add(it[1])
+        return S.OBJ_ROTATE_Y, L.mort_add_rotate_y(w.ptr, t, i, it[2], True)
+    refs = [add(it) for it in items]
+    assert all(i >= 0 for _, i in refs), "more objects than the reference's arrays hold"
+    li = L.mort_add_hittable_list(w.ptr, True)
+    for t, i in refs:
+        assert L.mort_list_add(w.ptr, li, t, i) == 0
+    return w, li
+
+
+def _scene_list_world(sid, order):
+    """scene `sid`'s objects in a new list order (`order` maps the permutation of its list entries)"""
+    src, _ = host.build_scene(sid, width=16, spp=1)
+    w = host.World()
+    so, wo = src.c.objs, w.c.objs
+    C.memmove(wo.host_sphere, so.host_sphere, so.num_spheres * C.sizeof(S.Sphere)); wo.num_spheres = so.num_spheres
+    C.memmove(wo.host_quad, so.host_quad, so.num_quads * C.sizeof(S.Quad)); wo.num_quads = so.num_quads
+    lst = so.host_hittable_list[0]
+    entries = [(lst.obj_types[i], lst.obj_idxs[i]) for i in range(lst.num_objs)]
+    li = host.lib().mort_add_hittable_list(w.ptr, True)
+    for t, i in order(entries):
+        host.lib().mort_list_add(w.ptr, li, t, i)
+    return w, li
+
+
+def _random_list(seed, n):
+    rng = np.random.default_rng(seed)
+    items = []
+    for _ in range(n):
+        k = rng.random()
+        c = tuple(np.round(rng.uniform(-20, 20, 3), int(rng.integers(0, 3))))  # rounded: equal minima are common
+        if k < 0.55:
+            items.append(("s", c, float(rng.choice([0.2, 0.5, 1.0, 2.0]))))
+        elif k < 0.8:
+            items.append(("q", c, tuple(rng.uniform(-3, 3, 3)), tuple(rng.uniform(-3, 3, 3))))
+        elif k < 0.9 and sum(it[0] == "t" for it in items) < 40:  # 50 translates / rotate_ys at most (objects.cuh)
+            items.append(("t", ("s", c, 0.5), tuple(rng.uniform(-5, 5, 3))))
+        elif sum(it[0] == "r" for it in items) < 40:
+            items.append(("r", ("q", c, (1.0, 0, 0), (0, 1.0, 0)), float(rng.uniform(-90, 90))))
+        else:
+            items.append(("s", c, 0.75))
+    return items
+
+
+BVH_BUILDS = {
+    "one_sphere": lambda: _list_world([("s", (0, 0, 0), 1.0)]),
+    "two_spheres": lambda: _list_world([("s", (1, 0, 0), 1.0), ("s", (-1, 0, 0), 0.5)]),
+    "two_spheres_tie": lambda: _list_world([("s", (0, 0, 0), 1.0), ("s", (0.5, 3, 0), 1.5)]),  # equal x minima
+    "two_mixed_tie": lambda: _list_world([("q", (-1, 0, 0), (0, 1, 0), (0, 0, 1)), ("s", (0, 5, 0), 1.0)]),
+    "three_spheres": lambda: _list_world([("s", (2, 0, 0), 0.5), ("s", (0, 0, 0), 0.5), ("s", (1, 0, 0), 0.5)]),
+    "three_ties": lambda: _list_world([("s", (0, 0, 0), 1.0)] * 3),
+    "equal_minima": lambda: _list_world([("s", (float(k % 3), float(k), 0), 1.0 + (k % 3)) for k in range(12)]),
+    "mixed_instances": lambda: _list_world([("q", (3, 0, 0), (1, 0, 0), (0, 1, 0)), ("s", (1, 0, 0), 0.5),
+                                            ("t", ("s", (0, 0, 0), 0.5), (-2, 0, 0)), ("r", ("q", (0, 0, 0), (1, 0, 0), (0, 1, 0)), 30.0),
+                                            ("s", (-3, 0, 0), 0.5), ("q", (2, 1, 0), (1, 0, 0), (0, 0, 1)), ("s", (2, 0, 0), 0.25),
+                                            ("t", ("q", (0, 0, 0), (0, 1, 0), (0, 0, 1)), (5, 0, 0))]),
+    "scene1_reversed": lambda: _scene_list_world(1, lambda e: e[::-1]),
+    "scene1_shuffled": lambda: _scene_list_world(1, lambda e: [e[i] for i in np.random.default_rng(1).permutation(len(e))]),
+    "scene10_shuffled": lambda: _scene_list_world(10, lambda e: [e[i] for i in np.random.default_rng(10).permutation(len(e))]),
+    **{f"random{n}": (lambda n=n: _list_world(_random_list(n, n))) for n in (4, 5, 17, 64, 200, 480)},
 }
