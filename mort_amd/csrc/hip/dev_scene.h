@@ -59,17 +59,27 @@ struct __attribute__((aligned(16))) DNode2 {
     uint32_t child0, child1;
     float e0, e1;
 };
-/* The same tree four children wide (scene_compile.h collapse_own_tree; the BVH megakernel's box step): 128 B = eight ds_read_b128,
- * child k's planes at [k] of each array.  A binary node's larger inner child is opened in place until four slots are full, so
- * one step tests what two to three binary steps did and the loads of a step are all independent.  Child references are
- * pre-scaled (below); an unused slot is 0xffff (never entered).  Boxes and margins are the binary tree's, bit for bit. */
+/* The same tree four children wide (scene_compile.h collapse_own_tree; the BVH megakernel's box step): 176 B = eleven ds_read_b128
+ * pieces, of which a step reads eight; child k's planes at [k] of each array.  A binary node's larger inner child is opened in place
+ * until four slots are full, so one step tests what two to three binary steps did and the loads of a step are all independent.
+ * Child references are pre-scaled (below); an unused slot is 0xffff (never entered) and all its planes are zero.  Boxes and margins
+ * are the binary tree's, bit for bit.
+ * Planes ordered by ray sign: every axis holds THREE pieces [min, max, min] (x[0] == x[2] bit for bit).  A ray whose reciprocal
+ * direction is positive on an axis enters at min and leaves at max, a negative one the other way round, so with s = 1 for a negative
+ * reciprocal the near planes are piece s and the far planes piece s + 1: one address per axis, the far read at an immediate offset of
+ * 16 B, and no v_min / v_max pair per axis and child to sort the two distances (mega_bvh.h own_prune_ordered). */
 struct __attribute__((aligned(16))) DNode4 {
-    float xmin[4], xmax[4], ymin[4], ymax[4], zmin[4], zmax[4], e[4];
+    float x[3][4], y[3][4], z[3][4], e[4]; /* [0] min, [1] max, [2] min again */
     uint32_t child[4];
-    uint32_t pad[4]; /* 144 B = 9 x 16: the lanes of a wave read the same 16-byte piece of DIFFERENT nodes, and a ds_read_b128 serves 16 lanes per LDS cycle from
-                      * 64 banks.  With a stride of 128 B those pieces lie on two bank positions (8-way conflicts, measured: 45 % of the kernel's LDS cycles);
-                      * an odd number of pieces per node spreads them over all sixteen */
+    /* 176 B = 11 x 16, no padding: the lanes of a wave read the same 16-byte piece of DIFFERENT nodes, and a ds_read_b128 serves 16 lanes
+     * per LDS cycle from 64 banks.  With a stride of 128 B those pieces lie on two bank positions (8-way conflicts, measured: 45 % of
+     * the kernel's LDS cycles); an ODD number of pieces per node (9 before the third piece per axis, 11 now) spreads them over all sixteen */
 };
+#define MORT_NODE4_X 0 /* first piece of each axis, of the margins and of the child references */
+#define MORT_NODE4_Y 3
+#define MORT_NODE4_Z 6
+#define MORT_NODE4_E 9
+#define MORT_NODE4_CHILD 10
 /* What the leaf step of the BVH megakernel reads, in ONE round trip to LDS: the one or two spheres of a reference leaf node by value;
  * then the leaf node's own box, bit for bit, for the final check of the winner.  112 B = 7 x 16, an odd number of pieces again.
  * References to both kinds of record are pre-scaled to 16-byte pieces so that an address is one shift-add: an inner child is
@@ -81,7 +91,7 @@ struct __attribute__((aligned(16))) DLeaf2 {
     uint32_t prims;   /* pa | pb << 16: their indices in the scene's sphere table */
     uint32_t pad[4];
 };
-#define MORT_NODE4_PIECES 9
+#define MORT_NODE4_PIECES 11
 #define MORT_LEAF2_PIECES 7
 #define MORT_OWN4_STACK 24 /* pending children per lane of the four-wide walk: a step pushes at most 3; the builder checks the worst path */
 /* Node of the UNIFIED tree (scene_compile.h build_unified): 32 B = two ds_read_b128.  The boxes of its two children as 8-bit offsets

@@ -116,7 +116,10 @@ template <typename T> __device__ __forceinline__ T *uni_p(T *p) {
 }
 
 enum { ST_T = 0, ST_L = 1, ST_S = 2, ST_DONE = 3 };
-enum { FL_TIE = 1, FL_REF = 2 };
+enum { FL_TIE = 1, FL_REF = 2, FL_MASK = 3 };
+/* bytes 1..3 of `flags`: the segment's byte offsets of the near x / y / z pieces of a four-wide node (own_sign_offset), kept in the
+ * spare bits of a register the walk already owns -- three more live registers are three more spilled ones */
+#define FL_SIGNS(ox, oy, oz) (int)(((ox) << 8) | ((oy) << 16) | ((oz) << 24))
 /* -DMORT_REGION_MARKS: comments in the ISA at region boundaries, for static instruction counts per region
  * (scripts/isa_regions.py) */
 #ifdef MORT_REGION_MARKS
@@ -202,6 +205,31 @@ DEV bool own_prune(float xmin, float xmax, float ymin, float ymax, float zmin, f
     return (tx - te < -tau) || (key > closest);
 }
 
+/* own_prune with the planes already ordered by the ray's sign: n* = the plane the ray meets first on that axis (min when the reciprocal
+ * is positive, max when it is negative), f* = the other one (DNode4's [min, max, min] pieces, dev_scene.h).  The same te, tx, tau and key
+ * as own_prune, bit for bit, without its six v_min / v_max that only sort each axis' two distances:
+ *  - p(b) = fma(b, i, -m) is ONE rounding of a function of b that is monotone for fixed i and m (increasing for i > 0, decreasing for
+ *    i < 0), so it is monotone itself, and the builder stores min <= max: min(p(min), p(max)) is p of the sign-chosen plane;
+ *  - a ray that reaches the box step has reciprocals with 1e-15 < |i| < 1e15 (own_inv_ok): no zero, infinity or NaN, and -0.0 cannot occur
+ *    (it would need an infinite direction), so the sign bit IS the sign.  p may overflow to an infinity but is never NaN (m is finite);
+ *  - equal planes (min == max, as in the all-zero boxes of unused child slots) give equal distances whichever is read: harmless.  The one
+ *    value that may differ is the sign of a zero distance (-0.0 < +0.0 to v_min_f32), which neither max(.., 0.001), |.|, tx - te nor the
+ *    comparisons can see.
+ * tests/test_prune_ordered.py compares both forms over the four-wide trees of Scenes 1 and 10 (mort_hip_debug_prune_forms). */
+DEV bool own_prune_ordered(float xn, float xf, float yn, float yf, float zn, float zf, float e, const OwnRay &r, float closest, float &te_out) {
+    const float pxn = __builtin_fmaf(xn, r.ix, -r.mx), pxf = __builtin_fmaf(xf, r.ix, -r.mx);
+    const float pyn = __builtin_fmaf(yn, r.iy, -r.my), pyf = __builtin_fmaf(yf, r.iy, -r.my);
+    const float pzn = __builtin_fmaf(zn, r.iz, -r.mz), pzf = __builtin_fmaf(zf, r.iz, -r.mz);
+    const float te = __builtin_fmaxf(__builtin_fmaxf(pxn, pyn), __builtin_fmaxf(pzn, 0.001f));
+    const float tx = __builtin_fminf(__builtin_fminf(pxf, pyf), pzf);
+    const float tau = __builtin_fmaf(__builtin_fmaxf(mort_fabsf(te), mort_fabsf(tx)), 9.5367431640625e-07f, r.band);
+    const float key = __builtin_fmaf(te, 0.992f, -__builtin_fmaf(e, r.invlen, tau));
+    te_out = te;
+    return (tx - te < -tau) || (key > closest);
+}
+/* byte offset of an axis' near piece within its three: 0 for a positive reciprocal, 16 for a negative one */
+DEV uint32_t own_sign_offset(float inv) { return (__builtin_bit_cast(uint32_t, inv) >> 27) & 16u; }
+
 /* own_prune for two boxes at once, the fused multiply-adds as v_pk_fma_f32 (two per lane and instruction; identical IEEE results).  On MI355X a packed
  * instruction costs a busy SIMD the issue time of two plain ones (calibration kind 4: 4.1 against 2.2 cycles), so a frame that fills the chip gains nothing -- but
  * a wave that has its SIMD almost to itself issues one instruction per ~5 cycles whatever its width, and that is the state of every chain-bound launch */
@@ -263,6 +291,11 @@ enum { K_SHADE = 0, K_FINISH = 1, K_NEWSAMPLE = 2, K_NEWPIX = 3 };
 #define MORT_T_KEEP 16
 #endif
 
+#ifdef MORT_BVH_PUSH_BRANCHFREE
+#define MORT_BVH_TSTACK_SPARE 1u /* traversal-stack levels beyond the builder's pending-children bound */
+#else
+#define MORT_BVH_TSTACK_SPARE 0u
+#endif
 #ifndef MORT_MIN_WAVES
 #define MORT_MIN_WAVES 3
 #endif
@@ -456,9 +489,10 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
     static_assert(sizeof(DNode4) == 16 * MORT_NODE4_PIECES && sizeof(DLeaf2) == 16 * MORT_LEAF2_PIECES, "record strides");
     const float4 *nodes4 = (const float4 *)(lds + BU_U(L.off_nodes4));
     const float4 *leafrecs = (const float4 *)(lds + BU_U(L.off_leafrecs));
-    /* traversal stack [level][thread] u16, addressed by the LDS byte offset of the lane's next free entry */
-    const uint32_t ts_base = BU_U(L.off_tstack) + 2u * threadIdx.x;
-#define TS_AT(off) (*(unsigned short *)(lds + (off)))
+    /* traversal stack [level][thread] u16, addressed by a POINTER to the lane's next free entry: as a byte offset from `lds` every push
+     * and pop paid a v_add for the static __shared__ block in front of the dynamic LDS, next to the update of the offset itself */
+    unsigned short *const ts_base = (unsigned short *)(lds + BU_U(L.off_tstack)) + threadIdx.x;
+#define TS_AT(ptr) (*(ptr))
     const DLambert *lambert = (const DLambert *)(lds + BU_U(L.off_lambert));
     const DMetal *metal = (const DMetal *)(lds + BU_U(L.off_metal));
     const DDielectric *dielectric = (const DDielectric *)(lds + BU_U(L.off_diel));
@@ -487,8 +521,8 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
     float ray_a = 1, closest = 0;
     int best = -1;         /* closest hit so far: leaf << 16 | (second sphere of the leaf) << 15 */
     uint32_t node = 0;     /* T: own-tree node; L: leaf record */
-    uint32_t spa = ts_base; /* pending children: next free entry of the lane's traversal stack */
-    int flags = 0;          /* FL_TIE / FL_REF */
+    unsigned short *spa = ts_base; /* pending children: next free entry of the lane's traversal stack */
+    int flags = 0;          /* FL_TIE / FL_REF | FL_SIGNS */
     /* bounce-stack levels below the LDS part: [level - DL][lane of the launch] in HBM, one coalesced 1 KB row per wave and level, touched
      * only by paths deeper than the LDS part (a private array is scratch memory sized for the deepest path in every lane) */
     float4 *stack_deep = BU_P(L.deep) + ((size_t)blockIdx.x * BLOCK + threadIdx.x);
@@ -580,19 +614,28 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                      * pushed farthest first.  The order only decides how soon `closest` shrinks -- equal distances are settled by
                      * the reference's own walk (FL_TIE), never by the order of visits */
                     const float4 *np = nodes4 + node;
-                    const float4 bx0 = np[0], bx1 = np[1], by0 = np[2], by1 = np[3], bz0 = np[4], bz1 = np[5], be = np[6];
-                    const uint4 ch = ((const uint4 *)np)[7];
                     float t0, t1, t2, t3;
-#ifdef MORT_BVH_PACKED_FMA
+#ifdef MORT_BVH_PACKED_FMA /* the measured variant keeps the unordered test on the min / max pieces */
+                    const float4 bx0 = np[MORT_NODE4_X], bx1 = np[MORT_NODE4_X + 1], by0 = np[MORT_NODE4_Y], by1 = np[MORT_NODE4_Y + 1];
+                    const float4 bz0 = np[MORT_NODE4_Z], bz1 = np[MORT_NODE4_Z + 1], be = np[MORT_NODE4_E];
+                    const uint4 ch = ((const uint4 *)np)[MORT_NODE4_CHILD];
                     bool m0, m1, m2, m3;
                     own_prune2(v2f_t{bx0.x, bx0.y}, v2f_t{bx1.x, bx1.y}, v2f_t{by0.x, by0.y}, v2f_t{by1.x, by1.y}, v2f_t{bz0.x, bz0.y}, v2f_t{bz1.x, bz1.y}, v2f_t{be.x, be.y}, orr, closest, t0, t1, m0, m1);
                     own_prune2(v2f_t{bx0.z, bx0.w}, v2f_t{bx1.z, bx1.w}, v2f_t{by0.z, by0.w}, v2f_t{by1.z, by1.w}, v2f_t{bz0.z, bz0.w}, v2f_t{bz1.z, bz1.w}, v2f_t{be.z, be.w}, orr, closest, t2, t3, m2, m3);
                     m2 = m2 || ch.z == 0xffffu; m3 = m3 || ch.w == 0xffffu;
 #else
-                    const bool m0 = own_prune(bx0.x, bx1.x, by0.x, by1.x, bz0.x, bz1.x, be.x, orr, closest, t0);
-                    const bool m1 = own_prune(bx0.y, bx1.y, by0.y, by1.y, bz0.y, bz1.y, be.y, orr, closest, t1);
-                    const bool m2 = own_prune(bx0.z, bx1.z, by0.z, by1.z, bz0.z, bz1.z, be.z, orr, closest, t2) || ch.z == 0xffffu;
-                    const bool m3 = own_prune(bx0.w, bx1.w, by0.w, by1.w, bz0.w, bz1.w, be.w, orr, closest, t3) || ch.w == 0xffffu;
+                    /* near planes at the axis' sign offset, far planes one piece further (dev_scene.h): three addresses, the rest is
+                     * the ds_read's immediate offset */
+                    const unsigned char *nb = (const unsigned char *)np;
+                    const float4 *ax = (const float4 *)(nb + (((uint32_t)flags >> 8) & 0xffu)) + MORT_NODE4_X;
+                    const float4 *ay = (const float4 *)(nb + (((uint32_t)flags >> 16) & 0xffu)) + MORT_NODE4_Y;
+                    const float4 *az = (const float4 *)(nb + ((uint32_t)flags >> 24)) + MORT_NODE4_Z;
+                    const float4 xn = ax[0], xf = ax[1], yn = ay[0], yf = ay[1], zn = az[0], zf = az[1], be = np[MORT_NODE4_E];
+                    const uint4 ch = ((const uint4 *)np)[MORT_NODE4_CHILD];
+                    const bool m0 = own_prune_ordered(xn.x, xf.x, yn.x, yf.x, zn.x, zf.x, be.x, orr, closest, t0);
+                    const bool m1 = own_prune_ordered(xn.y, xf.y, yn.y, yf.y, zn.y, zf.y, be.y, orr, closest, t1);
+                    const bool m2 = own_prune_ordered(xn.z, xf.z, yn.z, yf.z, zn.z, zf.z, be.z, orr, closest, t2) || ch.z == 0xffffu;
+                    const bool m3 = own_prune_ordered(xn.w, xf.w, yn.w, yf.w, zn.w, zf.w, be.w, orr, closest, t3) || ch.w == 0xffffu;
 #endif
                     uint32_t k0 = m0 ? 0xffffffffu : ((__float_as_uint(t0) & 0xffff0000u) | ch.x);
                     uint32_t k1 = m1 ? 0xffffffffu : ((__float_as_uint(t1) & 0xffff0000u) | ch.y);
@@ -601,13 +644,20 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
 #define MORT_CSWAP(a, b) do { const uint32_t lo_ = a < b ? a : b, hi_ = a < b ? b : a; a = lo_; b = hi_; } while (0)
                     MORT_CSWAP(k0, k1); MORT_CSWAP(k2, k3); MORT_CSWAP(k0, k2); MORT_CSWAP(k1, k3); MORT_CSWAP(k1, k2);
 #undef MORT_CSWAP
-                    if (k3 != 0xffffffffu) { TS_AT(spa) = (unsigned short)k3; spa += 2u * BLOCK; }
-                    if (k2 != 0xffffffffu) { TS_AT(spa) = (unsigned short)k2; spa += 2u * BLOCK; }
-                    if (k1 != 0xffffffffu) { TS_AT(spa) = (unsigned short)k1; spa += 2u * BLOCK; }
+#ifdef MORT_BVH_PUSH_BRANCHFREE /* measured variant: every key is stored, only a valid one advances the pointer.  The sort puts the
+                                 * invalid keys last, so they land on the free entry above the top: ONE spare level (MORT_BVH_TSTACK_SPARE) */
+                    TS_AT(spa) = (unsigned short)k3; spa += (k3 != 0xffffffffu) ? BLOCK : 0;
+                    TS_AT(spa) = (unsigned short)k2; spa += (k2 != 0xffffffffu) ? BLOCK : 0;
+                    TS_AT(spa) = (unsigned short)k1; spa += (k1 != 0xffffffffu) ? BLOCK : 0;
+#else
+                    if (k3 != 0xffffffffu) { TS_AT(spa) = (unsigned short)k3; spa += BLOCK; }
+                    if (k2 != 0xffffffffu) { TS_AT(spa) = (unsigned short)k2; spa += BLOCK; }
+                    if (k1 != 0xffffffffu) { TS_AT(spa) = (unsigned short)k1; spa += BLOCK; }
+#endif
                     uint32_t next = k0;
                     const bool none = k0 == 0xffffffffu;
                     const bool have = !none || spa != ts_base;
-                    if (none && spa != ts_base) { spa -= 2u * BLOCK; next = TS_AT(spa); }
+                    if (none && spa != ts_base) { spa -= BLOCK; next = TS_AT(spa); }
                     if (!have) { state = ST_S; kind = K_SHADE; }
                     else { node = next & 0x7fffu; if (next & 0x8000u) state = ST_L; }
                 }
@@ -646,7 +696,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                     }
                 }
                 if (spa != ts_base) {
-                    spa -= 2u * BLOCK;
+                    spa -= BLOCK;
                     const uint32_t next = TS_AT(spa);
                     node = next & 0x7fffu;
                     state = (next & 0x8000u) ? ST_L : ST_T;
@@ -667,7 +717,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
             if (state == ST_S) {
                 if (kind == K_SHADE) {
                     /* is the winner what bvh_node::hit returns?  (header comment) */
-                    bool need_ref = flags != 0;
+                    bool need_ref = (flags & FL_MASK) != 0;
                     if (!need_ref && best >= 0) { /* the winner's leaf box, from its record */
                         const float4 *lp = leafrecs + (best >> 16);
                         const float4 b0 = lp[4], b1 = lp[5];
@@ -876,7 +926,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                         closest = __builtin_inff();
                         best = -1;
                         node = 0; spa = ts_base;
-                        flags = ordinary ? 0 : FL_REF;
+                        flags = ordinary ? FL_SIGNS(own_sign_offset(orr.ix), own_sign_offset(orr.iy), own_sign_offset(orr.iz)) : FL_REF;
                         segments++;
                         state = ordinary ? ST_T : ST_S;
                     }

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -23,6 +24,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "mort_hip.h"
@@ -651,7 +653,7 @@ static int launch_bvh(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, 
         if (wide_ok) FB = 1024;
     }
     /* 1024 threads: image + traversal stacks + one bounce-stack level per lane must fit one CU's LDS, else the widest shape that does */
-    if (FB == 1024 && (size_t)((fa.hot_bytes + 15u) & ~15u) + (size_t)c->own4_stack * 1024u * 2u + 2048u + 1024u * 16u > 160u * 1024u) FB = 768;
+    if (FB == 1024 && (size_t)((fa.hot_bytes + 15u) & ~15u) + ((size_t)c->own4_stack + MORT_BVH_TSTACK_SPARE) * 1024u * 2u + 2048u + 1024u * 16u > 160u * 1024u) FB = 768;
     if (FB != 1024 && FB != 768 && FB != 512 && FB != 384) FB = 256;
     fa.drain_rounds = 3; /* batch thresholds as shares of the wave's LIVE lanes (they differ from fixed counts only once lanes have run out of pixels: the tail of a frame;
                           * three runs each, one box: N = 1 100.1-100.5 vs 100.3-102.9 ms, a rank of 2 75.6-78.6 vs 77.6-82.2 ms, ranks of 4 / 8 unchanged); DRAIN kernels
@@ -674,7 +676,7 @@ static int launch_bvh(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, 
     /* traversal stacks: the world's own four-wide bound (at most MORT_OWN4_STACK) */
     size_t lds_bytes = 0;
     int grid = 0;
-    int st = state_setup(c, cam, fa, (const void *)kern, FB, (uint32_t)c->own4_stack, 12, per_cu_cap, "BVH image does not fit one CU's LDS", s, lds_bytes, grid);
+    int st = state_setup(c, cam, fa, (const void *)kern, FB, (uint32_t)c->own4_stack + MORT_BVH_TSTACK_SPARE, 12, per_cu_cap, "BVH image does not fit one CU's LDS", s, lds_bytes, grid);
     if (st != MORT_OK) return st;
     st = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, chain_bound, sub, timed, s, [&](const FastArgs &pa) {
         hipError_t e_ = hipFuncSetAttribute((const void *)kern_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
@@ -1006,7 +1008,9 @@ extern "C" int mort_hip_debug_own_tree(const mort_world *w, int *out) {
             const uint32_t ref = nd.child[k];
             if (ref == 0xffffu) continue;
             out[7]++;
-            const Rec r{{nd.xmin[k], nd.xmax[k], nd.ymin[k], nd.ymax[k], nd.zmin[k], nd.zmax[k], nd.e[k]}};
+            const Rec r{{nd.x[0][k], nd.x[1][k], nd.y[0][k], nd.y[1][k], nd.z[0][k], nd.z[1][k], nd.e[k]}};
+            /* the third piece of each axis repeats the first (dev_scene.h) */
+            if (std::memcmp(&nd.x[2][k], &nd.x[0][k], 4) || std::memcmp(&nd.y[2][k], &nd.y[0][k], 4) || std::memcmp(&nd.z[2][k], &nd.z[0][k], 4)) same = false;
             if (ref & 0x8000u) {
                 const uint32_t l = (ref & 0x7fffu) / MORT_LEAF2_PIECES;
                 if ((ref & 0x7fffu) % MORT_LEAF2_PIECES || l >= seen.size() || seen[l]++) { out[6]++; continue; }
@@ -1022,6 +1026,86 @@ extern "C" int mort_hip_debug_own_tree(const mort_world *w, int *out) {
         }
     }
     out[8] = same ? 1 : 0;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the boxes of the occupied children of the world's four-wide tree, six
+ * floats each (xmin, xmax, ymin, ymax, zmin, zmax), at most max_boxes of them.  Returns how many there are, or a negative status. */
+extern "C" int mort_hip_debug_own_tree4_boxes(const mort_world *w, float *out, size_t max_boxes) {
+    if (!w || (!out && max_boxes)) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    size_t n = 0;
+    for (const DNode4 &nd : sb.comp.own_nodes4)
+        for (int k = 0; k < 4; k++) {
+            if (nd.child[k] == 0xffffu) continue;
+            if (n < max_boxes) { float *o = out + 6 * n; o[0] = nd.x[0][k]; o[1] = nd.x[1][k]; o[2] = nd.y[0][k]; o[3] = nd.y[1][k]; o[4] = nd.z[0][k]; o[5] = nd.z[1][k]; }
+            n++;
+        }
+    return (int)n;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the box step's two forms of the slab test, own_prune on (min, max) and
+ * own_prune_ordered on the sign-chosen (near, far) pieces, over the world's four-wide tree, the pieces chosen by own_sign_offset as in the kernel.
+ * rays: n x 7 floats (origin, direction, closest); ray r meets the nodes r % stride, r % stride + stride, ...  A ray whose reciprocals
+ * are not ordinary never reaches the box step and is only counted.  out[0] (occupied child, ray) pairs compared, [1] pairs whose te differs
+ * in any bit, [2] pairs whose skip decision differs, [3] rays left out, [4] four-wide nodes, [5] unused child slots with a non-zero plane
+ * or margin, [6] pairs skipped by both forms, [8..15] rays compared per sign octant (bit 0: x reciprocal negative, 1: y, 2: z). */
+extern "C" int mort_hip_debug_prune_forms(const mort_world *w, const float *rays, size_t n, int stride, unsigned long long *out) {
+    if (!w || !rays || !out || stride < 1) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const std::vector<DNode4> &nodes = sb.comp.own_nodes4;
+    for (int i = 0; i < 16; i++) out[i] = 0;
+    out[4] = nodes.size();
+    if (nodes.empty()) return MORT_OK;
+    for (const DNode4 &nd : nodes)
+        for (int k = 0; k < 4; k++) {
+            if (nd.child[k] != 0xffffu) continue;
+            const float v[10] = {nd.x[0][k], nd.x[1][k], nd.x[2][k], nd.y[0][k], nd.y[1][k], nd.y[2][k], nd.z[0][k], nd.z[1][k], nd.z[2][k], nd.e[k]};
+            for (float f : v) { uint32_t b; std::memcpy(&b, &f, 4); if (b) { out[5]++; break; } }
+        }
+    unsigned nthreads = std::thread::hardware_concurrency();
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    std::vector<std::array<unsigned long long, 16>> part(nthreads);
+    auto work = [&](unsigned t) {
+        std::array<unsigned long long, 16> &o = part[t];
+        o.fill(0);
+        for (size_t r = t; r < n; r += nthreads) {
+            const float *q = rays + 7 * r;
+            OwnRay orr; /* as the kernel's segment setup (mega_bvh.h) */
+            orr.ix = 1.0f / q[3]; orr.iy = 1.0f / q[4]; orr.iz = 1.0f / q[5];
+            orr.mx = q[0] * orr.ix; orr.my = q[1] * orr.iy; orr.mz = q[2] * orr.iz;
+            const float mm = __builtin_fmaxf(__builtin_fmaxf(mort_fabsf(orr.mx), mort_fabsf(orr.my)), mort_fabsf(orr.mz));
+            orr.band = mm * 4.76837158203125e-07f;
+            orr.invlen = 1.01f / mort_sqrtf(q[3] * q[3] + q[4] * q[4] + q[5] * q[5]);
+            if (!(own_inv_ok(orr.ix) && own_inv_ok(orr.iy) && own_inv_ok(orr.iz) && (mm < 1e30f))) { o[3]++; continue; }
+            const uint32_t sx = own_sign_offset(orr.ix) / 16u, sy = own_sign_offset(orr.iy) / 16u, sz = own_sign_offset(orr.iz) / 16u;
+            o[8 + (sx | sy << 1 | sz << 2)]++;
+            const float closest = q[6];
+            for (size_t ni = r % (size_t)stride; ni < nodes.size(); ni += (size_t)stride) {
+                const DNode4 &nd = nodes[ni];
+                for (int k = 0; k < 4; k++) {
+                    if (nd.child[k] == 0xffffu) continue;
+                    float te_a, te_b;
+                    const bool skip_a = own_prune(nd.x[0][k], nd.x[1][k], nd.y[0][k], nd.y[1][k], nd.z[0][k], nd.z[1][k], nd.e[k], orr, closest, te_a);
+                    const bool skip_b = own_prune_ordered(nd.x[sx][k], nd.x[sx + 1][k], nd.y[sy][k], nd.y[sy + 1][k], nd.z[sz][k], nd.z[sz + 1][k], nd.e[k], orr, closest, te_b);
+                    o[0]++;
+                    if (std::memcmp(&te_a, &te_b, 4) != 0) o[1]++;
+                    if (skip_a != skip_b) o[2]++;
+                    if (skip_a && skip_b) o[6]++;
+                }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < nthreads; t++) pool.emplace_back(work, t);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    for (const auto &o : part) for (int i = 0; i < 16; i++) if (i != 4 && i != 5) out[i] += o[i];
     return MORT_OK;
 }
 

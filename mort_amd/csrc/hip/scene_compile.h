@@ -373,8 +373,11 @@ struct Compiler {
         std::memset(&n4, 0, sizeof n4);
         for (int k = 0; k < 4; k++) n4.child[k] = 0xffffu;
         for (size_t i = 0; i < sl.size() && i < 4; i++) {
-            n4.xmin[i] = sl[i].lo[0]; n4.xmax[i] = sl[i].hi[0]; n4.ymin[i] = sl[i].lo[1]; n4.ymax[i] = sl[i].hi[1];
-            n4.zmin[i] = sl[i].lo[2]; n4.zmax[i] = sl[i].hi[2]; n4.e[i] = sl[i].e;
+            /* [min, max, min] per axis (dev_scene.h); the slots this loop leaves out stay all zero, third piece included */
+            n4.x[0][i] = n4.x[2][i] = sl[i].lo[0]; n4.x[1][i] = sl[i].hi[0];
+            n4.y[0][i] = n4.y[2][i] = sl[i].lo[1]; n4.y[1][i] = sl[i].hi[1];
+            n4.z[0][i] = n4.z[2][i] = sl[i].lo[2]; n4.z[1][i] = sl[i].hi[2];
+            n4.e[i] = sl[i].e;
             if (sl[i].ref & 0x8000u) { n4.child[i] = 0x8000u | ((sl[i].ref & 0x7fffu) * MORT_LEAF2_PIECES); continue; }
             const uint32_t ci = (uint32_t)out.own_nodes4.size();
             out.own_nodes4.push_back(DNode4{});
@@ -429,6 +432,8 @@ struct Compiler {
         }
         out.own_nodes4.push_back(DNode4{});
         out.own4_stack = collapse_emit(dp, 0, 0);
+        /* child references are 15-bit piece indices: at most 0x7fff / 11 = 2 978 four-wide nodes and 0x7fff / 7 = 4 681 leaf records;
+         * a larger world gets no four-wide tree (3 640 nodes fitted before the nodes grew from 9 to 11 pieces) */
         if (out.own4_stack > MORT_OWN4_STACK || out.own_nodes4.size() * MORT_NODE4_PIECES > 0x7fff || out.own_leaves.size() * MORT_LEAF2_PIECES > 0x7fff) out.own_nodes4.clear();
     }
 
