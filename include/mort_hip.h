@@ -168,7 +168,8 @@ int mort_hip_calib_hbm_copy(mort_ctx *ctx, size_t bytes, int reps, double *gbs_o
  * receives the HIP-event device time of the kernels (host forms: wall time of the loop).
  *
  * Features: one ray per pixel from the lens centre through the pixel centre (time 0.5), closest solid hit (t_min = 0.001), then the
- * constant media in scan order entered before it (no random distance).  albedo W*H*3: lambertian / isotropic = texture at the hit,
+ * constant media in scan order entered before it (no random distance).  A ray that starts inside a medium (boundary entry below t_min)
+ * does not enter it: that medium is passed over, so a camera inside smoke or fog sees the solids behind it.  albedo W*H*3: lambertian / isotropic = texture at the hit,
  * metal = its colour, dielectric / diffuse_light = 1; normal W*H*3: world space, front-face oriented (medium: -unit(dir)); depth W*H:
  * t * |dir|.  A miss: albedo = camera background, normal = 0, depth = 0 (the "no hit" sentinel).
  *

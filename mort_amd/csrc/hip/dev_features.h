@@ -79,8 +79,9 @@ DEV void feat_scan_solids(const DScene &sc, const Ray &r, float &closest, Best &
     }
 }
 
-/* the constant media in scan order after the solids: world::hit's two boundary_t calls and clamps to [t_min, closest],
- * no random distance -- a medium the ray enters before the closest solid is hit at its entry t1 */
+/* the constant media in scan order after the solids: world::hit's two boundary_t calls and its clamp of the exit to closest,
+ * no random distance -- a medium the ray enters before the closest solid is hit at its entry t1.  A ray that starts inside a
+ * medium (entry below t_min) does not enter it: that medium is no first hit, and the pixel shows what lies behind it */
 DEV void feat_media(const DScene &sc, const Ray &ray, float &closest, Best &best) {
     for (int i = 0; i < sc.n_items; i++) {
         const DItem it = sc.items[i];
@@ -88,7 +89,7 @@ DEV void feat_media(const DScene &sc, const Ray &ray, float &closest, Best &best
         float t1, t2;
         if (!boundary_t(sc, ray, it.first, it.count, -__builtin_inff(), __builtin_inff(), t1)) continue;
         if (!boundary_t(sc, ray, it.first, it.count, (float)((double)t1 + 0.0001), __builtin_inff(), t2)) continue;
-        if (t1 < 0.001f) t1 = 0.001f;
+        if (t1 < 0.001f) continue;
         if (t2 > closest) t2 = closest;
         if (t1 >= t2) continue;
         closest = t1;

@@ -892,6 +892,105 @@ void mort_oracle_light_random(const mort_world *w, int type, int idx, const floa
     memcpy(dir, d.e, sizeof d.e);
 }
 
+/* ---- batched, threaded forms of the entry points above (tests/feature_ref.py): loops, no arithmetic of their own ---- */
+enum { MORT_ORACLE_BATCH_OK = 0, MORT_ORACLE_BATCH_BAD_ARGS = -1, MORT_ORACLE_BATCH_NO_STREAM = -3 };
+
+/* would hit_dispatch on this object reach constant_medium_hit's random_float()? */
+static bool object_draws(const mort_world *w, int type, int idx, int depth) {
+    const mort_world_objects *o = &w->objs;
+    if (depth > 16) return true; /* a cyclic reference: refuse rather than recurse */
+    switch (type) {
+    case MORT_OBJ_CONSTANT_MEDIUM: return true;
+    case MORT_OBJ_TRANSLATE: return object_draws(w, o->host_translate[idx].obj_type, o->host_translate[idx].obj_idx, depth + 1);
+    case MORT_OBJ_ROTATE_Y: return object_draws(w, o->host_rotate_y[idx].obj_type, o->host_rotate_y[idx].obj_idx, depth + 1);
+    case MORT_OBJ_HITTABLE_LIST:
+        for (int i = 0; i < o->host_hittable_list[idx].num_objs; i++)
+            if (object_draws(w, o->host_hittable_list[idx].obj_types[i], o->host_hittable_list[idx].obj_idxs[i], depth + 1)) return true;
+        return false;
+    }
+    return false;
+}
+/* the same for world_hit: the objects its loops do not pass over */
+static bool world_draws(const mort_world *w) {
+    const mort_world_objects *o = &w->objs;
+    for (int b = 0; b < o->num_bvh; b++) {
+        if (o->host_bvh[b].skip) continue;
+        for (int n = 0; n < MORT_MAX_BVH_NODES; n++) {
+            const mort_bvh *v = &o->host_bvh[b];
+            if (v->is_internal_node[n]) continue;
+            if (object_draws(w, v->left_children_types[n], v->left_children_idxs[n], 0)) return true;
+            if (object_draws(w, v->right_children_types[n], v->right_children_idxs[n], 0)) return true;
+        }
+    }
+    if (w->bvh_mode) return false;
+    for (int i = 0; i < o->num_translates; i++) if (!o->host_translate[i].skip && object_draws(w, MORT_OBJ_TRANSLATE, i, 0)) return true;
+    for (int i = 0; i < o->num_rotate_y; i++) if (!o->host_rotate_y[i].skip && object_draws(w, MORT_OBJ_ROTATE_Y, i, 0)) return true;
+    for (int i = 0; i < o->num_constant_medium; i++) if (!o->host_constant_medium[i].skip) return true;
+    for (int i = 0; i < o->num_hittable_list; i++) if (!o->host_hittable_list[i].skip && object_draws(w, MORT_OBJ_HITTABLE_LIST, i, 0)) return true;
+    return false;
+}
+
+typedef struct {
+    const mort_world *w; int type, idx; /* type 0: world_hit */
+    int n, tid, nthreads;
+    const float *ray7, *t_min, *t_max; mort_rng_state *states; mort_oracle_hit *out; uint8_t *hit;
+} batch_job_t;
+
+#define BATCH_BLOCK 256
+static void *batch_job(void *arg) {
+    batch_job_t *j = arg;
+    for (int b = j->tid * BATCH_BLOCK; b < j->n; b += j->nthreads * BATCH_BLOCK)
+        for (int i = b; i < j->n && i < b + BATCH_BLOCK; i++) {
+            rng_t g = {j->states ? &j->states[i] : NULL, 0};
+            ctx_t c = {j->w, &g, 0};
+            const float *q = j->ray7 + 7 * (size_t)i;
+            ray r = {V(q[0], q[1], q[2]), V(q[3], q[4], q[5]), q[6]};
+            memset(&j->out[i], 0, sizeof j->out[i]);
+            j->hit[i] = j->type ? hit_dispatch(&c, j->type, j->idx, &r, j->t_min[i], j->t_max[i], &j->out[i])
+                                : world_hit(&c, &r, j->t_min[i], j->t_max[i], &j->out[i]);
+        }
+    return NULL;
+}
+
+static int batch_run(batch_job_t proto, int nthreads) {
+    if (!proto.w || proto.n < 0 || !proto.ray7 || !proto.t_min || !proto.t_max || !proto.out || !proto.hit) return MORT_ORACLE_BATCH_BAD_ARGS;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    batch_job_t jobs[256];
+    pthread_t th[256];
+    for (int t = 0; t < nthreads; t++) {
+        jobs[t] = proto; jobs[t].tid = t; jobs[t].nthreads = nthreads;
+        if (t > 0) pthread_create(&th[t], NULL, batch_job, &jobs[t]);
+    }
+    batch_job(&jobs[0]);
+    for (int t = 1; t < nthreads; t++) pthread_join(th[t], NULL);
+    return MORT_ORACLE_BATCH_OK;
+}
+
+int mort_oracle_world_hit_batch(const mort_world *w, int n, const float *ray7, const float *t_min, const float *t_max,
+                                mort_rng_state *states, mort_oracle_hit *out, uint8_t *hit, int nthreads) {
+    if (!w) return MORT_ORACLE_BATCH_BAD_ARGS;
+    if (!states && world_draws(w)) return MORT_ORACLE_BATCH_NO_STREAM;
+    return batch_run((batch_job_t){w, 0, 0, n, 0, 0, ray7, t_min, t_max, states, out, hit}, nthreads);
+}
+
+int mort_oracle_object_hit_batch(const mort_world *w, int type, int idx, int n, const float *ray7, const float *t_min, const float *t_max,
+                                 mort_rng_state *states, mort_oracle_hit *out, uint8_t *hit, int nthreads) {
+    if (!w || idx < 0) return MORT_ORACLE_BATCH_BAD_ARGS;
+    const mort_world_objects *o = &w->objs;
+    const int counts[] = {0, o->num_spheres, o->num_quads, o->num_translates, o->num_rotate_y, o->num_constant_medium, o->num_hittable_list};
+    if (type < MORT_OBJ_SPHERE || type > MORT_OBJ_HITTABLE_LIST || idx >= counts[type]) return MORT_ORACLE_BATCH_BAD_ARGS;
+    if (!states && object_draws(w, type, idx, 0)) return MORT_ORACLE_BATCH_NO_STREAM;
+    return batch_run((batch_job_t){w, type, idx, n, 0, 0, ray7, t_min, t_max, states, out, hit}, nthreads);
+}
+
+int mort_oracle_texture_value_batch(const mort_world *w, int n, const int *tex_type, const int *tex_idx, const float *u, const float *v,
+                                    const float *p, float *rgb) {
+    if (!w || n < 0 || !tex_type || !tex_idx || !u || !v || !p || !rgb) return MORT_ORACLE_BATCH_BAD_ARGS;
+    for (int i = 0; i < n; i++) mort_oracle_texture_value(w, tex_type[i], tex_idx[i], u[i], v[i], p + 3 * (size_t)i, rgb + 3 * (size_t)i);
+    return MORT_ORACLE_BATCH_OK;
+}
+
 /* mort_math.h entry points so tests can measure them against glibc */
 float mort_oracle_sinf(float x) { return mort_sinf(x); }
 float mort_oracle_cosf(float x) { return mort_cosf(x); }

@@ -55,6 +55,18 @@ void mort_oracle_texture_value(const mort_world *w, int tex_type, int tex_idx, f
 float mort_oracle_pdf_value(const mort_world *w, int type, int idx, const float origin[3], const float dir[3]);
 void mort_oracle_light_random(const mort_world *w, int type, int idx, const float origin[3], mort_rng_state *state, float dir[3]);
 
+/* Batched forms for tests that need a hit per pixel: n rays (ray7 as above, 7 floats each), per-ray t_min / t_max, the records
+ * and hit flags out, over `nthreads` host threads.  object_hit_batch runs the reference's hitDispatch (objects.cuh:858-887) on
+ * one object of the world alone.  `states` holds one stream per ray, or is NULL for a call that draws nothing: a call that
+ * would draw (a constant medium that is reached and not skipped) without streams returns -3 and computes nothing.
+ * Returns 0, or -1 for bad arguments. */
+int mort_oracle_world_hit_batch(const mort_world *w, int n, const float *ray7, const float *t_min, const float *t_max,
+                                mort_rng_state *states, mort_oracle_hit *out, uint8_t *hit, int nthreads);
+int mort_oracle_object_hit_batch(const mort_world *w, int type, int idx, int n, const float *ray7, const float *t_min, const float *t_max,
+                                 mort_rng_state *states, mort_oracle_hit *out, uint8_t *hit, int nthreads);
+int mort_oracle_texture_value_batch(const mort_world *w, int n, const int *tex_type, const int *tex_idx, const float *u, const float *v,
+                                    const float *p, float *rgb);
+
 float mort_oracle_sinf(float x);
 float mort_oracle_cosf(float x);
 void mort_oracle_sincosf(float x, float *s, float *c);

@@ -53,6 +53,13 @@ def lib():
             f = getattr(L, "mort_oracle_" + n); f.argtypes = [C.c_float]; f.restype = C.c_float
         L.mort_oracle_atan2f.argtypes = [C.c_float, C.c_float]; L.mort_oracle_atan2f.restype = C.c_float
         L.mort_oracle_sin.argtypes = [C.c_double]; L.mort_oracle_sin.restype = C.c_double
+        vp = C.c_void_p
+        L.mort_oracle_world_hit_batch.argtypes = [W, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]
+        L.mort_oracle_world_hit_batch.restype = C.c_int
+        L.mort_oracle_object_hit_batch.argtypes = [W, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]
+        L.mort_oracle_object_hit_batch.restype = C.c_int
+        L.mort_oracle_texture_value_batch.argtypes = [W, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.mort_oracle_texture_value_batch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -85,3 +92,62 @@ def render(world, cam, states=None, seed=S.DEFAULT_SEED, rows=None, nthreads=8, 
         raise RuntimeError(f"mort_oracle_render failed: {rc}")
     return dict(rgba=rgba, accum=accum, segments_px=seg, segments=int(st.segments), rng_draws=int(st.rng_draws),
                 states=states)
+
+
+# ---- batched hits (mort_oracle_*_batch): one record per ray ----
+HIT_DTYPE = np.dtype(dict(names=["p", "normal", "mat_idx", "mat_type", "t", "u", "v", "front_face"],
+                          formats=[("<f4", (3,)), ("<f4", (3,)), "<i4", "<i4", "<f4", "<f4", "<f4", "u1"],
+                          offsets=[Hit.p.offset, Hit.normal.offset, Hit.mat_idx.offset, Hit.mat_type.offset, Hit.t.offset, Hit.u.offset,
+                                   Hit.v.offset, Hit.front_face.offset], itemsize=C.sizeof(Hit)))
+BATCH_NO_STREAM = -3
+
+
+class OracleBatchError(RuntimeError):
+    def __init__(self, status, what):
+        self.status = status
+        super().__init__(f"{what}: {status}")
+
+
+def _batch_args(rays, t_min, t_max, states):
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 7)
+    n = rays.shape[0]
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, dtype=np.float32), (n,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, dtype=np.float32), (n,)))
+    if states is not None:
+        assert states.dtype == STATE_DTYPE and states.shape == (n,) and states.flags.c_contiguous
+    return rays, n, lo, hi, np.zeros(n, dtype=HIT_DTYPE), np.zeros(n, dtype=np.uint8)
+
+
+def world_hit_batch(world, rays, t_min, t_max, states=None, nthreads=8):
+    """world::hit for n rays (n, 7: origin, direction, time); t_min / t_max scalars or (n,).  states: one stream per ray
+    (STATE_DTYPE, advanced in place) or None when nothing draws.  Returns (records HIT_DTYPE (n,), hit bool (n,))."""
+    rays, n, lo, hi, out, hit = _batch_args(rays, t_min, t_max, states)
+    rc = lib().mort_oracle_world_hit_batch(world.ptr, n, rays.ctypes.data, lo.ctypes.data, hi.ctypes.data,
+                                           states.ctypes.data if states is not None else None, out.ctypes.data, hit.ctypes.data, nthreads)
+    if rc != 0:
+        raise OracleBatchError(rc, "mort_oracle_world_hit_batch")
+    return out, hit.astype(bool)
+
+
+def object_hit_batch(world, obj_type, obj_idx, rays, t_min, t_max, states=None, nthreads=8):
+    """hitDispatch on one object of the world alone, for n rays; arguments and result as world_hit_batch."""
+    rays, n, lo, hi, out, hit = _batch_args(rays, t_min, t_max, states)
+    rc = lib().mort_oracle_object_hit_batch(world.ptr, obj_type, obj_idx, n, rays.ctypes.data, lo.ctypes.data, hi.ctypes.data,
+                                            states.ctypes.data if states is not None else None, out.ctypes.data, hit.ctypes.data, nthreads)
+    if rc != 0:
+        raise OracleBatchError(rc, "mort_oracle_object_hit_batch")
+    return out, hit.astype(bool)
+
+
+def texture_value_batch(world, tex_type, tex_idx, u, v, p):
+    """texture value_dispatch for n points: tex_type / tex_idx / u / v (n,), p (n, 3) -> rgb (n, 3) float32."""
+    p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    tt, ti = (np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32), (n,))) for a in (tex_type, tex_idx))
+    u, v = (np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float32), (n,))) for a in (u, v))
+    rgb = np.zeros((n, 3), dtype=np.float32)
+    rc = lib().mort_oracle_texture_value_batch(world.ptr, n, tt.ctypes.data, ti.ctypes.data, u.ctypes.data, v.ctypes.data, p.ctypes.data,
+                                               rgb.ctypes.data)
+    if rc != 0:
+        raise OracleBatchError(rc, "mort_oracle_texture_value_batch")
+    return rgb

@@ -1,13 +1,15 @@
 """The feature pass and the a-trous denoiser on the MI355X: feat_kernel and atrous_kernel must give the host
 forms' bits (the same bodies, dev_features.h), with either traversal, under a row partition and on torch tensors; and they must
-leave the render's state alone -- the next frame is bit-identical to a run without them."""
+leave the render's state alone -- the next frame is bit-identical to a run without them.  feat_kernel is also held, word for
+word, to tests/feature_ref.py: the contract restated from the CPU oracle's entry points, which shares no code with it."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from mort_amd import hip, host
-from tests.worlds import FLAT_WORLDS, flat_camera, flat_world
+from tests.feature_ref import MEDIUM, SOLID, assert_same_words, oracle_features
+from tests.worlds import FLAT_WORLDS, PLACED, flat_camera, flat_world, random_world, set_view
 
 pytestmark = pytest.mark.gpu
 
@@ -70,6 +72,109 @@ def test_features_compose_under_a_partition(gpu_ctx, sid):
     finally:
         gpu_ctx.set_partition(0, 1, 8)
     _same_features(parts, ref, f"scene {sid}, two ranks")
+
+
+# ---- feat_kernel<false> (MORT_NO_GEN=1) and feat_kernel<true> against the oracle-made reference, tolerance 0 ----
+def _gpu_equals_oracle(ctx, world, cam, monkeypatch, what):
+    ref = oracle_features(world, cam, nthreads=16)
+    for no_gen in (False, True):
+        assert_same_words(_gpu_features(ctx, world, cam, no_gen, monkeypatch), ref, f"{what} MORT_NO_GEN={int(no_gen)}")
+    return ref
+
+
+def _sized(sid, width, height):
+    """a built-in scene's camera at an arbitrary frame size"""
+    world, cam = host.build_scene(sid, width=width, spp=1, aspect=width / (height + 0.5))
+    assert (cam.image_width, cam.image_height) == (width, height)
+    return world, cam
+
+
+@pytest.mark.parametrize("sid", range(1, 11))
+def test_features_equal_the_oracle_on_every_scene(gpu_ctx, monkeypatch, sid):
+    world, cam = host.build_scene(sid, width=160, spp=1)
+    ref = _gpu_equals_oracle(gpu_ctx, world, cam, monkeypatch, f"scene {sid}")
+    assert (ref["kind"] == SOLID).sum() > (0.005 if sid == 10 else 0.3) * ref["kind"].size
+    if sid == 7:
+        assert (ref["kind"] == MEDIUM).sum() > 0.1 * ref["kind"].size
+    if sid in (8, 9):
+        assert (ref["started_inside"] >= 1).all() and (ref["depth"] > 1).all(), "geometry, not the fog shell around the camera"
+
+
+@pytest.mark.parametrize("name", sorted(FLAT_WORLDS))
+def test_features_equal_the_oracle_on_awkward_worlds(gpu_ctx, monkeypatch, name):
+    spec = FLAT_WORLDS[name]
+    w, ids = flat_world(spec["prims"], media=spec.get("media", ()), late_list=spec.get("late_list", False))
+    cam = flat_camera(light=ids[spec["light"][1]] if spec.get("light") else None, spp=1)
+    ref = _gpu_equals_oracle(gpu_ctx, w, cam, monkeypatch, name)
+    assert name == "empty" or (ref["kind"] == SOLID).sum() > 0.02 * ref["kind"].size
+    assert not spec.get("media") or (ref["kind"] == MEDIUM).sum() > 0.02 * ref["kind"].size
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_features_equal_the_oracle_on_random_worlds(gpu_ctx, monkeypatch, seed):
+    """the first 8 random worlds of tests/test_host_mode.py from that test's four views"""
+    rng = np.random.default_rng(1000 + seed)
+    w, light = random_world(rng, n_spheres=int(rng.integers(1, 60)), n_quads=int(rng.integers(0, 12)), n_boxes=int(rng.integers(0, 3)),
+                            n_media=int(rng.integers(0, 3)), with_light=bool(seed % 2))
+    _, cam = host.build_scene(2, width=56, spp=1, depth=int(rng.integers(2, 20)))
+    for i in range(3):
+        cam.background.e[i] = float(rng.uniform(0.0, 0.8)) * (0 if light and seed % 4 == 1 else 1)
+    views = [((0, 2, 9), (0, 1, 0)), ((0.3, 0.05, 0.2), (4, 0.3, 1)), ((40, 25, -60), (0, 0, 0)), (tuple(rng.uniform(-5, 5, 3) + (0, 6, 0)), tuple(rng.uniform(-2, 2, 3)))]
+    solid = 0
+    for k, (frm, at) in enumerate(views):
+        set_view(cam, frm, at, vfov=int(rng.integers(20, 90)), defocus=float(rng.choice([0.0, 0.0, 0.8])))
+        solid += (_gpu_equals_oracle(gpu_ctx, w, cam, monkeypatch, f"random world {seed} view {k}")["kind"] == SOLID).sum()
+    assert solid > 0.3 * 4 * cam.image_width * cam.image_height
+
+
+@pytest.mark.parametrize("name", sorted(PLACED))
+def test_features_equal_the_oracle_from_placed_cameras(gpu_ctx, monkeypatch, name):
+    """what each case must show is asserted on the reference in tests/test_features_oracle.py"""
+    from tests import test_features_oracle as T
+    w, cam = PLACED[name]()
+    ref = _gpu_equals_oracle(gpu_ctx, w, cam, monkeypatch, name)
+    getattr(T, "_placed_" + name)(w, cam, ref)
+
+
+@pytest.mark.parametrize("nranks", [2, 3])
+def test_partitioned_features_equal_the_oracle(gpu_ctx, nranks):
+    world, cam = host.build_scene(9, width=120, spp=1)
+    ref = oracle_features(world, cam, nthreads=16)
+    gpu_ctx.upload_world(world)
+    H = cam.image_height
+    parts = {k: np.full(ref[k].shape, np.nan, dtype=np.float32) for k in KEYS}
+    seen = []
+    try:
+        for rank in range(nranks):
+            gpu_ctx.set_partition(rank, nranks, 8)
+            out = {k: np.full(ref[k].shape, np.nan, dtype=np.float32) for k in KEYS}
+            st = hip.lib().mort_hip_render_features(gpu_ctx._h, C.byref(cam), out["albedo"].ctypes.data, out["normal"].ctypes.data,
+                                                    out["depth"].ctypes.data, None)
+            assert st == 0
+            rows = [gpu_ctx.global_row(ly) for ly in range(gpu_ctx.local_rows(H))]
+            seen += rows
+            for k in KEYS:
+                parts[k][rows] = out[k][rows]
+    finally:
+        gpu_ctx.set_partition(0, 1, 8)
+    assert sorted(seen) == list(range(H))
+    assert_same_words(parts, ref, f"scene 9, {nranks} ranks")
+
+
+@pytest.mark.parametrize("sid,width,height", [(9, 61, 35), (6, 61, 35), (9, 5, 3), (1, 5, 3), (9, 1, 1), (6, 1, 1)])
+def test_ragged_frames_equal_the_oracle(gpu_ctx, monkeypatch, sid, width, height):
+    world, cam = _sized(sid, width, height)
+    ref = _gpu_equals_oracle(gpu_ctx, world, cam, monkeypatch, f"scene {sid} at {width}x{height}")
+    assert (ref["kind"] == SOLID).any()
+
+
+@pytest.mark.parametrize("sid,width,height", [(1, 1200, 675), (6, 800, 800), (9, 800, 800)])
+def test_large_frames_equal_the_oracle(gpu_ctx, monkeypatch, sid, width, height):
+    """sizes no other feature test reaches: many workgroups per row and per column, every pixel against the oracle"""
+    world, cam = host.build_scene(sid, width=width, spp=1)
+    assert (cam.image_width, cam.image_height) == (width, height)
+    ref = _gpu_equals_oracle(gpu_ctx, world, cam, monkeypatch, f"scene {sid} at {width}x{height}")
+    assert (ref["kind"] == SOLID).sum() > 0.5 * width * height
 
 
 PARAMS = [dict(), dict(iterations=0), dict(iterations=1), dict(iterations=3, sigma_color=0.7, sigma_depth=0.5, sigma_albedo=0.3, normal_log2_power=1),

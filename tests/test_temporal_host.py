@@ -401,7 +401,9 @@ def _sequence(sid, kind, frames=8, width=96, spp=4):
     return world, cams, frames_, ref
 
 
-QUALITY = [(1, "still", 0.45), (3, "still", 0.45), (6, "still", 0.45),
+# scene 8 (camera inside the fog shell): the limits are the ratios measured with the medium entry clamped to t_min,
+# 0.5112 still and exactly 1 with the keys (no tap passed the depth test); the fog passed over gives 0.511 and 0.478.
+QUALITY = [(1, "still", 0.45), (3, "still", 0.45), (6, "still", 0.45), (8, "still", 0.5113), (8, "keys", 1.0),
            (1, "keys", 0.82), (1, "mouse", 0.46), (3, "keys", 1.0), (3, "mouse", 0.96), (6, "keys", 0.37), (6, "mouse", 0.38)]
 
 

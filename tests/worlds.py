@@ -104,6 +104,67 @@ FLAT_WORLDS = {
 }
 
 
+def random_world(rng, n_spheres, n_quads, n_boxes, n_media, with_light):
+    """A random brute-force world: spheres (some moving, some huge, some tiny), quads, rotated / translated boxes, media in
+    sphere boundaries; every material kind.  Returns (world, light (type, idx) or None)."""
+    L = host.lib()
+    w = host.World()
+
+    palette = []
+
+    def material():
+        # the reference's tables are small (20 isotropics, 50 dielectrics, ...): draw from a palette of at most 16
+        if len(palette) >= 16:
+            return palette[int(rng.integers(0, len(palette)))]
+        m = new_material()
+        palette.append(m)
+        return m
+
+    def new_material():
+        k = rng.integers(0, 6)
+        col = tuple(rng.uniform(0.1, 0.95, 3))
+        if k == 0:
+            return S.MAT_METAL, L.mort_add_metal(w.ptr, host.vec3(*col), float(rng.uniform(0, 1)))
+        if k == 1:
+            return S.MAT_DIELECTRIC, L.mort_add_dielectric(w.ptr, float(rng.uniform(1.1, 2.0)))
+        if k == 2:
+            c = L.mort_add_solid_color(w.ptr, host.vec3(*col))
+            return S.MAT_ISOTROPIC, L.mort_add_isotropic(w.ptr, S.TEXTURE_SOLID, c)
+        if k == 3:
+            c1 = L.mort_add_solid_color(w.ptr, host.vec3(*col)); c2 = L.mort_add_solid_color(w.ptr, host.vec3(.9, .9, .9))
+            ck = L.mort_add_checker_texture(w.ptr, float(rng.uniform(0.2, 2.0)), S.TEXTURE_SOLID, c1, S.TEXTURE_SOLID, c2)
+            return S.MAT_LAMBERTIAN, L.mort_add_lambertian(w.ptr, S.TEXTURE_CHECKER, ck)
+        c = L.mort_add_solid_color(w.ptr, host.vec3(*col))
+        return S.MAT_LAMBERTIAN, L.mort_add_lambertian(w.ptr, S.TEXTURE_SOLID, c)
+
+    light = None
+    if with_light:
+        c = L.mort_add_solid_color(w.ptr, host.vec3(7, 7, 7))
+        lm = L.mort_add_diffuse_light(w.ptr, S.TEXTURE_SOLID, c)
+        q = L.mort_add_quad(w.ptr, host.vec3(-2, 6, -2), host.vec3(4, 0, 0), host.vec3(0, 0, 4), S.MAT_DIFFUSE_LIGHT, lm, False)
+        light = (S.OBJ_QUAD, q)
+    mt, mi = material()
+    L.mort_add_sphere(w.ptr, host.vec3(0, -1000, 0), 1000.0, mt, mi, False)  # ground: a huge sphere among small ones
+    for _ in range(n_spheres):
+        mt, mi = material()
+        c = rng.uniform(-6, 6, 3) * (1, 0.3, 1) + (0, 1.2, 0)
+        r = float(rng.choice([0.05, 0.2, 0.5, 1.0, 1.5]))
+        if rng.random() < 0.3:
+            L.mort_add_moving_sphere(w.ptr, host.vec3(*c), host.vec3(*(c + rng.uniform(-0.5, 0.5, 3))), r, mt, mi, False)
+        else:
+            L.mort_add_sphere(w.ptr, host.vec3(*c), r, mt, mi, False)
+    for _ in range(n_quads):
+        mt, mi = material()
+        L.mort_add_quad(w.ptr, host.vec3(*rng.uniform(-5, 5, 3)), host.vec3(*rng.uniform(-2, 2, 3)), host.vec3(*rng.uniform(-2, 2, 3)), mt, mi, False)
+    for _ in range(n_boxes):
+        mt, mi = material()
+        L.mort_rotated_box(w.ptr, host.vec3(*rng.uniform(0.3, 2.0, 3)), host.vec3(*(rng.uniform(-5, 5, 3) * (1, 0, 1))), float(rng.uniform(-60, 60)), mt, mi)
+    for _ in range(n_media):
+        b = L.mort_add_sphere(w.ptr, host.vec3(*(rng.uniform(-4, 4, 3) * (1, 0.2, 1) + (0, 1, 0))), float(rng.uniform(0.5, 2.5)), S.MAT_DIELECTRIC, L.mort_add_dielectric(w.ptr, 1.5), True)
+        c = L.mort_add_solid_color(w.ptr, host.vec3(*rng.uniform(0.2, 1.0, 3)))
+        L.mort_add_constant_medium(w.ptr, S.OBJ_SPHERE, b, float(rng.uniform(0.05, 3.0)), S.MAT_ISOTROPIC, L.mort_add_isotropic(w.ptr, S.TEXTURE_SOLID, c), False)
+    w.c.bvh_mode = False
+    return w, light
 
 
 def custom_bvh_world(spheres, noise_seed=1):
@@ -248,4 +309,73 @@ BVH_BUILDS = {
     "scene1_shuffled": lambda: _scene_list_world(1, lambda e: [e[i] for i in np.random.default_rng(1).permutation(len(e))]),
     "scene10_shuffled": lambda: _scene_list_world(10, lambda e: [e[i] for i in np.random.default_rng(10).permutation(len(e))]),
     **{f"random{n}": (lambda n=n: _list_world(_random_list(n, n))) for n in (4, 5, 17, 64, 200, 480)},
+}
+
+
+# ---- cameras shared by the feature tests (tests/test_features_oracle.py, tests/test_gpu_denoise.py) ----
+
+def bvh_camera(width=144, spp=9):
+    """the camera test_small_and_awkward_bvh_worlds (tests/test_gpu_parity.py) puts in front of the BVH_WORLDS"""
+    _, cam = host.build_scene(1, width=width, spp=spp, depth=12)
+    set_view(cam, (0.0, 0.6, 1.5), (0.0, 0.0, -1.0), vfov=60, defocus=0.0)
+    return cam
+
+
+def bvh_scene_views(sid):
+    """test_other_viewpoints' list (tests/test_gpu_parity.py) for the reference-BVH scenes 1 and 10: (lookfrom, lookat, vfov,
+    defocus) inside the sphere field, at and under the ground, straight up / down / along an axis, far out, 4 random ones"""
+    rng = np.random.default_rng(7 + sid)
+    views = [((0.5, 0.3, 0.5), (3.0, 0.3, 0.2)), ((0.0, 0.21, 2.0), (0.0, 0.21, -5.0)), ((2.0, -3.0, 1.0), (0.0, 1.0, 0.0)),
+             ((0.0, 30.0, 0.0), (0.0, 0.0, 0.001)), ((0.0, 0.5, 0.0), (0.0, 10.0, 0.0001)), ((5.0, 1.0, 0.0), (-5.0, 1.0, 0.0)),
+             ((300.0, 120.0, 200.0), (0.0, 0.0, 0.0)), ((0.0, 1.0, 0.0), (4.0, 1.0, 0.0))]
+    views += [(tuple(rng.uniform(-9, 9, 3) * (1, 0.2, 1) + (0, 0.5, 0)), tuple(rng.uniform(-6, 6, 3) * (1, 0.1, 1))) for _ in range(4)]
+    return [(frm, at, 20 if k % 3 else 70, 0.0 if k % 2 else 0.6) for k, (frm, at) in enumerate(views)]
+
+
+def gen_scene_views(sid):
+    """test_gen_other_viewpoints' list (tests/test_gpu_gen.py) for scenes 6, 7, 9: inside the box / the cluster, at floor
+    level, along an axis, from outside, from beyond the unified tree's reach (the fifth), 4 random ones"""
+    rng = np.random.default_rng(11 + sid)
+    views = [((278, 278, 100), (278, 278, 555)), ((278, 1.0, 278), (300, 1.0, 0)), ((100, 300, 100), (100, 0, 100.001)),
+             ((278, 278, -800), (278, 278, 0)), ((-3e5, 4e5, -9e5), (278, 278, 0)), ((130, 60, 200), (400, 200, 300))]
+    views += [(tuple(rng.uniform(0, 555, 3)), tuple(rng.uniform(0, 555, 3))) for _ in range(4)]
+    return [(frm, at, 40 if k % 3 else 80, 0.0 if k % 2 else 0.5) for k, (frm, at) in enumerate(views)]
+
+
+GEN_FAR_VIEW = 4  # index into gen_scene_views: the camera beyond the tree's reach
+
+
+def _placed_flat(prims, media, frm, at, vfov=55, width=96):
+    w, _ = flat_world(prims, media=media)
+    cam = flat_camera(spp=1, width=width)
+    set_view(cam, frm, at, vfov=vfov, defocus=0.0)
+    return w, cam
+
+
+def _placed_scene(sid, frm, at, vfov, width=96):
+    w, cam = host.build_scene(sid, width=width, spp=1)
+    set_view(cam, frm, at, vfov=vfov, defocus=0.0)
+    return w, cam
+
+
+_BACK = ("sphere", (0, 0, -4), 1.5, ("checker",))
+_MED = ((0, 0, -1), 0.5, 1.0, (.9, .4, .2))
+# Cameras placed on purpose.  name -> () -> (world, camera); tests/test_features_oracle.py states what each must show.
+PLACED = {
+    # every ray starts inside the medium: it is no first hit, the checkered sphere behind it is
+    "inside_small_medium": lambda: _placed_flat([_BACK], [_MED], (0.1, 0.05, -0.9), (0, 0, -4)),
+    # the final scene's fog shell (radius 5000) holds the camera: the sphere cluster under rotate_y / translate ...
+    "fog_cluster": lambda: _placed_scene(8, (100, 350, 0), (-20, 350, 480), 50),
+    # ... and the moving sphere at time 0.5
+    "fog_moving_sphere": lambda: _placed_scene(8, (400, 400, -150), (415, 400, 200), 40),
+    # a solid in front of, inside and behind a medium along the centre ray
+    "solid_before_medium": lambda: _placed_flat([("sphere", (0, 0, 0.5), 0.15, ("lamb", (.1, .2, .3)))], [_MED], (0, 0, 3), (0, 0, -1), vfov=30),
+    "solid_inside_medium": lambda: _placed_flat([("sphere", (0, 0, -1), 0.2, ("lamb", (.1, .2, .3)))], [_MED], (0, 0, 3), (0, 0, -1), vfov=30),
+    "solid_behind_medium": lambda: _placed_flat([("sphere", (0, 0, -3), 1.5, ("lamb", (.1, .2, .3)))], [_MED], (0, 0, 3), (0, 0, -1), vfov=30),
+    # a medium seen from so far away that fp32 leaves some silhouette rays a chord below constant_medium::hit's 0.0001 step
+    "grazed_medium": lambda: _placed_flat([], [((0, 0, 0), 100.0, 0.02, (1, 1, 1))], (3000, 1000, 7000), (0, 0, 0), vfov=2, width=160),
+    "quad_from_behind": lambda: _placed_flat([("quad", (-1, -0.5, -1.5), (2, 0, 0), (0, 1.5, 0.3), ("lamb", (.2, .5, .8)))], [], (0.3, 0.4, -5), (0, 0, -1.5)),
+    "inside_glass_sphere": lambda: _placed_flat(FLAT_WORLDS["concentric_glass"]["prims"], [], (0.05, 0.02, -1.0), (3, 0.5, -1)),
+    # the lens centre lies on the sphere (0, 0, -1) r 0.5: the root at t = 0 is below t_min, rays into the ball leave by its far side
+    "camera_on_surface": lambda: _placed_flat([("sphere", (0, 0, -1), 0.5, ("lamb", (.7, .3, .3)))], [], (0, 0, -0.5), (1, 0, -0.5), vfov=90),
 }
