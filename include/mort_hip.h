@@ -233,6 +233,38 @@ int mort_hip_temporal_host(const mort_temporal_params *params, const mort_camera
                            int nthreads, const float *accum, const float *normal, const float *depth, const float *hist_in, float *hist_out,
                            float *accum_out, float *variance_out, uint8_t *rgba_out, double *seconds);
 
+/* ---- the SVGF filter stage: a variance-guided a-trous filter over the accumulated colour (Schied et al., HPG 2017).
+ * NOT parity.  After the temporal step (or on a single frame): accum (W*H*3) and the features (albedo, normal W*H*3, depth W*H) as
+ * for mort_hip_denoise*, plus variance (W*H) = what mort_hip_temporal* writes as variance_out, the estimated variance of the
+ * accumulated luminance mean.  A negative value, or variance == NULL, means unknown: that pixel's variance is then estimated from
+ * the luminance of its 5x5 neighbourhood.  The filter works on E = C / max(A, 1e-3) and carries the variance of E's luminance with
+ * it; iteration i at step 2^i stops at luminance differences of sigma_luminance standard deviations (the 3x3 Gaussian of the
+ * variance), at depth, normal and albedo edges as the denoiser does, and never mixes hits with misses.  Outputs: accum_out (W*H*3),
+ * rgba_out (uchar4 W*H: the render's NaN guard and gamma tail) and variance_out (W*H: the filtered variance, in the units of the
+ * input); each may be NULL, none may alias an input or another output.  iterations == 0 returns accum unchanged, the render's own
+ * rgba and the prepared variance.  Whole image, whatever the context's partition.  None of these calls draws a random number or
+ * touches what the render keeps across frames. ---- */
+typedef struct mort_svgf_params {
+    int iterations;          /* 0..8; iteration i filters at step 2^i */
+    float sigma_luminance;   /* luminance difference in standard deviations of the (prefiltered) variance */
+    float sigma_depth;       /* relative depth difference per step */
+    float sigma_albedo;      /* albedo difference */
+    int normal_log2_power;   /* normal weight max(0, Np.Nq)^(2^k), k squarings; 0..16 */
+} mort_svgf_params;
+int mort_hip_svgf_defaults(mort_svgf_params *params);
+/* host buffers; the kernels' HIP-event time in *seconds */
+int mort_hip_svgf(mort_ctx *ctx, const mort_svgf_params *params, int width, int height, const float *accum, const float *albedo,
+                  const float *normal, const float *depth, const float *variance, float *accum_out, float *variance_out, uint8_t *rgba_out,
+                  double *seconds);
+/* the same on DEVICE buffers of the whole image, on `stream` (NULL = the context's); asynchronous when seconds is NULL */
+int mort_hip_svgf_device(mort_ctx *ctx, const mort_svgf_params *params, int width, int height, const void *d_accum, const void *d_albedo,
+                         const void *d_normal, const void *d_depth, const void *d_variance, void *d_accum_out, void *d_variance_out,
+                         void *d_rgba_out, void *stream, double *seconds);
+/* host loop of the same bodies: no GPU, no HIP runtime call */
+int mort_hip_svgf_host(const mort_svgf_params *params, int width, int height, int nthreads, const float *accum, const float *albedo,
+                       const float *normal, const float *depth, const float *variance, float *accum_out, float *variance_out,
+                       uint8_t *rgba_out, double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

@@ -11,6 +11,7 @@
  *                   [--keys WASD..] [--mouse dx,dy]        the reference's interactive loop, scripted: one idle tick per frame
  *                   [--denoise] [--features-out PREFIX]   first-hit features + a-trous denoiser on the last frame (single GPU / host)
  *                   [--temporal] [--variance-out F]       temporal accumulation across frames with reprojection (single GPU / host)
+ *                   [--svgf]                              variance-guided a-trous filter (SVGF) on the last frame (single GPU / host)
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -22,6 +23,10 @@
  * camera, none for frame 0); --out then holds the accumulated image of the last frame, --denoise filters the accumulated colour
  * with the last frame's features, --dump-f32 stays the raw render, and the JSON line gains "temporal_seconds" (features + temporal,
  * summed over frames).  --variance-out F writes the last step's variance estimate (W*H floats, -1 = unknown).
+ * --svgf (not with --denoise): after the last frame, the feature pass for its camera and the SVGF filter stage (default parameters)
+ * over its accumulators, the variance from the spatial estimate; with --temporal, over the accumulated colour with the last step's
+ * features and its variance.  --out then holds the filtered image (--dump-f32 stays the raw render, --variance-out the temporal
+ * step's variance) and the JSON line gains "svgf_seconds" (features + filter).
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -65,7 +70,7 @@ static int usage(void) {
     printf("Usage: mort <number_between_1_and_10> [--width W] [--aspect A] [--spp N] [--depth D] [--seed S] [--frames N] "
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
-           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F]\n");
+           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf]\n");
     return -1;
 }
 
@@ -107,7 +112,7 @@ int main(int argc, char **argv) {
     double aspect = 0;
     unsigned long long seed = MORT_DEFAULT_SEED;
     const char *out = NULL, *dump = NULL, *sin = NULL, *sout = NULL, *earth = NULL, *keys = NULL, *feat_out = NULL, *var_out = NULL;
-    int denoise = 0, temporal = 0;
+    int denoise = 0, temporal = 0, svgf = 0;
     int mouse_dx = 0, mouse_dy = 0;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
@@ -145,6 +150,7 @@ int main(int argc, char **argv) {
         else if (ARG("--features-out")) feat_out = argv[++i];
         else if (strcmp(argv[i], "--temporal") == 0) temporal = 1;
         else if (ARG("--variance-out")) var_out = argv[++i];
+        else if (strcmp(argv[i], "--svgf") == 0) svgf = 1;
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -152,6 +158,8 @@ int main(int argc, char **argv) {
     if (gpus > 1 && (dump || sin || sout)) { fprintf(stderr, "--dump-f32 / --states-in / --states-out are single-GPU options\n"); return -1; }
     if (gpus > 1 && (denoise || feat_out)) { fprintf(stderr, "--denoise / --features-out are single-GPU options\n"); return -1; }
     if (gpus > 1 && (temporal || var_out)) { fprintf(stderr, "--temporal / --variance-out are single-GPU options\n"); return -1; }
+    if (gpus > 1 && svgf) { fprintf(stderr, "--svgf is a single-GPU option\n"); return -1; }
+    if (svgf && denoise) { fprintf(stderr, "--svgf and --denoise exclude each other\n"); return -1; }
     if (var_out && !temporal) { fprintf(stderr, "--variance-out needs --temporal\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
@@ -216,7 +224,7 @@ int main(int argc, char **argv) {
     }
 
     uint8_t *rgba = calloc(npx, 4);
-    const int want_accum = dump || denoise || temporal;
+    const int want_accum = dump || denoise || temporal || svgf;
     float *accum = want_accum ? calloc(npx * 3, sizeof(float)) : NULL;
     if (!rgba || (want_accum && !accum)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
     /* --temporal: this frame's features (albedo unused), the ping-ponged history, the accumulated colour and the variance */
@@ -312,10 +320,10 @@ int main(int argc, char **argv) {
         }
     }
 
-    /* ---- --denoise / --features-out (single GPU or host mode): the last frame's camera; the PPM becomes the denoised image.  With
-     * --temporal the features are the last step's and the denoiser filters the accumulated colour ---- */
-    double denoise_sec = 0;
-    if (denoise || feat_out) {
+    /* ---- --denoise / --svgf / --features-out (single GPU or host mode): the last frame's camera; the PPM becomes the filtered image.
+     * With --temporal the features are the last step's and the filter takes the accumulated colour (--svgf: and its variance) ---- */
+    double denoise_sec = 0, svgf_sec = 0;
+    if (denoise || svgf || feat_out) {
         if (!temporal) {
             alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
             if (!alb || !nrm || !dep) { fprintf(stderr, "out of memory\n"); fail_exit(); }
@@ -332,6 +340,14 @@ int main(int argc, char **argv) {
             if (host_mode) { if ((st = mort_hip_denoise_host(&dp, W, H, threads, col, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_denoise_host"); }
             else if ((st = mort_hip_denoise(ctx, &dp, W, H, col, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(ctx, st, "mort_hip_denoise");
             denoise_sec = fs + ds;
+        }
+        if (svgf) {
+            const float *col = temporal ? tacc : accum;
+            mort_svgf_params sp;
+            mort_hip_svgf_defaults(&sp);
+            if (host_mode) { if ((st = mort_hip_svgf_host(&sp, W, H, threads, col, alb, nrm, dep, tvar, NULL, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_svgf_host"); }
+            else if ((st = mort_hip_svgf(ctx, &sp, W, H, col, alb, nrm, dep, tvar, NULL, NULL, rgba, &ds)) != MORT_OK) die(ctx, st, "mort_hip_svgf");
+            svgf_sec = fs + ds;
         }
         if (feat_out) {
             const char *suffix[3] = {"albedo", "normal", "depth"};
@@ -379,6 +395,7 @@ int main(int argc, char **argv) {
            (unsigned long long)stats.algorithmic_hbm_bytes, stats.algorithmic_hbm_bytes / stats.seconds / 1e9,
            stats.algorithmic_hbm_bytes / stats.seconds / 8e12, (unsigned long long)stats.reference_walks, stats.kernel_name);
     if (denoise) printf(", \"denoise_seconds\": %.6f", denoise_sec); /* feature pass + denoise, device time (host loops: wall time) */
+    if (svgf) printf(", \"svgf_seconds\": %.6f", svgf_sec); /* feature pass + SVGF filter, likewise */
     if (temporal) printf(", \"temporal_seconds\": %.6f", temporal_sec); /* feature passes + temporal steps over all frames, likewise */
     printf("}\n");
     if (out && mort_write_ppm(out, rgba, W, H) != 0) { fprintf(stderr, "cannot write %s\n", out); return EXIT_FAILURE; }

@@ -114,6 +114,14 @@ struct mort_ctx {
     /* temporal accumulation (temporal.hip): mort_hip_temporal's device copies of the host buffers */
     void *d_tio = nullptr;
     size_t tio_cap = 0;
+    /* SVGF filter stage (svgf.hip): a buffer that frees itself when mort_hip_shutdown deletes the context */
+    struct Scratch {
+        void *p = nullptr;
+        size_t cap = 0;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    };
+    Scratch svgf;    /* the filter's float4 planes: colour + variance ping-pong, (normal, depth), albedo */
+    Scratch svgf_io; /* mort_hip_svgf: the host buffers' device copies */
 };
 
 static inline int hip_fail(mort_ctx *c, hipError_t e, const char *what) {

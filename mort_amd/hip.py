@@ -30,6 +30,7 @@ EXPORTS = [
     "mort_hip_denoise_defaults", "mort_hip_render_features", "mort_hip_render_features_device", "mort_hip_denoise",
     "mort_hip_denoise_device", "mort_hip_render_features_host", "mort_hip_denoise_host",
     "mort_hip_temporal_defaults", "mort_hip_temporal", "mort_hip_temporal_device", "mort_hip_temporal_host",
+    "mort_hip_svgf_defaults", "mort_hip_svgf", "mort_hip_svgf_device", "mort_hip_svgf_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 HOST_TREE = 1
@@ -79,6 +80,21 @@ class TemporalParams(C.Structure):
     def __init__(self, **kw):
         super().__init__()
         lib().mort_hip_temporal_defaults(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SvgfParams(C.Structure):
+    """mort_svgf_params: SvgfParams() holds the tuned defaults (mort_hip_svgf_defaults); keyword arguments override them."""
+    _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
+                ("normal_log2_power", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mort_hip_svgf_defaults(C.byref(self))
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -138,6 +154,11 @@ def lib():
         L.mort_hip_temporal.argtypes = [ctx, tp, cp, cp, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_temporal.restype = C.c_int
         L.mort_hip_temporal_device.argtypes = [ctx, tp, cp, cp, C.c_int, C.c_int] + [vp] * 9 + [dp]; L.mort_hip_temporal_device.restype = C.c_int
         L.mort_hip_temporal_host.argtypes = [tp, cp, cp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_temporal_host.restype = C.c_int
+        sp = C.POINTER(SvgfParams)
+        L.mort_hip_svgf_defaults.argtypes = [sp]; L.mort_hip_svgf_defaults.restype = C.c_int
+        L.mort_hip_svgf.argtypes = [ctx, sp, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_svgf.restype = C.c_int
+        L.mort_hip_svgf_device.argtypes = [ctx, sp, C.c_int, C.c_int] + [vp] * 9 + [dp]; L.mort_hip_svgf_device.restype = C.c_int
+        L.mort_hip_svgf_host.argtypes = [sp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_svgf_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -300,6 +321,37 @@ class Context:
                                                  C.byref(sec) if sync else None), "mort_hip_temporal_device")
         return sec.value if sync else None
 
+    def svgf(self, accum, albedo, normal, depth, variance=None, params=None):
+        """The SVGF filter stage on full-image host arrays on the GPU (include/mort_hip.h): variance (H, W) as Context.temporal
+        returns it, None = the spatial estimate everywhere.  dict(accum (H, W, 3) f32, variance (H, W) f32, rgba (H, W, 4) u8,
+        seconds)."""
+        params = params if params is not None else SvgfParams()
+        W, H, ins, outs = _svgf_arrays(accum, albedo, normal, depth, variance)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_svgf(self._h, C.byref(params), W, H, *[_ptr(a) for a in ins], *[_ptr(a) for a in outs], C.byref(sec)),
+                  "mort_hip_svgf")
+        return dict(accum=outs[0], variance=outs[1], rgba=outs[2], seconds=sec.value)
+
+    def svgf_device(self, width, height, accum, albedo, normal, depth, variance=None, accum_out=None, variance_out=None, rgba_out=None,
+                    params=None, sync=False):
+        """The SVGF filter stage on torch tensors of the whole image (float32: W*H*3, *3, *3, *1; variance and variance_out W*H;
+        rgba_out uint8 W*H*4), on the current torch stream.  variance and the outputs may be None.  Asynchronous unless sync (then
+        returns the device seconds) or torch runs on its legacy default stream."""
+        import torch
+        params = params if params is not None else SvgfParams()
+        n = width * height
+        pairs = ((accum, 3), (albedo, 3), (normal, 3), (depth, 1), (variance, 1), (accum_out, 3), (variance_out, 1))
+        _check_tensors(torch, [(t, ch) for t, ch in pairs if t is not None], n)
+        if rgba_out is not None:
+            assert rgba_out.dtype == torch.uint8 and rgba_out.is_contiguous() and rgba_out.numel() == 4 * n and rgba_out.device == accum.device
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, accum.device, sync)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._chk(lib().mort_hip_svgf_device(self._h, C.byref(params), width, height, ptr(accum), ptr(albedo), ptr(normal), ptr(depth),
+                                             ptr(variance), ptr(accum_out), ptr(variance_out), ptr(rgba_out), stream,
+                                             C.byref(sec) if sync else None), "mort_hip_svgf_device")
+        return sec.value if sync else None
+
     def calib_valu(self, waves_per_simd, kind=0):
         """Shader cycles one SIMD needs per wave64 VALU instruction at `waves_per_simd` resident waves (include/mort_hip.h)."""
         r = CalibValu()
@@ -428,6 +480,28 @@ def temporal_host(prev_cam, cam, accum, normal, depth, hist_in, hist_out=None, p
     if rc != 0:
         raise MortHipError(rc, "mort_hip_temporal_host")
     return dict(history=outs[0], accum=outs[1], variance=outs[2], rgba=outs[3], seconds=sec.value)
+
+
+def _svgf_arrays(accum, albedo, normal, depth, variance):
+    H, W = np.asarray(depth).shape[:2]
+    ins = [np.ascontiguousarray(a, dtype=np.float32) for a in (accum, albedo, normal, depth)]
+    ins.append(np.ascontiguousarray(variance, dtype=np.float32) if variance is not None else None)
+    for a, ch in zip(ins, (3, 3, 3, 1, 1)):
+        if a is not None and a.size != W * H * ch:
+            raise ValueError(f"expected {W * H * ch} floats, got {a.size}")
+    outs = [np.zeros((H, W, 3), dtype=np.float32), np.zeros((H, W), dtype=np.float32), np.zeros((H, W, 4), dtype=np.uint8)]
+    return W, H, ins, outs
+
+
+def svgf_host(accum, albedo, normal, depth, variance=None, params=None, nthreads=1):
+    """The SVGF filter stage as a host loop (mort_hip_svgf_host), no GPU: dict(accum, variance, rgba, seconds) as Context.svgf."""
+    params = params if params is not None else SvgfParams()
+    W, H, ins, outs = _svgf_arrays(accum, albedo, normal, depth, variance)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_svgf_host(C.byref(params), W, H, nthreads, *[_ptr(a) for a in ins], *[_ptr(a) for a in outs], C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_svgf_host")
+    return dict(accum=outs[0], variance=outs[1], rgba=outs[2], seconds=sec.value)
 
 
 class TemporalHistory:
