@@ -265,6 +265,74 @@ int mort_hip_svgf_host(const mort_svgf_params *params, int width, int height, in
                        const float *normal, const float *depth, const float *variance, float *accum_out, float *variance_out,
                        uint8_t *rgba_out, double *seconds);
 
+/* ---- the view: a frame's whole chain kept on the device across frames.  NOT parity beyond its render.  A view
+ * belongs to a context and owns what the chain keeps between frames: the render's rgba and accumulators, the feature buffers, the
+ * ping-ponged temporal history with the previous camera, the accumulated and filtered colour, the variance.  One frame is
+ *   mort_hip_render_device -> mort_hip_render_features_device -> [mort_hip_temporal_device] -> [mort_hip_denoise_device |
+ *   mort_hip_svgf_device] -> uchar4
+ * on ONE stream with at most one host wait, and equals bit for bit what those calls give when chained by hand: the filter takes the
+ * accumulated colour (the raw accumulators without `temporal`), SVGF also the temporal variance (none without `temporal`), and the
+ * uchar4 of the last stage that ran is the frame.  Pixel RNG states continue from frame to frame exactly as under plain renders.
+ *
+ * Still camera: when the camera fields the feature pass reads (image size, background, centre, viewport) are bit-identical to the
+ * previous frame's and no world has been uploaded since, the pass is skipped and the previous buffers are kept (features_reused).
+ * mort_hip_upload_world makes the next frame recompute the features and start without history, as mort_hip_view_reset does for
+ * the history alone.  Several views may live on one context, of any sizes and parameters; their histories are independent and
+ * they share the context's stage scratch.  A view needs the whole-image partition (else MORT_ERR_UNSUPPORTED), a camera of its
+ * own width and height (else MORT_ERR_INVALID), and an uploaded world and seeded RNG states as the render does.
+ * mort_hip_shutdown frees the views still alive on its context; destroying a view after that is an error of the caller.
+ * A context and its views are not re-entrant. ---- */
+typedef struct mort_view mort_view;
+#define MORT_VIEW_FILTER_NONE 0
+#define MORT_VIEW_FILTER_DENOISE 1
+#define MORT_VIEW_FILTER_SVGF 2
+typedef struct mort_view_params {
+    int width, height;
+    int temporal;                 /* 0 / 1 */
+    int filter;                   /* MORT_VIEW_FILTER_* */
+    mort_temporal_params tp;      /* read when temporal */
+    mort_denoise_params dp;       /* read when filter == MORT_VIEW_FILTER_DENOISE */
+    mort_svgf_params sp;          /* read when filter == MORT_VIEW_FILTER_SVGF */
+} mort_view_params;
+typedef struct mort_view_stats {
+    mort_stats render;            /* as mort_hip_render_device fills it */
+    double features_seconds, temporal_seconds, filter_seconds; /* HIP events of the view; 0 for a stage that did not run */
+    double device_seconds;        /* first to last event of the frame: from where render.seconds starts to the end of the last stage */
+    int frame;                    /* frames before this one since the last reset (0 = the first) */
+    int features_reused;          /* 1: still camera, the previous frame's features were kept */
+    int history_reset;            /* 1: this frame started without history (frame == 0) */
+} mort_view_stats;
+/* what mort_hip_view_read copies out: floats per pixel in brackets, row 0 = bottom row */
+#define MORT_VIEW_RAW_ACCUM 0 /* [3] the render's accumulators */
+#define MORT_VIEW_ACCUM 1     /* [3] the accumulated colour; needs temporal */
+#define MORT_VIEW_FILTERED 2  /* [3] the filtered colour; needs a filter */
+#define MORT_VIEW_VARIANCE 3  /* [1] the temporal step's variance; needs temporal */
+#define MORT_VIEW_ALBEDO 4    /* [3] */
+#define MORT_VIEW_NORMAL 5    /* [3] */
+#define MORT_VIEW_DEPTH 6     /* [1] */
+#define MORT_VIEW_HISTORY 7   /* [MORT_TEMPORAL_HISTORY_FLOATS] the history the last frame wrote, three float4 planes; needs temporal */
+/* the three stages' own defaults; temporal 1, filter SVGF; width = height = 0 */
+int mort_hip_view_defaults(mort_view_params *p);
+/* MORT_OK or MORT_ERR_INVALID: sizes > 0, temporal 0 / 1, a known filter, and the stages' own checks of the parameters in use
+ * (what mort_hip_view_create applies; needs no GPU) */
+int mort_hip_view_check_params(const mort_view_params *p);
+int mort_hip_view_create(mort_ctx *ctx, const mort_view_params *p, mort_view **out);
+/* waits for the view's work in flight, then frees its buffers */
+void mort_hip_view_destroy(mort_view *v);
+/* forget the history: the next frame starts over (frame 0).  RNG states and feature buffers are not touched */
+int mort_hip_view_reset(mort_view *v);
+/* one frame into a host buffer (W*H*4 bytes, uchar4, row 0 = bottom row): one host wait, at the end.  `mode` as for
+ * mort_hip_render_device; stats may be NULL */
+int mort_hip_view_frame(mort_view *v, const mort_camera *cam, int mode, uint8_t *rgba_out, mort_view_stats *stats);
+/* the same into a DEVICE buffer on `stream` (a hipStream_t, NULL = the context's).  The view remembers the stream of its last
+ * frame and waits for it in its next call (a frame on another stream, mort_hip_view_read, mort_hip_view_destroy): a caller's
+ * stream must outlive that call.  stats == NULL: everything is enqueued and the
+ * call returns without waiting (MORT_MODE_WAVE stays blocking); otherwise one wait at the end, then the statistics */
+int mort_hip_view_frame_device(mort_view *v, const mort_camera *cam, int mode, void *d_rgba_out, void *stream, mort_view_stats *stats);
+/* copies one buffer of the last frame (MORT_VIEW_*) to the host, after waiting for that frame; MORT_ERR_INVALID for a buffer the
+ * view's configuration does not produce, or before the first frame */
+int mort_hip_view_read(mort_view *v, int what, void *host_out);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

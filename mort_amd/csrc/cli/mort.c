@@ -27,6 +27,12 @@
  * over its accumulators, the variance from the spatial estimate; with --temporal, over the accumulated colour with the last step's
  * features and its variance.  --out then holds the filtered image (--dump-f32 stays the raw render, --variance-out the temporal
  * step's variance) and the JSON line gains "svgf_seconds" (features + filter).
+ * On a single GPU any of --temporal / --denoise / --svgf / --features-out / --variance-out / --dump-f32 sends every frame through a
+ * view (mort_hip_view_frame): the chain stays on the device, one host wait per frame, only the uchar4 frame and the
+ * files asked for come back.  With --temporal every frame goes through the view (and is filtered, as a viewer would; nothing of the
+ * filter is fed back, so the files are the same); without it only the last frame does, the ones before are plain renders.  The
+ * files and the JSON keys are those of the last frame as above, the seconds the device times of the stages (a still camera skips
+ * the feature pass: "temporal_seconds" counts the passes that ran).
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -224,7 +230,9 @@ int main(int argc, char **argv) {
     }
 
     uint8_t *rgba = calloc(npx, 4);
-    const int want_accum = dump || denoise || temporal || svgf;
+    /* a single GPU keeps the chain on the device (a view): only --dump-f32 brings the accumulators back */
+    const int use_view = !host_mode && gpus == 1 && (temporal || denoise || svgf || feat_out || dump);
+    const int want_accum = dump || (host_mode && (denoise || temporal || svgf));
     float *accum = want_accum ? calloc(npx * 3, sizeof(float)) : NULL;
     if (!rgba || (want_accum && !accum)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
     /* --temporal: this frame's features (albedo unused), the ping-ponged history, the accumulated colour and the variance */
@@ -233,7 +241,7 @@ int main(int argc, char **argv) {
     mort_temporal_params tp;
     mort_hip_temporal_defaults(&tp);
     double temporal_sec = 0;
-    if (temporal) {
+    if (temporal && host_mode) {
         alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
         tacc = malloc(npx * 3 * sizeof(float)); tvar = malloc(npx * sizeof(float));
         for (int k = 0; k < 2; k++) hist[k] = aligned_alloc(16, npx * MORT_TEMPORAL_HISTORY_FLOATS * sizeof(float));
@@ -243,7 +251,9 @@ int main(int argc, char **argv) {
     memset(&stats, 0, sizeof stats);
     double total_ms = 0, frame_wall = 0;
     mort_ctx *ctx = NULL;
+    mort_view *view = NULL;
     mort_rng_state *hstates = NULL;
+    double denoise_sec = 0, svgf_sec = 0, view_feat_sec = 0;
     int st;
 
     if (host_mode) { /* ---- the kernel body as a host loop: no GPU ---- */
@@ -294,10 +304,31 @@ int main(int argc, char **argv) {
             free(s);
         } else if ((st = mort_hip_rng_seed(ctx, seed, W, H)) != MORT_OK) die(ctx, st, "mort_hip_rng_seed");
 
+        if (use_view) {
+            mort_view_params vp;
+            mort_hip_view_defaults(&vp);
+            vp.width = W; vp.height = H;
+            vp.temporal = temporal;
+            vp.filter = denoise ? MORT_VIEW_FILTER_DENOISE : svgf ? MORT_VIEW_FILTER_SVGF : MORT_VIEW_FILTER_NONE;
+            if ((st = mort_hip_view_create(ctx, &vp, &view)) != MORT_OK) die(ctx, st, "mort_hip_view_create");
+        }
         for (int f = 0; f < frames; f++) {
             if (f > 0) frame_input(&cam, keys, f, mouse_dx, mouse_dy);
             const double t0 = now_s();
-            if (gpus > 1 && !gather_shm) {
+            if (view && (temporal || f == frames - 1)) { /* render, features, temporal step and filter on the device; the frame's uchar4
+                                                          * comes back.  Without --temporal only the last frame is filtered or written:
+                                                          * the frames before it are plain renders, as they always were */
+                mort_view_stats vs;
+                if ((st = mort_hip_view_frame(view, &cam, mode, rgba, &vs)) != MORT_OK) die(ctx, st, "mort_hip_view_frame");
+                stats = vs.render;
+                if (temporal) temporal_sec += vs.features_seconds + vs.temporal_seconds;
+                /* feature pass + filter of the last frame, as before: under a still camera the pass that made the features in use
+                 * is an earlier frame's; with --temporal it is counted there */
+                if (!vs.features_reused) view_feat_sec = vs.features_seconds;
+                denoise_sec = svgf_sec = (temporal ? 0 : view_feat_sec) + vs.filter_seconds;
+            } else if (view) {
+                if ((st = mort_hip_render(ctx, &cam, mode, rgba, NULL, NULL, &stats)) != MORT_OK) die(ctx, st, "mort_hip_render");
+            } else if (gpus > 1 && !gather_shm) {
                 if ((st = mort_hip_render_gather(ctx, &cam, mode, rank == 0 ? rgba : NULL, &stats)) != MORT_OK) die(ctx, st, "mort_hip_render_gather");
             } else {
                 if ((st = mort_hip_render(ctx, &cam, mode, rgba, accum, NULL, &stats)) != MORT_OK) die(ctx, st, "mort_hip_render");
@@ -309,44 +340,48 @@ int main(int argc, char **argv) {
             frame_wall = now_s() - t0;
             total_ms += stats.seconds * 1e3;
             if (rank == 0) printf("Avg. time per frame: %3.1f ms\n", total_ms / (f + 1)); /* mort.cu:119 */
-            if (temporal) {
-                double fs = 0, ts = 0;
-                if ((st = mort_hip_render_features(ctx, &cam, alb, nrm, dep, &fs)) != MORT_OK) die(ctx, st, "mort_hip_render_features");
-                if ((st = mort_hip_temporal(ctx, &tp, f ? &prev_cam : NULL, &cam, W, H, accum, nrm, dep, f ? hist[(f + 1) & 1] : NULL, hist[f & 1],
-                                            tacc, tvar, rgba, &ts)) != MORT_OK) die(ctx, st, "mort_hip_temporal");
-                temporal_sec += fs + ts;
-                prev_cam = cam;
+        }
+        if (view) { /* what the files need of the last frame */
+            if (dump && (st = mort_hip_view_read(view, MORT_VIEW_RAW_ACCUM, accum)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
+            if (feat_out) {
+                alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
+                if (!alb || !nrm || !dep) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+                if ((st = mort_hip_view_read(view, MORT_VIEW_ALBEDO, alb)) != MORT_OK || (st = mort_hip_view_read(view, MORT_VIEW_NORMAL, nrm)) != MORT_OK ||
+                    (st = mort_hip_view_read(view, MORT_VIEW_DEPTH, dep)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
             }
+            if (var_out) {
+                tvar = malloc(npx * sizeof(float));
+                if (!tvar) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+                if ((st = mort_hip_view_read(view, MORT_VIEW_VARIANCE, tvar)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
+            }
+            mort_hip_view_destroy(view);
         }
     }
 
-    /* ---- --denoise / --svgf / --features-out (single GPU or host mode): the last frame's camera; the PPM becomes the filtered image.
-     * With --temporal the features are the last step's and the filter takes the accumulated colour (--svgf: and its variance) ---- */
-    double denoise_sec = 0, svgf_sec = 0;
+    /* ---- --denoise / --svgf / --features-out: the last frame's camera; the PPM becomes the filtered image.  With --temporal the
+     * features are the last step's and the filter takes the accumulated colour (--svgf: and its variance).  On the GPU the view
+     * has done all of this; what follows computes for --mode host only ---- */
     if (denoise || svgf || feat_out) {
-        if (!temporal) {
+        if (host_mode && !temporal) {
             alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
             if (!alb || !nrm || !dep) { fprintf(stderr, "out of memory\n"); fail_exit(); }
         }
         double fs = 0, ds = 0;
-        if (!temporal) { /* with --temporal: the last step's */
-            if (host_mode) { if ((st = mort_hip_render_features_host(&world, &cam, threads, tree ? MORT_HOST_TREE : 0, alb, nrm, dep, &fs)) != MORT_OK) die(NULL, st, "mort_hip_render_features_host"); }
-            else if ((st = mort_hip_render_features(ctx, &cam, alb, nrm, dep, &fs)) != MORT_OK) die(ctx, st, "mort_hip_render_features");
+        if (host_mode && !temporal) { /* with --temporal: the last step's */
+            if ((st = mort_hip_render_features_host(&world, &cam, threads, tree ? MORT_HOST_TREE : 0, alb, nrm, dep, &fs)) != MORT_OK) die(NULL, st, "mort_hip_render_features_host");
         }
-        if (denoise) {
+        if (host_mode && denoise) {
             const float *col = temporal ? tacc : accum;
             mort_denoise_params dp;
             mort_hip_denoise_defaults(&dp);
-            if (host_mode) { if ((st = mort_hip_denoise_host(&dp, W, H, threads, col, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_denoise_host"); }
-            else if ((st = mort_hip_denoise(ctx, &dp, W, H, col, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(ctx, st, "mort_hip_denoise");
+            if ((st = mort_hip_denoise_host(&dp, W, H, threads, col, alb, nrm, dep, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_denoise_host");
             denoise_sec = fs + ds;
         }
-        if (svgf) {
+        if (host_mode && svgf) {
             const float *col = temporal ? tacc : accum;
             mort_svgf_params sp;
             mort_hip_svgf_defaults(&sp);
-            if (host_mode) { if ((st = mort_hip_svgf_host(&sp, W, H, threads, col, alb, nrm, dep, tvar, NULL, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_svgf_host"); }
-            else if ((st = mort_hip_svgf(ctx, &sp, W, H, col, alb, nrm, dep, tvar, NULL, NULL, rgba, &ds)) != MORT_OK) die(ctx, st, "mort_hip_svgf");
+            if ((st = mort_hip_svgf_host(&sp, W, H, threads, col, alb, nrm, dep, tvar, NULL, NULL, rgba, &ds)) != MORT_OK) die(NULL, st, "mort_hip_svgf_host");
             svgf_sec = fs + ds;
         }
         if (feat_out) {

@@ -22,6 +22,7 @@
 #include "dev_features.h"
 #include "scene_blob.h"
 #include "mort_ctx.h"
+#include "mort_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -110,6 +111,9 @@ void feat_camera(FeatArgs &a, const mort_camera *cam) {
 }
 
 } // namespace
+
+static_assert(FEAT_BX == MORT_FEAT_BX && FEAT_BY == MORT_FEAT_BY, "mort_internal.h states the workgroup shape for view.hip");
+bool mort_denoise_params_ok(const mort_denoise_params *p) { return params_ok(p); }
 
 extern "C" int mort_hip_denoise_defaults(mort_denoise_params *p) {
     if (!p) return MORT_ERR_INVALID;

@@ -122,6 +122,8 @@ struct mort_ctx {
     };
     Scratch svgf;    /* the filter's float4 planes: colour + variance ping-pong, (normal, depth), albedo */
     Scratch svgf_io; /* mort_hip_svgf: the host buffers' device copies */
+    /* views (view.hip): the ones alive on this context, freed by mort_hip_shutdown */
+    std::vector<struct mort_view *> views;
 };
 
 static inline int hip_fail(mort_ctx *c, hipError_t e, const char *what) {

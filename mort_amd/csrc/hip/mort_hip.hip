@@ -208,6 +208,7 @@ extern "C" void mort_hip_shutdown(mort_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     quiesce(c);
+    mort_views_free(c);
     mort_hip_comm_destroy(c);
     hipFree(c->d_tile_keys); hipFree(c->d_tile_iota); hipFree(c->d_sort_tmp);
     hipFree(c->d_prio_count); hipFree(c->d_scene); hipFree(c->d_fast); hipFree(c->d_trav); hipFree(c->d_gen); hipFree(c->d_states); hipFree(c->d_seqmats);

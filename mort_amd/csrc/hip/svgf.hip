@@ -31,6 +31,7 @@
 #include "mort_hip.h"
 #include "dev_svgf.h"
 #include "mort_ctx.h"
+#include "mort_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -212,6 +213,9 @@ void launch_iter(const SvgfArgs &a, int lds, dim3 grid, dim3 block, hipStream_t 
 }
 
 } // namespace
+
+static_assert(FEAT_BX == MORT_FEAT_BX && FEAT_BY == MORT_FEAT_BY, "mort_internal.h states the workgroup shape for view.hip");
+bool mort_svgf_params_ok(const mort_svgf_params *p) { return params_ok(p); }
 
 extern "C" int mort_hip_svgf_defaults(mort_svgf_params *p) {
     if (!p) return MORT_ERR_INVALID;

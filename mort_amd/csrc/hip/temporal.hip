@@ -20,6 +20,7 @@
 #include "mort_hip.h"
 #include "dev_temporal.h"
 #include "mort_ctx.h"
+#include "mort_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -133,6 +134,9 @@ void tacc_host_row(void *p, int y) {
 }
 
 } // namespace
+
+static_assert(FEAT_BX == MORT_FEAT_BX && FEAT_BY == MORT_FEAT_BY, "mort_internal.h states the workgroup shape for view.hip");
+bool mort_temporal_params_ok(const mort_temporal_params *p) { return params_ok(p); }
 
 extern "C" int mort_hip_temporal_defaults(mort_temporal_params *p) {
     if (!p) return MORT_ERR_INVALID;

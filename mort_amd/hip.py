@@ -31,8 +31,14 @@ EXPORTS = [
     "mort_hip_denoise_device", "mort_hip_render_features_host", "mort_hip_denoise_host",
     "mort_hip_temporal_defaults", "mort_hip_temporal", "mort_hip_temporal_device", "mort_hip_temporal_host",
     "mort_hip_svgf_defaults", "mort_hip_svgf", "mort_hip_svgf_device", "mort_hip_svgf_host",
+    "mort_hip_view_defaults", "mort_hip_view_check_params", "mort_hip_view_create", "mort_hip_view_destroy", "mort_hip_view_reset",
+    "mort_hip_view_frame", "mort_hip_view_frame_device", "mort_hip_view_read",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
+FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
+# mort_hip_view_read: name -> (MORT_VIEW_* code, floats per pixel)
+VIEW_BUFFERS = {"raw_accum": (0, 3), "accum": (1, 3), "filtered": (2, 3), "variance": (3, 1), "albedo": (4, 3), "normal": (5, 3),
+                "depth": (6, 1), "history": (7, TEMPORAL_HISTORY_FLOATS)}
 HOST_TREE = 1
 
 
@@ -102,6 +108,31 @@ class SvgfParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ViewParams(C.Structure):
+    """mort_view_params: ViewParams(width, height) holds mort_hip_view_defaults (temporal on, SVGF, the three stages' defaults);
+    keyword arguments override them -- temporal, filter, tp / dp / sp (the stages' parameter structures)."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("temporal", C.c_int), ("filter", C.c_int), ("tp", TemporalParams),
+                ("dp", DenoiseParams), ("sp", SvgfParams)]
+
+    def __init__(self, width=0, height=0, **kw):
+        super().__init__()
+        lib().mort_hip_view_defaults(C.byref(self))
+        self.width, self.height = width, height
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class ViewStats(C.Structure):
+    """mort_view_stats"""
+    _fields_ = [("render", Stats), ("features_seconds", C.c_double), ("temporal_seconds", C.c_double), ("filter_seconds", C.c_double),
+                ("device_seconds", C.c_double), ("frame", C.c_int), ("features_reused", C.c_int), ("history_reset", C.c_int)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["render"] = self.render.asdict()
+        return d
+
+
 class MortHipError(RuntimeError):
     def __init__(self, status, what, detail=""):
         self.status = status
@@ -159,6 +190,15 @@ def lib():
         L.mort_hip_svgf.argtypes = [ctx, sp, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_svgf.restype = C.c_int
         L.mort_hip_svgf_device.argtypes = [ctx, sp, C.c_int, C.c_int] + [vp] * 9 + [dp]; L.mort_hip_svgf_device.restype = C.c_int
         L.mort_hip_svgf_host.argtypes = [sp, C.c_int, C.c_int, C.c_int] + [vp] * 8 + [dp]; L.mort_hip_svgf_host.restype = C.c_int
+        wp, view = C.POINTER(ViewParams), C.c_void_p
+        L.mort_hip_view_defaults.argtypes = [wp]; L.mort_hip_view_defaults.restype = C.c_int
+        L.mort_hip_view_check_params.argtypes = [wp]; L.mort_hip_view_check_params.restype = C.c_int
+        L.mort_hip_view_create.argtypes = [ctx, wp, C.POINTER(view)]; L.mort_hip_view_create.restype = C.c_int
+        L.mort_hip_view_destroy.argtypes = [view]; L.mort_hip_view_destroy.restype = None
+        L.mort_hip_view_reset.argtypes = [view]; L.mort_hip_view_reset.restype = C.c_int
+        L.mort_hip_view_frame.argtypes = [view, cp, C.c_int, vp, C.POINTER(ViewStats)]; L.mort_hip_view_frame.restype = C.c_int
+        L.mort_hip_view_frame_device.argtypes = [view, cp, C.c_int, vp, vp, C.POINTER(ViewStats)]; L.mort_hip_view_frame_device.restype = C.c_int
+        L.mort_hip_view_read.argtypes = [view, C.c_int, vp]; L.mort_hip_view_read.restype = C.c_int
         _lib = L
     return _lib
 
@@ -167,6 +207,7 @@ class Context:
     """One mort_ctx: one GPU, one partition, one uploaded world."""
 
     def __init__(self, device=0):
+        self._views = []  # the View objects alive on this context
         self._h = C.c_void_p()
         st = lib().mort_hip_init(device, C.byref(self._h))
         if st != 0:
@@ -179,8 +220,16 @@ class Context:
 
     def close(self):
         if self._h:
+            for v in self._views:  # mort_hip_shutdown frees them: their handles must not be used again
+                v._h = None
+            self._views = []
             lib().mort_hip_shutdown(self._h)
             self._h = None
+
+    def view(self, width, height, params=None, **kw):
+        """A View of this context (mort_hip_view_create): the whole frame chain kept on the device.  params: a ViewParams, or
+        keyword arguments for one (temporal, filter, tp, dp, sp)."""
+        return View(self, width, height, params, **kw)
 
     def __enter__(self):
         return self
@@ -363,6 +412,72 @@ class Context:
         g = C.c_double(0)
         self._chk(lib().mort_hip_calib_hbm_copy(self._h, nbytes, reps, C.byref(g)), "mort_hip_calib_hbm_copy")
         return g.value
+
+
+class View:
+    """One mort_view (include/mort_hip.h): render -> features -> [temporal] -> [denoise | SVGF] -> uchar4, resident
+    on the GPU across frames.  A context manager; closing the Context closes its views."""
+
+    def __init__(self, ctx, width, height, params=None, **kw):
+        self.ctx = ctx
+        self.params = ViewParams.from_buffer_copy(params) if params is not None else ViewParams(**kw)
+        self.params.width, self.params.height = width, height
+        self.width, self.height = width, height
+        self._h = C.c_void_p()
+        st = lib().mort_hip_view_create(ctx._h, C.byref(self.params), C.byref(self._h))
+        if st != 0:
+            self._h = None
+            ctx._chk(st, "mort_hip_view_create")
+        ctx._views.append(self)
+
+    def _handle(self):
+        if not self._h:
+            raise RuntimeError("the view (or its context) has been closed")
+        return self._h
+
+    def close(self):
+        if self._h:
+            lib().mort_hip_view_destroy(self._h)
+            self._h = None
+            self.ctx._views.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """Forget the history: the next frame starts over.  RNG states are not touched."""
+        self.ctx._chk(lib().mort_hip_view_reset(self._handle()), "mort_hip_view_reset")
+
+    def frame(self, cam, mode=MODE_MEGA):
+        """One frame, one host wait: dict(rgba (H, W, 4) u8, stats)."""
+        rgba = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        st = ViewStats()
+        self.ctx._chk(lib().mort_hip_view_frame(self._handle(), C.byref(cam), mode, rgba.ctypes.data, C.byref(st)), "mort_hip_view_frame")
+        return dict(rgba=rgba, stats=st.asdict())
+
+    def frame_device(self, cam, rgba, mode=MODE_MEGA, sync=False):
+        """One frame into a torch uint8 tensor of W*H*4 elements on this context's device, on the current torch stream.
+        Asynchronous (returns None) unless sync (then returns the stats) or torch runs on its legacy default stream."""
+        import torch
+        if rgba.dtype != torch.uint8 or not rgba.is_contiguous() or rgba.numel() != 4 * self.width * self.height or rgba.device.type != "cuda":
+            raise ValueError(f"expected a contiguous uint8 tensor of {4 * self.width * self.height} elements on the GPU")
+        stream, sync = _torch_stream(torch, rgba.device, sync)
+        st = ViewStats()
+        self.ctx._chk(lib().mort_hip_view_frame_device(self._handle(), C.byref(cam), mode, rgba.data_ptr(), stream, C.byref(st) if sync else None),
+                      "mort_hip_view_frame_device")
+        return st.asdict() if sync else None
+
+    def read(self, name):
+        """One buffer of the last frame as a numpy array (VIEW_BUFFERS): raw_accum / accum / filtered / albedo / normal (H, W, 3),
+        variance / depth (H, W), history (3, H, W, 4)."""
+        code, ch = VIEW_BUFFERS[name]
+        shape = (3, self.height, self.width, 4) if name == "history" else (self.height, self.width, ch) if ch > 1 else (self.height, self.width)
+        out = np.zeros(shape, dtype=np.float32)
+        self.ctx._chk(lib().mort_hip_view_read(self._handle(), code, out.ctypes.data), f"mort_hip_view_read({name})")
+        return out
 
 
 def seed_states_host(seed, width, height, dtype=None):
