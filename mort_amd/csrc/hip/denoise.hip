@@ -2,7 +2,7 @@
  * denoise.hip -- first-hit feature buffers and the edge-aware a-trous denoiser: a non-parity extra on top
  * of the untouched render path, for a viewable image at the sample counts an interactive frame can afford.
  *
- * Kernels (gfx950, wave64, 64x4-pixel workgroups: every wave covers 64 contiguous pixels of one row):
+ * Kernels (gfx950, wave64, the stages' 64x4-pixel workgroups of stage_common.h: every wave covers 64 contiguous pixels of one row):
  *   feat_kernel<TREE>             one primary ray per pixel (lens centre -> pixel centre, tm = 0.5), no random numbers:
  *                                 albedo, normal, depth of the first hit.  TREE: the unified-tree walk with its pending
  *                                 children in LDS (16 x 256 x 2 B), else the item scan.  Reads the scene in HBM.
@@ -12,6 +12,8 @@
  *
  * The host forms (mort_hip_render_features_host, mort_hip_denoise_host) run the same per-pixel bodies (dev_features.h)
  * on host threads and make no HIP runtime call.  Nothing here touches the render's RNG states, tile-cost cache or counters.
+ * The _device entry points' prologue and timed epilogue, the staging of the host-buffer forms and the shared scratch are
+ * stage_common.h's, as in temporal.hip and svgf.hip.
  */
 #include <hip/hip_runtime.h>
 
@@ -23,32 +25,30 @@
 #include "scene_blob.h"
 #include "mort_ctx.h"
 #include "mort_internal.h"
+#include "stage_common.h"
 
 #pragma clang fp contract(off)
-
-#define FEAT_BX 64
-#define FEAT_BY 4
 
 /* ====================================================================== device */
 
 template <bool TREE>
-__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) feat_kernel(const FeatArgs a) {
-    __shared__ unsigned short feat_stack[MORT_OWN_STACK * FEAT_BX * FEAT_BY];
-    const int tid = threadIdx.x + threadIdx.y * FEAT_BX;
-    const int x = blockIdx.x * FEAT_BX + threadIdx.x, ly = blockIdx.y * FEAT_BY + threadIdx.y;
+__global__ void __launch_bounds__(STAGE_BX * STAGE_BY) feat_kernel(const FeatArgs a) {
+    __shared__ unsigned short feat_stack[MORT_OWN_STACK * STAGE_BX * STAGE_BY];
+    const int tid = threadIdx.x + threadIdx.y * STAGE_BX;
+    const int x = blockIdx.x * STAGE_BX + threadIdx.x, ly = blockIdx.y * STAGE_BY + threadIdx.y;
     if (x >= a.width || ly >= a.local_rows) return;
-    feat_pixel<TREE>(a, x, ly, &feat_stack[tid], FEAT_BX * FEAT_BY);
+    feat_pixel<TREE>(a, x, ly, &feat_stack[tid], STAGE_BX * STAGE_BY);
 }
 
 template <bool FIRST, bool LAST>
-__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) atrous_kernel(const AtrousArgs a) {
-    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+__global__ void __launch_bounds__(STAGE_BX * STAGE_BY) atrous_kernel(const AtrousArgs a) {
+    const int x = blockIdx.x * STAGE_BX + threadIdx.x, y = blockIdx.y * STAGE_BY + threadIdx.y;
     if (x >= a.width || y >= a.height) return;
     dn_pixel<FIRST, LAST>(a, x, y);
 }
 
-__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) atrous_passthrough_kernel(const AtrousArgs a) {
-    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+__global__ void __launch_bounds__(STAGE_BX * STAGE_BY) atrous_passthrough_kernel(const AtrousArgs a) {
+    const int x = blockIdx.x * STAGE_BX + threadIdx.x, y = blockIdx.y * STAGE_BY + threadIdx.y;
     if (x >= a.width || y >= a.height) return;
     dn_passthrough(a, x, y);
 }
@@ -112,7 +112,6 @@ void feat_camera(FeatArgs &a, const mort_camera *cam) {
 
 } // namespace
 
-static_assert(FEAT_BX == MORT_FEAT_BX && FEAT_BY == MORT_FEAT_BY, "mort_internal.h states the workgroup shape for view.hip");
 bool mort_denoise_params_ok(const mort_denoise_params *p) { return params_ok(p); }
 
 extern "C" int mort_hip_denoise_defaults(mort_denoise_params *p) {
@@ -128,10 +127,7 @@ extern "C" int mort_hip_render_features_device(mort_ctx *c, const mort_camera *c
     if (!c || !cam || !d_albedo || !d_normal || !d_depth) return MORT_ERR_INVALID;
     if (!c->have_world) return MORT_ERR_NO_WORLD;
     const int W = cam->image_width, H = cam->image_height;
-    if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, switch_stream(c, s));
+    if (!stage_size_ok(W, H)) return MORT_ERR_INVALID;
 
     FeatArgs a;
     std::memset(&a, 0, sizeof a);
@@ -148,21 +144,16 @@ extern "C" int mort_hip_render_features_device(mort_ctx *c, const mort_camera *c
         a.gw.n_chains = c->gen.n_chains; a.gw.root = c->gen.root; a.gw.first_medium = c->gen.first_medium;
         a.gw.gx = c->gen.gx; a.gw.gy = c->gen.gy; a.gw.gz = c->gen.gz; a.gw.gR = c->gen.gR; a.gw.mnear = c->gen.mnear; a.gw.kmin = c->gen.kmin;
     }
-    if (seconds) HIPCHK(c, hipEventRecord(c->ev0, s));
+    hipStream_t s;
+    const int st = stage_begin(c, stream, 0, seconds, &s);
+    if (st != MORT_OK) return st;
     if (a.local_rows > 0) {
-        const dim3 grid((W + FEAT_BX - 1) / FEAT_BX, (a.local_rows + FEAT_BY - 1) / FEAT_BY), block(FEAT_BX, FEAT_BY);
+        const dim3 grid = stage_grid(W, a.local_rows), block = stage_block();
         if (tree) hipLaunchKernelGGL(feat_kernel<true>, grid, block, 0, s, a);
         else hipLaunchKernelGGL(feat_kernel<false>, grid, block, 0, s, a);
         HIPCHK(c, hipGetLastError());
     }
-    if (seconds) {
-        HIPCHK(c, hipEventRecord(c->ev1, s));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *seconds = ms * 1e-3;
-    }
-    return MORT_OK;
+    return stage_end(c, s, seconds);
 }
 
 extern "C" int mort_hip_render_features(mort_ctx *c, const mort_camera *cam, float *albedo_out, float *normal_out, float *depth_out,
@@ -175,18 +166,15 @@ extern "C" int mort_hip_render_features(mort_ctx *c, const mort_camera *cam, flo
     const int lr = mort_hip_local_rows(c, H);
     const size_t npx = (size_t)W * (size_t)lr;
     HIPCHK(c, switch_stream(c, c->stream));
-    int st = ensure_buf(c, &c->d_feat, &c->feat_cap, npx * 7 * sizeof(float));
+    /* the packed owned rows: the whole image without a partition */
+    StagePlane pl[3] = {{nullptr, albedo_out, npx * 12}, {nullptr, normal_out, npx * 12}, {nullptr, depth_out, npx * 4}};
+    int st = stage_upload(c, pl, 3);
     if (st != MORT_OK) return st;
-    float *d_alb = (float *)c->d_feat, *d_nrm = d_alb + 3 * npx, *d_dep = d_nrm + 3 * npx;
+    float *d_alb = (float *)pl[0].dev, *d_nrm = (float *)pl[1].dev, *d_dep = (float *)pl[2].dev;
     double sec = 0;
     if ((st = mort_hip_render_features_device(c, cam, d_alb, d_nrm, d_dep, c->stream, &sec)) != MORT_OK) return st;
     if (seconds) *seconds = sec;
-    if (c->part.nranks == 1) {
-        HIPCHK(c, hipMemcpy(albedo_out, d_alb, npx * 12, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(normal_out, d_nrm, npx * 12, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(depth_out, d_dep, npx * 4, hipMemcpyDeviceToHost));
-        return MORT_OK;
-    }
+    if (c->part.nranks == 1) return stage_download(c, pl, 3);
     for (int ly = 0; ly < lr; ly++) {
         const size_t y = (size_t)mort_hip_global_row(c, ly), W3 = (size_t)W * 3;
         HIPCHK(c, hipMemcpy(albedo_out + y * W3, d_alb + (size_t)ly * W3, W3 * 4, hipMemcpyDeviceToHost));
@@ -212,13 +200,7 @@ extern "C" int mort_hip_render_features_host(const mort_world *world, const mort
     job.a.albedo = albedo_out; job.a.normal = normal_out; job.a.depth = depth_out;
     const mortc::Compiled &o = sb.comp;
     job.tree = (flags & MORT_HOST_TREE) && o.g_ok && camera_in_reach(cam, o.g_lo, o.g_hi, o.g_reach, 0.0f);
-    if (job.tree) {
-        GenWalk &gw = job.a.gw;
-        gw.nodes = o.g_nodes.data(); gw.entries = o.g_entries.data(); gw.chains = o.g_chains.data();
-        gw.ranks = o.g_ranks.data(); gw.n_spheres = (int)o.spheres.size();
-        gw.n_chains = (int)(o.g_chains.size() / 2); gw.root = o.g_root; gw.first_medium = o.g_first_medium;
-        gw.gx = o.g_c[0]; gw.gy = o.g_c[1]; gw.gz = o.g_c[2]; gw.gR = o.g_R; gw.mnear = o.g_mnear; gw.kmin = o.g_kmin;
-    }
+    if (job.tree) job.a.gw = gen_walk_of(o);
     const double t0 = now_s();
     run_rows(H, nthreads, feat_host_row, &job);
     if (seconds) *seconds = now_s() - t0;
@@ -231,19 +213,14 @@ extern "C" int mort_hip_denoise_device(mort_ctx *c, const mort_denoise_params *p
                                        const void *d_normal, const void *d_depth, void *d_accum_out, void *d_rgba_out, void *stream,
                                        double *seconds) {
     if (!c || !params_ok(p) || !d_accum || !d_albedo || !d_normal || !d_depth) return MORT_ERR_INVALID;
-    if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, switch_stream(c, s));
+    if (!stage_size_ok(W, H)) return MORT_ERR_INVALID;
     const size_t npx = (size_t)W * (size_t)H;
     const int n = p->iterations;
-    if (n > 1) { /* e ping-pong, g0, g1 */
-        const int st = ensure_buf(c, &c->d_dn, &c->dn_cap, npx * 4 * sizeof(float4));
-        if (st != MORT_OK) return st;
-    }
-    float4 *e0 = (float4 *)c->d_dn, *e1 = e0 + npx, *g0 = e1 + npx, *g1 = g0 + npx;
-    const dim3 grid((W + FEAT_BX - 1) / FEAT_BX, (H + FEAT_BY - 1) / FEAT_BY), block(FEAT_BX, FEAT_BY);
-    if (seconds) HIPCHK(c, hipEventRecord(c->ev0, s));
+    hipStream_t s;
+    const int st = stage_begin(c, stream, n > 1 ? npx * 4 * sizeof(float4) : 0, seconds, &s); /* e ping-pong, g0, g1 */
+    if (st != MORT_OK) return st;
+    float4 *e0 = (float4 *)c->stage_planes.p, *e1 = e0 + npx, *g0 = e1 + npx, *g1 = g0 + npx; /* not dereferenced where n <= 1 */
+    const dim3 grid = stage_grid(W, H), block = stage_block();
     for (int i = 0; i < (n > 0 ? n : 1); i++) {
         AtrousArgs a = atrous_args(p, W, H, i);
         a.C = (const float *)d_accum; a.A = (const float *)d_albedo; a.N = (const float *)d_normal; a.D = (const float *)d_depth;
@@ -257,14 +234,7 @@ extern "C" int mort_hip_denoise_device(mort_ctx *c, const mort_denoise_params *p
         else hipLaunchKernelGGL((atrous_kernel<false, false>), grid, block, 0, s, a);
         HIPCHK(c, hipGetLastError());
     }
-    if (seconds) {
-        HIPCHK(c, hipEventRecord(c->ev1, s));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *seconds = ms * 1e-3;
-    }
-    return MORT_OK;
+    return stage_end(c, s, seconds);
 }
 
 extern "C" int mort_hip_denoise(mort_ctx *c, const mort_denoise_params *p, int W, int H, const float *accum, const float *albedo,
@@ -274,21 +244,15 @@ extern "C" int mort_hip_denoise(mort_ctx *c, const mort_denoise_params *p, int W
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, switch_stream(c, c->stream));
     const size_t npx = (size_t)W * (size_t)H;
-    /* C, A, N (3 floats each), D, accum_out (3 floats), rgba (4 bytes) */
-    int st = ensure_buf(c, &c->d_dnio, &c->dnio_cap, npx * 15 * sizeof(float));
+    StagePlane pl[6] = {{accum, nullptr, npx * 12}, {albedo, nullptr, npx * 12}, {normal, nullptr, npx * 12}, {depth, nullptr, npx * 4},
+                        {nullptr, accum_out, npx * 12}, {nullptr, rgba_out, npx * 4}};
+    int st = stage_upload(c, pl, 6);
     if (st != MORT_OK) return st;
-    float *dC = (float *)c->d_dnio, *dA = dC + 3 * npx, *dN = dA + 3 * npx, *dD = dN + 3 * npx, *dO = dD + npx;
-    uint8_t *dR = (uint8_t *)(dO + 3 * npx);
-    HIPCHK(c, hipMemcpy(dC, accum, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dA, albedo, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dN, normal, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dD, depth, npx * 4, hipMemcpyHostToDevice));
     double sec = 0;
-    if ((st = mort_hip_denoise_device(c, p, W, H, dC, dA, dN, dD, dO, dR, c->stream, &sec)) != MORT_OK) return st;
+    if ((st = mort_hip_denoise_device(c, p, W, H, pl[0].dev, pl[1].dev, pl[2].dev, pl[3].dev, pl[4].dev, pl[5].dev, c->stream, &sec)) != MORT_OK)
+        return st;
     if (seconds) *seconds = sec;
-    if (accum_out) HIPCHK(c, hipMemcpy(accum_out, dO, npx * 12, hipMemcpyDeviceToHost));
-    if (rgba_out) HIPCHK(c, hipMemcpy(rgba_out, dR, npx * 4, hipMemcpyDeviceToHost));
-    return MORT_OK;
+    return stage_download(c, pl, 6);
 }
 
 extern "C" int mort_hip_denoise_host(const mort_denoise_params *p, int W, int H, int nthreads, const float *accum, const float *albedo,

@@ -27,42 +27,11 @@ struct FeatArgs {
     float *albedo, *normal, *depth; /* packed owned rows: 3, 3, 1 floats per pixel */
 };
 
-/* gen_world_hit's tree walk over the solids with the pending far children at stack[k * stride] (an LDS column on the
- * device, a local array on the host), and the scan for the rays the walk does not decide.  No media. */
+/* the single-lane tree walk over the solids (dev_gen.h) with the pending far children at stack[k * stride] (an LDS column on
+ * the device, a local array on the host), and the scan for the rays the walk does not decide.  No media. */
 DEV void feat_tree_solids(const DScene &sc, const GenWalk &gw, const Ray &ray, unsigned short *stack, int stride, float &closest, uint32_t &best) {
-    GenRay gr;
-    const bool ordinary = gen_ray_setup(ray, gw.gx, gw.gy, gw.gz, gw.gR, gw.mnear, gw.kmin, gr);
-    const float ray_a = vlen2(ray.d);
-    closest = __builtin_inff();
-    best = GBEST_NONE;
-    int flags = ordinary ? 0 : GFL_REF;
-    if (ordinary && gw.root != 0xffffu) {
-        int sp = 0;
-        uint32_t cur = gw.root;
-        for (;;) {
-            if (cur & 0x8000u) {
-                uint32_t pos = GLEAF_FIRST(cur);
-                for (int cnt = (int)GLEAF_COUNT(cur); cnt > 0; cnt--, pos++)
-                    gen_leaf_test(sc, gw.chains, gw.ranks, gw.n_spheres, sc.spheres, sc.quads, gw.entries[pos], ray, ray_a, closest, best, flags);
-                if (sp == 0) break;
-                cur = stack[--sp * stride];
-                continue;
-            }
-            const DNodeQ nq = gw.nodes[cur & 0x7fffu];
-            const GenBoxes nd = gen_node_decode(nq.ox, nq.oy, nq.oz, nq.exps, nq.q0, nq.q1, nq.q2, nq.children);
-            float te0, te1;
-            const bool m0 = gen_prune(nd.x0min, nd.x0max, nd.y0min, nd.y0max, nd.z0min, nd.z0max, gr, closest, te0);
-            const bool m1 = gen_prune(nd.x1min, nd.x1max, nd.y1min, nd.y1max, nd.z1min, nd.z1max, gr, closest, te1);
-            if (m0 && m1) {
-                if (sp == 0) break;
-                cur = stack[--sp * stride];
-            } else if (!m0 && !m1) {
-                const bool first0 = te0 <= te1;
-                stack[sp++ * stride] = (unsigned short)(first0 ? nd.c1 : nd.c0);
-                cur = first0 ? nd.c0 : nd.c1;
-            } else cur = m0 ? nd.c1 : nd.c0;
-        }
-    }
+    int flags;
+    gen_walk_solids(sc, gw, ray, stack, stride, closest, best, flags);
     if (flags) gen_scan_solids(sc, gw.first_medium, gw.chains, gw.n_chains, ray, closest, best);
 }
 
@@ -185,6 +154,23 @@ DEV uchar4 dn_rgba(float r, float g, float b) {
 /* B3-spline taps (1/16, 1/4, 3/8, 1/4, 1/16) */
 DEV float dn_kernel(int i) { return (i == 0 || i == 4) ? 0.0625f : (i == 2 ? 0.375f : 0.25f); }
 
+/* w_n of DESIGN.md 4.9: max(0, Np.Nq)^(2^npow) */
+DEV float dn_wn(float ax, float ay, float az, float bx, float by, float bz, int npow) {
+    const float nd = ax * bx + ay * by + az * bz;
+    float wn = nd > 0.0f ? nd : 0.0f;
+    for (int k = 0; k < npow; k++) wn = wn * wn;
+    return wn;
+}
+
+/* iterations == 0, for the denoiser and the SVGF filter (Args: AtrousArgs or SvgfArgs): the accumulators unchanged and the
+ * render's own rgba; either output may be null */
+template <class Args>
+DEV void dn_pass(const Args &a, size_t p) {
+    const float r = a.C[3 * p], g = a.C[3 * p + 1], b = a.C[3 * p + 2];
+    if (a.accum_out) { a.accum_out[3 * p] = r; a.accum_out[3 * p + 1] = g; a.accum_out[3 * p + 2] = b; }
+    if (a.rgba_out) a.rgba_out[p] = dn_rgba(r, g, b);
+}
+
 /* One iteration of the filter over the whole image.  Internal layout, float4 per pixel:
  *   e[]  = (E.r, E.g, E.b, 0)   ping-pong between iterations
  *   g0[] = (N.x, N.y, N.z, D)   written by iteration 0
@@ -247,9 +233,7 @@ DEV void dn_pixel(const AtrousArgs &a, int x, int y) {
             if (miss_p != miss_q) continue; /* weight 0 */
             float wn = 1.0f, xd = 0.0f;
             if (!miss_p) {
-                const float nd = c.nx * q.nx + c.ny * q.ny + c.nz * q.nz;
-                wn = nd > 0.0f ? nd : 0.0f;
-                for (int k = 0; k < a.npow; k++) wn = wn * wn;
+                wn = dn_wn(c.nx, c.ny, c.nz, q.nx, q.ny, q.nz, a.npow);
                 xd = mort_fabsf(c.d - q.d) / (a.sd * c.d);
             }
             const float der = c.er - q.er, deg = c.eg - q.eg, deb = c.eb - q.eb;
@@ -268,6 +252,8 @@ DEV void dn_pixel(const AtrousArgs &a, int x, int y) {
         e.x = er; e.y = eg; e.z = eb; e.w = 0.0f;
         a.e_out[p] = e;
     } else {
+        /* svgf_pixel (dev_svgf.h) ends on the same tail; it is written out in both, because moving it into a function of its own
+         * changes the register allocation of atrous_kernel<true, true> */
         float r = er * mort_fmaxf(c.ar, 1e-3f), g = eg * mort_fmaxf(c.ag, 1e-3f), b = eb * mort_fmaxf(c.ab, 1e-3f);
         if (r != r) r = 0.0f;
         if (g != g) g = 0.0f;
@@ -277,12 +263,9 @@ DEV void dn_pixel(const AtrousArgs &a, int x, int y) {
     }
 }
 
-/* iterations == 0: the accumulators unchanged and the render's own rgba */
+/* iterations == 0 */
 DEV void dn_passthrough(const AtrousArgs &a, int x, int y) {
-    const size_t p = (size_t)x + (size_t)y * (size_t)a.width;
-    const float r = a.C[3 * p], g = a.C[3 * p + 1], b = a.C[3 * p + 2];
-    if (a.accum_out) { a.accum_out[3 * p] = r; a.accum_out[3 * p + 1] = g; a.accum_out[3 * p + 2] = b; }
-    if (a.rgba_out) a.rgba_out[p] = dn_rgba(r, g, b);
+    dn_pass(a, (size_t)x + (size_t)y * (size_t)a.width);
 }
 
 #endif

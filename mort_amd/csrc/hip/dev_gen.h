@@ -1,7 +1,8 @@
 /*
  * dev_gen.h -- the pieces of the unified-tree closest-hit search (scene_compile.h build_unified) that every form of it
  * shares: the state-machine megakernel (mega_gen.hip), the wavefront traversal kernel (wave_gen.hip) and the single-lane
- * walk that the host loop and the CPU tests run (gen_world_hit below).  One body per step, so the forms cannot drift.
+ * walk (gen_walk_solids below) that the host loop and the CPU tests run through gen_world_hit and the feature pass through
+ * feat_tree_solids (dev_features.h).  One body per step, so the forms cannot drift.
  *
  * Replaces the brute-force part of world::hit (world.cuh:122-168) for worlds without reference BVHs; the proof that the
  * tree walk returns the scan's primitive is in the header of build_unified.
@@ -246,17 +247,16 @@ DEV Best gen_decode_best(const DScene &sc, const int *chains, uint32_t best, flo
     return b;
 }
 
-/* ---- the whole closest-hit search as ONE lane runs it (host loop, CPU tests): the same steps the kernels schedule
- * across a wave.  Returns false on a miss.  scans: counts the segments the scan decided. ---- */
-DEV bool gen_world_hit(const DScene &sc, const GenWalk &gw, const Ray &ray, Rng &rng, Best &out, unsigned long long *scans) {
+/* ---- the tree walk over the solids as ONE lane runs it, its pending far children at stack[k * stride], k < MORT_OWN_STACK (a
+ * local array with stride 1, or the lane's column of an LDS array).  flags: GFL_REF for a ray the walk does not decide ---- */
+DEV void gen_walk_solids(const DScene &sc, const GenWalk &gw, const Ray &ray, unsigned short *stack, int stride, float &closest, uint32_t &best, int &flags) {
     GenRay gr;
     const bool ordinary = gen_ray_setup(ray, gw.gx, gw.gy, gw.gz, gw.gR, gw.mnear, gw.kmin, gr);
     const float ray_a = vlen2(ray.d);
-    float closest = __builtin_inff();
-    uint32_t best = GBEST_NONE;
-    int flags = ordinary ? 0 : GFL_REF;
+    closest = __builtin_inff();
+    best = GBEST_NONE;
+    flags = ordinary ? 0 : GFL_REF;
     if (ordinary && gw.root != 0xffffu) {
-        unsigned short stack[MORT_OWN_STACK];
         int sp = 0;
         uint32_t cur = gw.root;
         for (;;) {
@@ -265,7 +265,7 @@ DEV bool gen_world_hit(const DScene &sc, const GenWalk &gw, const Ray &ray, Rng 
                 for (int cnt = (int)GLEAF_COUNT(cur); cnt > 0; cnt--, pos++)
                     gen_leaf_test(sc, gw.chains, gw.ranks, gw.n_spheres, sc.spheres, sc.quads, gw.entries[pos], ray, ray_a, closest, best, flags);
                 if (sp == 0) break;
-                cur = stack[--sp];
+                cur = stack[--sp * stride];
                 continue;
             }
             const DNodeQ nq = gw.nodes[cur & 0x7fffu];
@@ -275,17 +275,27 @@ DEV bool gen_world_hit(const DScene &sc, const GenWalk &gw, const Ray &ray, Rng 
             const bool m1 = gen_prune(nd.x1min, nd.x1max, nd.y1min, nd.y1max, nd.z1min, nd.z1max, gr, closest, te1);
             if (m0 && m1) {
                 if (sp == 0) break;
-                cur = stack[--sp];
+                cur = stack[--sp * stride];
             } else if (!m0 && !m1) {
                 const bool first0 = te0 <= te1;
-                stack[sp++] = (unsigned short)(first0 ? nd.c1 : nd.c0);
+                stack[sp++ * stride] = (unsigned short)(first0 ? nd.c1 : nd.c0);
                 cur = first0 ? nd.c0 : nd.c1;
             } else cur = m0 ? nd.c1 : nd.c0;
         }
     }
+}
+
+/* ---- the whole closest-hit search as ONE lane runs it (host loop, CPU tests): the same steps the kernels schedule
+ * across a wave.  Returns false on a miss.  scans: counts the segments the scan decided. ---- */
+DEV bool gen_world_hit(const DScene &sc, const GenWalk &gw, const Ray &ray, Rng &rng, Best &out, unsigned long long *scans) {
+    float closest;
+    uint32_t best;
+    int flags;
+    unsigned short stack[MORT_OWN_STACK];
+    gen_walk_solids(sc, gw, ray, stack, 1, closest, best, flags);
     if (flags) {
 #if defined(MORT_DEBUG_SCANS) && !defined(__HIP_DEVICE_COMPILE__)
-        printf("scan: flags %d best %08x closest %.9g o (%g %g %g) d (%g %g %g) inv (%g %g %g)\n", flags, best, closest, ray.o.x, ray.o.y, ray.o.z, ray.d.x, ray.d.y, ray.d.z, gr.ix, gr.iy, gr.iz);
+        printf("scan: flags %d best %08x closest %.9g o (%g %g %g) d (%g %g %g) inv (%g %g %g)\n", flags, best, closest, ray.o.x, ray.o.y, ray.o.z, ray.d.x, ray.d.y, ray.d.z, 1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
 #endif
         if (scans) *scans += 1;
         gen_scan_solids(sc, gw.first_medium, gw.chains, gw.n_chains, ray, closest, best);

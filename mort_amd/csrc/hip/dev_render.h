@@ -31,6 +31,9 @@ struct RenderArgs {
     int debug_lofs;        /* -DMORT_DEBUG_PRINT builds: packed pixel offset whose segments are printed (MORT_DEBUG_PIXEL), else unused */
 };
 
+/* a camera vector of the C ABI as the launch arguments hold it */
+static inline V3 to_v3(const mort_vec3 &v) { return mk(v.e[0], v.e[1], v.e[2]); }
+
 DEV int global_row(int ly, int rank, int nranks, int rpb) {
     const int lb = ly / rpb, within = ly - lb * rpb;
     return (lb * nranks + rank) * rpb + within;

@@ -5,7 +5,8 @@
  * written here, so host and device agree bit for bit.
  *
  * Not part of the parity path: nothing here draws a random number, touches a pixel's XORWOW state or is inlined into a render
- * kernel.  dn_expf, dn_kernel, dn_rgba come from dev_features.h, unchanged.
+ * kernel.  dn_expf, dn_kernel, dn_rgba, the normal weight dn_wn and the pass-through body dn_pass come from dev_features.h, shared
+ * with the denoiser.
  *
  * A body reads its taps through a source object (tap(qx, qy), var(qx, qy)): the buffers in memory (the host loop, and the
  * kernels that load every tap from global memory) or a workgroup's tile staged in LDS.  The arithmetic and its order do not
@@ -36,14 +37,6 @@ struct SvgfArgs {
 };
 
 DEV float sv_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-
-/* w_n of DESIGN.md 4.9: max(0, Np.Nq)^(2^npow) */
-DEV float sv_wn(float ax, float ay, float az, float bx, float by, float bz, int npow) {
-    const float nd = ax * bx + ay * by + az * bz;
-    float wn = nd > 0.0f ? nd : 0.0f;
-    for (int k = 0; k < npow; k++) wn = wn * wn;
-    return wn;
-}
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Prepare: demodulate, pack the features, set the variance of l(E) (from the temporal variance, or the spatial estimate)
@@ -117,7 +110,7 @@ DEV void svgf_prep_pixel(const SvgfArgs &a, const Src &src, int x, int y) {
                 if (miss_p != miss_q) continue;
                 float wn = 1.0f, xd = 0.0f;
                 if (!miss_p) {
-                    wn = sv_wn(nx, ny, nz, q.nx, q.ny, q.nz, a.npow);
+                    wn = dn_wn(nx, ny, nz, q.nx, q.ny, q.nz, a.npow);
                     const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy, ring = ax > ay ? ax : ay;
                     if (ring > 0) xd = mort_fabsf(dp - q.d) / ((a.sd1 * (float)ring) * dp);
                 }
@@ -207,7 +200,7 @@ DEV void svgf_pixel(const SvgfArgs &a, const Src &src, int x, int y) {
             if (miss_p != miss_q) continue; /* weight 0 */
             float wn = 1.0f, xd = 0.0f;
             if (!miss_p) {
-                wn = sv_wn(c.nx, c.ny, c.nz, q.nx, q.ny, q.nz, a.npow);
+                wn = dn_wn(c.nx, c.ny, c.nz, q.nx, q.ny, q.nz, a.npow);
                 xd = mort_fabsf(c.d - q.d) / (a.sd * c.d);
             }
             const float xl = mort_fabsf(lp - sv_lum(q.er, q.eg, q.eb)) / lden;
@@ -240,9 +233,7 @@ DEV void svgf_pixel(const SvgfArgs &a, const Src &src, int x, int y) {
 /* iterations == 0: the accumulators unchanged, the render's own rgba and the prepared variance */
 DEV void svgf_passthrough(const SvgfArgs &a, int x, int y) {
     const size_t p = (size_t)x + (size_t)y * (size_t)a.width;
-    const float r = a.C[3 * p], g = a.C[3 * p + 1], b = a.C[3 * p + 2];
-    if (a.accum_out) { a.accum_out[3 * p] = r; a.accum_out[3 * p + 1] = g; a.accum_out[3 * p + 2] = b; }
-    if (a.rgba_out) a.rgba_out[p] = dn_rgba(r, g, b);
+    dn_pass(a, p);
     if (a.variance_out) {
         const float4 h = a.g1[p];
         const float k = sv_lum(mort_fmaxf(h.x, 1e-3f), mort_fmaxf(h.y, 1e-3f), mort_fmaxf(h.z, 1e-3f));

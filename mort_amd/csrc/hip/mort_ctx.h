@@ -105,23 +105,22 @@ struct mort_ctx {
     /* mort_hip_render_gather: the render's statistics are collected after the gather's one host wait */
     bool defer_stats = false;
     std::function<int(mort_stats *)> pending_stats;
-    /* feature pass and denoiser (denoise.hip): their own scratch, nothing the render keeps across frames */
-    void *d_feat = nullptr;          /* mort_hip_render_features: packed albedo / normal / depth of the owned rows */
-    void *d_dn = nullptr;            /* the filter's float4 buffers: colour ping-pong, (normal, depth), albedo */
-    void *d_dnio = nullptr;          /* mort_hip_denoise: the host buffers' device copies */
-    size_t feat_cap = 0, dn_cap = 0, dnio_cap = 0;
-    hipStream_t dn_stream = nullptr; /* stream of the last feature / denoise / temporal launch */
-    /* temporal accumulation (temporal.hip): mort_hip_temporal's device copies of the host buffers */
-    void *d_tio = nullptr;
-    size_t tio_cap = 0;
-    /* SVGF filter stage (svgf.hip): a buffer that frees itself when mort_hip_shutdown deletes the context */
+    /* the stages (feature pass, denoiser, temporal step, SVGF filter; stage_common.h): scratch that frees itself when
+     * mort_hip_shutdown deletes the context, nothing the render keeps across frames */
     struct Scratch {
         void *p = nullptr;
         size_t cap = 0;
         ~Scratch() { if (p) (void)hipFree(p); }
     };
-    Scratch svgf;    /* the filter's float4 planes: colour + variance ping-pong, (normal, depth), albedo */
-    Scratch svgf_io; /* mort_hip_svgf: the host buffers' device copies */
+    /* Both are shared by every stage, whatever the image size; each call sizes and carves them anew and expects nothing of
+     * their contents.  That is safe because every user passes through switch_stream first: a call on another stream than
+     * the previous stage's waits for that stream, and calls on one stream run in order, so no two stages are in flight over
+     * the same bytes; a call that has to grow a buffer frees it with hipFree, which waits for the device's outstanding work
+     * as it did when one stage ran twice at growing sizes.  The host-buffer forms, stage_io's only users, are blocking:
+     * they return after their downloads, with the buffer idle */
+    Scratch stage_planes; /* the filters' four float4 planes: colour (+ variance) ping-pong, (normal, depth), albedo */
+    Scratch stage_io;     /* the host-buffer forms' device copies of the caller's buffers (stage_upload) */
+    hipStream_t dn_stream = nullptr; /* stream of the last stage launch */
     /* views (view.hip): the ones alive on this context, freed by mort_hip_shutdown */
     std::vector<struct mort_view *> views;
 };
@@ -142,8 +141,10 @@ static inline int ensure_buf(mort_ctx *c, void **p, size_t *cap, size_t need) {
     *cap = need;
     return MORT_OK;
 }
+static inline int ensure_buf(mort_ctx *c, mort_ctx::Scratch &b, size_t need) { return ensure_buf(c, &b.p, &b.cap, need); }
 
-/* a feature / denoise / temporal call on another stream than the previous one: that one may still read the scratch buffers */
+/* a stage call (feature pass, denoiser, temporal step, SVGF filter) on another stream than the previous one: that one may still
+ * use the shared stage scratch */
 static inline hipError_t switch_stream(mort_ctx *c, hipStream_t s) {
     hipError_t e = hipSuccess;
     if (c->dn_stream && c->dn_stream != s) e = hipStreamSynchronize(c->dn_stream);

@@ -152,7 +152,7 @@ static hipError_t quiesce(mort_ctx *c) {
     if (c->stream) e = hipStreamSynchronize(c->stream);
     if (c->last_stream && c->last_stream != c->stream) { hipError_t e2 = hipStreamSynchronize(c->last_stream); if (e == hipSuccess) e = e2; }
     c->last_stream = nullptr;
-    if (c->dn_stream && c->dn_stream != c->stream) { hipError_t e2 = hipStreamSynchronize(c->dn_stream); if (e == hipSuccess) e = e2; } /* denoise.hip */
+    if (c->dn_stream && c->dn_stream != c->stream) { hipError_t e2 = hipStreamSynchronize(c->dn_stream); if (e == hipSuccess) e = e2; } /* the stages */
     c->dn_stream = nullptr;
     return e;
 }
@@ -215,7 +215,6 @@ extern "C" void mort_hip_shutdown(mort_ctx *c) {
     hipFree(c->d_substates); hipFree(c->d_vaccum);
     hipFree(c->d_rgba); hipFree(c->d_accum); hipFree(c->d_segpx); hipFree(c->d_counters); hipFree(c->d_wf);
     hipFree(c->d_tile_cost); hipFree(c->d_tile_order); hipFree(c->d_probe_states); hipFree(c->d_deep); hipFree(c->d_wave_log);
-    hipFree(c->d_feat); hipFree(c->d_dn); hipFree(c->d_dnio); hipFree(c->d_tio);
     if (c->h_live) hipHostFree(c->h_live);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);

@@ -16,11 +16,6 @@ hipError_t mort_tile_sort_desc(const unsigned *d_cost, unsigned *d_keys_out, uns
 hipError_t mort_tile_heavy_count(const unsigned *d_keys_desc, int n, unsigned percent, unsigned max_r, const unsigned long long *d_frame_total,
                                  unsigned long long lanes, unsigned *d_out, hipStream_t s);
 
-/* denoise.hip, temporal.hip, svgf.hip: the workgroup of the feature / filter / temporal kernels in pixels (each file's FEAT_BX x
- * FEAT_BY, asserted equal there); a grid of 65535 of them per axis bounds the image those stages and a view take */
-#define MORT_FEAT_BX 64
-#define MORT_FEAT_BY 4
-
 /* denoise.hip, temporal.hip, svgf.hip: the parameter checks of the stage calls, for mort_hip_view_check_params */
 bool mort_denoise_params_ok(const mort_denoise_params *p);
 bool mort_temporal_params_ok(const mort_temporal_params *p);

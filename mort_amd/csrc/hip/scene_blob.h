@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "scene_compile.h"
-#include "dev_render.h"
+#include "dev_gen.h"
 
 /* ---- validation of every index the kernels will dereference ---- */
 static inline bool tex_ok(const mort_world *w, int type, int idx, int depth) {
@@ -120,8 +120,17 @@ static inline void scene_view(const SceneBlob &sb, const unsigned char *base, DS
     s.lds_bytes = (uint32_t)sb.hot_bytes;
 }
 
+/* what a single-lane walk of the compiled world's unified tree needs (dev_gen.h), its arrays read where the compiler left them */
+static inline GenWalk gen_walk_of(const mortc::Compiled &o) {
+    GenWalk gw;
+    gw.nodes = o.g_nodes.data(); gw.entries = o.g_entries.data(); gw.chains = o.g_chains.data();
+    gw.ranks = o.g_ranks.data(); gw.n_spheres = (int)o.spheres.size();
+    gw.n_chains = (int)(o.g_chains.size() / 2); gw.root = o.g_root; gw.first_medium = o.g_first_medium;
+    gw.gx = o.g_c[0]; gw.gy = o.g_c[1]; gw.gz = o.g_c[2]; gw.gR = o.g_R; gw.mnear = o.g_mnear; gw.kmin = o.g_kmin;
+    return gw;
+}
+
 /* the camera half of the launch arguments (camera.cuh:13-45 after initialize()) */
-static inline V3 to_v3(const mort_vec3 &v) { V3 r; r.x = v.e[0]; r.y = v.e[1]; r.z = v.e[2]; return r; }
 static inline void render_args_camera(RenderArgs &a, const mort_camera *cam) {
     a.width = cam->image_width; a.height = cam->image_height;
     a.sqrt_spp = cam->sqrt_spp; a.bounce_limit = cam->bounce_limit;

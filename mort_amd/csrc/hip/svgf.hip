@@ -3,7 +3,7 @@
  * variance that temporal accumulation writes (temporal.hip) or, where that is unknown, by a spatial estimate.  A non-parity
  * extra like the denoiser (denoise.hip) and the temporal step.
  *
- * Kernels (gfx950, wave64, 64x4-pixel workgroups: every wave covers 64 contiguous pixels of one row):
+ * Kernels (gfx950, wave64, the stages' 64x4-pixel workgroups of stage_common.h: every wave covers 64 contiguous pixels of one row):
  *   svgf_prep_kernel<HAVE_VAR, TILE>   demodulates, packs (N, D) and A as float4, sets the variance of the demodulated
  *                                      luminance: V / k^2 where the caller's variance is known, else the 5x5 spatial estimate.
  *                                      TILE: the workgroup's 68x8 neighbourhood (l, N, D) staged in LDS (10.6 KB); with
@@ -32,28 +32,26 @@
 #include "dev_svgf.h"
 #include "mort_ctx.h"
 #include "mort_internal.h"
+#include "stage_common.h"
 
 #pragma clang fp contract(off)
-
-#define FEAT_BX 64
-#define FEAT_BY 4
 
 /* ====================================================================== device */
 
 template <bool HAVE_VAR, bool TILE>
-__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) svgf_prep_kernel(const SvgfArgs a) {
-    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+__global__ void __launch_bounds__(STAGE_BX * STAGE_BY) svgf_prep_kernel(const SvgfArgs a) {
+    const int x = blockIdx.x * STAGE_BX + threadIdx.x, y = blockIdx.y * STAGE_BY + threadIdx.y;
     if constexpr (TILE) {
-        constexpr int TW = FEAT_BX + 4, TH = FEAT_BY + 4;
+        constexpr int TW = STAGE_BX + 4, TH = STAGE_BY + 4;
         __shared__ float4 t_nd[TW * TH];
         __shared__ float t_l[TW * TH];
-        const int x0 = blockIdx.x * FEAT_BX - 2, y0 = blockIdx.y * FEAT_BY - 2;
+        const int x0 = blockIdx.x * STAGE_BX - 2, y0 = blockIdx.y * STAGE_BY - 2;
         bool stage = true;
         if constexpr (HAVE_VAR) { /* the tile serves the spatial estimate only: skip it where the whole workgroup knows its variance */
             const bool unknown = x < a.width && y < a.height && !(a.V[(size_t)x + (size_t)y * (size_t)a.width] >= 0.0f);
             stage = __syncthreads_or(unknown) != 0;
         }
-        for (int i = threadIdx.x + threadIdx.y * FEAT_BX; stage && i < TW * TH; i += FEAT_BX * FEAT_BY) {
+        for (int i = threadIdx.x + threadIdx.y * STAGE_BX; stage && i < TW * TH; i += STAGE_BX * STAGE_BY) {
             const int qx = x0 + i % TW, qy = y0 + i / TW;
             float4 g;
             g.x = 0.0f; g.y = 0.0f; g.z = 0.0f; g.w = 0.0f;
@@ -77,13 +75,13 @@ __global__ void __launch_bounds__(FEAT_BX * FEAT_BY) svgf_prep_kernel(const Svgf
 }
 
 template <bool LAST, int TILE>
-__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) svgf_iter_kernel(const SvgfArgs a) {
-    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+__global__ void __launch_bounds__(STAGE_BX * STAGE_BY) svgf_iter_kernel(const SvgfArgs a) {
+    const int x = blockIdx.x * STAGE_BX + threadIdx.x, y = blockIdx.y * STAGE_BY + threadIdx.y;
     if constexpr (TILE > 0) { /* a.step == TILE */
-        constexpr int TW = FEAT_BX + 4 * TILE, TH = FEAT_BY + 4 * TILE;
+        constexpr int TW = STAGE_BX + 4 * TILE, TH = STAGE_BY + 4 * TILE;
         __shared__ float4 t_e[TW * TH], t_g0[TW * TH], t_g1[TW * TH];
-        const int x0 = blockIdx.x * FEAT_BX - 2 * TILE, y0 = blockIdx.y * FEAT_BY - 2 * TILE;
-        for (int i = threadIdx.x + threadIdx.y * FEAT_BX; i < TW * TH; i += FEAT_BX * FEAT_BY) {
+        const int x0 = blockIdx.x * STAGE_BX - 2 * TILE, y0 = blockIdx.y * STAGE_BY - 2 * TILE;
+        for (int i = threadIdx.x + threadIdx.y * STAGE_BX; i < TW * TH; i += STAGE_BX * STAGE_BY) {
             const int qx = x0 + i % TW, qy = y0 + i / TW;
             float4 e, g, h;
             e.x = 0.0f; e.y = 0.0f; e.z = 0.0f; e.w = 0.0f;
@@ -105,8 +103,8 @@ __global__ void __launch_bounds__(FEAT_BX * FEAT_BY) svgf_iter_kernel(const Svgf
     }
 }
 
-__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) svgf_passthrough_kernel(const SvgfArgs a) {
-    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+__global__ void __launch_bounds__(STAGE_BX * STAGE_BY) svgf_passthrough_kernel(const SvgfArgs a) {
+    const int x = blockIdx.x * STAGE_BX + threadIdx.x, y = blockIdx.y * STAGE_BY + threadIdx.y;
     if (x >= a.width || y >= a.height) return;
     svgf_passthrough(a, x, y);
 }
@@ -127,12 +125,6 @@ bool params_ok(const mort_svgf_params *p) {
     return true;
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 /* required inputs present, no output overlapping an input or another output */
 bool buffers_ok(int W, int H, const void *accum, const void *albedo, const void *normal, const void *depth, const void *variance,
                 void *accum_out, void *variance_out, void *rgba_out) {
@@ -142,18 +134,14 @@ bool buffers_ok(int W, int H, const void *accum, const void *albedo, const void 
     const size_t in_b[5] = {npx * 12, npx * 12, npx * 12, npx * 4, npx * 4};
     void *outs[3] = {accum_out, variance_out, rgba_out};
     const size_t out_b[3] = {npx * 12, npx * 4, npx * 4};
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 5; i++) if (overlap(outs[o], out_b[o], ins[i], in_b[i])) return false;
-        for (int j = 0; j < o; j++) if (overlap(outs[o], out_b[o], outs[j], out_b[j])) return false;
-    }
-    return true;
+    return buffers_disjoint(ins, in_b, 5, outs, out_b, 3);
 }
 
 /* the checks every form makes */
 int check_call(const mort_svgf_params *p, int W, int H, const void *accum, const void *albedo, const void *normal, const void *depth,
                const void *variance, void *accum_out, void *variance_out, void *rgba_out) {
     if (!params_ok(p)) return MORT_ERR_INVALID;
-    if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
+    if (!stage_size_ok(W, H)) return MORT_ERR_INVALID;
     if (!buffers_ok(W, H, accum, albedo, normal, depth, variance, accum_out, variance_out, rgba_out)) return MORT_ERR_INVALID;
     return MORT_OK;
 }
@@ -214,7 +202,6 @@ void launch_iter(const SvgfArgs &a, int lds, dim3 grid, dim3 block, hipStream_t 
 
 } // namespace
 
-static_assert(FEAT_BX == MORT_FEAT_BX && FEAT_BY == MORT_FEAT_BY, "mort_internal.h states the workgroup shape for view.hip");
 bool mort_svgf_params_ok(const mort_svgf_params *p) { return params_ok(p); }
 
 extern "C" int mort_hip_svgf_defaults(mort_svgf_params *p) {
@@ -229,16 +216,12 @@ extern "C" int mort_hip_svgf_device(mort_ctx *c, const mort_svgf_params *p, int 
     if (!c) return MORT_ERR_INVALID;
     int st = check_call(p, W, H, d_accum, d_albedo, d_normal, d_depth, d_variance, d_accum_out, d_variance_out, d_rgba_out);
     if (st != MORT_OK) return st;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, switch_stream(c, s));
-    const size_t npx = (size_t)W * (size_t)H;
-    if ((st = ensure_buf(c, &c->svgf.p, &c->svgf.cap, npx * 4 * sizeof(float4))) != MORT_OK) return st;
-    float4 *scratch = (float4 *)c->svgf.p;
     const int lds = lds_steps();
     const int n = p->iterations;
-    const dim3 grid((W + FEAT_BX - 1) / FEAT_BX, (H + FEAT_BY - 1) / FEAT_BY), block(FEAT_BX, FEAT_BY);
-    if (seconds) HIPCHK(c, hipEventRecord(c->ev0, s));
+    const dim3 grid = stage_grid(W, H), block = stage_block();
+    hipStream_t s;
+    if ((st = stage_begin(c, stream, (size_t)W * (size_t)H * 4 * sizeof(float4), seconds, &s)) != MORT_OK) return st;
+    float4 *scratch = (float4 *)c->stage_planes.p;
     const SvgfArgs pa = svgf_args(p, W, H, -1, d_accum, d_albedo, d_normal, d_depth, d_variance, scratch, d_accum_out, d_variance_out, d_rgba_out);
     if (d_variance) {
         if (lds) hipLaunchKernelGGL((svgf_prep_kernel<true, true>), grid, block, 0, s, pa);
@@ -258,14 +241,7 @@ extern "C" int mort_hip_svgf_device(mort_ctx *c, const mort_svgf_params *p, int 
         else launch_iter<false>(a, lds, grid, block, s);
         HIPCHK(c, hipGetLastError());
     }
-    if (seconds) {
-        HIPCHK(c, hipEventRecord(c->ev1, s));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *seconds = ms * 1e-3;
-    }
-    return MORT_OK;
+    return stage_end(c, s, seconds);
 }
 
 extern "C" int mort_hip_svgf(mort_ctx *c, const mort_svgf_params *p, int W, int H, const float *accum, const float *albedo, const float *normal,
@@ -277,24 +253,15 @@ extern "C" int mort_hip_svgf(mort_ctx *c, const mort_svgf_params *p, int W, int 
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, switch_stream(c, c->stream));
     const size_t npx = (size_t)W * (size_t)H;
-    /* C, A, N (3 floats each), D, V, accum_out (3 floats), variance_out, rgba (4 bytes) */
-    if ((st = ensure_buf(c, &c->svgf_io.p, &c->svgf_io.cap, npx * 17 * sizeof(float))) != MORT_OK) return st;
-    float *dC = (float *)c->svgf_io.p, *dA = dC + 3 * npx, *dN = dA + 3 * npx, *dD = dN + 3 * npx, *dV = dD + npx, *dO = dV + npx, *dW = dO + 3 * npx;
-    uint8_t *dR = (uint8_t *)(dW + npx);
-    HIPCHK(c, hipMemcpy(dC, accum, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dA, albedo, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dN, normal, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dD, depth, npx * 4, hipMemcpyHostToDevice));
-    if (variance) HIPCHK(c, hipMemcpy(dV, variance, npx * 4, hipMemcpyHostToDevice));
+    StagePlane pl[8] = {{accum, nullptr, npx * 12}, {albedo, nullptr, npx * 12}, {normal, nullptr, npx * 12}, {depth, nullptr, npx * 4},
+                        {variance, nullptr, npx * 4}, {nullptr, accum_out, npx * 12}, {nullptr, variance_out, npx * 4}, {nullptr, rgba_out, npx * 4}};
+    if ((st = stage_upload(c, pl, 8)) != MORT_OK) return st;
     double sec = 0;
-    if ((st = mort_hip_svgf_device(c, p, W, H, dC, dA, dN, dD, variance ? dV : nullptr, accum_out ? dO : nullptr, variance_out ? dW : nullptr,
-                                   rgba_out ? dR : nullptr, c->stream, &sec)) != MORT_OK)
+    if ((st = mort_hip_svgf_device(c, p, W, H, pl[0].dev, pl[1].dev, pl[2].dev, pl[3].dev, pl[4].dev, pl[5].dev, pl[6].dev, pl[7].dev, c->stream,
+                                   &sec)) != MORT_OK)
         return st;
     if (seconds) *seconds = sec;
-    if (accum_out) HIPCHK(c, hipMemcpy(accum_out, dO, npx * 12, hipMemcpyDeviceToHost));
-    if (variance_out) HIPCHK(c, hipMemcpy(variance_out, dW, npx * 4, hipMemcpyDeviceToHost));
-    if (rgba_out) HIPCHK(c, hipMemcpy(rgba_out, dR, npx * 4, hipMemcpyDeviceToHost));
-    return MORT_OK;
+    return stage_download(c, pl, 8);
 }
 
 extern "C" int mort_hip_svgf_host(const mort_svgf_params *p, int W, int H, int nthreads, const float *accum, const float *albedo,

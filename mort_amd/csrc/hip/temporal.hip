@@ -2,7 +2,7 @@
  * temporal.hip -- temporal accumulation across frames with camera reprojection: a non-parity extra between the
  * render and the denoiser, so that a still camera converges and a moving one keeps what it can of the frames before.
  *
- * Kernel (gfx950, wave64, 64x4-pixel workgroups: every wave covers 64 contiguous pixels of one row):
+ * Kernel (gfx950, wave64, the stages' 64x4-pixel workgroups of stage_common.h: every wave covers 64 contiguous pixels of one row):
  *   tacc_kernel<STILL>   one lane per pixel, tacc_pixel (dev_temporal.h).  STILL: the previous camera is bit-identical to this
  *                        one (decided once per call on the host) and every pixel reads its own history; else the hit point is
  *                        reprojected into the previous frame and the history is a bilinear gather of up to four pixels.
@@ -21,17 +21,15 @@
 #include "dev_temporal.h"
 #include "mort_ctx.h"
 #include "mort_internal.h"
+#include "stage_common.h"
 
 #pragma clang fp contract(off)
-
-#define FEAT_BX 64
-#define FEAT_BY 4
 
 /* ====================================================================== device */
 
 template <bool STILL>
-__global__ void __launch_bounds__(FEAT_BX * FEAT_BY) tacc_kernel(const TaccArgs a) {
-    const int x = blockIdx.x * FEAT_BX + threadIdx.x, y = blockIdx.y * FEAT_BY + threadIdx.y;
+__global__ void __launch_bounds__(STAGE_BX * STAGE_BY) tacc_kernel(const TaccArgs a) {
+    const int x = blockIdx.x * STAGE_BX + threadIdx.x, y = blockIdx.y * STAGE_BY + threadIdx.y;
     if (x >= a.width || y >= a.height) return;
     tacc_pixel<STILL>(a, x, y);
 }
@@ -51,26 +49,16 @@ bool params_ok(const mort_temporal_params *p) {
     return true;
 }
 
-V3 v3_of(const mort_vec3 &v) { return mk(v.e[0], v.e[1], v.e[2]); }
-
-bool same_vec(const mort_vec3 &a, const mort_vec3 &b) { return std::memcmp(&a, &b, sizeof a) == 0; }
-
 /* the previous camera is bit-identical where the reprojection looks: centre, viewport, image size */
 bool camera_still(const mort_camera *prev, const mort_camera *cam) {
     return same_vec(prev->center, cam->center) && same_vec(prev->pixel00_loc, cam->pixel00_loc) && same_vec(prev->pixel_delta_u, cam->pixel_delta_u) &&
            same_vec(prev->pixel_delta_v, cam->pixel_delta_v) && prev->image_width == cam->image_width && prev->image_height == cam->image_height;
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 /* the checks every form makes on the parameters, the cameras and the size */
 int check_call(const mort_temporal_params *p, const mort_camera *prev, const mort_camera *cam, int W, int H) {
     if (!params_ok(p) || !cam) return MORT_ERR_INVALID;
-    if (W <= 0 || H <= 0 || W >= 65536 * FEAT_BX || H >= 65536 * FEAT_BY) return MORT_ERR_INVALID;
+    if (!stage_size_ok(W, H)) return MORT_ERR_INVALID;
     if (cam->image_width != W || cam->image_height != H || cam->sqrt_spp < 1) return MORT_ERR_INVALID;
     if (prev && (prev->image_width != W || prev->image_height != H)) return MORT_ERR_INVALID;
     return MORT_OK;
@@ -85,11 +73,7 @@ bool buffers_ok(const mort_camera *prev, int W, int H, const void *accum, const 
     const size_t in_b[4] = {npx * 12, npx * 12, npx * 4, hb};
     void *outs[4] = {hout, accum_out, variance_out, rgba_out};
     const size_t out_b[4] = {hb, npx * 12, npx * 4, npx * 4};
-    for (int o = 0; o < 4; o++) {
-        for (int i = 0; i < 4; i++) if (overlap(outs[o], out_b[o], ins[i], in_b[i])) return false;
-        for (int j = 0; j < o; j++) if (overlap(outs[o], out_b[o], outs[j], out_b[j])) return false;
-    }
-    return true;
+    return buffers_disjoint(ins, in_b, 4, outs, out_b, 4);
 }
 
 /* the kernel arguments of a checked call (the same bits for the kernel and the host loop) */
@@ -108,10 +92,10 @@ int temporal_args(const mort_temporal_params *p, const mort_camera *prev, const 
     a.n_c = (float)(cam->sqrt_spp * cam->sqrt_spp);
     a.cap = (float)(still ? p->max_samples : p->motion_max_samples);
     a.tol = p->depth_tolerance; a.nmin = p->normal_min;
-    a.center = v3_of(cam->center); a.pixel00 = v3_of(cam->pixel00_loc); a.du = v3_of(cam->pixel_delta_u); a.dv = v3_of(cam->pixel_delta_v);
+    a.center = to_v3(cam->center); a.pixel00 = to_v3(cam->pixel00_loc); a.du = to_v3(cam->pixel_delta_u); a.dv = to_v3(cam->pixel_delta_v);
     if (!still) {
-        a.pc = v3_of(prev->center); a.pdu = v3_of(prev->pixel_delta_u); a.pdv = v3_of(prev->pixel_delta_v);
-        a.po = vsub(v3_of(prev->pixel00_loc), a.pc);
+        a.pc = to_v3(prev->center); a.pdu = to_v3(prev->pixel_delta_u); a.pdv = to_v3(prev->pixel_delta_v);
+        a.po = vsub(to_v3(prev->pixel00_loc), a.pc);
         a.nrm = vcross(a.pdu, a.pdv);
         a.k = vdot(a.nrm, a.po);
         a.g11 = vdot(a.pdu, a.pdu); a.g12 = vdot(a.pdu, a.pdv); a.g22 = vdot(a.pdv, a.pdv);
@@ -135,7 +119,6 @@ void tacc_host_row(void *p, int y) {
 
 } // namespace
 
-static_assert(FEAT_BX == MORT_FEAT_BX && FEAT_BY == MORT_FEAT_BY, "mort_internal.h states the workgroup shape for view.hip");
 bool mort_temporal_params_ok(const mort_temporal_params *p) { return params_ok(p); }
 
 extern "C" int mort_hip_temporal_defaults(mort_temporal_params *p) {
@@ -151,25 +134,15 @@ extern "C" int mort_hip_temporal_device(mort_ctx *c, const mort_temporal_params 
     if (!c) return MORT_ERR_INVALID;
     TaccArgs a;
     bool still;
-    const int st = temporal_args(p, prev_cam, cam, W, H, d_accum, d_normal, d_depth, d_hist_in, d_hist_out, d_accum_out, d_variance_out,
-                                 d_rgba_out, a, still);
+    int st = temporal_args(p, prev_cam, cam, W, H, d_accum, d_normal, d_depth, d_hist_in, d_hist_out, d_accum_out, d_variance_out,
+                           d_rgba_out, a, still);
     if (st != MORT_OK) return st;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, switch_stream(c, s));
-    const dim3 grid((W + FEAT_BX - 1) / FEAT_BX, (H + FEAT_BY - 1) / FEAT_BY), block(FEAT_BX, FEAT_BY);
-    if (seconds) HIPCHK(c, hipEventRecord(c->ev0, s));
-    if (still) hipLaunchKernelGGL(tacc_kernel<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(tacc_kernel<false>, grid, block, 0, s, a);
+    hipStream_t s;
+    if ((st = stage_begin(c, stream, 0, seconds, &s)) != MORT_OK) return st;
+    if (still) hipLaunchKernelGGL(tacc_kernel<true>, stage_grid(W, H), stage_block(), 0, s, a);
+    else hipLaunchKernelGGL(tacc_kernel<false>, stage_grid(W, H), stage_block(), 0, s, a);
     HIPCHK(c, hipGetLastError());
-    if (seconds) {
-        HIPCHK(c, hipEventRecord(c->ev1, s));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *seconds = ms * 1e-3;
-    }
-    return MORT_OK;
+    return stage_end(c, s, seconds);
 }
 
 extern "C" int mort_hip_temporal(mort_ctx *c, const mort_temporal_params *p, const mort_camera *prev_cam, const mort_camera *cam, int W, int H,
@@ -181,26 +154,16 @@ extern "C" int mort_hip_temporal(mort_ctx *c, const mort_temporal_params *p, con
     if (!buffers_ok(prev_cam, W, H, accum, normal, depth, hist_in, hist_out, accum_out, variance_out, rgba_out)) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, switch_stream(c, c->stream));
-    const size_t npx = (size_t)W * (size_t)H, hf = npx * MORT_TEMPORAL_HISTORY_FLOATS;
-    /* history in, history out (float4 planes first), C, N (3 floats each), D, accum_out (3 floats), variance, rgba (4 bytes) */
-    st = ensure_buf(c, &c->d_tio, &c->tio_cap, (2 * hf + 12 * npx) * sizeof(float));
-    if (st != MORT_OK) return st;
-    float *dHi = (float *)c->d_tio, *dHo = dHi + hf, *dC = dHo + hf, *dN = dC + 3 * npx, *dD = dN + 3 * npx, *dO = dD + npx, *dV = dO + 3 * npx;
-    uint8_t *dR = (uint8_t *)(dV + npx);
-    HIPCHK(c, hipMemcpy(dC, accum, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dN, normal, npx * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dD, depth, npx * 4, hipMemcpyHostToDevice));
-    if (hist_in) HIPCHK(c, hipMemcpy(dHi, hist_in, hf * 4, hipMemcpyHostToDevice));
+    const size_t npx = (size_t)W * (size_t)H, hb = npx * MORT_TEMPORAL_HISTORY_FLOATS * sizeof(float);
+    StagePlane pl[8] = {{accum, nullptr, npx * 12}, {normal, nullptr, npx * 12}, {depth, nullptr, npx * 4}, {hist_in, nullptr, hb},
+                        {nullptr, hist_out, hb}, {nullptr, accum_out, npx * 12}, {nullptr, variance_out, npx * 4}, {nullptr, rgba_out, npx * 4}};
+    if ((st = stage_upload(c, pl, 8)) != MORT_OK) return st;
     double sec = 0;
-    if ((st = mort_hip_temporal_device(c, p, prev_cam, cam, W, H, dC, dN, dD, hist_in ? dHi : nullptr, dHo, accum_out ? dO : nullptr,
-                                       variance_out ? dV : nullptr, rgba_out ? dR : nullptr, c->stream, &sec)) != MORT_OK)
+    if ((st = mort_hip_temporal_device(c, p, prev_cam, cam, W, H, pl[0].dev, pl[1].dev, pl[2].dev, pl[3].dev, pl[4].dev, pl[5].dev, pl[6].dev,
+                                       pl[7].dev, c->stream, &sec)) != MORT_OK)
         return st;
     if (seconds) *seconds = sec;
-    HIPCHK(c, hipMemcpy(hist_out, dHo, hf * 4, hipMemcpyDeviceToHost));
-    if (accum_out) HIPCHK(c, hipMemcpy(accum_out, dO, npx * 12, hipMemcpyDeviceToHost));
-    if (variance_out) HIPCHK(c, hipMemcpy(variance_out, dV, npx * 4, hipMemcpyDeviceToHost));
-    if (rgba_out) HIPCHK(c, hipMemcpy(rgba_out, dR, npx * 4, hipMemcpyDeviceToHost));
-    return MORT_OK;
+    return stage_download(c, pl, 8);
 }
 
 extern "C" int mort_hip_temporal_host(const mort_temporal_params *p, const mort_camera *prev_cam, const mort_camera *cam, int W, int H,

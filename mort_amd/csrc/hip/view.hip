@@ -8,7 +8,7 @@
  * chained by hand.  What this file adds is the residency (the view owns every buffer the chain passes on, the ping-ponged
  * history and the previous camera), the single host wait per frame (the render's statistics are deferred as
  * mort_hip_render_gather defers them; the stage times come from the view's own events, read after that wait), the skipped
- * feature pass under a still camera, and the invalidation rules.
+ * feature pass under a still camera, and the invalidation rules.  The size limit is the stages' (stage_common.h).
  */
 #include <hip/hip_runtime.h>
 
@@ -20,6 +20,7 @@
 #include "mort_hip.h"
 #include "mort_ctx.h"
 #include "mort_internal.h"
+#include "stage_common.h"
 
 /* the view's events of a frame: after the features, after the temporal step, after the filter.  The render is bracketed by the
  * context's own pair (ev0, ev1: what mort_stats.seconds is), which nothing records again before the frame's statistics are read */
@@ -56,8 +57,6 @@ struct mort_view {
 
 namespace {
 
-bool same_vec(const mort_vec3 &a, const mort_vec3 &b) { return std::memcmp(&a, &b, sizeof a) == 0; }
-
 /* bit-identical in every field the feature pass reads (denoise.hip feat_camera) */
 bool same_feature_camera(const mort_camera &a, const mort_camera &b) {
     return a.image_width == b.image_width && a.image_height == b.image_height && same_vec(a.background, b.background) &&
@@ -72,8 +71,9 @@ void free_buffers(mort_view *v) {
     for (hipEvent_t e : v->ev) if (e) (void)hipEventDestroy(e);
 }
 
-/* a frame that failed half way leaves nothing to build on */
+/* a frame that failed half way leaves nothing to build on, and its render's deferred statistics are not collected */
 int frame_failed(mort_view *v, int st) {
+    v->ctx->pending_stats = nullptr;
     v->have_frame = v->have_feat = false;
     v->frame = 0;
     return st;
@@ -119,10 +119,10 @@ int view_frame(mort_view *v, const mort_camera *cam, int mode, void *d_dst, uint
     if (!reuse) {
         v->have_feat = false;
         st = mort_hip_render_features_device(c, cam, v->albedo(), v->normal(), v->depth(), s, nullptr);
-        if (st != MORT_OK) { c->pending_stats = nullptr; return frame_failed(v, st); }
+        if (st != MORT_OK) return frame_failed(v, st);
         v->feat_cam = *cam; v->feat_serial = c->world_serial; v->have_feat = true;
     }
-    if (timed && hipEventRecord(v->ev[EV_FEAT], s) != hipSuccess) { c->pending_stats = nullptr; return frame_failed(v, MORT_ERR_HIP); }
+    if (timed && hipEventRecord(v->ev[EV_FEAT], s) != hipSuccess) return frame_failed(v, MORT_ERR_HIP);
 
     /* ---- temporal step, filter: the last stage that runs writes the frame's uchar4 ---- */
     const void *colour = v->d_accum, *variance = nullptr;
@@ -132,20 +132,20 @@ int view_frame(mort_view *v, const mort_camera *cam, int mode, void *d_dst, uint
         st = mort_hip_temporal_device(c, &v->p.tp, fresh ? nullptr : &v->prev_cam, cam, W, H, v->d_accum, v->normal(), v->depth(),
                                       fresh ? nullptr : v->d_hist[v->hist_cur], v->d_hist[out], v->d_tacc, v->d_var, filter ? nullptr : d_dst,
                                       s, nullptr);
-        if (st != MORT_OK) { c->pending_stats = nullptr; return frame_failed(v, st); }
+        if (st != MORT_OK) return frame_failed(v, st);
         v->hist_cur = out;
         colour = v->d_tacc; variance = v->d_var;
         if (!filter) d_src = nullptr;
-        if (timed && hipEventRecord(v->ev[EV_TEMPORAL], s) != hipSuccess) { c->pending_stats = nullptr; return frame_failed(v, MORT_ERR_HIP); }
+        if (timed && hipEventRecord(v->ev[EV_TEMPORAL], s) != hipSuccess) return frame_failed(v, MORT_ERR_HIP);
     }
     if (filter) {
         if (v->p.filter == MORT_VIEW_FILTER_DENOISE)
             st = mort_hip_denoise_device(c, &v->p.dp, W, H, colour, v->albedo(), v->normal(), v->depth(), v->d_facc, d_dst, s, nullptr);
         else
             st = mort_hip_svgf_device(c, &v->p.sp, W, H, colour, v->albedo(), v->normal(), v->depth(), variance, v->d_facc, nullptr, d_dst, s, nullptr);
-        if (st != MORT_OK) { c->pending_stats = nullptr; return frame_failed(v, st); }
+        if (st != MORT_OK) return frame_failed(v, st);
         d_src = nullptr;
-        if (timed && hipEventRecord(v->ev[EV_FILTER], s) != hipSuccess) { c->pending_stats = nullptr; return frame_failed(v, MORT_ERR_HIP); }
+        if (timed && hipEventRecord(v->ev[EV_FILTER], s) != hipSuccess) return frame_failed(v, MORT_ERR_HIP);
     }
 
     /* ---- the frame leaves: only the uchar4 moves ---- */
@@ -153,7 +153,7 @@ int view_frame(mort_view *v, const mort_camera *cam, int mode, void *d_dst, uint
     if (h_dst) e = hipMemcpyAsync(v->h_out, d_src ? d_src : d_dst, npx * 4, hipMemcpyDeviceToHost, s);
     else if (d_src) e = hipMemcpyAsync(d_dst, d_src, npx * 4, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess && wait) e = hipStreamSynchronize(s); /* the one host wait */
-    if (e != hipSuccess) { c->pending_stats = nullptr; hip_fail(c, e, "view frame"); return frame_failed(v, MORT_ERR_HIP); }
+    if (e != hipSuccess) { hip_fail(c, e, "view frame"); return frame_failed(v, MORT_ERR_HIP); }
     if (h_dst) std::memcpy(h_dst, v->h_out, npx * 4);
 
     const int index = v->frame;
@@ -206,7 +206,7 @@ extern "C" int mort_hip_view_defaults(mort_view_params *p) {
 
 extern "C" int mort_hip_view_check_params(const mort_view_params *p) {
     if (!p) return MORT_ERR_INVALID;
-    if (p->width <= 0 || p->height <= 0 || p->width >= 65536 * MORT_FEAT_BX || p->height >= 65536 * MORT_FEAT_BY) return MORT_ERR_INVALID; /* the stages' grid limits */
+    if (!stage_size_ok(p->width, p->height)) return MORT_ERR_INVALID; /* the stages' grid limits */
     if (p->temporal != 0 && p->temporal != 1) return MORT_ERR_INVALID;
     if (p->filter != MORT_VIEW_FILTER_NONE && p->filter != MORT_VIEW_FILTER_DENOISE && p->filter != MORT_VIEW_FILTER_SVGF) return MORT_ERR_INVALID;
     if (p->temporal && !mort_temporal_params_ok(&p->tp)) return MORT_ERR_INVALID;
