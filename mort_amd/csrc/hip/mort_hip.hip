@@ -236,6 +236,35 @@ extern "C" int mort_hip_set_partition(mort_ctx *c, const mort_partition *p) {
     return MORT_OK;
 }
 
+/* the LDS kernels handle: one BVH over spheres as the whole world */
+static bool one_sphere_bvh(const mortc::Compiled &o) { return o.items.size() == 1 && o.items[0].kind == ITEM_BVH && o.quads.empty(); }
+
+/* The two LDS images of such a world: the BVH megakernel's (four-wide nodes, leaf records with their spheres by value, every small
+ * table) and the wavefront traversal kernel's (binary nodes, leaf nodes, spheres), with the offsets of their parts.  fits: both
+ * within MORT_BVH_IMAGE_MAX, the condition of mega_bvh_kernel and wave_bvh.h.  No HIP call. */
+#define MORT_BVH_IMAGE_MAX (72 * 1024)
+struct BvhImages {
+    std::vector<unsigned char> fb, tb;
+    uint32_t f_nodes4, f_leafrecs, f_lambert, f_metal, f_diel, f_dlight, f_iso, f_solid, f_checker, t_nodes2, t_leaves, t_spheres;
+    bool fits;
+};
+static void build_bvh_images(const mortc::Compiled &o, BvhImages &im) {
+    std::vector<unsigned char> &fb = im.fb, &tb = im.tb;
+    im.f_nodes4 = (uint32_t)place(fb, o.own_nodes4); im.f_leafrecs = (uint32_t)place(fb, o.own_leafrecs);
+    im.f_lambert = (uint32_t)place(fb, o.lambert); im.f_metal = (uint32_t)place(fb, o.metal); im.f_diel = (uint32_t)place(fb, o.dielectric);
+    im.f_dlight = (uint32_t)place(fb, o.dlight); im.f_iso = (uint32_t)place(fb, o.isotropic);
+    im.f_solid = (uint32_t)place(fb, o.solid); im.f_checker = (uint32_t)place(fb, o.checker);
+    fb.resize((fb.size() + 15) & ~(size_t)15, 0);
+    im.t_nodes2 = (uint32_t)place(tb, o.own_nodes); im.t_leaves = (uint32_t)place(tb, o.own_leaves); im.t_spheres = (uint32_t)place(tb, o.spheres);
+    tb.resize((tb.size() + 15) & ~(size_t)15, 0);
+    im.fits = fb.size() <= MORT_BVH_IMAGE_MAX && tb.size() <= MORT_BVH_IMAGE_MAX;
+}
+
+/* 1024-thread groups of mega_bvh_kernel: image + traversal stacks + one bounce-stack level per lane must fit one CU's LDS */
+static bool bvh_wide_block_fits(uint32_t image_bytes, int own4_stack) {
+    return (size_t)((image_bytes + 15u) & ~15u) + ((size_t)own4_stack + MORT_BVH_TSTACK_SPARE) * 1024u * 2u + 2048u + 1024u * 16u <= 160u * 1024u;
+}
+
 extern "C" int mort_hip_upload_world(mort_ctx *c, const mort_world *w) {
     if (!c || !w) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
@@ -262,20 +291,15 @@ extern "C" int mort_hip_upload_world(mort_ctx *c, const mort_world *w) {
     c->list_types = o.list_types; c->list_idxs = o.list_idxs;
     for (int i = 0; i < MORT_NUM_HITTABLE_LIST; i++) { c->list_first[i] = o.list_first[i]; c->list_count[i] = o.list_count[i]; }
     c->n_wspheres = (int)o.wspheres.size(); c->n_wquads = (int)o.wquads.size(); c->n_lists = w->objs.num_hittable_list;
-    /* the LDS kernels handle: one BVH over spheres as the whole world */
-    c->wave_ok = (o.items.size() == 1 && o.items[0].kind == ITEM_BVH && o.quads.empty());
+    c->wave_ok = one_sphere_bvh(o);
     if (c->wave_ok && !o.own_nodes.empty() && !o.own_nodes4.empty()) {
-        /* two LDS images: the BVH megakernel's (four-wide nodes, leaf records with their spheres by value, every small
-         * table) and the wavefront traversal kernel's (binary nodes, leaf nodes, spheres) */
-        std::vector<unsigned char> fb, tb;
-        c->f_nodes4 = (uint32_t)place(fb, o.own_nodes4); c->f_leafrecs = (uint32_t)place(fb, o.own_leafrecs);
-        c->f_lambert = (uint32_t)place(fb, o.lambert); c->f_metal = (uint32_t)place(fb, o.metal); c->f_diel = (uint32_t)place(fb, o.dielectric);
-        c->f_dlight = (uint32_t)place(fb, o.dlight); c->f_iso = (uint32_t)place(fb, o.isotropic);
-        c->f_solid = (uint32_t)place(fb, o.solid); c->f_checker = (uint32_t)place(fb, o.checker);
-        fb.resize((fb.size() + 15) & ~(size_t)15, 0);
-        c->t_nodes2 = (uint32_t)place(tb, o.own_nodes); c->t_leaves = (uint32_t)place(tb, o.own_leaves); c->t_spheres = (uint32_t)place(tb, o.spheres);
-        tb.resize((tb.size() + 15) & ~(size_t)15, 0);
-        if (fb.size() <= 72 * 1024 && tb.size() <= 72 * 1024) {
+        BvhImages im;
+        build_bvh_images(o, im);
+        const std::vector<unsigned char> &fb = im.fb, &tb = im.tb;
+        c->f_nodes4 = im.f_nodes4; c->f_leafrecs = im.f_leafrecs; c->f_lambert = im.f_lambert; c->f_metal = im.f_metal; c->f_diel = im.f_diel;
+        c->f_dlight = im.f_dlight; c->f_iso = im.f_iso; c->f_solid = im.f_solid; c->f_checker = im.f_checker;
+        c->t_nodes2 = im.t_nodes2; c->t_leaves = im.t_leaves; c->t_spheres = im.t_spheres;
+        if (im.fits) {
             HIPCHK(c, hipMalloc(&c->d_fast, fb.size()));
             HIPCHK(c, hipMemcpy(c->d_fast, fb.data(), fb.size(), hipMemcpyHostToDevice));
             HIPCHK(c, hipMalloc(&c->d_trav, tb.size()));
@@ -653,7 +677,7 @@ static int launch_bvh(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, 
         if (wide_ok) FB = 1024;
     }
     /* 1024 threads: image + traversal stacks + one bounce-stack level per lane must fit one CU's LDS, else the widest shape that does */
-    if (FB == 1024 && (size_t)((fa.hot_bytes + 15u) & ~15u) + ((size_t)c->own4_stack + MORT_BVH_TSTACK_SPARE) * 1024u * 2u + 2048u + 1024u * 16u > 160u * 1024u) FB = 768;
+    if (FB == 1024 && !bvh_wide_block_fits(fa.hot_bytes, c->own4_stack)) FB = 768;
     if (FB != 1024 && FB != 768 && FB != 512 && FB != 384) FB = 256;
     fa.drain_rounds = 3; /* batch thresholds as shares of the wave's LIVE lanes (they differ from fixed counts only once lanes have run out of pixels: the tail of a frame;
                           * three runs each, one box: N = 1 100.1-100.5 vs 100.3-102.9 ms, a rank of 2 75.6-78.6 vs 77.6-82.2 ms, ranks of 4 / 8 unchanged); DRAIN kernels
@@ -1026,6 +1050,30 @@ extern "C" int mort_hip_debug_own_tree(const mort_world *w, int *out) {
         }
     }
     out[8] = same ? 1 : 0;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): what mort_hip_upload_world and the launch of mega_bvh_kernel decide from
+ * a world's own trees -- out[0] 1 if the world is one reference BVH over spheres, [1] 1 if it has a four-wide tree, [2] bytes of the BVH
+ * megakernel's LDS image (0 without a four-wide tree), [3] bytes of the wavefront traversal kernel's, [4] the limit on either, [5] 1 if mega_bvh_kernel and the wavefront
+ * pipeline serve the world (both images within the limit), [6] the traversal stack levels the launch sizes for, [7] 1 if 1024-thread
+ * groups fit one CU's LDS with that image and stack. */
+extern "C" int mort_hip_debug_bvh_images(const mort_world *w, int *out) {
+    if (!w || !out) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    out[0] = one_sphere_bvh(o) ? 1 : 0; out[1] = (!o.own_nodes.empty() && !o.own_nodes4.empty()) ? 1 : 0; out[4] = MORT_BVH_IMAGE_MAX;
+    if (!out[0] || o.own_nodes.empty()) return MORT_OK;
+    BvhImages im;
+    build_bvh_images(o, im);
+    out[3] = (int)im.tb.size(); /* the binary tree's image exists without a four-wide tree, and tells how big the world is */
+    if (!out[1]) return MORT_OK;
+    out[2] = (int)im.fb.size(); out[5] = im.fits ? 1 : 0;
+    out[6] = o.own4_stack > 1 ? o.own4_stack : 1;
+    out[7] = (im.fits && bvh_wide_block_fits((uint32_t)im.fb.size(), out[6])) ? 1 : 0;
     return MORT_OK;
 }
 

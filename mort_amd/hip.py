@@ -506,6 +506,29 @@ def render_host(world, cam, states=None, seed=S.DEFAULT_SEED, nthreads=1, tree=F
     return dict(rgba=rgba, accum=accum, segments_px=seg, stats=stt.asdict(), states=st8)
 
 
+def debug_own_tree(world):
+    """mort_hip_debug_own_tree (host only): dict of the nine facts of this build's own trees over the world (mort_hip.hip)."""
+    fn = lib().mort_hip_debug_own_tree
+    fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    out = (C.c_int * 9)()
+    st = fn(C.cast(world.ptr, C.c_void_p), out)
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_own_tree")
+    return dict(zip(("n2", "leaves", "depth2", "n4", "stack4", "reached", "bad", "slots", "same"), list(out)))
+
+
+def debug_bvh_images(world):
+    """mort_hip_debug_bvh_images (host only): what mort_hip_upload_world and the launch of mega_bvh_kernel will decide for the world --
+    dict(sphere_bvh, four_wide, fast_bytes, trav_bytes, limit, fits, stack_levels, wide_fits) (mort_hip.hip)."""
+    fn = lib().mort_hip_debug_bvh_images
+    fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    out = (C.c_int * 8)()
+    st = fn(C.cast(world.ptr, C.c_void_p), out)
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_bvh_images")
+    return dict(zip(("sphere_bvh", "four_wide", "fast_bytes", "trav_bytes", "limit", "fits", "stack_levels", "wide_fits"), list(out)))
+
+
 def _feature_arrays(W, H):
     return dict(albedo=np.zeros((H, W, 3), dtype=np.float32), normal=np.zeros((H, W, 3), dtype=np.float32),
                 depth=np.zeros((H, W), dtype=np.float32))

@@ -379,3 +379,294 @@ PLACED = {
     # the lens centre lies on the sphere (0, 0, -1) r 0.5: the root at t = 0 is below t_min, rays into the ball leave by its far side
     "camera_on_surface": lambda: _placed_flat([("sphere", (0, 0, -1), 0.5, ("lamb", (.7, .3, .3)))], [], (0, 0, -0.5), (1, 0, -0.5), vfov=90),
 }
+
+
+# ---- random worlds that are one reference BVH over spheres (tests/test_bvh_random_host.py, tests/test_gpu_bvh_random.py) ----
+# The BVH megakernel and wave_bvh.h walk a tree of this build's own over the reference's leaf nodes (scene_compile.h): these
+# families give that builder tree shapes the built-in scenes do not have.
+
+def _ok(v, what):
+    if v < 0:
+        raise RuntimeError(f"{what} failed: a table of the reference's capacities is full")
+    return v
+
+
+def _bvh_palette(w, rng, extras):
+    """the materials every sphere of a random BVH world draws from: 12 solid Lambertians, metals of fuzz 0 / 0.3 / 1, glass
+    1.5 and 1 / 1.5 (the last two entries); extras: a checker and a noise Lambertian as well"""
+    L = host.lib()
+    pal = []
+    for _ in range(12):
+        col = _ok(L.mort_add_solid_color(w.ptr, host.vec3(*rng.uniform(0.1, 0.95, 3))), "mort_add_solid_color")
+        pal.append((S.MAT_LAMBERTIAN, _ok(L.mort_add_lambertian(w.ptr, S.TEXTURE_SOLID, col), "mort_add_lambertian")))
+    if extras:
+        c1 = _ok(L.mort_add_solid_color(w.ptr, host.vec3(.2, .3, .1)), "mort_add_solid_color")
+        c2 = _ok(L.mort_add_solid_color(w.ptr, host.vec3(.9, .9, .9)), "mort_add_solid_color")
+        ck = _ok(L.mort_add_checker_texture(w.ptr, 0.4, S.TEXTURE_SOLID, c1, S.TEXTURE_SOLID, c2), "mort_add_checker_texture")
+        pal.append((S.MAT_LAMBERTIAN, _ok(L.mort_add_lambertian(w.ptr, S.TEXTURE_CHECKER, ck), "mort_add_lambertian")))
+        g = S.HostRng(); L.mort_host_rng_init(C.byref(g), 5, 0)
+        nz = _ok(L.mort_add_noise_texture(w.ptr, 3.0, C.byref(g)), "mort_add_noise_texture")
+        pal.append((S.MAT_LAMBERTIAN, _ok(L.mort_add_lambertian(w.ptr, S.TEXTURE_NOISE, nz), "mort_add_lambertian")))
+    for fuzz in (0.0, 0.3, 1.0):
+        pal.append((S.MAT_METAL, _ok(L.mort_add_metal(w.ptr, host.vec3(*rng.uniform(0.5, 0.95, 3)), fuzz), "mort_add_metal")))
+    for ior in (1.5, 1.0 / 1.5):
+        pal.append((S.MAT_DIELECTRIC, _ok(L.mort_add_dielectric(w.ptr, ior), "mort_add_dielectric")))
+    return pal
+
+
+# Each family: (rng, n) -> (spheres, view requests).  A sphere is (centre, radius, material) with material None = drawn from the
+# whole palette, "glass" / "glass_in" = the dielectrics 1.5 and 1 / 1.5, "solid" = anything but glass.  A view request is
+# (target, direction towards the camera, vfov, defocus_angle, share of the frame the spheres should cover) -- _fit_view turns it
+# into a camera -- or ("fixed", lookfrom, lookat, vfov, defocus_angle).  vfov is a whole number of degrees (the reference's camera
+# keeps an int).
+
+def _covered(frm, at, vfov, cen, rad, nx=24, ny=14):
+    """share of an nx x ny grid of pinhole rays of a 16:9 camera that meet one of the spheres (centres cen (n, 3), radii rad)"""
+    frm, at = np.asarray(frm, float), np.asarray(at, float)
+    wv = frm - at; wv /= np.linalg.norm(wv)
+    uv = np.cross((0.0, 1.0, 0.0), wv); uv /= np.linalg.norm(uv)
+    vv = np.cross(wv, uv)
+    h = np.tan(np.radians(vfov) / 2)
+    xs = ((np.arange(nx) + 0.5) / nx * 2 - 1) * h * 16 / 9
+    ys = ((np.arange(ny) + 0.5) / ny * 2 - 1) * h
+    d = (xs[None, :, None] * uv + ys[:, None, None] * vv - wv).reshape(-1, 3)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    oc = cen - frm                                           # (n, 3)
+    b = (d.astype(np.float32) @ oc.T.astype(np.float32))     # (rays, n); the camera is outside every sphere
+    hit = (b > 0) & (b * b > ((oc * oc).sum(1) - rad * rad).astype(np.float32)[None, :])
+    return float(hit.any(1).mean())
+
+
+def _fit_view(sph, ends, target, direction, vfov, defocus, want):
+    """the camera on the ray target + d * direction whose frame the spheres cover most nearly to the share `want`, among
+    distances d from where the field's reach about the target fills a third of the frame's height downwards (ratio 0.64, then
+    0.8 about the best of those), outside
+    every sphere along its motion by a tenth of its radius and a lens' width.  target None: the centre of the sphere nearest the
+    middle of the field -- a sphere's centre as target means that coming closer covers more of the frame."""
+    cen = np.array([0.5 * (np.asarray(c) + np.asarray(e)) for (c, _, _), e in zip(sph, ends)], float)
+    c1 = np.array([c for c, _, _ in sph], float)
+    c2 = np.array(ends, float)
+    rad = np.array([r for _, r, _ in sph], float)
+    if target is None:
+        target = cen[np.argmin(np.abs(cen - 0.5 * (cen.min(0) + cen.max(0))).sum(1))]
+    target = np.asarray(target, float)
+    dirn = np.asarray(direction, float); dirn = dirn / np.linalg.norm(dirn)
+    reach = float((np.linalg.norm(cen - target, axis=1) + rad).max())
+    best = None
+    fine = (48, 27) if len(sph) <= 64 else (16, 9)
+    ab = c2 - c1
+    ab2 = np.maximum((ab * ab).sum(1), 1e-30)
+    for k in list(range(0, 36, 2)) + [-1, 1]:
+        if k in (-1, 1):                                    # the two distances next to the best of the even ones
+            if best is None:
+                continue
+            k += best[2]
+        d = 3.0 * reach / np.tan(np.radians(vfov) / 2) * 0.8 ** k
+        frm = target + d * dirn
+        lens = d * np.tan(np.radians(defocus) / 2) * 1.5
+        t = np.clip(((frm - c1) * ab).sum(1) / ab2, 0, 1)     # distance from the camera to each sphere's path of centres
+        if (np.linalg.norm(c1 + t[:, None] * ab - frm, axis=1) < 1.1 * rad + lens + 1e-3).any():
+            continue
+        cov = _covered(frm, target, vfov, cen, rad, *fine)
+        if best is None or abs(cov - want) < abs(best[0] - want):
+            best = (cov, frm, k if k % 2 == 0 else best[2])
+    assert best is not None, "no camera position outside every sphere"
+    return tuple(float(v) for v in best[1]), tuple(float(v) for v in target), vfov, defocus
+
+
+def _slab_side(n):
+    return max(1.5, 0.55 * float(np.sqrt(n)))
+
+
+def _fam_uniform(rng, n):
+    s = _slab_side(n)
+    sph = [((float(rng.uniform(-s, s)), float(rng.uniform(0, 2)), float(rng.uniform(-s, s))), float(rng.uniform(0.05, 0.9)), None) for _ in range(n)]
+    mid = min(range(n), key=lambda i: abs(sph[i][0][0]) + abs(sph[i][0][2]))
+    views = [(None, (0.0, 0.45, 1.0), 40, 0.0, 0.45),          # the slab from above its edge
+             (sph[mid][0], (1.0, 0.3, 0.35), 65, 0.4, 0.6),               # the sphere nearest the middle from among the others, with a lens
+             (None, (-1.0, -0.03, 0.07), 30, 0.0, 0.5)]        # from outside, at ground level
+    return sph, views
+
+
+def _fam_cluster(rng, n):
+    k = max(1, n // 24)
+    g = max(1, int(np.ceil(np.sqrt(k))))
+    cells = rng.permutation(g * g)[:k]
+    cen = [(1.6 * (int(c) % g - 0.5 * (g - 1)), 0.8 + 0.9 * float(rng.integers(0, 2)), 1.6 * (int(c) // g - 0.5 * (g - 1))) for c in cells]
+    sph = []
+    for i in range(n):
+        c = cen[i % k]
+        p = rng.normal(0.0, 0.22, 3)
+        sph.append(((c[0] + float(p[0]), c[1] + float(p[1]), c[2] + float(p[2])), float(rng.choice([0.02, 0.1, 0.4], p=[0.3, 0.4, 0.3])), None))
+    views = [(None, (0.0, 0.7, 1.0), 38, 0.0, 0.45),           # every cluster
+             (max(sph[0::k], key=lambda q: q[1])[0], (0.55, 0.25, 0.8), 40, 0.0, 0.55),                  # one cluster close up
+             (None, (-1.0, 0.04, 0.12), 24, 0.3, 0.45)]        # along the grid's rows, with a lens
+    return sph, views
+
+
+def _fam_scales(rng, n):
+    s = 2.0 + 1.5 * float(n) ** (1.0 / 3.0)
+    sph = [(tuple(float(v) for v in rng.uniform(-s, s, 3)), float(10.0 ** rng.uniform(-2.5, 1.5)), None) for _ in range(n)]
+    c, r, _ = max(sph, key=lambda q: q[1])
+    views = [(c, (0.1, 0.35, 1.0), 40, 0.0, 0.5),              # the largest sphere and what sticks out of it, from outside every sphere
+             (c, (1.0, 1.02, 1.04), 75, 0.0, 0.6),             # from a corner of the field
+             ("fixed", (c[0] + 0.3 * r, c[1] - 0.2 * r, c[2] + 0.1 * r), (c[0] - r, c[1], c[2] + r), 70, 0.0)]  # INSIDE the largest sphere
+    return sph, views
+
+
+BVH_INTERIOR_VIEW = ("scales", 2)  # the one view that starts inside a sphere on purpose: no background to see
+
+
+def _fam_line(rng, n):
+    x0 = -0.3 * (n - 1)
+    sph = [((x0 + 0.6 * i, 0.0, 0.0), 0.5, None) for i in range(n)]  # radius 0.5 every 0.6: each overlaps its neighbours
+    views = [((x0 + 0.6 * (n // 2), 0.0, 0.0), (0.2, 0.28, 1.0), 40, 0.0, 0.4),   # across the line
+             ((x0 + 0.6 * (n // 4), 0.0, 0.0), (-1.0, 0.012, 0.0015), 2, 0.0, 0.4)]  # along it from far away, a narrow field of view
+    return sph, views
+
+
+def _fam_shells(rng, n):
+    k = max(1, (n + 9) // 10)
+    g = max(1, int(np.ceil(np.sqrt(k))))
+    cen = [(2.9 * (j % g - 0.5 * (g - 1)), 1.3, 2.9 * (j // g - 0.5 * (g - 1))) for j in range(k)]
+    sph = []
+    for i in range(n):
+        j, lvl = i % k, i // k
+        r = 1.25 * 0.8 ** lvl                       # a geometric series inwards from 1.25
+        c = cen[j]
+        if rng.random() < 0.5:                       # nearly concentric: off centre by a few 1e-4 of the radius
+            c = tuple(float(v + d) for v, d in zip(c, rng.uniform(-3e-4, 3e-4, 3) * r))
+        kind = ("glass", "glass_in", "glass", "solid")[lvl % 4] if rng.random() < 0.8 else None
+        sph.append((c, r, kind))
+    views = [(None, (0.0, 0.6, 1.0), 38, 0.0, 0.5),
+             (cen[0], (0.35, 0.3, 0.9), 42, 0.0, 0.55),                   # one nest of shells close up
+             (None, (-1.0, 0.05, 0.09), 26, 0.0, 0.45)]        # along the rows of nests
+    return sph, views
+
+
+def _fam_ties(rng, n):
+    s = _slab_side(n)
+    again = max(2, n // 6) if n >= 3 else 1          # every repeated sphere occurs three times or more: a reference leaf node holds two
+    base = n - again
+    sph = [((float(rng.uniform(-s, s)), float(rng.uniform(0, 2)), float(rng.uniform(-s, s))), float(rng.uniform(0.2, 0.9)), None) for _ in range(base)]
+    few = sorted((int(i) for i in rng.choice(base, size=min(base, 3, max(1, again // 2)), replace=False)), key=lambda i: -sph[i][1])
+    c0 = sph[few[0]][0]
+    for d in range(again):                           # the few spheres that occur again and again:
+        c, r, _ = sph[few[d % len(few)]]
+        sph.append((c, r, None))                     # the same centre and radius, another material drawn
+    sph = [sph[int(i)] for i in rng.permutation(n)]
+    views = [(None, (0.0, 0.45, 1.0), 40, 0.0, 0.45),
+             (c0, (0.4, 0.35, 0.85), 45, 0.0, 0.55),                      # the most repeated sphere close up
+             (None, (1.0, 0.02, -0.4), 50, 0.0, 0.55)]
+    return sph, views
+
+
+_BVH_FAMILY = {"uniform": _fam_uniform, "cluster": _fam_cluster, "scales": _fam_scales, "line": _fam_line, "shells": _fam_shells,
+               "ties": _fam_ties}
+BVH_FAMILIES = tuple(_BVH_FAMILY)
+
+
+def random_bvh_world(rng, n, family, extras=False, emissive=False):
+    """A world that is one reference BVH over n spheres of `family` (see _fam_*), materials from a small shared palette so that
+    1000 spheres stay within the reference's tables; about 15 % of the spheres move (none in `line`).  extras: checker and
+    noise Lambertians in the palette; emissive: the LAST sphere of the n is a light above the field instead.
+    Returns (world, views, light) -- views (lookfrom, lookat, vfov, defocus_angle) for set_view, light = (S.OBJ_SPHERE, index) of
+    the emissive sphere after the BVH build has reordered the spheres (a camera's light_obj_type / light_obj_idx), or None."""
+    L = host.lib()
+    w = host.World()
+    pal = _bvh_palette(w, rng, extras)
+    sph, requests = _BVH_FAMILY[family](rng, n)
+    assert len(sph) == n
+    if emissive:
+        top = max(c[1] + r for c, r, _ in sph[:-1]) if n > 1 else 2.0
+        sph[-1] = ((0.0, top + 2.5, 0.0), 1.5, "light")
+    lst = _ok(L.mort_add_hittable_list(w.ptr, True), "mort_add_hittable_list")
+    ends, motion = [], {}
+    for c, r, kind in sph:
+        if kind == "light":
+            col = _ok(L.mort_add_solid_color(w.ptr, host.vec3(6, 6, 6)), "mort_add_solid_color")
+            mt, mi = S.MAT_DIFFUSE_LIGHT, _ok(L.mort_add_diffuse_light(w.ptr, S.TEXTURE_SOLID, col), "mort_add_diffuse_light")
+        elif kind == "glass":
+            mt, mi = pal[-2]
+        elif kind == "glass_in":
+            mt, mi = pal[-1]
+        elif kind == "solid":
+            mt, mi = pal[int(rng.integers(0, len(pal) - 2))]
+        else:
+            mt, mi = pal[int(rng.integers(0, len(pal)))]
+        if (c, r) in motion:                         # a repeated sphere repeats its motion: an exact duplicate
+            c2 = motion[c, r]
+        elif family != "line" and kind != "light" and rng.random() < 0.15:
+            c2 = tuple(float(a + d) for a, d in zip(c, rng.uniform(-1, 1, 3) * max(r, 0.3)))
+        else:
+            c2 = c
+        motion[c, r] = c2
+        if c2 != c:
+            i = _ok(L.mort_add_moving_sphere(w.ptr, host.vec3(*c), host.vec3(*c2), r, mt, mi, True), "mort_add_moving_sphere")
+        else:
+            i = _ok(L.mort_add_sphere(w.ptr, host.vec3(*c), r, mt, mi, True), "mort_add_sphere")
+        ends.append(c2)
+        if L.mort_list_add(w.ptr, lst, S.OBJ_SPHERE, i) != 0:
+            raise RuntimeError("mort_list_add failed: the list is full")
+    _ok(L.mort_add_bvh(w.ptr, lst, False), "mort_add_bvh")
+    w.c.bvh_mode = True
+    views = [tuple(q[1:]) if q[0] == "fixed" else _fit_view(sph, ends, *q) for q in requests]
+    light = None
+    if emissive:
+        o = w.c.objs
+        idx = [i for i in range(o.num_spheres) if o.host_sphere[i].mat_type == S.MAT_DIFFUSE_LIGHT]
+        assert len(idx) == 1
+        light = (S.OBJ_SPHERE, idx[0])
+    return w, views, light
+
+
+# The catalogue: name -> (family, spheres, seed, extras, emissive).  Two seeds of every family at 2 .. 7 spheres (2: one leaf
+# node, no own tree), 64, 300, the family's size just below and just above the 72 KB limit on the LDS images
+# (mort_hip.hip build_bvh_images; found on the CPU, tests/test_bvh_random_host.py holds the census) and 1000, the list's
+# capacity; seed 1 of the 64s and 300s with checker and noise textures.
+BVH_LIMIT_SIZES = {"uniform": (650, 660), "cluster": (640, 660), "scales": (640, 650), "line": (670, 680), "shells": (640, 660),
+                   "ties": (650, 670)}
+BVH_RANDOM = {f"{fam}_{n}_s{seed}": (fam, n, seed, seed == 1 and n in (64, 300), False)
+              for fam in BVH_FAMILIES for n in (2, 3, 4, 5, 7, 64, 300) + BVH_LIMIT_SIZES[fam] + (1000,) for seed in (0, 1)}
+# worlds whose own tree has no four-wide form (pending-children bound above MORT_OWN4_STACK) although their size is well within
+# the image limit
+BVH_RANDOM.update({f"{fam}_{n}_s{seed}": (fam, n, seed, False, False)
+                   for fam, n, seed in (("ties", 460, 1), ("scales", 430, 1), ("scales", 620, 0), ("scales", 620, 1))})
+# one emissive sphere above a uniform field: the light object of tests that name one
+BVH_RANDOM["uniform_300_lit"] = ("uniform", 300, 2, True, True)
+_bvh_random_built = {}
+
+
+def bvh_random_case(name):
+    """(world, views, light) of a catalogue entry, built once per process; nothing may change the world"""
+    if name not in _bvh_random_built:
+        fam, n, seed, extras, emissive = BVH_RANDOM[name]
+        rng = np.random.default_rng([seed, n, BVH_FAMILIES.index(fam)])
+        _bvh_random_built[name] = random_bvh_world(rng, n, fam, extras=extras, emissive=emissive)
+    return _bvh_random_built[name]
+
+
+def bvh_random_camera(name, k, light=None, width=96):
+    """view k of a catalogue entry as a 96 x 54 camera: 4 spp (9 on every seventh (entry, view) pair), bounce limits from 2 to 20
+    in turn.  light: (type, index) to name as the camera's light object; width: another image width, 16 : 9 as well."""
+    _, views, _ = bvh_random_case(name)
+    i = sorted(BVH_RANDOM).index(name) * 3 + k
+    _, cam = host.build_scene(1, width=width, spp=9 if i % 7 == 0 else 4, depth=(2, 5, 8, 12, 20)[i % 5])
+    if light is not None:
+        cam.light_obj_type, cam.light_obj_idx = light
+    frm, at, vfov, defocus = views[k]
+    set_view(cam, frm, at, vfov=vfov, defocus=defocus)
+    return cam
+
+
+def bvh_random_prediction(name):
+    """What the host will decide for a catalogue entry, from the two device-free debug entries of libmort_hip.so:
+    dict(tree = the nine facts of mort_hip_debug_own_tree, image = those of mort_hip_debug_bvh_images, state = 1 no own tree /
+    2 own tree without a four-wide form / 3 both, fits = mega_bvh_kernel and the wavefront pipeline serve the world,
+    kernel = the family megakernel mode renders it with)"""
+    from mort_amd import hip
+    w, _, _ = bvh_random_case(name)
+    t, im = hip.debug_own_tree(w), hip.debug_bvh_images(w)
+    state = 1 if t["leaves"] < 2 else 2 if t["n4"] == 0 else 3
+    fits = bool(im["fits"])
+    return dict(tree=t, image=im, state=state, fits=fits, kernel="mega_bvh_kernel" if fits else "mega_kernel")
