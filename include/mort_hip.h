@@ -333,6 +333,46 @@ int mort_hip_view_frame_device(mort_view *v, const mort_camera *cam, int mode, v
  * view's configuration does not produce, or before the first frame */
 int mort_hip_view_read(mort_view *v, int what, void *host_out);
 
+/* ---- ray queries: closest hit and occlusion for batches of the caller's own rays.  The render's own traversal
+ * (world::hit over the flattened items, the unified-tree walk with its scan for the rays it does not decide, the transform chains,
+ * the media, the hit record) behind an entry point: picking, line of sight, shadow rays and probes agree with the renderer bit for bit.
+ *
+ * A closest-hit query is the reference's world::hit(ray, interval(0.001, t_max), rec).  t_min is the render's 0.001 -- the only
+ * value world::hit is ever given, built into the box tests -- and NOT a parameter.  t_max is per ray and may be +inf; a root equal to
+ * t_max is accepted (both primitive tests accept it).  !(t_max > 0.001f), NaN included, is a miss and nothing is traced.
+ * Zero-length, non-finite and axis-parallel directions and origins anywhere are legal: the answer is world::hit's.
+ *
+ * states == NULL: every constant medium is passed over, as if its `skip` were set, and no random number is drawn.
+ * states != NULL: one 48-byte XORWOW stream per ray; media are evaluated exactly as world::hit does, drawing from that ray's
+ * stream, which is advanced in place (only d and v[] are written; a ray that draws nothing leaves its stream's bits as they were).
+ *
+ * The record: a miss is all zero.  A sphere's (u, v) are sphere_uv of its outward normal; a medium hit has normal (1, 0, 0),
+ * MORT_HIT_FRONT_FACE and u = v = 0 (the reference leaves u, v indeterminate there).
+ * Occlusion: out[i] = 1 iff a solid is hit in [0.001, t_max]; media never occlude and nothing is drawn: the MORT_HIT_HIT flag of
+ * the closest-hit query with states == NULL.
+ *
+ * Forms as for the stages: the host-buffer form is blocking and stages its data through the context; the _device form takes DEVICE
+ * buffers (16-byte aligned), runs on `stream` (NULL = the context's) and is asynchronous when seconds is NULL; the _host form is
+ * the same per-ray body on `nthreads` host threads and makes no HIP call (flags: MORT_HOST_TREE as for
+ * mort_hip_render_features_host).  `seconds`: HIP-event time of the kernel (host form: wall time of the loop), may be NULL.
+ * n == 0 is MORT_OK and launches nothing.  Outputs must not overlap inputs.  Queries need an uploaded world (else
+ * MORT_ERR_NO_WORLD) but no seeded pixel RNG, ignore the partition, and touch nothing the render keeps across frames (pixel
+ * states, tile-cost cache, counters). ---- */
+typedef struct mort_ray { float origin[3], dir[3], time, t_max; } mort_ray; /* 32 B; the first seven floats are the oracle's ray7 */
+typedef struct mort_hit { float p[3], normal[3], t, u, v; int32_t mat_type, mat_idx; uint32_t flags; } mort_hit; /* 48 B */
+#define MORT_HIT_HIT 1u
+#define MORT_HIT_FRONT_FACE 2u
+#define MORT_HIT_MEDIUM 4u
+MORT_SA(sizeof(mort_ray) == 32 && sizeof(mort_hit) == 48, "ray query layout");
+int mort_hip_query_closest(mort_ctx *ctx, size_t n, const mort_ray *rays, mort_rng_state *states, mort_hit *out, double *seconds);
+int mort_hip_query_closest_device(mort_ctx *ctx, size_t n, const void *d_rays, void *d_states, void *d_out, void *stream, double *seconds);
+int mort_hip_query_closest_host(const mort_world *world, size_t n, const mort_ray *rays, mort_rng_state *states, int nthreads, int flags,
+                                mort_hit *out, double *seconds);
+int mort_hip_query_occluded(mort_ctx *ctx, size_t n, const mort_ray *rays, uint8_t *out, double *seconds);
+int mort_hip_query_occluded_device(mort_ctx *ctx, size_t n, const void *d_rays, void *d_out, void *stream, double *seconds);
+int mort_hip_query_occluded_host(const mort_world *world, size_t n, const mort_ray *rays, int nthreads, int flags, uint8_t *out,
+                                 double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

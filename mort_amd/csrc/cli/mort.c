@@ -12,6 +12,7 @@
  *                   [--denoise] [--features-out PREFIX]   first-hit features + a-trous denoiser on the last frame (single GPU / host)
  *                   [--temporal] [--variance-out F]       temporal accumulation across frames with reprojection (single GPU / host)
  *                   [--svgf]                              variance-guided a-trous filter (SVGF) on the last frame (single GPU / host)
+ *                   [--pick X,Y]                          no render: the closest-hit record under pixel (X, Y) as one JSON line
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -33,6 +34,12 @@
  * filter is fed back, so the files are the same); without it only the last frame does, the ones before are plain renders.  The
  * files and the JSON keys are those of the last frame as above, the seconds the device times of the stages (a still camera skips
  * the feature pass: "temporal_seconds" counts the passes that ran).
+ *
+ * --pick X,Y (single GPU / host; row 0 = bottom row, as every buffer): renders nothing; one closest-hit query (mort_hip_query_closest,
+ * or mort_hip_query_closest_host under --mode host, which needs no GPU) for the feature pass's primary ray of that pixel -- lens
+ * centre through the pixel centre, time 0.5, t_max = inf, no streams, so media are passed over -- printed as one JSON line:
+ * pick, hit, t, p, normal, u, v, mat_type, mat_idx, front_face, medium, mode, seconds.  Floats are printed with nine significant
+ * digits, which identify a float32; a non-finite one as NaN / Infinity / -Infinity.
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -76,7 +83,7 @@ static int usage(void) {
     printf("Usage: mort <number_between_1_and_10> [--width W] [--aspect A] [--spp N] [--depth D] [--seed S] [--frames N] "
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
-           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf]\n");
+           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y]\n");
     return -1;
 }
 
@@ -100,6 +107,35 @@ static unsigned char *load_earth(const char *path, const char *argv0, int *w, in
     return NULL;
 }
 
+/* a float32 as JSON: nine significant digits, which identify it; NaN / Infinity / -Infinity as Python's json module reads and writes them */
+static void print_f32(float v) {
+    if (v != v) printf("NaN");
+    else if (v - v != 0.0f) printf(v > 0 ? "Infinity" : "-Infinity");
+    else { /* always with a fraction or an exponent, so that a reader keeps it a float: -0.0 stays negative */
+        char b[32];
+        snprintf(b, sizeof b, "%.9g", (double)v);
+        printf("%s%s", b, strpbrk(b, ".e") ? "" : ".0");
+    }
+}
+static void print_v3(const char *key, const float *v) {
+    printf(", \"%s\": [", key);
+    for (int k = 0; k < 3; k++) { if (k) printf(", "); print_f32(v[k]); }
+    printf("]");
+}
+
+/* --pick: the feature pass's primary ray of pixel (x, y) (dev_features.h feat_pixel: lens centre through the pixel centre, time 0.5) */
+static mort_ray pick_ray(const mort_camera *cam, int x, int y) {
+    mort_ray r;
+    for (int k = 0; k < 3; k++) {
+        const float sample = (cam->pixel00_loc.e[k] + (float)x * cam->pixel_delta_u.e[k]) + (float)y * cam->pixel_delta_v.e[k];
+        r.origin[k] = cam->center.e[k];
+        r.dir[k] = sample - cam->center.e[k];
+    }
+    r.time = 0.5f;
+    r.t_max = 1.0f / 0.0f;
+    return r;
+}
+
 /* input() before frame f (mort.cu:49-91,94): the f-th character of --keys held down, the --mouse delta dragged */
 static void frame_input(mort_camera *cam, const char *keys, int f, int mdx, int mdy) {
     int k = 0;
@@ -120,6 +156,7 @@ int main(int argc, char **argv) {
     const char *out = NULL, *dump = NULL, *sin = NULL, *sout = NULL, *earth = NULL, *keys = NULL, *feat_out = NULL, *var_out = NULL;
     int denoise = 0, temporal = 0, svgf = 0;
     int mouse_dx = 0, mouse_dy = 0;
+    int pick = 0, pick_x = 0, pick_y = 0;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -157,6 +194,7 @@ int main(int argc, char **argv) {
         else if (strcmp(argv[i], "--temporal") == 0) temporal = 1;
         else if (ARG("--variance-out")) var_out = argv[++i];
         else if (strcmp(argv[i], "--svgf") == 0) svgf = 1;
+        else if (ARG("--pick")) { pick = 1; if (sscanf(argv[++i], "%d,%d", &pick_x, &pick_y) != 2) { fprintf(stderr, "--pick X,Y\n"); return -1; } }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -167,6 +205,7 @@ int main(int argc, char **argv) {
     if (gpus > 1 && svgf) { fprintf(stderr, "--svgf is a single-GPU option\n"); return -1; }
     if (svgf && denoise) { fprintf(stderr, "--svgf and --denoise exclude each other\n"); return -1; }
     if (var_out && !temporal) { fprintf(stderr, "--variance-out needs --temporal\n"); return -1; }
+    if (pick && gpus > 1) { fprintf(stderr, "--pick is a single-GPU option\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;
@@ -194,6 +233,33 @@ int main(int argc, char **argv) {
     const int W = cam.image_width, H = cam.image_height;
     const size_t npx = (size_t)W * H;
     const int eff = mort_camera_effective_spp(&cam);
+
+    if (pick) { /* ---- no render: one closest-hit query ---- */
+        if (pick_x < 0 || pick_x >= W || pick_y < 0 || pick_y >= H) { fprintf(stderr, "--pick %d,%d is outside the %dx%d image\n", pick_x, pick_y, W, H); return -1; }
+        const mort_ray ray = pick_ray(&cam, pick_x, pick_y);
+        mort_hit h;
+        double sec = 0;
+        int pst;
+        if (host_mode) {
+            if ((pst = mort_hip_query_closest_host(&world, 1, &ray, NULL, 1, tree ? MORT_HOST_TREE : 0, &h, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_closest_host");
+        } else {
+            mort_ctx *pctx = NULL;
+            if ((pst = mort_hip_init(device, &pctx)) != MORT_OK) die(NULL, pst, "mort_hip_init");
+            if ((pst = mort_hip_upload_world(pctx, &world)) != MORT_OK) die(pctx, pst, "mort_hip_upload_world");
+            if ((pst = mort_hip_query_closest(pctx, 1, &ray, NULL, &h, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_closest");
+            mort_hip_shutdown(pctx);
+        }
+        printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"pick\": [%d, %d], \"hit\": %d, \"t\": ", scene, W, H, pick_x, pick_y, (h.flags & MORT_HIT_HIT) ? 1 : 0);
+        print_f32(h.t);
+        print_v3("p", h.p); print_v3("normal", h.normal);
+        printf(", \"u\": "); print_f32(h.u);
+        printf(", \"v\": "); print_f32(h.v);
+        printf(", \"mat_type\": %d, \"mat_idx\": %d, \"front_face\": %d, \"medium\": %d, \"mode\": \"%s\", \"seconds\": %.6f}\n", (int)h.mat_type, (int)h.mat_idx,
+               (h.flags & MORT_HIT_FRONT_FACE) ? 1 : 0, (h.flags & MORT_HIT_MEDIUM) ? 1 : 0, host_mode ? "host" : "mega", sec);
+        mort_world_free(&world);
+        free(texels);
+        return 0;
+    }
 
     /* ---- ranks: fork before anything touches the GPU ---- */
     int rank = 0;

@@ -189,9 +189,10 @@ DEV void gen_apply_t(const uint32_t *ranks, int n_spheres, float t, uint32_t e, 
 }
 
 /* world::hit's scan over the solids as the reference runs it (world.cuh:122-168 through the flattened items): the exact
- * answer for the rays the tree walk does not decide */
-DEV void gen_scan_solids(const DScene &sc, int first_medium, const int *chains, int n_chains, const Ray &r, float &closest, uint32_t &best) {
-    closest = __builtin_inff();
+ * answer for the rays the tree walk does not decide.  closest0: the far end of the interval, +inf for a path segment
+ * (gen_scan_solids), a caller's t_max for a ray query (dev_query.h) */
+DEV void gen_scan_solids_from(const DScene &sc, int first_medium, const int *chains, int n_chains, const Ray &r, float closest0, float &closest, uint32_t &best) {
+    closest = closest0;
     Best b; b.kind = HIT_NONE; b.t = 0; b.prim = 0; b.chain_first = 0; b.chain_count = 0;
     for (int i = 0; i < first_medium; i++) {
         const DItem it = sc.items[i];
@@ -205,6 +206,9 @@ DEV void gen_scan_solids(const DScene &sc, int first_medium, const int *chains, 
             for (int k = 1; k < n_chains; k++) if (chains[2 * k] == b.chain_first && chains[2 * k + 1] == b.chain_count) cid = (uint32_t)k;
         best = GENT(b.kind == HIT_QUAD ? 1u : 0u, cid, (uint32_t)b.prim);
     }
+}
+DEV void gen_scan_solids(const DScene &sc, int first_medium, const int *chains, int n_chains, const Ray &r, float &closest, uint32_t &best) {
+    gen_scan_solids_from(sc, first_medium, chains, n_chains, r, __builtin_inff(), closest, best);
 }
 
 /* the constant media, after every solid, in scan order, with the solids' closest_so_far
@@ -248,12 +252,16 @@ DEV Best gen_decode_best(const DScene &sc, const int *chains, uint32_t best, flo
 }
 
 /* ---- the tree walk over the solids as ONE lane runs it, its pending far children at stack[k * stride], k < MORT_OWN_STACK (a
- * local array with stride 1, or the lane's column of an LDS array).  flags: GFL_REF for a ray the walk does not decide ---- */
-DEV void gen_walk_solids(const DScene &sc, const GenWalk &gw, const Ray &ray, unsigned short *stack, int stride, float &closest, uint32_t &best, int &flags) {
+ * local array with stride 1, or the lane's column of an LDS array).  flags: GFL_REF for a ray the walk does not decide.
+ * closest0: where closest_so_far starts -- +inf for a path segment (gen_walk_solids), a caller's t_max for a ray query.
+ * ANY: return at the first accepted root (an occlusion query); best is then some primitive hit in the interval, not the closest ---- */
+template <bool ANY>
+DEV void gen_walk_solids_from(const DScene &sc, const GenWalk &gw, const Ray &ray, unsigned short *stack, int stride, float closest0, float &closest, uint32_t &best,
+                              int &flags) {
     GenRay gr;
     const bool ordinary = gen_ray_setup(ray, gw.gx, gw.gy, gw.gz, gw.gR, gw.mnear, gw.kmin, gr);
     const float ray_a = vlen2(ray.d);
-    closest = __builtin_inff();
+    closest = closest0;
     best = GBEST_NONE;
     flags = ordinary ? 0 : GFL_REF;
     if (ordinary && gw.root != 0xffffu) {
@@ -262,8 +270,10 @@ DEV void gen_walk_solids(const DScene &sc, const GenWalk &gw, const Ray &ray, un
         for (;;) {
             if (cur & 0x8000u) {
                 uint32_t pos = GLEAF_FIRST(cur);
-                for (int cnt = (int)GLEAF_COUNT(cur); cnt > 0; cnt--, pos++)
+                for (int cnt = (int)GLEAF_COUNT(cur); cnt > 0; cnt--, pos++) {
                     gen_leaf_test(sc, gw.chains, gw.ranks, gw.n_spheres, sc.spheres, sc.quads, gw.entries[pos], ray, ray_a, closest, best, flags);
+                    if (ANY && best != GBEST_NONE) return;
+                }
                 if (sp == 0) break;
                 cur = stack[--sp * stride];
                 continue;
@@ -283,6 +293,9 @@ DEV void gen_walk_solids(const DScene &sc, const GenWalk &gw, const Ray &ray, un
             } else cur = m0 ? nd.c1 : nd.c0;
         }
     }
+}
+DEV void gen_walk_solids(const DScene &sc, const GenWalk &gw, const Ray &ray, unsigned short *stack, int stride, float &closest, uint32_t &best, int &flags) {
+    gen_walk_solids_from<false>(sc, gw, ray, stack, stride, __builtin_inff(), closest, best, flags);
 }
 
 /* ---- the whole closest-hit search as ONE lane runs it (host loop, CPU tests): the same steps the kernels schedule

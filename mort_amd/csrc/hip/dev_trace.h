@@ -224,8 +224,12 @@ DEV void run_quads(const DScene &sc, const Ray &rw, int first, int count, int cf
     }
 }
 
-/* ---- bvh::hit, threaded (objects.cuh:664-723) ---- */
-DEV void run_bvh(const DScene &sc, const Ray &r, int first, int count, float t_min, float &closest, Best &best) {
+/* ---- bvh::hit, threaded (objects.cuh:664-723) ----
+ * NAN_CLOSEST: once a NaN root has been accepted (a zero-length or NaN direction: a caller's ray, dev_query.h), closest_so_far is NaN and
+ * aabb::hit reports every box as hit -- `t1 < t_max` never lowers a NaN t_max and `t_max <= t_min` is false -- where slab_hit's fminf drops
+ * the NaN and prunes as if nothing had been hit yet.  The ray queries ask for the reference's answer there too; the render's walk is as it was */
+template <bool NAN_CLOSEST>
+DEV void run_bvh_t(const DScene &sc, const Ray &r, int first, int count, float t_min, float &closest, Best &best) {
     const SlabRay sr = slab_ray(r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z);
     const float a = vlen2(r.d);
     const int end = first + count;
@@ -234,7 +238,7 @@ DEV void run_bvh(const DScene &sc, const Ray &r, int first, int count, float t_m
         const DBvhNode nd = sc.nodes[node];
         const bool leaf = nd.skip >> 31;
         const int skip = (int)(nd.skip & 0x7fffffffu);
-        if (!slab_hit(nd, sr, closest)) { node = skip; continue; } /* t_min = 0.001f: the only value world::hit passes */
+        if (!((NAN_CLOSEST && closest != closest) || slab_hit(nd, sr, closest))) { node = skip; continue; } /* t_min = 0.001f: the only value world::hit passes */
         if (!leaf) { node = node + 1; continue; }
         const uint32_t pa = nd.prims & 0xffffu, pb = nd.prims >> 16;
 #pragma unroll
@@ -256,6 +260,9 @@ DEV void run_bvh(const DScene &sc, const Ray &r, int first, int count, float t_m
         }
         node = skip;
     }
+}
+DEV void run_bvh(const DScene &sc, const Ray &r, int first, int count, float t_min, float &closest, Best &best) {
+    run_bvh_t<false>(sc, r, first, count, t_min, closest, best);
 }
 
 /* closest t over a medium's boundary sub-items in [t_min, t_max] (hitDispatch of

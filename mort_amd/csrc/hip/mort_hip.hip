@@ -1077,6 +1077,23 @@ extern "C" int mort_hip_debug_bvh_images(const mort_world *w, int *out) {
     return MORT_OK;
 }
 
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): where the unified tree of a world may be walked from -- out[0] 1 if
+ * the world has a unified tree (else the rest is 0), [1..3] the low corner of its solids' box, [4..6] the high corner, [7] the reach:
+ * a ray origin o is walked iff lo[k] - reach <= o[k] <= hi[k] + reach on every axis (camera_in_reach; per ray in dev_query.h). */
+extern "C" int mort_hip_debug_gen_reach(const mort_world *w, float *out) {
+    if (!w || !out) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    if (!o.g_ok) return MORT_OK;
+    out[0] = 1;
+    for (int k = 0; k < 3; k++) { out[1 + k] = o.g_lo[k]; out[4 + k] = o.g_hi[k]; }
+    out[7] = o.g_reach;
+    return MORT_OK;
+}
+
 /* diagnostic (not in include/mort_hip.h; host only, no HIP call): the boxes of the occupied children of the world's four-wide tree, six
  * floats each (xmin, xmax, ymin, ymax, zmin, zmax), at most max_boxes of them.  Returns how many there are, or a negative status. */
 extern "C" int mort_hip_debug_own_tree4_boxes(const mort_world *w, float *out, size_t max_boxes) {

@@ -33,6 +33,8 @@ EXPORTS = [
     "mort_hip_svgf_defaults", "mort_hip_svgf", "mort_hip_svgf_device", "mort_hip_svgf_host",
     "mort_hip_view_defaults", "mort_hip_view_check_params", "mort_hip_view_create", "mort_hip_view_destroy", "mort_hip_view_reset",
     "mort_hip_view_frame", "mort_hip_view_frame_device", "mort_hip_view_read",
+    "mort_hip_query_closest", "mort_hip_query_closest_device", "mort_hip_query_closest_host",
+    "mort_hip_query_occluded", "mort_hip_query_occluded_device", "mort_hip_query_occluded_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -40,6 +42,12 @@ FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
 VIEW_BUFFERS = {"raw_accum": (0, 3), "accum": (1, 3), "filtered": (2, 3), "variance": (3, 1), "albedo": (4, 3), "normal": (5, 3),
                 "depth": (6, 1), "history": (7, TEMPORAL_HISTORY_FLOATS)}
 HOST_TREE = 1
+# ray queries (mort_ray, mort_hit of include/mort_hip.h)
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("dir", "<f4", (3,)), ("time", "<f4"), ("t_max", "<f4")])
+HIT_DTYPE = np.dtype([("p", "<f4", (3,)), ("normal", "<f4", (3,)), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("mat_type", "<i4"),
+                      ("mat_idx", "<i4"), ("flags", "<u4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48
+HIT_HIT, HIT_FRONT_FACE, HIT_MEDIUM = 1, 2, 4
 
 
 class Partition(C.Structure):
@@ -199,6 +207,13 @@ def lib():
         L.mort_hip_view_frame.argtypes = [view, cp, C.c_int, vp, C.POINTER(ViewStats)]; L.mort_hip_view_frame.restype = C.c_int
         L.mort_hip_view_frame_device.argtypes = [view, cp, C.c_int, vp, vp, C.POINTER(ViewStats)]; L.mort_hip_view_frame_device.restype = C.c_int
         L.mort_hip_view_read.argtypes = [view, C.c_int, vp]; L.mort_hip_view_read.restype = C.c_int
+        wd, sz = C.POINTER(S.World), C.c_size_t
+        L.mort_hip_query_closest.argtypes = [ctx, sz, vp, vp, vp, dp]; L.mort_hip_query_closest.restype = C.c_int
+        L.mort_hip_query_closest_device.argtypes = [ctx, sz, vp, vp, vp, vp, dp]; L.mort_hip_query_closest_device.restype = C.c_int
+        L.mort_hip_query_closest_host.argtypes = [wd, sz, vp, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_query_closest_host.restype = C.c_int
+        L.mort_hip_query_occluded.argtypes = [ctx, sz, vp, vp, dp]; L.mort_hip_query_occluded.restype = C.c_int
+        L.mort_hip_query_occluded_device.argtypes = [ctx, sz, vp, vp, vp, dp]; L.mort_hip_query_occluded_device.restype = C.c_int
+        L.mort_hip_query_occluded_host.argtypes = [wd, sz, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_query_occluded_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -401,6 +416,47 @@ class Context:
                                              C.byref(sec) if sync else None), "mort_hip_svgf_device")
         return sec.value if sync else None
 
+    def query_closest(self, rays, states=None):
+        """Closest hit of every ray on the GPU (mort_hip_query_closest): rays RAY_DTYPE (n,) or float32 (n, 8); states None = media
+        passed over, else (n,) 48-byte XORWOW streams, advanced IN PLACE.  dict(hits HIT_DTYPE (n,), seconds)."""
+        rays, st8 = _query_rays(rays), _query_states(states, rays)
+        hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_query_closest(self._h, rays.shape[0], rays.ctypes.data, _ptr(st8), hits.ctypes.data, C.byref(sec)),
+                  "mort_hip_query_closest")
+        return dict(hits=hits, seconds=sec.value)
+
+    def query_occluded(self, rays):
+        """Is a solid hit in [0.001, t_max], per ray, on the GPU (mort_hip_query_occluded): dict(occluded uint8 (n,), seconds)."""
+        rays = _query_rays(rays)
+        out = np.zeros(rays.shape[0], dtype=np.uint8)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_query_occluded(self._h, rays.shape[0], rays.ctypes.data, out.ctypes.data, C.byref(sec)),
+                  "mort_hip_query_occluded")
+        return dict(occluded=out, seconds=sec.value)
+
+    def query_closest_device(self, rays, hits, states=None, sync=False):
+        """The closest-hit query on torch tensors on this context's device, on the current torch stream: rays float32 of 8 n
+        elements, hits of 48 n bytes (any dtype), states None or 48 n bytes, advanced in place.  Asynchronous unless sync (then
+        returns the device seconds) or torch runs on its legacy default stream."""
+        import torch
+        n = _check_query_tensors(torch, rays, ((hits, 48), (states, 48)))
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, rays.device, sync)
+        self._chk(lib().mort_hip_query_closest_device(self._h, n, rays.data_ptr(), states.data_ptr() if states is not None else None,
+                                                      hits.data_ptr(), stream, C.byref(sec) if sync else None), "mort_hip_query_closest_device")
+        return sec.value if sync else None
+
+    def query_occluded_device(self, rays, occluded, sync=False):
+        """The occlusion query on torch tensors: rays as for query_closest_device, occluded uint8 of n elements."""
+        import torch
+        n = _check_query_tensors(torch, rays, ((occluded, 1),))
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, rays.device, sync)
+        self._chk(lib().mort_hip_query_occluded_device(self._h, n, rays.data_ptr(), occluded.data_ptr(), stream, C.byref(sec) if sync else None),
+                  "mort_hip_query_occluded_device")
+        return sec.value if sync else None
+
     def calib_valu(self, waves_per_simd, kind=0):
         """Shader cycles one SIMD needs per wave64 VALU instruction at `waves_per_simd` resident waves (include/mort_hip.h)."""
         r = CalibValu()
@@ -527,6 +583,69 @@ def debug_bvh_images(world):
     if st != 0:
         raise MortHipError(st, "mort_hip_debug_bvh_images")
     return dict(zip(("sphere_bvh", "four_wide", "fast_bytes", "trav_bytes", "limit", "fits", "stack_levels", "wide_fits"), list(out)))
+
+
+def debug_gen_reach(world):
+    """mort_hip_debug_gen_reach (host only): dict(tree, lo (3,), hi (3,), reach) -- whether the world has a unified tree, the box
+    of its solids and how far from that box a ray origin may lie for the walk (float32, as the kernels compare them)."""
+    fn = lib().mort_hip_debug_gen_reach
+    fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.c_void_p]
+    out = np.zeros(8, dtype=np.float32)
+    st = fn(C.cast(world.ptr, C.c_void_p), out.ctypes.data)
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_gen_reach")
+    return dict(tree=bool(out[0]), lo=out[1:4].copy(), hi=out[4:7].copy(), reach=out[7])
+
+
+def _query_rays(rays):
+    """rays as a contiguous RAY_DTYPE (n,) array: RAY_DTYPE already, or float32 (n, 8) = origin, direction, time, t_max"""
+    rays = np.asarray(rays)
+    if rays.dtype != RAY_DTYPE:
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8).view(RAY_DTYPE).reshape(-1)
+    return np.ascontiguousarray(rays).reshape(-1)
+
+
+def _query_states(states, rays):
+    """the caller's streams as the bytes the library advances in place (no copy), or None"""
+    if states is None:
+        return None
+    if not (isinstance(states, np.ndarray) and states.flags.c_contiguous and states.flags.writeable and states.nbytes == 48 * rays.shape[0]):
+        raise ValueError(f"expected a contiguous writeable array of {rays.shape[0]} 48-byte streams")
+    return states
+
+
+def _check_query_tensors(torch, rays, outs):
+    if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8 or rays.device.type != "cuda":
+        raise ValueError("expected a contiguous float32 tensor of 8 floats per ray on the GPU")
+    n = rays.numel() // 8
+    for t, size in outs:
+        if t is not None and (not t.is_contiguous() or t.numel() * t.element_size() != size * n or t.device != rays.device):
+            raise ValueError(f"expected a contiguous tensor of {size * n} bytes on {rays.device}")
+    return n
+
+
+def query_closest_host(world, rays, states=None, tree=False, nthreads=1):
+    """The closest-hit query as a host loop (mort_hip_query_closest_host), no GPU: arguments and result as Context.query_closest."""
+    rays, st8 = _query_rays(rays), _query_states(states, _query_rays(rays))
+    hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_query_closest_host(world.ptr, rays.shape[0], rays.ctypes.data, _ptr(st8), nthreads, HOST_TREE if tree else 0,
+                                           hits.ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_query_closest_host")
+    return dict(hits=hits, seconds=sec.value)
+
+
+def query_occluded_host(world, rays, tree=False, nthreads=1):
+    """The occlusion query as a host loop (mort_hip_query_occluded_host), no GPU: result as Context.query_occluded."""
+    rays = _query_rays(rays)
+    out = np.zeros(rays.shape[0], dtype=np.uint8)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_query_occluded_host(world.ptr, rays.shape[0], rays.ctypes.data, nthreads, HOST_TREE if tree else 0,
+                                            out.ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_query_occluded_host")
+    return dict(occluded=out, seconds=sec.value)
 
 
 def _feature_arrays(W, H):

@@ -8,7 +8,8 @@ graph), waves per SIMD that allocation allows, spilled registers, private (scrat
   * one of the state-machine megakernels (mega_bvh_kernel, mega_gen_kernel) touches private memory beyond a callee frame or spills
     a vector register: their state loops are built to run without scratch.  The 1024-thread variants are compiled
     for 128 VGPRs (four waves per SIMD): mega_bvh_kernel<1024> may keep at most 32 registers / 128 B in private memory (rarely
-    touched per-pixel values, read and written in the shade step only), mega_gen_kernel<1024> is a measurement build.
+    touched per-pixel values, read and written in the shade step only), mega_gen_kernel<1024> is a measurement build, or
+  * a ray-query kernel (query_closest_kernel, query_occluded_kernel) spills or uses any private memory.
 """
 import os, re, subprocess, sys, tempfile, shutil
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
@@ -37,7 +38,7 @@ finally:
     shutil.rmtree(tmp, ignore_errors=True)
 bad = []
 print(f"{'kernel':58s} {'wg':>5s} {'vgpr':>5s} {'waves/SIMD':>10s} {'v-spill':>7s} {'s-spill':>7s} {'private B':>9s} {'static LDS':>10s}")
-OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_")
+OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_")
 for r in sorted(rows, key=lambda r: r["name"]):
     if not any(o in r["name"] for o in OWN) and "--all" not in sys.argv:
         continue  # rocPRIM's sort kernels (tile_sort.hip): listed with --all
@@ -51,6 +52,8 @@ for r in sorted(rows, key=lambda r: r["name"]):
         wide = r["name"].startswith("mega_bvh_kernel<1024")
         if (r["vspill"] > (32 if wide else 0)) or r["private"] > 128:
             bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (state loop must run without scratch)")
+    if r["name"].startswith("query_") and (r["vspill"] or r["private"]):
+        bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the ray queries run without scratch)")
 if bad:
     print("\n".join("RESOURCE CHECK FAILED: " + b for b in bad), file=sys.stderr)
     sys.exit(1 if check else 0)
