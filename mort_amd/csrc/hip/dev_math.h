@@ -119,4 +119,82 @@ DEV Onb onb_from_w(V3 w) { /* onb.cuh:41-51 */
 }
 DEV V3 onb_local(const Onb &o, V3 a) { return vadd(vadd(vscale(a.x, o.u), vscale(a.y, o.v)), vscale(a.z, o.w)); }
 
+/* ---- short forms of x / a and sqrtf(x): exact by construction, on a guarded range only ----
+ *
+ * hipcc expands an fp32 division (denormals on) into
+ *     a' = v_div_scale(a), x' = v_div_scale(x), r0 = v_rcp_f32(a'), e = fma(-a', r0, 1), r = fma(e, r0, r0),
+ *     q0 = x' * r, e1 = fma(-a', q0, x'), q1 = fma(e1, r, q0), e2 = fma(-a', q1, x'), q = v_div_fmas(e2, r, q1), v_div_fixup(q, a, x)
+ * and sqrtf into
+ *     x' = x < 2^-96 ? x * 2^32 : x, s = v_sqrt_f32(x'), dn / up = s with the integer pattern - 1 / + 1,
+ *     s = dn if fma(-dn, s, x') <= 0, s = up if fma(-up, s, x') > 0, the unscale by 2^-16, x itself for a zero or +infinity.
+ * The short forms are these sequences without the steps that are identities on the guarded range:
+ *   - v_div_scale returns its operand and leaves VCC clear (v_div_fmas is then a plain fma) unless an operand is zero, the denominator
+ *     is denormal, 1 / a or x / a is denormal, exponent(x) - exponent(a) >= 96 or the numerator's biased exponent is <= 23;
+ *     v_div_fixup returns the quotient it is given unless an operand is zero, infinite or NaN or the quotient leaves the normal range.
+ *     With 2^-40 <= a <= 2^40 (div_den_ok) and 2^-85 <= |x| < 2^56 (div_num_ok bounds |x| from above) the exponent difference lies in
+ *     [-125, 95] and none of these holds: the quotient is the compiler's, bit for bit, r prepared once per denominator;
+ *   - a numerator below 2^-85 (zero and denormals included) is NOT exact here (a zero may lose its sign), but its quotient is finite
+ *     and below 2^-44 in magnitude in both forms: a caller that rejects everything below a threshold such as t_min = 0.001 needs no guard;
+ *   - 2^-96 <= x < 2^100 (sqrt_arg_ok) is neither scaled nor a zero or an infinity.
+ * The compare forms are integer range checks of the bit pattern: NaN, infinities, negative values and both zeros fall outside.
+ * Everything outside the guards takes the plain operators.  The host side of DEV is the plain operators throughout.
+ * (div_num_ok states the numerator's bound for the tests of div_by alone; the leaf step bounds its numerators through half_b^2 < 2^110 and the
+ * discriminant's range instead, mega_bvh.h sphere_short_ok, which the device test of sphere_hit_root_fast covers.)
+ * tests/test_exact_forms_host.py runs the *_model functions (the same fma sequences with the hardware's seed as a parameter) against
+ * gcc's / and sqrtf; tests/test_gpu_exact_forms.py runs the device forms against the device's / and sqrtf, boundaries included. */
+#define MORT_DIV_DEN_LO 0x2b800000u /* 2^-40 */
+#define MORT_DIV_DEN_HI 0x53800000u /* 2^40 */
+#define MORT_DIV_NUM_HI 0x5b800000u /* 2^56 */
+#define MORT_SQRT_LO 0x0f800000u    /* 2^-96 */
+#define MORT_SQRT_HI 0x71800000u    /* 2^100 */
+DEV bool div_den_ok(float a) { return __builtin_bit_cast(uint32_t, a) - MORT_DIV_DEN_LO <= MORT_DIV_DEN_HI - MORT_DIV_DEN_LO; }
+DEV bool div_num_ok(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7fffffffu) < MORT_DIV_NUM_HI; }
+DEV bool sqrt_arg_ok(float x) { return __builtin_bit_cast(uint32_t, x) - MORT_SQRT_LO < MORT_SQRT_HI - MORT_SQRT_LO; }
+
+/* the models: seed r0 = the hardware's v_rcp_f32(a), s = v_sqrt_f32(x) */
+DEV float div_by_model_prepare(float a, float r0) { const float e = __builtin_fmaf(-a, r0, 1.0f); return __builtin_fmaf(e, r0, r0); }
+DEV float div_by_model(float x, float a, float r) {
+    const float q0 = x * r;
+    const float e1 = __builtin_fmaf(-a, q0, x);
+    const float q1 = __builtin_fmaf(e1, r, q0);
+    const float e2 = __builtin_fmaf(-a, q1, x);
+    return __builtin_fmaf(e2, r, q1);
+}
+DEV float sqrt_ord_model(float x, float s) {
+    const float dn = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) - 1u);
+    const float up = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) + 1u);
+    const float vp = __builtin_fmaf(-dn, s, x), vs = __builtin_fmaf(-up, s, x);
+    float t = (vp <= 0.0f) ? dn : s;
+    t = (vs > 0.0f) ? up : t;
+    return t;
+}
+
+/* a denominator prepared once: ok = div_den_ok(a); r is meaningful only then */
+struct DivBy { float a, r; bool ok; };
+DEV DivBy div_prepare(float a) {
+    DivBy d; d.a = a; d.ok = div_den_ok(a);
+#if defined(__HIP_DEVICE_COMPILE__)
+    d.r = div_by_model_prepare(a, __builtin_amdgcn_rcpf(a));
+#else
+    d.r = 0.0f;
+#endif
+    return d;
+}
+/* x / d.a for d.ok and div_num_ok(x) (see above for numerators below 2^-85) */
+DEV float div_by(float x, const DivBy &d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return div_by_model(x, d.a, d.r);
+#else
+    return x / d.a;
+#endif
+}
+/* sqrtf(x) for sqrt_arg_ok(x) */
+DEV float sqrt_ord(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return sqrt_ord_model(x, __builtin_amdgcn_sqrtf(x));
+#else
+    return mort_sqrtf(x);
+#endif
+}
+
 #endif

@@ -44,6 +44,10 @@
  *
  *  - Hit record rebuilt only for the winner; sphere uv (acosf/atan2f) only when
  *    the material's texture reads it.
+ *
+ *  - Leaf step: sphere::hit's square root and its divisions by the ray's `a` in the compiler's own instruction sequences minus the steps that are
+ *    identities for ordinary values (range scaling, fix-up, class check), one reciprocal per segment for all of them (dev_math.h sqrt_ord, DivBy;
+ *    sphere_hit_root_fast below).  Guarded: whatever lies outside the range takes the plain operators.  178 -> 143 vector instructions per step.
  */
 #ifndef MORT_MEGA_BVH_H
 #define MORT_MEGA_BVH_H
@@ -176,6 +180,59 @@ DEV float sphere_hit_root(const DSphere &s, const Ray &r, float a, float t_min, 
     const float half_b = vdot(oc, r.d);
     const float c = vlen2(oc) - s.radius * s.radius;
     const float discriminant = half_b * half_b - a * c;
+    if (discriminant < 0) return -1.0f;
+    const float sqrtd = mort_sqrtf(discriminant);
+    float root = (-half_b - sqrtd) / a;
+    if (root < t_min || t_max < root) {
+        root = (-half_b + sqrtd) / a;
+        if (root < t_min || t_max < root) return -1.0f;
+    }
+    return root;
+}
+
+/* The leaf step's form of sphere_hit_root: the same value, bit for bit, with the root and the two divisions by the ray's `a` in their
+ * short forms (dev_math.h sqrt_ord, div_by; `dv` = div_prepare(a), once per leaf step) wherever the guards hold, and the generic code
+ * above, unchanged, for everything else -- a negative discriminant (the common miss), NaN, zeros, infinities, far-out scales:
+ *  - dv.ok: 2^-40 <= a <= 2^40;
+ *  - 2^-96 <= discriminant < 2^100, ONE unsigned compare of its bits that also sends negative values and NaN to the generic code
+ *    (whose first test is the miss), so sqrtd < 2^50;
+ *  - half_b * half_b < 2^110, hence |half_b| < 2^55 (rounding is monotone) and both numerators |-half_b -+ sqrtd| < 2^56;
+ *  - a numerator below 2^-85 gives a root below 2^-44 in either form: rejected by `root < t_min` either way for any t_min >= 2^-44
+ *    (the kernels pass 0.001), so only roots that can be accepted have to be exact, and those are.
+ * No root of the short branch is NaN (all operands finite, the quotient below 2^96), so "a NaN root counts as accepted" concerns the
+ * generic branch alone.  Callers: r.tm finite, static spheres with a zero velocity (sphere_quadratic).  tests/test_gpu_exact_forms.py
+ * compares the two functions on the device over both branches. */
+DEV bool sphere_short_ok(float discriminant, float hb2, const DivBy &dv) { return dv.ok && sqrt_arg_ok(discriminant) && hb2 < 0x1p110f; }
+/* sphere_hit_root's first four lines, the centre WITHOUT sphere_center's select of the static one (a compare and three v_cndmask per sphere):
+ * a sphere that does not move stores a zero velocity (scene_compile.h to_dsphere) and the ray's time is finite (get_ray: a random_float in
+ * (0, 1]), so c + tm * 0 = c + (+-0) is c in every bit except that a centre coordinate of -0 becomes +0.  That can change one thing: the sign of
+ * a ZERO coordinate of oc (when the origin's coordinate is a zero too), hence the sign of a zero product in half_b -- which shows only if the
+ * other products cancel it, i.e. in the sign of a half_b that is zero.  vlen2(oc), c, hb2 and the discriminant take squares and are the same
+ * bits; -(+-0) -+ sqrtd is -+sqrtd for sqrtd != 0, and for sqrtd == 0 both roots are zeros, below t_min whatever their sign.  So neither the
+ * decision nor an accepted root sees it (tests/test_gpu_exact_forms.py: static spheres with zero and negative-zero coordinates). */
+struct SphereQuad { float half_b, hb2, discriminant; };
+DEV SphereQuad sphere_quadratic(const DSphere &s, const Ray &r, float a) {
+    SphereQuad q;
+    const V3 oc = vsub(r.o, vadd(mk(s.cx, s.cy, s.cz), vscale(r.tm, mk(s.vx, s.vy, s.vz))));
+    q.half_b = vdot(oc, r.d);
+    const float c = vlen2(oc) - s.radius * s.radius;
+    q.hb2 = q.half_b * q.half_b;
+    q.discriminant = q.hb2 - a * c;
+    return q;
+}
+DEV float sphere_hit_root_fast(const DSphere &s, const Ray &r, const DivBy &dv, float t_min, float t_max) {
+    const float a = dv.a;
+    const SphereQuad q = sphere_quadratic(s, r, a);
+    const float half_b = q.half_b, discriminant = q.discriminant;
+    if (sphere_short_ok(discriminant, q.hb2, dv)) {
+        const float sqrtd = sqrt_ord(discriminant);
+        float root = div_by(-half_b - sqrtd, dv);
+        if (root < t_min || t_max < root) {
+            root = div_by(-half_b + sqrtd, dv);
+            if (root < t_min || t_max < root) return -1.0f;
+        }
+        return root;
+    }
     if (discriminant < 0) return -1.0f;
     const float sqrtd = mort_sqrtf(discriminant);
     float root = (-half_b - sqrtd) / a;
@@ -519,6 +576,11 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
     float ray_time0 = 0;
     OwnRay orr; orr.ix = orr.iy = orr.iz = 1; orr.mx = orr.my = orr.mz = 0; orr.band = 0; orr.invlen = 1;
     float ray_a = 1, closest = 0;
+    /* the segment's prepared denominator: one reciprocal, set with ray_a in the set-up block, for the up to four divisions of every leaf step of the segment, and
+     * cleared when the segment's search is over, so that it holds a register from the set-up block to the last leaf step only (16 spilled registers instead of
+     * 15).  Live through the shade step as well (17 spilled) the headline frame is 1.2 ms faster but Scene 10 1.6 % slower; recomputed in every leaf step the
+     * frame is slower than without the short forms */
+    float ray_a_rcp = 1; /* div_prepare(ray_a).r */
     int best = -1;         /* closest hit so far: leaf << 16 | (second sphere of the leaf) << 15 */
     uint32_t node = 0;     /* T: own-tree node; L: leaf record */
     unsigned short *spa = ts_base; /* pending children: next free entry of the lane's traversal stack */
@@ -683,13 +745,14 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                 DSphere sa, sb;
                 sa.cx = a0.x; sa.cy = a0.y; sa.cz = a0.z; sa.radius = a0.w; sa.vx = a1.x; sa.vy = a1.y; sa.vz = a1.z; sa.mat = __float_as_uint(a1.w);
                 sb.cx = b0.x; sb.cy = b0.y; sb.cz = b0.z; sb.radius = b0.w; sb.vx = b1.x; sb.vy = b1.y; sb.vz = b1.z; sb.mat = __float_as_uint(b1.w);
-                const float ta = sphere_hit_root(sa, ray, ray_a, 0.001f, closest);
+                DivBy dv; dv.a = ray_a; dv.r = ray_a_rcp; dv.ok = div_den_ok(ray_a); /* the band check is two instructions; the reciprocal is the segment's */
+                const float ta = sphere_hit_root_fast(sa, ray, dv, 0.001f, closest);
                 if (ta != -1.0f) {
                     if (ta == closest && best >= 0) flags |= FL_TIE; /* the reference keeps whichever it visits last */
                     closest = ta; best = (int)(node << 16);
                 }
                 if (two == 2u) {
-                    const float tb = sphere_hit_root(sb, ray, ray_a, 0.001f, closest);
+                    const float tb = sphere_hit_root_fast(sb, ray, dv, 0.001f, closest);
                     if (tb != -1.0f) {
                         if (tb == closest && best >= 0) flags |= FL_TIE;
                         closest = tb; best = (int)((node << 16) | 0x8000u);
@@ -716,6 +779,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                 REGION("S:verify");
             if (state == ST_S) {
                 if (kind == K_SHADE) {
+                    ray_a_rcp = 0; /* the segment's search is over: nothing reads the reciprocal before the set-up block writes the next one, so it holds no register in the shade step */
                     /* is the winner what bvh_node::hit returns?  (header comment) */
                     bool need_ref = (flags & FL_MASK) != 0;
                     if (!need_ref && best >= 0) { /* the winner's leaf box, from its record */
@@ -917,6 +981,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                 REGION("S:setup");
                     if (kind == K_SHADE) { /* start world::hit for the new ray */
                         ray_a = vlen2(ray.d);
+                        ray_a_rcp = div_prepare(ray_a).r;
                         orr.ix = 1.0f / ray.d.x; orr.iy = 1.0f / ray.d.y; orr.iz = 1.0f / ray.d.z;
                         orr.mx = ray.o.x * orr.ix; orr.my = ray.o.y * orr.iy; orr.mz = ray.o.z * orr.iz;
                         const float mm = __builtin_fmaxf(__builtin_fmaxf(mort_fabsf(orr.mx), mort_fabsf(orr.my)), mort_fabsf(orr.mz));

@@ -1174,6 +1174,126 @@ extern "C" int mort_hip_debug_prune_forms(const mort_world *w, const float *rays
     return MORT_OK;
 }
 
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): dev_math.h's guards of the short forms, per value: bit 0 div_den_ok,
+ * bit 1 div_num_ok, bit 2 sqrt_arg_ok */
+extern "C" int mort_hip_debug_exact_guards(const float *v, size_t n, unsigned char *flags) {
+    if ((!v || !flags) && n) return MORT_ERR_INVALID;
+    for (size_t i = 0; i < n; i++) flags[i] = (unsigned char)((div_den_ok(v[i]) ? 1 : 0) | (div_num_ok(v[i]) ? 2 : 0) | (sqrt_arg_ok(v[i]) ? 4 : 0));
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the MODELS of the short forms (dev_math.h: the fma sequences as plain
+ * C++, the hardware's seed a parameter) against the host's correctly rounded operators.
+ *   what 0: sqrt_ord_model(x[i], seed) against sqrtf(x[i]), seed = sqrtf(x[i]) moved by every offset in [seed_lo, seed_hi] units of its
+ *           last place; `a` is not read;
+ *   what 1: div_by_model(x[i], a[i], div_by_model_prepare(a[i], seed)) against x[i] / a[i], seed = fl(1 / a[i]) moved likewise.
+ * Inputs outside the guards (sqrt_arg_ok; div_den_ok and 2^-85 <= |x| < 2^56) are only counted.  out[0] comparisons, [1] those that
+ * differ in any bit, [2] inputs outside the guards, [8..15] the indices of the first inputs that differ. */
+extern "C" int mort_hip_debug_exact_forms_model(int what, const float *x, const float *a, size_t n, int seed_lo, int seed_hi, unsigned long long *out) {
+    if (!x || !out || (what != 0 && what != 1) || (what == 1 && !a) || seed_lo > seed_hi) return MORT_ERR_INVALID;
+    for (int i = 0; i < 16; i++) out[i] = 0;
+    for (size_t i = 0; i < n; i++) {
+        const bool inside = what == 0 ? sqrt_arg_ok(x[i]) : (div_den_ok(a[i]) && div_num_ok(x[i]) && mort_fabsf(x[i]) >= 0x1p-85f);
+        if (!inside) { out[2]++; continue; }
+        const float want = what == 0 ? mort_sqrtf(x[i]) : x[i] / a[i];
+        const float seed0 = what == 0 ? want : 1.0f / a[i];
+        for (int k = seed_lo; k <= seed_hi; k++) {
+            const float seed = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, seed0) + (uint32_t)k);
+            const float got = what == 0 ? sqrt_ord_model(x[i], seed) : div_by_model(x[i], a[i], div_by_model_prepare(a[i], seed));
+            out[0]++;
+            if (std::memcmp(&got, &want, 4) != 0) { if (out[1] < 8) out[8 + out[1]] = i; out[1]++; }
+        }
+    }
+    return MORT_OK;
+}
+
+/* the device forms against the device's own operators, one element per lane and round (mort_hip_debug_exact_forms_device) */
+__device__ __forceinline__ void exact_forms_count(unsigned long long *slot, bool cond) {
+    const unsigned long long m = __ballot(cond);
+    if (m != 0ull && (int)(threadIdx.x & 63u) == __ffsll((long long)m) - 1) atomicAdd(slot, (unsigned long long)__popcll(m));
+}
+static __global__ void __launch_bounds__(256) exact_forms_kernel(int what, const float *in, size_t n, unsigned long long *out) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    const size_t rounds = (n + stride - 1) / stride; /* every lane runs every round: the ballots see whole waves */
+    for (size_t k = 0; k < rounds; k++) {
+        const size_t i = k * stride + (size_t)blockIdx.x * 256 + threadIdx.x;
+        const bool live = i < n;
+        bool compared = false, differs = false, outside = false, small = false, short_path = false, generic_path = false, short_hit = false, generic_hit = false;
+        if (live && what == 0) {
+            const float x = in[i];
+            if (sqrt_arg_ok(x)) {
+                compared = true;
+                differs = __float_as_uint(sqrt_ord(x)) != __float_as_uint(mort_sqrtf(x));
+            } else outside = true;
+        } else if (live && what == 1) {
+            const float x = in[2 * i], a = in[2 * i + 1];
+            const DivBy dv = div_prepare(a);
+            if (dv.ok && div_num_ok(x)) {
+                const float got = div_by(x, dv), want = x / a;
+                if (mort_fabsf(x) >= 0x1p-85f) { compared = true; differs = __float_as_uint(got) != __float_as_uint(want); }
+                else { small = true; differs = !(mort_fabsf(got) < 0x1p-44f && mort_fabsf(want) < 0x1p-44f); } /* both finite and below any t_min >= 2^-44 */
+            } else outside = true;
+        } else if (live) {
+            const float *q = in + 16 * i;
+            Ray ray; ray.o = mk(q[0], q[1], q[2]); ray.d = mk(q[3], q[4], q[5]); ray.tm = q[6];
+            const float t_max = q[7];
+            DSphere s;
+            s.cx = q[8]; s.cy = q[9]; s.cz = q[10]; s.radius = q[11]; s.vx = q[12]; s.vy = q[13]; s.vz = q[14];
+            s.mat = q[15] != 0.0f ? 0x80000000u : 0u; /* bit 31: the sphere moves (dev_scene.h) */
+            const float a = vlen2(ray.d);
+            const DivBy dv = div_prepare(a);
+            const float got = sphere_hit_root_fast(s, ray, dv, 0.001f, t_max), want = sphere_hit_root(s, ray, a, 0.001f, t_max);
+            compared = true;
+            differs = __float_as_uint(got) != __float_as_uint(want);
+            const SphereQuad sq = sphere_quadratic(s, ray, a);
+            short_path = sphere_short_ok(sq.discriminant, sq.hb2, dv);
+            generic_path = !short_path && !(sq.discriminant < 0);
+            short_hit = short_path && want != -1.0f;
+            generic_hit = generic_path && want != -1.0f;
+        }
+        exact_forms_count(&out[0], compared);
+        exact_forms_count(&out[2], outside);
+        exact_forms_count(&out[3], small);
+        exact_forms_count(&out[4], short_path);
+        exact_forms_count(&out[5], generic_path);
+        exact_forms_count(&out[6], short_hit);
+        exact_forms_count(&out[7], generic_hit);
+        if (differs) { const unsigned long long at = atomicAdd(&out[1], 1ull); if (at < 8ull) out[8 + at] = (unsigned long long)i; }
+    }
+}
+
+/* diagnostic (not in include/mort_hip.h): one launch of the kernel above on `device`, the short forms against the plain operators ON THE DEVICE.
+ *   what 0: in = n values x: sqrt_ord(x) against sqrtf(x) where sqrt_arg_ok(x);
+ *   what 1: in = n pairs (x, a): div_by(x, div_prepare(a)) against x / a where div_den_ok(a) and div_num_ok(x); a numerator below 2^-85 is
+ *           checked for what dev_math.h promises instead: both quotients below 2^-44 in magnitude;
+ *   what 2: in = n records of 16 floats (ray origin, direction, time, t_max; sphere centre, radius, velocity, moves != 0):
+ *           sphere_hit_root_fast against sphere_hit_root with t_min = 0.001, a = the direction's squared length.
+ * out[0] elements compared bit for bit, [1] elements that fail, [2] outside the guards (what 0, 1), [3] small numerators (what 1), what 2:
+ * [4] records on the short branch, [5] on the generic branch past its miss test, [6] / [7] accepted roots of either, [8..15] first failing elements. */
+extern "C" int mort_hip_debug_exact_forms_device(int device, int what, const float *in, size_t n, unsigned long long *out) {
+    if (!in || !out || what < 0 || what > 2 || n == 0) return MORT_ERR_INVALID;
+    const size_t per = what == 0 ? 1 : what == 1 ? 2 : 16;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    float *d_in = nullptr;
+    unsigned long long *d_out = nullptr;
+    int st = MORT_OK;
+    if (hipMalloc((void **)&d_in, n * per * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_out, 16 * sizeof(unsigned long long)) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && (hipMemcpy(d_in, in, n * per * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemset(d_out, 0, 16 * sizeof(unsigned long long)) != hipSuccess)) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        const size_t blocks = (n + 255) / 256;
+        exact_forms_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256)>>>(what, d_in, n, d_out);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+
 extern "C" int mort_hip_render_device(mort_ctx *c, const mort_camera *cam, int mode, void *d_rgba, void *d_accum,
                                       void *stream, mort_stats *stats) {
     return render_device_impl(c, cam, mode, d_rgba, d_accum, nullptr, stream, stats);

@@ -66,6 +66,8 @@ struct Compiled {
     float g_c[3] = {0, 0, 0}, g_R = 0, g_mnear = 0, g_kmin = 0;
 };
 
+/* A sphere that does not move gets a ZERO velocity: the BVH megakernel's leaf step computes every centre as c + tm * v without looking at the
+ * moves bit (mega_bvh.h sphere_quadratic); the hit record still selects by the bit. */
 static inline DSphere to_dsphere(const mort_sphere &s) {
     DSphere d;
     d.cx = s.center1.e[0]; d.cy = s.center1.e[1]; d.cz = s.center1.e[2]; d.radius = s.radius;
