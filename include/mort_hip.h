@@ -373,6 +373,42 @@ int mort_hip_query_occluded_device(mort_ctx *ctx, size_t n, const void *d_rays, 
 int mort_hip_query_occluded_host(const mort_world *world, size_t n, const mort_ray *rays, int nthreads, int flags, uint8_t *out,
                                  double *seconds);
 
+/* ---- radiance queries: the path-traced colour arriving along batches of the caller's own rays.  The render's
+ * path above the traversal -- ray_color's bounce loop, the material scatter, the mixture pdf towards the light, the media, the
+ * unwind -- behind an entry point: light and reflection probes, panorama / fisheye / stereo cameras and lightmap texels get the
+ * renderer's own answer, bit for bit the reference's ray_color.
+ *
+ * The ray is the ray queries' mort_ray.  Its `time` is ray_color's r.time(): every scattered ray carries it.  Its t_max is
+ * IGNORED: ray_color always searches [0.001, inf).  Zero-length, non-finite and axis-parallel directions and origins anywhere are
+ * legal: the answer is ray_color's.
+ *
+ * states is required: one 48-byte XORWOW stream per ray, advanced in place (only d and v[] are written; a ray that draws nothing
+ * leaves its stream's bits as they were).
+ *
+ * rgb_out is 3 n floats: rgb_out[i] = ((0 + c_1) + c_2) + ... + c_samples in fp32, c_k the k-th ray_color of ray i, the paths
+ * drawing from stream i one after the other (Camera::render's pixel_color = pixel_color + ray_color(...)).  No scale, no NaN guard,
+ * no gamma: a NaN stays a NaN and the caller scales.  bounce_limit == 0 returns 0 and draws nothing; a path that reaches the
+ * limit contributes 0, as in the reference.
+ *
+ * Forms, `seconds`, n == 0, alignment and overlap as for the ray queries; the streams count as an output.  NULL params, rays,
+ * states or rgb_out and samples < 1 are MORT_ERR_INVALID; bounce_limit and the light object are checked as mort_hip_render
+ * checks the camera's (MORT_ERR_CAPACITY; MORT_ERR_INVALID / MORT_ERR_UNSUPPORTED).  The calls need an uploaded world (else
+ * MORT_ERR_NO_WORLD) but no seeded pixel RNG, ignore the partition, and touch nothing the render keeps across frames. ---- */
+typedef struct mort_radiance_params {
+    int bounce_limit;                  /* 0..MORT_MAX_BOUNCE_LIMIT; ray_color's cam->bounce_limit */
+    int samples;                       /* >= 1: paths per ray, drawn one after the other from the ray's stream */
+    float background[3];               /* what a miss returns (cam->background) */
+    int light_obj_type, light_obj_idx; /* -1 = no light sampling; else as mort_camera's */
+} mort_radiance_params;
+MORT_SA(sizeof(mort_radiance_params) == 28, "radiance query layout");
+int mort_hip_radiance_params_from_camera(const mort_camera *cam, mort_radiance_params *out); /* samples = 1 */
+int mort_hip_query_radiance(mort_ctx *ctx, const mort_radiance_params *params, size_t n, const mort_ray *rays, mort_rng_state *states,
+                            float *rgb_out, double *seconds);
+int mort_hip_query_radiance_device(mort_ctx *ctx, const mort_radiance_params *params, size_t n, const void *d_rays, void *d_states,
+                                   void *d_rgb_out, void *stream, double *seconds);
+int mort_hip_query_radiance_host(const mort_world *world, const mort_radiance_params *params, size_t n, const mort_ray *rays,
+                                 mort_rng_state *states, int nthreads, int flags, float *rgb_out, double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

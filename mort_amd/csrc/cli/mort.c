@@ -13,6 +13,7 @@
  *                   [--temporal] [--variance-out F]       temporal accumulation across frames with reprojection (single GPU / host)
  *                   [--svgf]                              variance-guided a-trous filter (SVGF) on the last frame (single GPU / host)
  *                   [--pick X,Y]                          no render: the closest-hit record under pixel (X, Y) as one JSON line
+ *                   [--probe X,Y[,N]]                     no render: the path-traced colour along the ray through pixel (X, Y) as one JSON line
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -40,6 +41,11 @@
  * centre through the pixel centre, time 0.5, t_max = inf, no streams, so media are passed over -- printed as one JSON line:
  * pick, hit, t, p, normal, u, v, mat_type, mat_idx, front_face, medium, mode, seconds.  Floats are printed with nine significant
  * digits, which identify a float32; a non-finite one as NaN / Infinity / -Infinity.
+ *
+ * --probe X,Y[,N] (single GPU / host): renders nothing; one radiance query (mort_hip_query_radiance, or mort_hip_query_radiance_host
+ * under --mode host) for the same ray as --pick: N paths (default 1) with the scene camera's bounce limit (--depth), background and
+ * light object, drawn from subsequence X + Y * W of --seed, which is that pixel's stream at the start of a render.  One JSON line:
+ * probe, samples, origin, dir, time, rgb (the unscaled sum of the N colours), mode, seconds.
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -83,7 +89,7 @@ static int usage(void) {
     printf("Usage: mort <number_between_1_and_10> [--width W] [--aspect A] [--spp N] [--depth D] [--seed S] [--frames N] "
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
-           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y]\n");
+           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]]\n");
     return -1;
 }
 
@@ -157,6 +163,7 @@ int main(int argc, char **argv) {
     int denoise = 0, temporal = 0, svgf = 0;
     int mouse_dx = 0, mouse_dy = 0;
     int pick = 0, pick_x = 0, pick_y = 0;
+    int probe = 0, probe_x = 0, probe_y = 0, probe_n = 1;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -195,6 +202,7 @@ int main(int argc, char **argv) {
         else if (ARG("--variance-out")) var_out = argv[++i];
         else if (strcmp(argv[i], "--svgf") == 0) svgf = 1;
         else if (ARG("--pick")) { pick = 1; if (sscanf(argv[++i], "%d,%d", &pick_x, &pick_y) != 2) { fprintf(stderr, "--pick X,Y\n"); return -1; } }
+        else if (ARG("--probe")) { probe = 1; if (sscanf(argv[++i], "%d,%d,%d", &probe_x, &probe_y, &probe_n) < 2 || probe_n < 1) { fprintf(stderr, "--probe X,Y[,N]\n"); return -1; } }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -206,6 +214,7 @@ int main(int argc, char **argv) {
     if (svgf && denoise) { fprintf(stderr, "--svgf and --denoise exclude each other\n"); return -1; }
     if (var_out && !temporal) { fprintf(stderr, "--variance-out needs --temporal\n"); return -1; }
     if (pick && gpus > 1) { fprintf(stderr, "--pick is a single-GPU option\n"); return -1; }
+    if (probe && (gpus > 1 || pick)) { fprintf(stderr, "--probe is a single-GPU option and excludes --pick\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;
@@ -256,6 +265,39 @@ int main(int argc, char **argv) {
         printf(", \"v\": "); print_f32(h.v);
         printf(", \"mat_type\": %d, \"mat_idx\": %d, \"front_face\": %d, \"medium\": %d, \"mode\": \"%s\", \"seconds\": %.6f}\n", (int)h.mat_type, (int)h.mat_idx,
                (h.flags & MORT_HIT_FRONT_FACE) ? 1 : 0, (h.flags & MORT_HIT_MEDIUM) ? 1 : 0, host_mode ? "host" : "mega", sec);
+        mort_world_free(&world);
+        free(texels);
+        return 0;
+    }
+
+    if (probe) { /* ---- no render: one radiance query ---- */
+        if (probe_x < 0 || probe_x >= W || probe_y < 0 || probe_y >= H) { fprintf(stderr, "--probe %d,%d is outside the %dx%d image\n", probe_x, probe_y, W, H); return -1; }
+        const mort_ray ray = pick_ray(&cam, probe_x, probe_y);
+        mort_radiance_params rp;
+        mort_hip_radiance_params_from_camera(&cam, &rp);
+        rp.samples = probe_n;
+        mort_rng_state *states = (mort_rng_state *)malloc(npx * sizeof *states); /* the run's pixel streams; the probe takes its pixel's */
+        if (!states) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+        int pst;
+        if ((pst = mort_hip_rng_seed_host(seed, W, H, states)) != MORT_OK) die(NULL, pst, "mort_hip_rng_seed_host");
+        mort_rng_state stream = states[(size_t)probe_x + (size_t)probe_y * W];
+        free(states);
+        float rgb[3] = {0, 0, 0};
+        double sec = 0;
+        if (host_mode) {
+            if ((pst = mort_hip_query_radiance_host(&world, &rp, 1, &ray, &stream, 1, tree ? MORT_HOST_TREE : 0, rgb, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_radiance_host");
+        } else {
+            mort_ctx *pctx = NULL;
+            if ((pst = mort_hip_init(device, &pctx)) != MORT_OK) die(NULL, pst, "mort_hip_init");
+            if ((pst = mort_hip_upload_world(pctx, &world)) != MORT_OK) die(pctx, pst, "mort_hip_upload_world");
+            if ((pst = mort_hip_query_radiance(pctx, &rp, 1, &ray, &stream, rgb, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_radiance");
+            mort_hip_shutdown(pctx);
+        }
+        printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"probe\": [%d, %d], \"samples\": %d", scene, W, H, probe_x, probe_y, probe_n);
+        print_v3("origin", ray.origin); print_v3("dir", ray.dir);
+        printf(", \"time\": "); print_f32(ray.time);
+        print_v3("rgb", rgb);
+        printf(", \"mode\": \"%s\", \"seconds\": %.6f}\n", host_mode ? "host" : "mega", sec);
         mort_world_free(&world);
         free(texels);
         return 0;

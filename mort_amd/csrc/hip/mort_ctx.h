@@ -175,6 +175,26 @@ static inline bool camera_in_reach(const mort_camera *cam, const float lo[3], co
     return true;
 }
 
+/* the light object a camera or a radiance query names must be primitives the light-sampling code can index (pdf.cuh:60-80),
+ * checked against the host copy of the uploaded world's lists */
+static inline int check_light(const mort_ctx *c, int type, int idx) {
+    if (type == -1) return MORT_OK;
+    if (type == MORT_OBJ_SPHERE) return (idx >= 0 && idx < c->n_wspheres) ? MORT_OK : MORT_ERR_INVALID;
+    if (type == MORT_OBJ_QUAD) return (idx >= 0 && idx < c->n_wquads) ? MORT_OK : MORT_ERR_INVALID;
+    if (type == MORT_OBJ_HITTABLE_LIST) {
+        if (idx < 0 || idx >= c->n_lists || idx >= MORT_NUM_HITTABLE_LIST) return MORT_ERR_INVALID;
+        if (c->list_count[idx] <= 0) return MORT_ERR_INVALID;
+        for (int i = 0; i < c->list_count[idx]; i++) {
+            const int t = c->list_types[c->list_first[idx] + i], k = c->list_idxs[c->list_first[idx] + i];
+            if (t == MORT_OBJ_SPHERE) { if (k < 0 || k >= c->n_wspheres) return MORT_ERR_INVALID; }
+            else if (t == MORT_OBJ_QUAD) { if (k < 0 || k >= c->n_wquads) return MORT_ERR_INVALID; }
+            else if (t == MORT_OBJ_HITTABLE_LIST) return MORT_ERR_UNSUPPORTED; /* nested light lists */
+        }
+        return MORT_OK;
+    }
+    return MORT_OK; /* any other tag samples nothing: pdf 0, direction (1,0,0) (objects.cuh:961,978) */
+}
+
 static inline double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 /* run `fn(arg, row)` for rows [0, rows) on `nthreads` host threads (1..256), rows handed out one at a time */

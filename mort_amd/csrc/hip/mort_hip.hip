@@ -422,25 +422,6 @@ extern "C" int mort_hip_rng_store(mort_ctx *c, mort_rng_state *states, int width
     return MORT_OK;
 }
 
-
-static int check_light(const mort_ctx *c, int type, int idx) {
-    if (type == -1) return MORT_OK;
-    if (type == MORT_OBJ_SPHERE) return (idx >= 0 && idx < c->n_wspheres) ? MORT_OK : MORT_ERR_INVALID;
-    if (type == MORT_OBJ_QUAD) return (idx >= 0 && idx < c->n_wquads) ? MORT_OK : MORT_ERR_INVALID;
-    if (type == MORT_OBJ_HITTABLE_LIST) {
-        if (idx < 0 || idx >= c->n_lists || idx >= MORT_NUM_HITTABLE_LIST) return MORT_ERR_INVALID;
-        if (c->list_count[idx] <= 0) return MORT_ERR_INVALID;
-        for (int i = 0; i < c->list_count[idx]; i++) {
-            const int t = c->list_types[c->list_first[idx] + i], k = c->list_idxs[c->list_first[idx] + i];
-            if (t == MORT_OBJ_SPHERE) { if (k < 0 || k >= c->n_wspheres) return MORT_ERR_INVALID; }
-            else if (t == MORT_OBJ_QUAD) { if (k < 0 || k >= c->n_wquads) return MORT_ERR_INVALID; }
-            else if (t == MORT_OBJ_HITTABLE_LIST) return MORT_ERR_UNSUPPORTED; /* nested light lists */
-        }
-        return MORT_OK;
-    }
-    return MORT_OK; /* any other tag samples nothing: pdf 0, direction (1,0,0) (objects.cuh:961,978) */
-}
-
 /* ---- wavefront mode over one reference BVH of spheres: one wf_trav + one wf_shade launch per front (wave_common.h wf_render) ---- */
 static int launch_wave(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, hipStream_t s, LaunchPlan &plan) {
     WfArgs w;

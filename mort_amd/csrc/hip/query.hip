@@ -25,10 +25,9 @@
 #include "mort_ctx.h"
 #include "mort_internal.h"
 #include "stage_common.h"
+#include "query_common.h"
 
 #pragma clang fp contract(off)
-
-constexpr int QUERY_BLOCK = 256;
 
 /* ====================================================================== device */
 
@@ -52,11 +51,6 @@ __global__ void __launch_bounds__(QUERY_BLOCK) query_occluded_kernel(const Query
 
 namespace {
 
-constexpr size_t kHostChunk = 1024;                                  /* rays a host thread takes at a time */
-constexpr size_t kMaxRays = (size_t)0x7fffffff * (size_t)QUERY_BLOCK; /* a 1-D grid of 256-thread groups */
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 /* no output (the streams are one: they are written in place) overlaps the rays or another output */
 bool query_buffers_ok(size_t n, const void *rays, void *states, void *hits, void *occ) {
     const void *ins[1] = {rays};
@@ -64,20 +58,6 @@ bool query_buffers_ok(size_t n, const void *rays, void *states, void *hits, void
     void *outs[3] = {states, hits, occ};
     const size_t out_bytes[3] = {n * sizeof(mort_rng_state), n * sizeof(mort_hit), n};
     return buffers_disjoint(ins, in_bytes, 1, outs, out_bytes, 3);
-}
-
-/* the launch arguments over the context's scene in HBM; the unified tree where the world has one */
-void query_args_device(const mort_ctx *c, QueryArgs &a) {
-    std::memset(&a, 0, sizeof a);
-    a.sc = c->sc;
-    if (!c->gen_ok) return;
-    const unsigned char *g = (const unsigned char *)c->d_gen;
-    a.gw.nodes = (const DNodeQ *)(g + c->gen.o_nodes); a.gw.entries = (const uint32_t *)(g + c->gen.o_entries);
-    a.gw.chains = (const int *)(g + c->gen.o_chains); a.gw.ranks = c->gen.ranks; a.gw.n_spheres = c->gen.n_spheres;
-    a.gw.n_chains = c->gen.n_chains; a.gw.root = c->gen.root; a.gw.first_medium = c->gen.first_medium;
-    a.gw.gx = c->gen.gx; a.gw.gy = c->gen.gy; a.gw.gz = c->gen.gz; a.gw.gR = c->gen.gR; a.gw.mnear = c->gen.mnear; a.gw.kmin = c->gen.kmin;
-    for (int k = 0; k < 3; k++) { a.lo[k] = c->gen_lo[k]; a.hi[k] = c->gen_hi[k]; }
-    a.reach = c->gen_reach;
 }
 
 struct QueryHostJob { QueryArgs a; bool tree, closest; };
@@ -109,16 +89,9 @@ int query_host(const mort_world *world, size_t n, const mort_ray *rays, mort_rng
     const int st = build_scene_blob(world, sb);
     if (st != MORT_OK) return st;
     QueryHostJob job;
-    std::memset(&job.a, 0, sizeof job.a);
-    scene_view(sb, sb.bytes.data(), job.a.sc);
-    const mortc::Compiled &o = sb.comp;
-    job.tree = (flags & MORT_HOST_TREE) && o.g_ok;
+    job.tree = (flags & MORT_HOST_TREE) && sb.comp.g_ok;
     job.closest = hits != nullptr;
-    if (job.tree) {
-        job.a.gw = gen_walk_of(o);
-        for (int k = 0; k < 3; k++) { job.a.lo[k] = o.g_lo[k]; job.a.hi[k] = o.g_hi[k]; }
-        job.a.reach = o.g_reach;
-    }
+    query_args_host(sb, job.tree, job.a);
     job.a.n = n; job.a.rays = rays; job.a.states = states; job.a.hits = hits; job.a.occluded = occ;
     const double t0 = now_s();
     run_rows((int)((n + kHostChunk - 1) / kHostChunk), nthreads, query_host_chunk, &job);

@@ -35,6 +35,7 @@ EXPORTS = [
     "mort_hip_view_frame", "mort_hip_view_frame_device", "mort_hip_view_read",
     "mort_hip_query_closest", "mort_hip_query_closest_device", "mort_hip_query_closest_host",
     "mort_hip_query_occluded", "mort_hip_query_occluded_device", "mort_hip_query_occluded_host",
+    "mort_hip_radiance_params_from_camera", "mort_hip_query_radiance", "mort_hip_query_radiance_device", "mort_hip_query_radiance_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -48,6 +49,12 @@ HIT_DTYPE = np.dtype([("p", "<f4", (3,)), ("normal", "<f4", (3,)), ("t", "<f4"),
                       ("mat_idx", "<i4"), ("flags", "<u4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48
 HIT_HIT, HIT_FRONT_FACE, HIT_MEDIUM = 1, 2, 4
+
+
+class RADIANCE_PARAMS(C.Structure):
+    """mort_radiance_params of include/mort_hip.h"""
+    _fields_ = [("bounce_limit", C.c_int), ("samples", C.c_int), ("background", C.c_float * 3),
+                ("light_obj_type", C.c_int), ("light_obj_idx", C.c_int)]
 
 
 class Partition(C.Structure):
@@ -214,6 +221,12 @@ def lib():
         L.mort_hip_query_occluded.argtypes = [ctx, sz, vp, vp, dp]; L.mort_hip_query_occluded.restype = C.c_int
         L.mort_hip_query_occluded_device.argtypes = [ctx, sz, vp, vp, vp, dp]; L.mort_hip_query_occluded_device.restype = C.c_int
         L.mort_hip_query_occluded_host.argtypes = [wd, sz, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_query_occluded_host.restype = C.c_int
+        rp = C.POINTER(RADIANCE_PARAMS)
+        L.mort_hip_radiance_params_from_camera.argtypes = [vp, rp]; L.mort_hip_radiance_params_from_camera.restype = C.c_int
+        L.mort_hip_query_radiance.argtypes = [ctx, rp, sz, vp, vp, vp, dp]; L.mort_hip_query_radiance.restype = C.c_int
+        L.mort_hip_query_radiance_device.argtypes = [ctx, rp, sz, vp, vp, vp, vp, dp]; L.mort_hip_query_radiance_device.restype = C.c_int
+        L.mort_hip_query_radiance_host.argtypes = [wd, rp, sz, vp, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_query_radiance_host.restype = C.c_int
+        L.mort_hip_debug_radiance_lds_levels.argtypes = []; L.mort_hip_debug_radiance_lds_levels.restype = C.c_int
         _lib = L
     return _lib
 
@@ -457,6 +470,29 @@ class Context:
                   "mort_hip_query_occluded_device")
         return sec.value if sync else None
 
+    def query_radiance(self, params, rays, states):
+        """Path-traced colour along every ray on the GPU (mort_hip_query_radiance): params RADIANCE_PARAMS, rays as for
+        query_closest (t_max is ignored), states (n,) 48-byte XORWOW streams, advanced IN PLACE.  dict(rgb float32 (n, 3), seconds):
+        the fp32 sum of params.samples paths per ray, unscaled, NaN kept."""
+        rays = _query_rays(rays)
+        st8 = _query_states(states, rays)
+        rgb = np.zeros((rays.shape[0], 3), dtype=np.float32)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_query_radiance(self._h, C.byref(params), rays.shape[0], rays.ctypes.data, _ptr(st8), rgb.ctypes.data,
+                                                C.byref(sec)), "mort_hip_query_radiance")
+        return dict(rgb=rgb, seconds=sec.value)
+
+    def query_radiance_device(self, params, rays, states, rgb, sync=False):
+        """The radiance query on torch tensors: rays and states as for query_closest_device (states required), rgb of 12 n bytes."""
+        import torch
+        n = _check_query_tensors(torch, rays, ((states, 48), (rgb, 12)))
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, rays.device, sync)
+        self._chk(lib().mort_hip_query_radiance_device(self._h, C.byref(params), n, rays.data_ptr(), states.data_ptr() if states is not None else None,
+                                                       rgb.data_ptr() if rgb is not None else None, stream, C.byref(sec) if sync else None),
+                  "mort_hip_query_radiance_device")
+        return sec.value if sync else None
+
     def calib_valu(self, waves_per_simd, kind=0):
         """Shader cycles one SIMD needs per wave64 VALU instruction at `waves_per_simd` resident waves (include/mort_hip.h)."""
         r = CalibValu()
@@ -646,6 +682,34 @@ def query_occluded_host(world, rays, tree=False, nthreads=1):
     if rc != 0:
         raise MortHipError(rc, "mort_hip_query_occluded_host")
     return dict(occluded=out, seconds=sec.value)
+
+
+def radiance_params_from_camera(cam, samples=1):
+    """RADIANCE_PARAMS with the camera's bounce limit, background and light object (mort_hip_radiance_params_from_camera)."""
+    p = RADIANCE_PARAMS()
+    rc = lib().mort_hip_radiance_params_from_camera(C.cast(C.byref(cam), C.c_void_p), C.byref(p))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_radiance_params_from_camera")
+    p.samples = samples
+    return p
+
+
+def radiance_lds_levels():
+    """mort_hip_debug_radiance_lds_levels (host only): the bounce-stack levels the radiance kernels keep in LDS."""
+    return lib().mort_hip_debug_radiance_lds_levels()
+
+
+def query_radiance_host(world, params, rays, states, tree=False, nthreads=1):
+    """The radiance query as a host loop (mort_hip_query_radiance_host), no GPU: arguments and result as Context.query_radiance."""
+    rays = _query_rays(rays)
+    st8 = _query_states(states, rays)
+    rgb = np.zeros((rays.shape[0], 3), dtype=np.float32)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_query_radiance_host(world.ptr, C.byref(params), rays.shape[0], rays.ctypes.data, _ptr(st8), nthreads,
+                                            HOST_TREE if tree else 0, rgb.ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_query_radiance_host")
+    return dict(rgb=rgb, seconds=sec.value)
 
 
 def _feature_arrays(W, H):

@@ -9,7 +9,9 @@ graph), waves per SIMD that allocation allows, spilled registers, private (scrat
     a vector register: their state loops are built to run without scratch.  The 1024-thread variants are compiled
     for 128 VGPRs (four waves per SIMD): mega_bvh_kernel<1024> may keep at most 32 registers / 128 B in private memory (rarely
     touched per-pixel values, read and written in the shade step only), mega_gen_kernel<1024> is a measurement build, or
-  * a ray-query kernel (query_closest_kernel, query_occluded_kernel) spills or uses any private memory.
+  * a ray-query kernel (query_closest_kernel, query_occluded_kernel) spills or uses any private memory, or
+  * a radiance-query kernel (query_radiance_kernel) spills a vector register or keeps more in private memory than the bounce-stack
+    levels behind its LDS part: MORT_MAX_BOUNCE_LIMIT x 16 B and one 16-byte slot, 1040 B.
 """
 import os, re, subprocess, sys, tempfile, shutil
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
@@ -52,8 +54,10 @@ for r in sorted(rows, key=lambda r: r["name"]):
         wide = r["name"].startswith("mega_bvh_kernel<1024")
         if (r["vspill"] > (32 if wide else 0)) or r["private"] > 128:
             bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (state loop must run without scratch)")
-    if r["name"].startswith("query_") and (r["vspill"] or r["private"]):
+    if r["name"].startswith("query_") and not r["name"].startswith("query_radiance_") and (r["vspill"] or r["private"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the ray queries run without scratch)")
+    if r["name"].startswith("query_radiance_") and (r["vspill"] or r["private"] > 1040):
+        bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the search loop must not spill; 1040 B for the deep bounce levels)")
 if bad:
     print("\n".join("RESOURCE CHECK FAILED: " + b for b in bad), file=sys.stderr)
     sys.exit(1 if check else 0)
