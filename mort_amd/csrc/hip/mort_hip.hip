@@ -265,6 +265,50 @@ static bool bvh_wide_block_fits(uint32_t image_bytes, int own4_stack) {
     return (size_t)((image_bytes + 15u) & ~15u) + ((size_t)own4_stack + MORT_BVH_TSTACK_SPARE) * 1024u * 2u + 2048u + 1024u * 16u <= 160u * 1024u;
 }
 
+/* The LDS image of a world with a unified tree (o.g_ok): the tree, every small table and, when image + primitives stay within
+ * MORT_GEN_PRIMS_LDS_MAX, the primitives; behind the LDS part the scan ranks, which stay in HBM.  g: the table offsets and the tree's
+ * constants as the kernels take them (g.ranks is left null: it points into the device copy).  fits: the LDS part is within
+ * MORT_GEN_IMAGE_MAX, the condition of mega_gen_kernel and wave_gen.hip.  No HIP call. */
+#define MORT_GEN_PRIMS_LDS_MAX (48 * 1024)
+#ifndef MORT_GEN_IMAGE_MAX
+#define MORT_GEN_IMAGE_MAX (124 * 1024) /* + traversal stacks of 768 threads (24 KB) + the launch arguments: one workgroup per CU */
+#endif
+struct GenImage {
+    std::vector<unsigned char> gb;
+    GenArgs g;
+    size_t table_bytes, prim_bytes, lds_part, o_ranks; /* the image before the primitives, the primitives, the whole LDS part */
+    bool fits;
+};
+static void build_gen_image(const mortc::Compiled &o, GenImage &gi) {
+    std::vector<unsigned char> &gb = gi.gb;
+    GenArgs &g = gi.g;
+    std::memset(&g, 0, sizeof g);
+    g.o_nodes = (uint32_t)place(gb, o.g_nodes); g.o_leaves = g.o_nodes; g.o_entries = (uint32_t)place(gb, o.g_entries);
+    g.o_chains = (uint32_t)place(gb, o.g_chains); g.o_xforms = (uint32_t)place(gb, o.xforms);
+    g.o_items = (uint32_t)place(gb, o.items); g.o_subitems = (uint32_t)place(gb, o.subitems); g.o_media = (uint32_t)place(gb, o.media);
+    g.o_lambert = (uint32_t)place(gb, o.lambert); g.o_metal = (uint32_t)place(gb, o.metal); g.o_diel = (uint32_t)place(gb, o.dielectric);
+    g.o_dlight = (uint32_t)place(gb, o.dlight); g.o_iso = (uint32_t)place(gb, o.isotropic);
+    g.o_solid = (uint32_t)place(gb, o.solid); g.o_checker = (uint32_t)place(gb, o.checker); g.o_image = (uint32_t)place(gb, o.image);
+    g.o_lfirst = (uint32_t)place(gb, std::vector<int>(o.list_first, o.list_first + MORT_NUM_HITTABLE_LIST));
+    g.o_lcount = (uint32_t)place(gb, std::vector<int>(o.list_count, o.list_count + MORT_NUM_HITTABLE_LIST));
+    gi.table_bytes = gb.size();
+    gi.prim_bytes = o.spheres.size() * sizeof(DSphere) + o.quads.size() * sizeof(DQuad) + o.wspheres.size() * sizeof(DSphere) +
+                    o.wquads.size() * sizeof(DQuad) + (o.list_types.size() + o.list_idxs.size()) * sizeof(int) + 6 * 32;
+    if (gi.table_bytes + gi.prim_bytes <= MORT_GEN_PRIMS_LDS_MAX) {
+        g.prims_in_lds = 1;
+        g.o_spheres = (uint32_t)place(gb, o.spheres); g.o_quads = (uint32_t)place(gb, o.quads);
+        g.o_wspheres = (uint32_t)place(gb, o.wspheres); g.o_wquads = (uint32_t)place(gb, o.wquads);
+        g.o_ltypes = (uint32_t)place(gb, o.list_types); g.o_lidxs = (uint32_t)place(gb, o.list_idxs);
+    }
+    gb.resize((gb.size() + 15) & ~(size_t)15, 0);
+    gi.lds_part = gb.size();
+    gi.o_ranks = place(gb, o.g_ranks); /* HBM only: read when two hits have equal t */
+    g.n_spheres = (int)o.spheres.size();
+    g.root = o.g_root; g.first_medium = o.g_first_medium; g.n_chains = (int)(o.g_chains.size() / 2);
+    g.gx = o.g_c[0]; g.gy = o.g_c[1]; g.gz = o.g_c[2]; g.gR = o.g_R; g.mnear = o.g_mnear; g.kmin = o.g_kmin;
+    gi.fits = gi.lds_part <= MORT_GEN_IMAGE_MAX;
+}
+
 extern "C" int mort_hip_upload_world(mort_ctx *c, const mort_world *w) {
     if (!c || !w) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
@@ -311,38 +355,15 @@ extern "C" int mort_hip_upload_world(mort_ctx *c, const mort_world *w) {
     }
     /* unified-tree megakernel: LDS image = tree + every small table (+ the primitives when they fit) */
     if (o.g_ok && !std::getenv("MORT_NO_GEN")) {
-        std::vector<unsigned char> gb;
-        GenArgs g;
-        std::memset(&g, 0, sizeof g);
-        g.o_nodes = (uint32_t)place(gb, o.g_nodes); g.o_leaves = g.o_nodes; g.o_entries = (uint32_t)place(gb, o.g_entries);
-        g.o_chains = (uint32_t)place(gb, o.g_chains); g.o_xforms = (uint32_t)place(gb, o.xforms);
-        g.o_items = (uint32_t)place(gb, o.items); g.o_subitems = (uint32_t)place(gb, o.subitems); g.o_media = (uint32_t)place(gb, o.media);
-        g.o_lambert = (uint32_t)place(gb, o.lambert); g.o_metal = (uint32_t)place(gb, o.metal); g.o_diel = (uint32_t)place(gb, o.dielectric);
-        g.o_dlight = (uint32_t)place(gb, o.dlight); g.o_iso = (uint32_t)place(gb, o.isotropic);
-        g.o_solid = (uint32_t)place(gb, o.solid); g.o_checker = (uint32_t)place(gb, o.checker); g.o_image = (uint32_t)place(gb, o.image);
-        g.o_lfirst = (uint32_t)place(gb, std::vector<int>(o.list_first, o.list_first + MORT_NUM_HITTABLE_LIST));
-        g.o_lcount = (uint32_t)place(gb, std::vector<int>(o.list_count, o.list_count + MORT_NUM_HITTABLE_LIST));
-        const size_t prim_bytes = o.spheres.size() * sizeof(DSphere) + o.quads.size() * sizeof(DQuad) + o.wspheres.size() * sizeof(DSphere) +
-                                  o.wquads.size() * sizeof(DQuad) + (o.list_types.size() + o.list_idxs.size()) * sizeof(int) + 6 * 32;
-        if (gb.size() + prim_bytes <= 48 * 1024) {
-            g.prims_in_lds = 1;
-            g.o_spheres = (uint32_t)place(gb, o.spheres); g.o_quads = (uint32_t)place(gb, o.quads);
-            g.o_wspheres = (uint32_t)place(gb, o.wspheres); g.o_wquads = (uint32_t)place(gb, o.wquads);
-            g.o_ltypes = (uint32_t)place(gb, o.list_types); g.o_lidxs = (uint32_t)place(gb, o.list_idxs);
-        }
-        gb.resize((gb.size() + 15) & ~(size_t)15, 0);
-        const size_t lds_part = gb.size();
-        const size_t o_ranks = place(gb, o.g_ranks); /* HBM only: read when two hits have equal t */
-#ifndef MORT_GEN_IMAGE_MAX
-#define MORT_GEN_IMAGE_MAX (124 * 1024) /* + traversal stacks of 768 threads (24 KB) + the launch arguments: one workgroup per CU */
-#endif
-        if (lds_part <= MORT_GEN_IMAGE_MAX) {
+        GenImage gi;
+        build_gen_image(o, gi);
+        if (gi.fits) {
+            const std::vector<unsigned char> &gb = gi.gb;
+            GenArgs g = gi.g;
             HIPCHK(c, hipMalloc(&c->d_gen, gb.size()));
             HIPCHK(c, hipMemcpy(c->d_gen, gb.data(), gb.size(), hipMemcpyHostToDevice));
-            c->gen_bytes = (uint32_t)lds_part;
-            g.ranks = (const uint32_t *)((const unsigned char *)c->d_gen + o_ranks); g.n_spheres = (int)o.spheres.size();
-            g.root = o.g_root; g.first_medium = o.g_first_medium; g.n_chains = (int)(o.g_chains.size() / 2);
-            g.gx = o.g_c[0]; g.gy = o.g_c[1]; g.gz = o.g_c[2]; g.gR = o.g_R; g.mnear = o.g_mnear; g.kmin = o.g_kmin;
+            c->gen_bytes = (uint32_t)gi.lds_part;
+            g.ranks = (const uint32_t *)((const unsigned char *)c->d_gen + gi.o_ranks);
             c->gen = g;
             for (int k = 0; k < 3; k++) { c->gen_lo[k] = o.g_lo[k]; c->gen_hi[k] = o.g_hi[k]; }
             c->gen_reach = o.g_reach;
@@ -1072,6 +1093,31 @@ extern "C" int mort_hip_debug_gen_reach(const mort_world *w, float *out) {
     out[0] = 1;
     for (int k = 0; k < 3; k++) { out[1 + k] = o.g_lo[k]; out[4 + k] = o.g_hi[k]; }
     out[7] = o.g_reach;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the unified tree of a world and what mort_hip_upload_world decides
+ * from it (build_gen_image, MORT_NO_GEN aside) -- iout[0] 1 if the world has a unified tree (else the rest is 0), [1] nodes, [2] entries,
+ * [3] depth, [4] chain ids (id 0, no transform, included), [5] bytes of the LDS image before the primitives, [6] bytes of the primitives,
+ * [7] 1 if the primitives are in the image, [8] bytes of the LDS part of the image, [9] 1 if that is within MORT_GEN_IMAGE_MAX (the
+ * unified-tree kernels serve the world), [10] MORT_GEN_IMAGE_MAX, [11] the limit on image + primitives for the primitives to be in LDS,
+ * [12] nodes whose split the depth cap chose over the best surface-area split (gen_emit);
+ * fout[0] g_R, [1] g_mnear, [2] g_kmin, [3] g_reach, [4..6] g_c (gen_ray_setup's arguments). */
+extern "C" int mort_hip_debug_gen_tree(const mort_world *w, int *iout, float *fout) {
+    if (!w || !iout || !fout) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 13; i++) iout[i] = 0;
+    for (int i = 0; i < 7; i++) fout[i] = 0;
+    if (!o.g_ok) return MORT_OK;
+    GenImage gi;
+    build_gen_image(o, gi);
+    iout[0] = 1; iout[1] = (int)o.g_nodes.size(); iout[2] = (int)o.g_entries.size(); iout[3] = o.g_depth; iout[4] = gi.g.n_chains;
+    iout[5] = (int)gi.table_bytes; iout[6] = (int)gi.prim_bytes; iout[7] = gi.g.prims_in_lds; iout[8] = (int)gi.lds_part;
+    iout[9] = gi.fits ? 1 : 0; iout[10] = MORT_GEN_IMAGE_MAX; iout[11] = MORT_GEN_PRIMS_LDS_MAX; iout[12] = o.g_capped;
+    fout[0] = gi.g.gR; fout[1] = gi.g.mnear; fout[2] = gi.g.kmin; fout[3] = o.g_reach; fout[4] = gi.g.gx; fout[5] = gi.g.gy; fout[6] = gi.g.gz;
     return MORT_OK;
 }
 

@@ -59,6 +59,7 @@ struct Compiled {
     uint32_t g_root = 0xffffu;       /* child reference of the root (0xffff: no solid primitive at all) */
     int g_first_medium = 0;          /* items[g_first_medium ..) are the constant media, tested after the tree */
     int g_depth = 0;
+    int g_capped = 0;                /* nodes whose split the depth cap chose: the best SAH split would not have fitted below */
     float g_lo[3] = {0, 0, 0}, g_hi[3] = {0, 0, 0}; /* bounding box of the solids */
     float g_reach = 0;               /* ray origins must stay within this distance of that box (pads are sized for it) */
     /* spheres seen from far away: a ray whose origin is further than g_mnear - g_R from g_c widens its own error band
@@ -620,7 +621,7 @@ struct Compiler {
         }
         /* both halves must fit below: at most LEAF_MAX * 2^(left-1) primitives each */
         const long long cap = (long long)MORT_GEN_LEAF_MAX << (left - 1 < 40 ? left - 1 : 40);
-        double best = 1e300; int bax = 0, bsplit = n / 2;
+        double best = 1e300, best_any = 1e300; int bax = 0, bsplit = n / 2;
         std::vector<int> tmp(n);
         std::vector<double> ra(n);
         for (int ax = 0; ax < 3; ax++) {
@@ -630,13 +631,13 @@ struct Compiler {
             for (int i = n - 2; i >= 0; i--) { r = box_union(r, pr[tmp[i]].wb); ra[i] = box_area(r); }
             Box l = pr[tmp[0]].wb;
             for (int i = 1; i < n; i++) {
-                if (i <= cap && n - i <= cap) {
-                    const double c = box_area(l) * i + ra[i] * (n - i);
-                    if (c < best) { best = c; bax = ax; bsplit = i; }
-                }
+                const double c = box_area(l) * i + ra[i] * (n - i);
+                if (c < best_any) best_any = c;
+                if (i <= cap && n - i <= cap && c < best) { best = c; bax = ax; bsplit = i; }
                 l = box_union(l, pr[tmp[i]].wb);
             }
         }
+        if (best_any < best) out.g_capped++;
         std::stable_sort(ids.begin() + lo, ids.begin() + hi, [&](int a, int b) { return pr[a].wb.lo[bax] + pr[a].wb.hi[bax] < pr[b].wb.lo[bax] + pr[b].wb.hi[bax]; });
         const size_t me = out.g_nodes.size();
         out.g_nodes.push_back(DNodeQ{});
@@ -691,7 +692,7 @@ struct Compiler {
         out.g_ok = false;
         out.g_nodes.clear(); out.g_entries.clear(); out.g_chains.clear(); out.g_ranks.clear();
         gen_too_big = false;
-        out.g_root = 0xffffu; out.g_depth = 0;
+        out.g_root = 0xffffu; out.g_depth = 0; out.g_capped = 0;
         out.g_chains.push_back(0); out.g_chains.push_back(0); /* id 0: no transform */
         std::vector<GPrim> pr;
         bool seen_medium = false;

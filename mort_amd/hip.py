@@ -633,6 +633,26 @@ def debug_gen_reach(world):
     return dict(tree=bool(out[0]), lo=out[1:4].copy(), hi=out[4:7].copy(), reach=out[7])
 
 
+def debug_gen_tree(world):
+    """mort_hip_debug_gen_tree (host only): the unified tree of a world and what mort_hip_upload_world decides from it --
+    dict(tree, nodes, entries, depth, chains (chain ids, id 0 = no transform included), image_bytes (the LDS image before the
+    primitives), prim_bytes, prims_in_lds, lds_bytes (the LDS part of the image), fits (within image_max), image_max,
+    prims_lds_max (the limit on image + primitives), capped (nodes whose split the depth cap chose), R, mnear, kmin, reach (float32), centre (3,))."""
+    fn = lib().mort_hip_debug_gen_tree
+    fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+    iout = (C.c_int * 13)()
+    fout = np.zeros(7, dtype=np.float32)
+    st = fn(C.cast(world.ptr, C.c_void_p), iout, fout.ctypes.data)
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_gen_tree")
+    d = dict(zip(("tree", "nodes", "entries", "depth", "chains", "image_bytes", "prim_bytes", "prims_in_lds", "lds_bytes", "fits",
+                  "image_max", "prims_lds_max", "capped"), list(iout)))
+    for key in ("tree", "prims_in_lds", "fits"):
+        d[key] = bool(d[key])
+    d.update(R=fout[0], mnear=fout[1], kmin=fout[2], reach=fout[3], centre=fout[4:7].copy())
+    return d
+
+
 def _query_rays(rays):
     """rays as a contiguous RAY_DTYPE (n,) array: RAY_DTYPE already, or float32 (n, 8) = origin, direction, time, t_max"""
     rays = np.asarray(rays)

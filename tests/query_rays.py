@@ -50,6 +50,10 @@ def _bvh_random(name):
     return lambda: (Wd.bvh_random_case(name)[0], Wd.bvh_random_camera(name, 0, width=48))
 
 
+def _gen_random(name):
+    return lambda: (Wd.gen_random_case(name)[0], Wd.gen_random_camera(name, 0, width=48))
+
+
 def _random(seed):
     def make():  # the worlds of tests/test_features_oracle.py's random test, from its first view
         rng = np.random.default_rng(1000 + seed)
@@ -64,12 +68,18 @@ def _random(seed):
 # eight of BVH_RANDOM: every family, one `ties` world, one above the limit on the LDS images (ties_670: BVH_LIMIT_SIZES)
 BVH_RANDOM_PICK = ("uniform_64_s1", "cluster_300_s0", "scales_7_s0", "line_64_s0", "shells_300_s1", "ties_64_s0", "ties_670_s1", "uniform_2_s0")
 
+# six of GEN_RANDOM (worlds without a reference BVH, from their first camera): radii over four decades, a world 1e6 from
+# the origin, duplicates with the primitives outside the LDS image (ties_360: GEN_LIMIT_SIZES), 75 chain ids, the line at the
+# depth the catalogue's cap entries have below them, and the largest world the reference's tables hold
+GEN_RANDOM_PICK = ("scales_150_s0", "offset_150_s1", "ties_360_s0", "instances_150_s1", "line_150_s1", "mixed_3500_s0")
+
 WORLDS = {}
 WORLDS.update({f"scene{sid}": _scene(sid) for sid in range(1, 11)})
 WORLDS.update({f"flat:{n}": _flat(n) for n in Wd.FLAT_WORLDS})
 WORLDS.update({f"bvh:{n}": _bvh(n) for n in Wd.BVH_WORLDS})
 WORLDS.update({f"placed:{n}": _placed(n) for n in Wd.PLACED})
 WORLDS.update({f"bvhrandom:{n}": _bvh_random(n) for n in BVH_RANDOM_PICK})
+WORLDS.update({f"genrandom:{n}": _gen_random(n) for n in GEN_RANDOM_PICK})
 WORLDS.update({f"random:{k}": _random(k) for k in range(10)})
 
 # worlds without a solid primitive: no ray can hit a solid, so the hit-rate and occlusion censuses do not apply to them

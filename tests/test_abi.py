@@ -140,3 +140,27 @@ def test_four_wide_tree_on_small_and_random_worlds():
         assert n2 == leaves - 1 and depth2 <= 15, (name, list(out))
         assert 1 <= n4 <= max(1, n2 // 2 + 1) and reached == leaves and bad == 0 and same == 1, (name, list(out))
         assert slots == n4 - 1 + leaves and 1 <= stack4 <= 24, (name, list(out))
+
+
+def test_unified_tree_report():
+    """mort_hip_debug_gen_tree (host only, not in include/mort_hip.h): the unified tree of a world and what mort_hip_upload_world decides
+    from it, through the function the upload itself calls.  The Cornell box keeps its primitives in the LDS image, the final scene
+    does not; a reference-BVH world has no unified tree; NULL arguments are refused."""
+    import ctypes as C
+    from mort_amd import hip, host
+    assert "mort_hip_debug_gen_tree" not in hip.EXPORTS and "mort_hip_debug_gen_tree" not in declared("mort_hip.h", "mort_hip_")
+    t = hip.debug_gen_tree(host.build_scene(6, width=16, spp=1)[0])
+    assert (t["tree"], t["nodes"], t["entries"], t["depth"], t["chains"], t["image_bytes"], t["prim_bytes"]) == (True, 8, 13, 6, 2, 952, 2240)
+    assert t["prims_in_lds"] and t["fits"] and t["lds_bytes"] == 3104 and t["capped"] == 0
+    assert t["image_max"] == 124 * 1024 and t["prims_lds_max"] == 48 * 1024
+    assert t["mnear"] == 3 * t["R"] + 1 and t["kmin"] > 0 and t["reach"] == hip.debug_gen_reach(host.build_scene(6, width=16, spp=1)[0])["reach"]
+    t = hip.debug_gen_tree(host.build_scene(9, width=16, spp=1)[0])
+    assert (t["tree"], t["nodes"], t["entries"], t["depth"], t["image_bytes"], t["prim_bytes"]) == (True, 1999, 3408, 15, 78472, 456864)
+    assert not t["prims_in_lds"] and t["fits"] and t["lds_bytes"] == 78480
+    t = hip.debug_gen_tree(host.build_scene(1, width=16, spp=1)[0])
+    assert not t["tree"] and t["nodes"] == t["entries"] == t["lds_bytes"] == 0 and not t["fits"]
+    fn = hip.lib().mort_hip_debug_gen_tree
+    fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    w = host.build_scene(6, width=16, spp=1)[0]
+    i, f = (C.c_int * 13)(), (C.c_float * 7)()
+    assert fn(None, i, f) == -1 and fn(C.cast(w.ptr, C.c_void_p), None, f) == -1 and fn(C.cast(w.ptr, C.c_void_p), i, None) == -1

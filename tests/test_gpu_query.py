@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 # two awkward worlds (instances under chains in the tree; a list scanned after a medium: the item loop with media);
 # two random reference BVHs (one `ties`, one above the limit on the LDS images); three random worlds
 WORLDS = ("scene1", "scene3", "scene6", "scene7", "scene9", "scene10", "flat:boxes_and_instances", "flat:media_then_list",
-          "bvhrandom:ties_64_s0", "bvhrandom:ties_670_s1", "random:0", "random:3", "random:7")
+          "bvhrandom:ties_64_s0", "bvhrandom:ties_670_s1", "random:0", "random:3", "random:7") + tuple(f"genrandom:{n}" for n in Q.GEN_RANDOM_PICK)
 SIZES = (1, 63, 64, 65, 255, 256, 257, 1296)
 NO_WORLD, INVALID = -4, -1
 

@@ -16,9 +16,11 @@ pytestmark = pytest.mark.gpu
 
 # (world, bounce limit or None = the camera's, samples): scene 1 the item loop over a reference BVH; 6 light, quads, deep paths; 7
 # media and NaN; 9 the tree with its primitives in L2, shallow and deep (the deep one with one sample: the oracle's side of three
-# takes several seconds); a lit flat world with media; a PLACED world (a solid inside a medium, seen from outside)
+# takes several seconds); a lit flat world with media; a PLACED world (a solid inside a medium, seen from outside); and two of
+# tests/query_rays.py GEN_RANDOM_PICK: 75 chain ids with the primitives in LDS, duplicates with the primitives in L2
+GEN_RANDOM_CASES = ("genrandom:instances_150_s1", "genrandom:ties_360_s0")
 CASES = [(n, None, k) for n in ("scene1", "scene6", "scene7", "flat:lit_by_quad_with_media", "placed:solid_inside_medium") for k in (1, 3)] + \
-    [("scene9", 4, 1), ("scene9", 4, 3), ("scene9", 40, 1)]
+    [("scene9", 4, 1), ("scene9", 4, 3), ("scene9", 40, 1)] + [(n, 8, k) for n in GEN_RANDOM_CASES for k in (1, 3)]
 SIZES = (1, 63, 64, 65, 255, 256, 257, 1300)
 NO_WORLD, INVALID, CAPACITY = -4, -1, -7
 

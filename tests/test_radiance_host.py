@@ -19,7 +19,8 @@ F = np.float32
 
 SCENES = tuple(f"scene{k}" for k in range(1, 11))
 WORLDS = SCENES + tuple(n for n in Q.WORLDS if n.startswith(("flat:", "bvh:", "placed:"))) + \
-    ("bvhrandom:uniform_64_s1", "bvhrandom:ties_64_s0", "bvhrandom:ties_670_s1", "bvhrandom:uniform_2_s0")
+    ("bvhrandom:uniform_64_s1", "bvhrandom:ties_64_s0", "bvhrandom:ties_670_s1", "bvhrandom:uniform_2_s0") + \
+    ("genrandom:instances_150_s1", "genrandom:ties_360_s0")
 # the worlds every parameter is varied on: reference BVH, light + quads + deep paths, media + NaN, the final scene, a lit flat world
 VARIED = ("scene1", "scene6", "scene7", "scene9", "flat:lit_by_quad_with_media")
 TREES = [False, True]

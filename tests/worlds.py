@@ -670,3 +670,546 @@ def bvh_random_prediction(name):
     state = 1 if t["leaves"] < 2 else 2 if t["n4"] == 0 else 3
     fits = bool(im["fits"])
     return dict(tree=t, image=im, state=state, fits=fits, kernel="mega_bvh_kernel" if fits else "mega_kernel")
+
+
+# ---- random worlds WITHOUT a reference BVH (tests/test_gen_random_host.py, tests/test_gpu_gen_random.py) ----
+# mega_gen_kernel, wf_trav_gen and the tree forms of the feature and query kernels walk this build's unified tree
+# (scene_compile.h build_unified).  Each family below is aimed at one part of that builder or of dev_gen.h; the cameras are placed
+# with the tree's own constants (hip.debug_gen_tree): one where the static sphere pad applies (|o - G| <= 2 R + 1), one where the
+# per-ray band widens (beyond mnear, within reach), and on some entries one beyond reach.
+#
+# A family: (rng, n, seed) -> dict(prims, media, light, shift, scale).  A primitive is ("s", centre, radius, end of its motion or None) |
+# ("q", Q, u, v) | ("box", size, translation, degrees) (a rotated box: six quads under translate(rotate_y(list))) |
+# ("inst", kind, primitive, a, b) with kind "TR" translate a (rotate_y b degrees (primitive)), "TT" translate a (translate b
+# (primitive)), "T" translate a, "R" rotate_y b; followed by an optional material: "light", "glass", or None = drawn from the palette.
+# n counts the entries of the unified tree: a box is six of them, a medium's boundary is none.
+
+GEN_TRANSLATES = GEN_ROTATIONS = 50   # the reference's tables (objects.cuh)
+
+
+def _v(a):
+    return tuple(float(x) for x in a)
+
+
+def _gen_mixed_prims(rng, n, s=None, boxes=True, radii=(0.05, 0.2, 0.5, 0.9)):
+    """spheres (15 % moving, one ground sphere among them from 3 on), quads, up to two rotated boxes: n tree entries in a slab"""
+    nb = 0 if not boxes else 2 if n >= 30 else 1 if n >= 14 else 0
+    m = n - 6 * nb
+    ns = max(1, int(round(0.3 * m))) if m > 1 else m
+    nq = m - ns
+    s = s or max(1.5, 0.4 * float(np.sqrt(n)))
+    prims = []
+    for i in range(ns):
+        if i == 0 and ns >= 3:
+            prims.append(("s", (0.0, -1000.0, 0.0), 1000.0, None))       # ground: a giant among ordinary spheres
+            continue
+        c = (float(rng.uniform(-s, s)), float(rng.uniform(0.1, 2.2)), float(rng.uniform(-s, s)))
+        r = float(rng.choice(radii))
+        end = _v(np.asarray(c) + rng.uniform(-0.5, 0.5, 3)) if rng.random() < 0.15 else None
+        prims.append(("s", c, r, end))
+    for _ in range(nq):
+        q = (float(rng.uniform(-s, s)), float(rng.uniform(0.0, 2.5)), float(rng.uniform(-s, s)))
+        prims.append(("q", q, _v(rng.uniform(-1.2, 1.2, 3)), _v(rng.uniform(-1.2, 1.2, 3))))
+    for _ in range(nb):
+        prims.append(("box", _v(rng.uniform(0.4, 1.6, 3)), (float(rng.uniform(-s, s)), 0.0, float(rng.uniform(-s, s))), float(rng.uniform(-60, 60))))
+    return prims, s
+
+
+def _gen_media(rng, s, k):
+    return [((float(rng.uniform(-s, s)) * 0.6, 1.0, float(rng.uniform(-s, s)) * 0.6), float(rng.uniform(0.6, 1.8)), float(rng.uniform(0.1, 2.0))) for _ in range(k)]
+
+
+def _gfam_mixed(rng, n, seed):
+    prims, s = _gen_mixed_prims(rng, n)
+    light = n >= 5 and seed == 1
+    if light:
+        i = max(j for j, p in enumerate(prims) if p[0] == "q")
+        prims[i] = ("q", (-1.5, 5.0, -1.5), (3.0, 0.0, 0.0), (0.0, 0.0, 3.0), "light")
+    return dict(prims=prims, media=_gen_media(rng, s, 1 + seed) if n >= 47 else [], light=light)
+
+
+def _gfam_offset(rng, n, seed):
+    """a mixed world far from the origin: seed 0 about 3e4 away and 5 times as large, seed 1 about 1e6 away and 300 times as
+    large (one ulp of a coordinate is 0.06 there, and the tree's R carries 1e-3 of the distance from the origin)"""
+    prims, s = _gen_mixed_prims(rng, n, radii=(0.3, 0.5, 0.9))
+    return dict(prims=prims, media=_gen_media(rng, s, 1) if n >= 47 else [], light=False,
+                shift=((3e4, -2e4, 2.5e4), (1e6, 0.0, -1e6))[seed], scale=(5.0, 300.0)[seed])
+
+
+def _gfam_scales(rng, n, seed):
+    """spheres only, radii log-uniform over four decades (1e-3 .. 10), centres in a box of half side 4 whatever n is; seed 1 of the
+    sizes 2 and 3 draws every radius from the top of the range, so that all are giants"""
+    lo, hi = (0.9, 1.0) if (seed == 1 and n in (2, 3)) else (-3.0, 1.0)
+    return dict(prims=[("s", _v(rng.uniform(-4, 4, 3)), float(10.0 ** rng.uniform(lo, hi)), None) for _ in range(n)], media=[], light=False)
+
+
+def _gfam_quads(rng, n, seed):
+    """quads only: axis-aligned sheets on shared planes (zero extent on one axis), slivers with |u| / |v| about 1e3, and a floor and a
+    back wall that span the world next to small quads"""
+    s = max(2.0, 0.55 * float(n) ** (1.0 / 3.0) * 1.6)
+    prims = []
+    if n >= 3:
+        prims.append(("q", (-2 * s, -s, -2 * s), (4 * s, 0.0, 0.0), (0.0, 0.0, 4 * s)))     # floor
+    if n >= 5:
+        prims.append(("q", (-2 * s, -s, -s), (4 * s, 0.0, 0.0), (0.0, 3 * s, 0.0)))        # back wall
+    planes = [round(float(v), 1) for v in rng.uniform(-s, s, 4)]
+    while len(prims) < n:
+        k = rng.random()
+        a, b = float(rng.uniform(-s, s)), float(rng.uniform(-s, s))
+        if k < 0.5:                                  # a sheet in one of a few shared axis-aligned planes
+            ax = int(rng.integers(0, 3)); p = planes[int(rng.integers(0, len(planes)))]
+            e1, e2 = [j for j in range(3) if j != ax]
+            q = [0.0, 0.0, 0.0]; u = [0.0, 0.0, 0.0]; v = [0.0, 0.0, 0.0]
+            q[ax] = p; q[e1] = a; q[e2] = b; u[e1] = float(rng.uniform(0.3, 1.5)); v[e2] = float(rng.uniform(0.3, 1.5))
+            prims.append(("q", tuple(q), tuple(u), tuple(v)))
+        elif k < 0.7:                                # a sliver
+            d = rng.normal(size=3); d /= np.linalg.norm(d)
+            e = np.cross(d, rng.normal(size=3)); e /= np.linalg.norm(e)
+            L = float(rng.uniform(1.0, 2.0) * s)
+            prims.append(("q", (a, float(rng.uniform(-s, s)), b), _v(d * L), _v(e * L * 1e-3 * float(rng.uniform(0.5, 2.0)))))
+        else:
+            prims.append(("q", (a, float(rng.uniform(-s, s)), b), _v(rng.uniform(-1.0, 1.0, 3)), _v(rng.uniform(-1.0, 1.0, 3))))
+    return dict(prims=prims[:n], media=[], light=False)
+
+
+def _gfam_line(rng, n, seed):
+    """spheres and quads along a slanted line, size and spacing growing geometrically over four decades: the surface-area split
+    peels the large end off one primitive at a time until the depth cap takes over"""
+    g = 10.0 ** (4.0 / max(n - 1, 1))
+    d = np.array([1.0, 0.05, 0.3]); d /= np.linalg.norm(d)
+    prims, x = [], 0.0
+    for i in range(n):
+        r = 0.01 * g ** i
+        c = d * x + rng.uniform(-0.2, 0.2, 3) * r
+        if i % 3 == 2:
+            e1 = np.cross(d, (0.0, 1.0, 0.0)); e1 /= np.linalg.norm(e1)
+            e2 = np.cross(d, e1)
+            prims.append(("q", _v(c - r * (e1 + e2)), _v(2 * r * e1 + 0.3 * r * d), _v(2 * r * e2)))
+        else:
+            prims.append(("s", _v(c), float(r), None))
+        x += 1.2 * r * (1.0 + g)
+    return dict(prims=prims, media=[], light=False)
+
+
+def _gfam_ties(rng, n, seed):
+    """groups of two to five identical spheres (a moving one repeats its motion) and identical quads, and quads lying in another
+    quad's plane: equal t, which the scan order decides"""
+    s = max(1.5, 0.4 * float(np.sqrt(n)))
+    prims = [("s", (0.0, -1000.0, 0.0), 1000.0, None)] if n >= 6 else []
+    while len(prims) < n:
+        k = min(int(rng.integers(2, 6)), n - len(prims))
+        c = (float(rng.uniform(-s, s)), float(rng.uniform(0.2, 2.2)), float(rng.uniform(-s, s)))
+        kind = rng.random()
+        if kind < 0.5:
+            r = float(rng.uniform(0.2, 0.8))
+            end = _v(np.asarray(c) + rng.uniform(-0.5, 0.5, 3)) if rng.random() < 0.15 else None
+            prims += [("s", c, r, end)] * k
+        else:
+            u, v = rng.uniform(-1.5, 1.5, 3), rng.uniform(-1.5, 1.5, 3)
+            if kind < 0.8:
+                prims += [("q", c, _v(u), _v(v))] * k
+            else:                                    # smaller quads inside the first one's parallelogram
+                prims.append(("q", c, _v(u), _v(v)))
+                for j in range(1, k):
+                    f = 0.5 ** j
+                    prims.append(("q", _v(np.asarray(c) + 0.25 * u + 0.25 * v), _v(u * f), _v(v * f)))
+    prims = prims[:1] + [prims[1:][int(i)] for i in rng.permutation(len(prims) - 1)] if len(prims) > 2 else prims
+    return dict(prims=prims, media=_gen_media(rng, s, 1) if n >= 47 else [], light=False)
+
+
+def _gfam_instances(rng, n, seed):
+    """single spheres (some moving) and quads under translate(rotate_y()), translate(translate()), translate() and rotate_y() until
+    the reference's 50 translates and 50 rotations are used up, two rotated boxes (six quads sharing one chain each) from 30
+    primitives on, and plain primitives for the rest of n"""
+    nb = 2 if n >= 30 else 1 if n >= 14 else 0
+    T = GEN_TRANSLATES - nb; R = GEN_ROTATIONS - nb
+    s = max(1.5, 0.4 * float(np.sqrt(n)))
+    prims = []
+    kinds = ("TR", "TT", "T", "R")
+    i = 0
+    while len(prims) < n - 6 * nb:
+        kind = kinds[i % 4]; i += 1
+        need = {"TR": (1, 1), "TT": (2, 0), "T": (1, 0), "R": (0, 1)}[kind]
+        if need[0] > T or need[1] > R:
+            if T == 0 and R == 0 or i > 400:
+                break
+            continue
+        T -= need[0]; R -= need[1]
+        if rng.random() < 0.6:
+            c = _v(rng.uniform(-0.3, 0.3, 3))
+            end = _v(np.asarray(c) + rng.uniform(-0.4, 0.4, 3)) if rng.random() < 0.25 else None
+            base = ("s", c, float(rng.uniform(0.15, 0.7)), end)
+        else:
+            base = ("q", _v(rng.uniform(-0.5, 0.5, 3)), _v(rng.uniform(-1.2, 1.2, 3)), _v(rng.uniform(-1.2, 1.2, 3)))
+        a = (float(rng.uniform(-s, s)), float(rng.uniform(0.3, 2.2)), float(rng.uniform(-s, s)))
+        if kind == "R":                              # a rotation about the y axis keeps the distance from it: place the primitive itself
+            base = (base[0], _v(np.asarray(base[1]) + a)) + base[2:]
+            if base[0] == "s" and base[3] is not None:
+                base = base[:3] + (_v(np.asarray(base[3]) + a),)
+        b = float(rng.uniform(-80, 80)) if kind in ("TR", "R") else _v(rng.uniform(-0.5, 0.5, 3))
+        prims.append(("inst", kind, base, a, b))
+    rest = n - 6 * nb - len(prims)
+    if rest > 0:
+        prims += _gen_mixed_prims(rng, rest, s, boxes=False)[0]
+    for _ in range(nb):
+        prims.append(("box", _v(rng.uniform(0.4, 1.6, 3)), (float(rng.uniform(-s, s)), 0.0, float(rng.uniform(-s, s))), float(rng.uniform(-60, 60))))
+    return dict(prims=prims, media=[], light=False)
+
+
+_GEN_FAMILY = {"mixed": _gfam_mixed, "scales": _gfam_scales, "offset": _gfam_offset, "quads": _gfam_quads, "line": _gfam_line,
+               "ties": _gfam_ties, "instances": _gfam_instances}
+GEN_FAMILIES = tuple(_GEN_FAMILY)
+
+
+def _rot_y(p, deg):
+    st, ct = np.sin(np.radians(deg)), np.cos(np.radians(deg))
+    p = np.asarray(p, float)
+    return np.array([ct * p[0] + st * p[2], p[1], -st * p[0] + ct * p[2]])
+
+
+def _covered_gen(frm, at, vfov, cen, rad, Q, U, V, nx=16, ny=9):
+    """share of an nx x ny grid of pinhole rays of a 16:9 camera that meet a sphere (cen (n, 3), rad) or a quad (Q, U, V (m, 3))"""
+    frm, at = np.asarray(frm, float), np.asarray(at, float)
+    wv = frm - at; wv /= np.linalg.norm(wv)
+    uv = np.cross((0.0, 1.0, 0.0), wv)
+    if np.linalg.norm(uv) < 1e-9:
+        uv = np.array([1.0, 0.0, 0.0])
+    uv /= np.linalg.norm(uv)
+    vv = np.cross(wv, uv)
+    h = np.tan(np.radians(vfov) / 2)
+    xs = ((np.arange(nx) + 0.5) / nx * 2 - 1) * h * 16 / 9
+    ys = ((np.arange(ny) + 0.5) / ny * 2 - 1) * h
+    d = (xs[None, :, None] * uv + ys[:, None, None] * vv - wv).reshape(-1, 3)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    hit = np.zeros(len(d), bool)
+    if len(cen):
+        oc = cen - frm
+        b = d @ oc.T
+        c = (oc * oc).sum(1) - rad * rad
+        hit |= (((b > 0) & (b * b > c[None, :])) | (c[None, :] < 0)).any(1)
+    if len(Q):
+        n = np.cross(U, V)
+        w = n / np.maximum((n * n).sum(1, keepdims=True), 1e-300)
+        den = d @ n.T                                             # (rays, m)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = ((Q - frm) * n).sum(1)[None, :] / den
+            p = frm[None, None, :] + t[:, :, None] * d[:, None, :] - Q[None, :, :]
+            al = (w[None] * np.cross(p, V[None])).sum(2)
+            be = (w[None] * np.cross(U[None], p)).sum(2)
+            hit |= ((t > 1e-3) & (al >= 0) & (al <= 1) & (be >= 0) & (be <= 1)).any(1)
+    return float(hit.mean())
+
+
+_GEN_VFOVS = (1, 2, 3, 5, 8, 12, 18, 26, 36, 48, 62, 78)
+_GEN_DIRS = ((0.25, 0.45, 1.0), (1.0, 0.3, 0.35), (-0.8, 0.6, 0.5), (-0.3, 0.2, -1.0), (0.6, 1.0, -0.4))
+
+
+def _gen_far(pos, t):
+    """gen_ray_setup's `far` for an origin, in float32 as the device computes it"""
+    F = np.float32
+    e = [F(F(pos[k]) - t["centre"][k]) for k in range(3)]
+    return F(F(np.sqrt(F(F(F(e[0] * e[0]) + F(e[1] * e[1])) + F(e[2] * e[2])))) * F(1.000001)) + t["R"]
+
+
+def gen_in_reach(pos, rad, reach):
+    """camera_in_reach (mort_ctx.h) for a camera centre and lens radius, in float32"""
+    F = np.float32
+    return all(F(F(pos[k]) - F(rad)) >= F(reach["lo"][k] - reach["reach"]) and F(F(pos[k]) + F(rad)) <= F(reach["hi"][k] + reach["reach"]) for k in range(3))
+
+
+def _gen_fit(proxy, cands, want):
+    """the (lookfrom, lookat, vfov) among the candidates (lookfrom, lookat) and the whole-degree fields of view whose frame the
+    primitives cover most nearly to the share `want`"""
+    best = None
+    for frm, at in cands:
+        lo, hi = 0, len(_GEN_VFOVS) - 1
+        tried = {}
+        while lo <= hi:                                # coverage falls as the field of view widens about a target that is hit
+            mid = (lo + hi) // 2
+            tried[mid] = cov = _covered_gen(frm, at, _GEN_VFOVS[mid], *proxy)
+            if cov > want:
+                lo = mid + 1
+            else:
+                hi = mid - 1
+        for i, cov in tried.items():
+            if best is None or abs(cov - want) < abs(best[0] - want):
+                best = (cov, frm, at, _GEN_VFOVS[i])
+    return _v(best[1]), _v(best[2]), best[3]
+
+
+def random_gen_world(rng, n, family, seed, far_view=False, tele_view=False):
+    """A world without a reference BVH of n tree entries of `family`, materials from a small shared palette.
+    Returns (world, views, light, info): views (lookfrom, lookat, vfov, defocus_angle) for set_view -- view 0 within 2 R + 1 of the
+    tree's centre, view 1 beyond mnear within reach, then (far_view) one beyond reach and (tele_view) ("tele", origin, target, span):
+    a telescope (tests/grazing.py microscope) four fifths of the reach away, whose square viewport frames the field of ordinary
+    spheres -- there u |oc|^2 exceeds the small spheres' r^2, sphere::hit accepts rays that pass far outside every static pad, and
+    only the per-ray band of gen_ray_setup keeps the walk from pruning them; light = (type, index) of the quad light or None;
+    info = dict(spheres = world-space (centre, end, radius) of the tree's spheres, moving, instances, shift)."""
+    from mort_amd import hip
+    L = host.lib()
+    w = host.World()
+    pal = _bvh_palette(w, rng, True)
+    spec = _GEN_FAMILY[family](rng, n, seed)
+    shift = np.asarray(spec.get("shift", (0.0, 0.0, 0.0)), float); scale = float(spec.get("scale", 1.0))
+    lightmat = None
+    light = None
+    sph, quads = [], []                                  # world-space proxies: (c1, c2, r), (Q, u, v)
+    moving = instances = 0
+
+    def mat(p, k):
+        nonlocal lightmat
+        if len(p) > k and p[k] == "light":
+            if lightmat is None:
+                col = _ok(L.mort_add_solid_color(w.ptr, host.vec3(7, 7, 7)), "mort_add_solid_color")
+                lightmat = (S.MAT_DIFFUSE_LIGHT, _ok(L.mort_add_diffuse_light(w.ptr, S.TEXTURE_SOLID, col), "mort_add_diffuse_light"))
+            return lightmat
+        return pal[int(rng.integers(0, len(pal)))]
+
+    def place(x):                                        # the family's coordinates -> the world's
+        return np.asarray(x, float) * scale + shift
+
+    def add(p, skip, to_world, top):
+        """adds a sphere or a quad (coordinates already final, in its own frame); to_world maps a point of that frame to the world"""
+        nonlocal moving, light
+        if p[0] == "s":
+            mt, mi = mat(p, 4)
+            c, r, end = np.asarray(p[1], float), float(p[2]), p[3]
+            if end is not None:
+                moving += 1
+                i = _ok(L.mort_add_moving_sphere(w.ptr, host.vec3(*c), host.vec3(*end), r, mt, mi, skip), "mort_add_moving_sphere")
+            else:
+                i = _ok(L.mort_add_sphere(w.ptr, host.vec3(*c), r, mt, mi, skip), "mort_add_sphere")
+            sph.append((to_world(c), to_world(c if end is None else end), r))
+            return S.OBJ_SPHERE, i
+        mt, mi = mat(p, 4)
+        q, u, v = (np.asarray(x, float) for x in p[1:4])
+        i = _ok(L.mort_add_quad(w.ptr, host.vec3(*q), host.vec3(*u), host.vec3(*v), mt, mi, skip), "mort_add_quad")
+        if mt == S.MAT_DIFFUSE_LIGHT and top:
+            light = (S.OBJ_QUAD, i)
+        o = to_world(q)
+        quads.append((o, to_world(q + u) - o, to_world(q + v) - o))
+        return S.OBJ_QUAD, i
+
+    def scaled(p, with_shift):
+        sh = shift if with_shift else 0.0
+        if p[0] == "s":
+            return ("s", _v(np.asarray(p[1], float) * scale + sh), p[2] * scale, None if p[3] is None else _v(np.asarray(p[3], float) * scale + sh)) + tuple(p[4:])
+        return ("q", _v(np.asarray(p[1], float) * scale + sh), _v(np.asarray(p[2], float) * scale), _v(np.asarray(p[3], float) * scale)) + tuple(p[4:])
+
+    for p in spec["prims"]:
+        if p[0] in ("s", "q"):
+            add(scaled(p, True), False, lambda x: np.asarray(x, float), True)
+        elif p[0] == "box":
+            size, tr, deg = np.asarray(p[1], float) * scale, place(p[2]), p[3]
+            mt, mi = mat(p, 4)
+            L.mort_rotated_box(w.ptr, host.vec3(*size), host.vec3(*tr), deg, mt, mi)
+            f = lambda x, tr=tr, deg=deg: _rot_y(x, deg) + tr
+            for q, u, v in (((0, 0, size[2]), (size[0], 0, 0), (0, size[1], 0)), ((size[0], 0, size[2]), (0, 0, -size[2]), (0, size[1], 0)),
+                            ((size[0], 0, 0), (-size[0], 0, 0), (0, size[1], 0)), ((0, 0, 0), (0, 0, size[2]), (0, size[1], 0)),
+                            ((0, size[1], size[2]), (size[0], 0, 0), (0, 0, -size[2])), ((0, 0, 0), (size[0], 0, 0), (0, 0, size[2]))):
+                q, u, v = (np.asarray(x, float) for x in (q, u, v))
+                quads.append((f(q), f(q + u) - f(q), f(q + v) - f(q)))
+            instances += 1
+        else:
+            _, kind, base, a, b = p
+            a = np.asarray(a, float)
+            instances += 1
+            if kind == "TR":
+                f = lambda x, a=a, b=b: _rot_y(x, b) + a
+                t, i = add(base, True, f, False)
+                r = _ok(L.mort_add_rotate_y(w.ptr, t, i, b, True), "mort_add_rotate_y")
+                _ok(L.mort_add_translate(w.ptr, S.OBJ_ROTATE_Y, r, host.vec3(*a), False), "mort_add_translate")
+            elif kind == "TT":
+                bb = np.asarray(b, float)
+                f = lambda x, a=a, bb=bb: np.asarray(x, float) + bb + a
+                t, i = add(base, True, f, False)
+                r = _ok(L.mort_add_translate(w.ptr, t, i, host.vec3(*bb), True), "mort_add_translate")
+                _ok(L.mort_add_translate(w.ptr, S.OBJ_TRANSLATE, r, host.vec3(*a), False), "mort_add_translate")
+            elif kind == "T":
+                f = lambda x, a=a: np.asarray(x, float) + a
+                t, i = add(base, True, f, False)
+                _ok(L.mort_add_translate(w.ptr, t, i, host.vec3(*a), False), "mort_add_translate")
+            else:
+                f = lambda x, b=b: _rot_y(x, b)
+                t, i = add(base, True, f, False)
+                _ok(L.mort_add_rotate_y(w.ptr, t, i, b, False), "mort_add_rotate_y")
+    iso = None
+    for centre, radius, density in spec["media"]:
+        bnd = _ok(L.mort_add_sphere(w.ptr, host.vec3(*place(centre)), radius * scale, pal[-2][0], pal[-2][1], True), "mort_add_sphere")
+        if iso is None:
+            col = _ok(L.mort_add_solid_color(w.ptr, host.vec3(.8, .8, .9)), "mort_add_solid_color")
+            iso = _ok(L.mort_add_isotropic(w.ptr, S.TEXTURE_SOLID, col), "mort_add_isotropic")
+        _ok(L.mort_add_constant_medium(w.ptr, S.OBJ_SPHERE, bnd, density / scale, S.MAT_ISOTROPIC, iso, False), "mort_add_constant_medium")
+    w.c.bvh_mode = False
+
+    # ---- cameras, from the tree's own constants ----
+    t = hip.debug_gen_tree(w); reach = hip.debug_gen_reach(w)
+    assert t["tree"] and t["entries"] == n, (family, n, t)
+    cen = np.array([0.5 * (a + b) for a, b, _ in sph], float).reshape(-1, 3)
+    rad = np.array([r for _, _, r in sph], float)
+    Q = np.array([q for q, _, _ in quads], float).reshape(-1, 3)
+    U = np.array([u for _, u, _ in quads], float).reshape(-1, 3)
+    V = np.array([v for _, _, v in quads], float).reshape(-1, 3)
+    if len(Q) > 500:                                    # fitting only: every k-th quad behind the first eight is enough
+        keep = np.r_[0:8, 8:len(Q):-(-len(Q) // 500)]
+        Q, U, V = Q[keep], U[keep], V[keep]
+    proxy = (cen, rad, Q, U, V)
+    G = t["centre"].astype(float)
+    near = 2.0 * float(t["R"]) + 1.0
+    lo, hi = reach["lo"].astype(float), reach["hi"].astype(float)
+    mid = 0.5 * (lo + hi)
+    big = family == "line"                              # the line is seen at its large end
+    aim = [G] if not big else [np.asarray(sph[-1][0] if spec["prims"][-1][0] == "s" else quads[-1][0], float)]
+    if len(cen) == 0:
+        aim = [mid * 0.3, np.array([0.0, -0.5 * (hi[1] - lo[1]), -0.4 * (hi[2] - lo[2])])]
+    if not big:                                         # a few primitives leave the middle empty: aim at one of them as well
+        pc = np.concatenate([cen, Q + 0.5 * (U + V)]) if len(Q) else cen
+        ps = np.concatenate([rad, 0.5 * np.sqrt(np.linalg.norm(np.cross(U, V), axis=1))]) if len(Q) else rad
+        ordinary = ps <= max(near, 0.25 * np.linalg.norm(hi - lo))
+        if ordinary.any():
+            idx = np.flatnonzero(ordinary)
+            aim.append(pc[idx[np.argmax(ps[idx])]])
+            aim.append(pc[idx[np.argmin(np.linalg.norm(pc[idx] - aim[0], axis=1))]])
+    dirs = [np.asarray(d, float) / np.linalg.norm(d) for d in (_GEN_DIRS if n <= 600 else _GEN_DIRS[:3])]
+    views = []
+    cands = []
+    for d in dirs:
+        for f in (0.93, 0.6, 0.3) + ((0.1,) if n <= 150 else ()):
+            pos = G + d * f * near
+            if _gen_far(pos, t) > t["mnear"]:
+                continue
+            for at in aim:
+                if np.linalg.norm(at - pos) > 1e-6 * (1 + np.abs(pos).max()):
+                    cands.append((pos, at))
+            if len(cen) == 0 or f == 0.3:
+                cands.append((pos, pos - d + np.array([0.0, -0.4, 0.0])))          # outwards and down
+    views.append(_gen_fit(proxy, cands, 0.6) + (0.0,))
+    cands = []
+    lens = 0.3 if (n % 2 == 1 and seed == 1) else 0.0
+    outer = [np.linalg.norm(c - G) + r for c, r in zip(cen, rad) if r < 500.0 * scale]   # the ground aside, from outside every sphere too
+    for d in dirs:
+        for f in (1.08, 1.5, 2.5) + ((1.6 * max(outer) / near,) if outer and 1.6 * max(outer) > 1.08 * near else ()):
+            if len(cen) == 0:                           # no sphere, no band to widen (mnear = 1e30, kmin = 0): a camera outside the solids' box
+                pos = mid + d * (0.8 + 0.5 * f) * np.linalg.norm(hi - lo)
+            else:
+                pos = G + d * (f * near + 1e-3 * np.abs(G).max())
+                if not (_gen_far(pos, t) > t["mnear"]):
+                    continue
+            if not gen_in_reach(pos, 0.2 * np.linalg.norm(pos - G), reach):
+                continue
+            for at in aim:
+                cands.append((pos, at))
+    views.append(_gen_fit(proxy, cands, 0.6) + (lens,))
+    if far_view:
+        d = dirs[0]
+        k = 1.05
+        while True:
+            pos = mid + d * k * (float(reach["reach"]) + np.linalg.norm(hi - lo)) / np.abs(d).max()
+            if not gen_in_reach(pos, 0.0, reach):
+                break
+            k *= 1.1
+        views.append(_gen_fit(proxy, [(pos, a) for a in aim + [mid]], 0.6) + (0.0,))
+    if tele_view:
+        d = np.array([0.6, 0.02, 0.8]); d /= np.linalg.norm(d)
+        dist = 0.8 * float(reach["reach"]) / np.abs(d).max()
+        while not gen_in_reach(G + d * dist, 0.0, reach):
+            dist *= 0.9
+        span = 2.4 * max(float(t["R"]) - 1e-3 * (1.0 + np.abs(np.r_[lo, hi]).max()), 1.0)
+        views.append(("tele", _v(G + d * dist), _v(G + np.array([0.0, 0.15 * span, 0.0])), span))
+    info = dict(spheres=sph, moving=moving, instances=instances, shift=shift, scale=scale, n_spheres=len(sph), n_quads=len(quads))
+    return w, views, light, info
+
+
+# The catalogue: name -> (family, tree entries, seed).  Two seeds of every family at 1 (not `ties`: a tie takes two), 2, 3, 5, 47 and
+# 48 (the two sides of the default MORT_GEN_MIN_PRIMS), 150, the family's sizes just below and just above the 48 KB rule that puts
+# the primitives into the LDS image (mort_hip.hip build_gen_image; found on the CPU with hip.debug_gen_tree,
+# tests/test_gen_random_host.py holds the census) and 1000; `mixed` and `quads` once more near the capacity of the reference's
+# sphere and quad tables.
+GEN_LIMIT_SIZES = {"mixed": (300, 310), "scales": (540, 550), "offset": (300, 310), "quads": (260, 270), "line": (390, 410), "ties": (330, 360),
+                   "instances": (290, 300)}
+GEN_CAPACITY_SIZES = {"mixed": 3500, "quads": 2490}
+GEN_SMALL_SIZES = (1, 2, 3, 5, 47, 48, 150)
+
+
+def gen_random_sizes(fam):
+    return tuple(n for n in GEN_SMALL_SIZES if not (fam == "ties" and n == 1)) + GEN_LIMIT_SIZES[fam] + (1000,) + \
+        ((GEN_CAPACITY_SIZES[fam],) if fam in GEN_CAPACITY_SIZES else ())
+
+
+GEN_RANDOM = {f"{fam}_{n}_s{seed}": (fam, n, seed) for fam in GEN_FAMILIES for n in gen_random_sizes(fam) for seed in (0, 1)}
+# the entries with a third camera, beyond the tree's reach: the one-lane kernel renders it, wavefront mode refuses it
+# the entries with a telescope as their last camera: the families with a ground sphere at the origin (so a reach of thousands of
+# units), at the sizes from 150 on (smaller fields, and the far-away and all-sizes worlds, leave such a frame without sky)
+GEN_TELE_FAMILIES = ("mixed", "ties", "instances")
+GEN_FAR_VIEWS = tuple(f"{fam}_{n}_s0" for fam in ("mixed", "scales", "quads", "ties", "instances") for n in (5, 150))
+_gen_random_built = {}
+
+
+def gen_has_tele(name):
+    fam, n, _ = GEN_RANDOM[name]
+    return fam in GEN_TELE_FAMILIES and n >= 150
+
+
+def gen_random_case(name):
+    """(world, views, light, info) of a catalogue entry, built once per process; nothing may change the world"""
+    if name not in _gen_random_built:
+        fam, n, seed = GEN_RANDOM[name]
+        rng = np.random.default_rng([seed, n, GEN_FAMILIES.index(fam)])
+        _gen_random_built[name] = random_gen_world(rng, n, fam, seed, far_view=name in GEN_FAR_VIEWS, tele_view=gen_has_tele(name))
+    return _gen_random_built[name]
+
+
+def gen_random_camera(name, k, width=None):
+    """view k of a catalogue entry as a 16 : 9 camera, 64 wide up to 150 primitives, 48 wide up to 1100, 32 beyond: 4 spp (9 on
+    every seventh (entry, view) pair), bounce limits from 2 to 20 in turn; the world's quad light, if it has one, is the camera's
+    light object."""
+    _, views, light, _ = gen_random_case(name)
+    n = GEN_RANDOM[name][1]
+    i = sorted(GEN_RANDOM).index(name) * 3 + k
+    cam = flat_camera(light=light, spp=9 if i % 7 == 0 else 4, width=width or (64 if n <= 150 else 48 if n <= 1100 else 32), depth=(2, 5, 8, 12, 20)[i % 5])
+    if views[k][0] == "tele":
+        from tests.grazing import microscope
+        microscope(cam, views[k][1], views[k][2], views[k][3], W=cam.image_width, H=cam.image_height)
+        cam.samples_per_pixel, cam.sqrt_spp, cam.recip_sqrt_spp, cam.pixel_samples_scale = 4, 2, 0.5, 0.25
+        return cam
+    frm, at, vfov, defocus = views[k]
+    set_view(cam, frm, at, vfov=vfov, defocus=defocus)
+    return cam
+
+
+def gen_camera_lens(cam):
+    """the lens radius choose_family widens camera_in_reach by, in float32"""
+    F = np.float32
+    r = F(0)
+    for v in (cam.defocus_disk_u, cam.defocus_disk_v):
+        for k in range(3):
+            r = F(r + F(abs(F(v.e[k]))))
+    return r
+
+
+GEN_MIN_PRIMS = 48  # the default of MORT_GEN_MIN_PRIMS (mort_hip.hip choose_family)
+
+
+def gen_random_prediction(name, min_prims=GEN_MIN_PRIMS):
+    """What the host will decide for a catalogue entry, from the two device-free debug entries of libmort_hip.so:
+    dict(tree = the facts of mort_hip_debug_gen_tree, has_tree, prims_in_lds, in_reach[k], near[k] (gen_ray_setup leaves the
+    camera centre's band alone), kernel[k] = the family megakernel mode renders view k with: mega_gen_kernel where the camera
+    is in reach and the tree has at least min_prims entries, else mega_kernel)"""
+    from mort_amd import hip
+    w, views, _, _ = gen_random_case(name)
+    t, reach = hip.debug_gen_tree(w), hip.debug_gen_reach(w)
+    ok = t["tree"] and t["fits"]
+    inr, near, kern = [], [], []
+    for k in range(len(views)):
+        cam = gen_random_camera(name, k)
+        pos = [cam.center.e[j] for j in range(3)]
+        inr.append(bool(ok and gen_in_reach(pos, gen_camera_lens(cam), reach)))
+        near.append(bool(not (_gen_far(pos, t) > t["mnear"])))
+        kern.append("mega_gen_kernel" if inr[-1] and t["entries"] >= min_prims else "mega_kernel")
+    return dict(tree=t, reach=reach, has_tree=bool(ok), prims_in_lds=bool(t["prims_in_lds"]), in_reach=inr, near=near, kernel=kern)
+
+
+# the near views that stand inside a sphere: the ball |o - G| <= 2 R + 1 the first camera must lie in is inside a sphere that is the
+# whole world, or a giant, or the large end of the line -- (almost) no background to see
+GEN_INTERIOR_VIEWS = (("line_2_s0", 0), ("mixed_1_s1", 0), ("mixed_2_s0", 0), ("scales_1000_s1", 0), ("scales_1_s1", 0), ("scales_2_s1", 0),
+                      ("scales_3_s1", 0), ("scales_550_s1", 0))
