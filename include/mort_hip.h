@@ -409,6 +409,56 @@ int mort_hip_query_radiance_device(mort_ctx *ctx, const mort_radiance_params *pa
 int mort_hip_query_radiance_host(const mort_world *world, const mort_radiance_params *params, size_t n, const mort_ray *rays,
                                  mort_rng_state *states, int nthreads, int flags, float *rgb_out, double *seconds);
 
+/* ---- light probes: path-traced radiance projected onto SH9 on the device.  For each probe position the nine
+ * real spherical-harmonics coefficients (bands 0..2) per colour channel of the incoming radiance: one fused kernel builds the
+ * rays in registers, runs the radiance queries' own path body and reduces in the wave, so 108 bytes per probe leave the device.
+ * The summation order below is part of the contract: GPU kernel, host loop and any restatement of it agree to the bit.
+ *
+ * For probe p and direction j < D (D = params->directions), everything fp32 and nothing contracted:
+ *   ray      origin position_p, direction dirs[j] exactly as given (NOT normalised), time time_p; searched as a radiance query
+ *            searches, [0.001, inf).
+ *   stream   states[p D + j], advanced in place (only d and v[] are written; a direction that draws nothing keeps its bits).
+ *   s_j      ((0 + c_1) + c_2) + ... + c_samples, the radiance query's sum of rp.samples paths.
+ *   g_j      s_j with every component c != c replaced by 0 (the render's NaN guard).
+ *   Y_k      with (x, y, z) = dirs[j], c0 = 0.2820948f, c1 = 0.4886025f, c2 = 1.0925484f, c3 = 0.31539157f, c4 = 0.5462742f:
+ *            Y0 = c0, Y1 = c1*y, Y2 = c1*z, Y3 = c1*x, Y4 = (c2*x)*y, Y5 = (c2*y)*z, Y6 = c3*((3.0f*z)*z - 1.0f), Y7 = (c2*x)*z,
+ *            Y8 = c4*(x*x - y*y).
+ *   term     term[j][k][ch] = Y_k * g_j[ch].
+ *   sum      directions in batches of 64; within a batch the 64 terms are summed by a balanced binary tree over neighbouring
+ *            indices (x = x[0::2] + x[1::2], six times); the batch sums are added in ascending batch order starting from batch
+ *            0's sum (no leading 0 +); sh_out[p][k][ch] = scale * acc, scale = (float)(4 pi / (double)(D samples)).
+ *
+ * dirs == NULL is the library's own set, the spherical Fibonacci points, computed in double and rounded once to float:
+ * z = 1.0 - (2.0 j + 1.0) / D, r = sqrt(1.0 - z z), phi = j * (pi * (3.0 - sqrt(5.0))), the point (r cos phi, r sin phi, z);
+ * mort_hip_probe_directions writes it and needs no GPU.  The _device form keeps the set of the last D in a buffer the context
+ * owns.  A caller's own set must be equal-weight; that is not checked.  Zero-length, non-finite and unnormalised directions are
+ * legal: the answer is the formulas'.
+ *
+ * mort_hip_sh9_irradiance (plain host code): E(n) = sum_k A_l(k) sh[k] Y_k(n) per channel, A_0 = pi, A_1 = 2 pi / 3, A_2 = pi / 4
+ * (Ramamoorthi-Hanrahan), Y_k the expressions above with the same constants, evaluated in double and rounded once; `normal`
+ * is used as given and should be of unit length.
+ *
+ * Forms, `seconds`, alignment and overlap as for the queries; the streams count as an output.  NULL params, probes, states or
+ * sh_out, directions outside 64..4096 or not a multiple of 64, samples < 1, n D above the queries' ray limit (or n above
+ * 2^31 - 1: one workgroup per probe) and overlapping buffers are MORT_ERR_INVALID; bounce_limit and the light object are checked
+ * as the radiance queries check them.  n == 0 is MORT_OK and launches nothing.  The calls need an uploaded world (else
+ * MORT_ERR_NO_WORLD) but no seeded pixel RNG, ignore the partition, and touch nothing the render keeps across frames. ---- */
+typedef struct mort_probe { float position[3]; float time; } mort_probe; /* 16 B */
+typedef struct mort_probe_params {
+    mort_radiance_params rp; /* bounce_limit, samples (paths per direction), background, light object: as for the radiance queries */
+    int directions;          /* D: 64..4096, a multiple of 64 */
+} mort_probe_params;
+#define MORT_SH9_FLOATS 27 /* [9 coefficients][3 channels] per probe */
+MORT_SA(sizeof(mort_probe) == 16 && sizeof(mort_probe_params) == sizeof(mort_radiance_params) + 4, "light probe layout");
+int mort_hip_probe_directions(int directions, float *dirs_out /* 3 D */);
+int mort_hip_probe_bake(mort_ctx *ctx, const mort_probe_params *params, size_t n, const mort_probe *probes, const float *dirs /* 3 D or NULL */,
+                        mort_rng_state *states /* n D */, float *sh_out /* 27 n */, double *seconds);
+int mort_hip_probe_bake_device(mort_ctx *ctx, const mort_probe_params *params, size_t n, const void *d_probes, const void *d_dirs /* or NULL */,
+                               void *d_states, void *d_sh_out, void *stream, double *seconds);
+int mort_hip_probe_bake_host(const mort_world *world, const mort_probe_params *params, size_t n, const mort_probe *probes, const float *dirs,
+                             mort_rng_state *states, int nthreads, int flags, float *sh_out, double *seconds);
+int mort_hip_sh9_irradiance(const float sh[MORT_SH9_FLOATS], const float normal[3], float rgb_out[3]);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

@@ -14,6 +14,7 @@
  *                   [--svgf]                              variance-guided a-trous filter (SVGF) on the last frame (single GPU / host)
  *                   [--pick X,Y]                          no render: the closest-hit record under pixel (X, Y) as one JSON line
  *                   [--probe X,Y[,N]]                     no render: the path-traced colour along the ray through pixel (X, Y) as one JSON line
+ *                   [--sh-probe X,Y,Z[,D[,N]]]            no render: the SH9 light probe at world position (X, Y, Z) as one JSON line
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -46,6 +47,12 @@
  * under --mode host) for the same ray as --pick: N paths (default 1) with the scene camera's bounce limit (--depth), background and
  * light object, drawn from subsequence X + Y * W of --seed, which is that pixel's stream at the start of a render.  One JSON line:
  * probe, samples, origin, dir, time, rgb (the unscaled sum of the N colours), mode, seconds.
+ *
+ * --sh-probe X,Y,Z[,D[,N]] (single GPU / host; excludes --pick and --probe): renders nothing; bakes one light probe
+ * (mort_hip_probe_bake, or mort_hip_probe_bake_host under --mode host) at world position (X, Y, Z), time 0.5: D directions of the
+ * library's own set (default 256), N paths per direction (default 1), the scene camera's bounce limit (--depth), background and
+ * light object, the streams subsequences 0 .. D - 1 of --seed.  One JSON line: sh (9 x 3), directions, samples, position, mode,
+ * seconds.
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -89,7 +96,7 @@ static int usage(void) {
     printf("Usage: mort <number_between_1_and_10> [--width W] [--aspect A] [--spp N] [--depth D] [--seed S] [--frames N] "
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
-           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]]\n");
+           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]]\n");
     return -1;
 }
 
@@ -164,6 +171,8 @@ int main(int argc, char **argv) {
     int mouse_dx = 0, mouse_dy = 0;
     int pick = 0, pick_x = 0, pick_y = 0;
     int probe = 0, probe_x = 0, probe_y = 0, probe_n = 1;
+    int sh_probe = 0, sh_d = 256, sh_n = 1;
+    float sh_pos[3] = {0, 0, 0};
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -203,6 +212,10 @@ int main(int argc, char **argv) {
         else if (strcmp(argv[i], "--svgf") == 0) svgf = 1;
         else if (ARG("--pick")) { pick = 1; if (sscanf(argv[++i], "%d,%d", &pick_x, &pick_y) != 2) { fprintf(stderr, "--pick X,Y\n"); return -1; } }
         else if (ARG("--probe")) { probe = 1; if (sscanf(argv[++i], "%d,%d,%d", &probe_x, &probe_y, &probe_n) < 2 || probe_n < 1) { fprintf(stderr, "--probe X,Y[,N]\n"); return -1; } }
+        else if (ARG("--sh-probe")) {
+            sh_probe = 1;
+            if (sscanf(argv[++i], "%f,%f,%f,%d,%d", &sh_pos[0], &sh_pos[1], &sh_pos[2], &sh_d, &sh_n) < 3 || sh_n < 1) { fprintf(stderr, "--sh-probe X,Y,Z[,D[,N]]\n"); return -1; }
+        }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -215,6 +228,8 @@ int main(int argc, char **argv) {
     if (var_out && !temporal) { fprintf(stderr, "--variance-out needs --temporal\n"); return -1; }
     if (pick && gpus > 1) { fprintf(stderr, "--pick is a single-GPU option\n"); return -1; }
     if (probe && (gpus > 1 || pick)) { fprintf(stderr, "--probe is a single-GPU option and excludes --pick\n"); return -1; }
+    if (sh_probe && (gpus > 1 || pick || probe)) { fprintf(stderr, "--sh-probe is a single-GPU option and excludes --pick and --probe\n"); return -1; }
+    if (sh_probe && (sh_d < 64 || sh_d > 4096 || sh_d % 64)) { fprintf(stderr, "--sh-probe: D is a multiple of 64 in 64..4096\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;
@@ -297,6 +312,44 @@ int main(int argc, char **argv) {
         print_v3("origin", ray.origin); print_v3("dir", ray.dir);
         printf(", \"time\": "); print_f32(ray.time);
         print_v3("rgb", rgb);
+        printf(", \"mode\": \"%s\", \"seconds\": %.6f}\n", host_mode ? "host" : "mega", sec);
+        mort_world_free(&world);
+        free(texels);
+        return 0;
+    }
+
+    if (sh_probe) { /* ---- no render: one light probe ---- */
+        mort_probe_params pp;
+        mort_hip_radiance_params_from_camera(&cam, &pp.rp);
+        pp.rp.samples = sh_n;
+        pp.directions = sh_d;
+        mort_probe pr;
+        for (int k = 0; k < 3; k++) pr.position[k] = sh_pos[k];
+        pr.time = 0.5f;
+        mort_rng_state *states = (mort_rng_state *)malloc((size_t)sh_d * sizeof *states); /* subsequences 0 .. D - 1 of the seed */
+        if (!states) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+        int pst;
+        if ((pst = mort_hip_rng_seed_host(seed, sh_d, 1, states)) != MORT_OK) die(NULL, pst, "mort_hip_rng_seed_host");
+        float sh[MORT_SH9_FLOATS];
+        double sec = 0;
+        if (host_mode) {
+            if ((pst = mort_hip_probe_bake_host(&world, &pp, 1, &pr, NULL, states, threads, tree ? MORT_HOST_TREE : 0, sh, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_probe_bake_host");
+        } else {
+            mort_ctx *pctx = NULL;
+            if ((pst = mort_hip_init(device, &pctx)) != MORT_OK) die(NULL, pst, "mort_hip_init");
+            if ((pst = mort_hip_upload_world(pctx, &world)) != MORT_OK) die(pctx, pst, "mort_hip_upload_world");
+            if ((pst = mort_hip_probe_bake(pctx, &pp, 1, &pr, NULL, states, sh, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_probe_bake");
+            mort_hip_shutdown(pctx);
+        }
+        free(states);
+        printf("{\"scene\": %d, \"sh\": [", scene);
+        for (int k = 0; k < 9; k++) {
+            printf("%s[", k ? ", " : "");
+            for (int ch = 0; ch < 3; ch++) { if (ch) printf(", "); print_f32(sh[k * 3 + ch]); }
+            printf("]");
+        }
+        printf("], \"directions\": %d, \"samples\": %d", sh_d, sh_n);
+        print_v3("position", pr.position);
         printf(", \"mode\": \"%s\", \"seconds\": %.6f}\n", host_mode ? "host" : "mega", sec);
         mort_world_free(&world);
         free(texels);

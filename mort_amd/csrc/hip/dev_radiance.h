@@ -46,23 +46,13 @@ DEV bool radiance_world_hit(const QueryArgs &q, const Ray &ray, Rng &rng, Best &
     return true;
 }
 
-/* one radiance query: rgb[i] = ((0 + c_1) + c_2) + ... + c_samples, c_k the k-th ray_color of ray i drawn from stream i.
+/* the paths of one ray: ((0 + c_1) + c_2) + ... + c_samples, c_k the k-th ray_color of ray0 drawn from rng, both in the
+ * caller's registers (a radiance query loads them, a light probe builds the ray: dev_probe.h).
  * The first lds_levels bounce-stack levels of this ray live at lds_stack[level * lds_stride] (the kernel: the lane's column of
  * an LDS array; the host loop: a local array), the rest in the private array, as in render_pixel */
 template <bool TREE>
-DEV void radiance_ray(const RadianceArgs &a, size_t i, unsigned short *walk, int walk_stride, float4 *lds_stack, int lds_levels, int lds_stride) {
+DEV V3 radiance_paths(const RadianceArgs &a, const Ray ray0, Rng &rng, unsigned short *walk, int walk_stride, float4 *lds_stack, int lds_levels, int lds_stride) {
     const DScene &sc = a.q.sc;
-    Ray ray0;
-    float t_max_ignored; /* ray_color always searches [0.001, inf) */
-    query_load_ray(a.q.rays, i, ray0, t_max_ignored);
-
-    Rng rng;
-    {
-        const mort_rng_state *st = a.q.states + i;
-        rng.d = st->d; rng.v0 = st->v[0]; rng.v1 = st->v[1]; rng.v2 = st->v[2]; rng.v3 = st->v[3]; rng.v4 = st->v[4];
-        rng.draws = 0;
-    }
-
     StackEntry stack[MORT_MAX_BOUNCE_LIMIT];
     unsigned long long ident_mask = 0ull; /* levels whose entry is the identity (dielectric): not stored */
     V3 color = mk(0, 0, 0);
@@ -109,6 +99,24 @@ DEV void radiance_ray(const RadianceArgs &a, size_t i, unsigned short *walk, int
             ray = ray0; /* the next path of the same ray */
         }
     }
+    return color;
+}
+
+/* one radiance query: rgb[i] = the paths' sum for ray i drawn from stream i */
+template <bool TREE>
+DEV void radiance_ray(const RadianceArgs &a, size_t i, unsigned short *walk, int walk_stride, float4 *lds_stack, int lds_levels, int lds_stride) {
+    Ray ray0;
+    float t_max_ignored; /* ray_color always searches [0.001, inf) */
+    query_load_ray(a.q.rays, i, ray0, t_max_ignored);
+
+    Rng rng;
+    {
+        const mort_rng_state *st = a.q.states + i;
+        rng.d = st->d; rng.v0 = st->v[0]; rng.v1 = st->v[1]; rng.v2 = st->v[2]; rng.v3 = st->v[3]; rng.v4 = st->v[4];
+        rng.draws = 0;
+    }
+
+    const V3 color = radiance_paths<TREE>(a, ray0, rng, walk, walk_stride, lds_stack, lds_levels, lds_stride);
 
     { /* d and v[] only: the words this path never reads keep the caller's bits */
         mort_rng_state *st = a.q.states + i;

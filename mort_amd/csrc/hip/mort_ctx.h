@@ -120,6 +120,8 @@ struct mort_ctx {
      * they return after their downloads, with the buffer idle */
     Scratch stage_planes; /* the filters' four float4 planes: colour (+ variance) ping-pong, (normal, depth), albedo */
     Scratch stage_io;     /* the host-buffer forms' device copies of the caller's buffers (stage_upload) */
+    Scratch probe_dirs;   /* light probes (probe.hip): the library's own direction set for the last D asked for, 3 D floats */
+    int probe_dirs_d = 0; /* that D; 0 = none yet */
     hipStream_t dn_stream = nullptr; /* stream of the last stage launch */
     /* views (view.hip): the ones alive on this context, freed by mort_hip_shutdown */
     std::vector<struct mort_view *> views;

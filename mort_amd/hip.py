@@ -36,6 +36,7 @@ EXPORTS = [
     "mort_hip_query_closest", "mort_hip_query_closest_device", "mort_hip_query_closest_host",
     "mort_hip_query_occluded", "mort_hip_query_occluded_device", "mort_hip_query_occluded_host",
     "mort_hip_radiance_params_from_camera", "mort_hip_query_radiance", "mort_hip_query_radiance_device", "mort_hip_query_radiance_host",
+    "mort_hip_probe_directions", "mort_hip_probe_bake", "mort_hip_probe_bake_device", "mort_hip_probe_bake_host", "mort_hip_sh9_irradiance",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -55,6 +56,23 @@ class RADIANCE_PARAMS(C.Structure):
     """mort_radiance_params of include/mort_hip.h"""
     _fields_ = [("bounce_limit", C.c_int), ("samples", C.c_int), ("background", C.c_float * 3),
                 ("light_obj_type", C.c_int), ("light_obj_idx", C.c_int)]
+
+
+# light probes (mort_probe, mort_probe_params of include/mort_hip.h)
+PROBE_DTYPE = np.dtype([("position", "<f4", (3,)), ("time", "<f4")])
+assert PROBE_DTYPE.itemsize == 16
+SH9_FLOATS = 27
+
+
+class PROBE_PARAMS(C.Structure):
+    """mort_probe_params of include/mort_hip.h"""
+    _fields_ = [("rp", RADIANCE_PARAMS), ("directions", C.c_int)]
+
+    def __init__(self, rp=None, directions=256):
+        super().__init__()
+        if rp is not None:
+            C.memmove(C.byref(self.rp), C.byref(rp), C.sizeof(RADIANCE_PARAMS))
+        self.directions = directions
 
 
 class Partition(C.Structure):
@@ -227,6 +245,12 @@ def lib():
         L.mort_hip_query_radiance_device.argtypes = [ctx, rp, sz, vp, vp, vp, vp, dp]; L.mort_hip_query_radiance_device.restype = C.c_int
         L.mort_hip_query_radiance_host.argtypes = [wd, rp, sz, vp, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_query_radiance_host.restype = C.c_int
         L.mort_hip_debug_radiance_lds_levels.argtypes = []; L.mort_hip_debug_radiance_lds_levels.restype = C.c_int
+        pp = C.POINTER(PROBE_PARAMS)
+        L.mort_hip_probe_directions.argtypes = [C.c_int, vp]; L.mort_hip_probe_directions.restype = C.c_int
+        L.mort_hip_probe_bake.argtypes = [ctx, pp, sz, vp, vp, vp, vp, dp]; L.mort_hip_probe_bake.restype = C.c_int
+        L.mort_hip_probe_bake_device.argtypes = [ctx, pp, sz, vp, vp, vp, vp, vp, dp]; L.mort_hip_probe_bake_device.restype = C.c_int
+        L.mort_hip_probe_bake_host.argtypes = [wd, pp, sz, vp, vp, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_probe_bake_host.restype = C.c_int
+        L.mort_hip_sh9_irradiance.argtypes = [vp, vp, vp]; L.mort_hip_sh9_irradiance.restype = C.c_int
         _lib = L
     return _lib
 
@@ -493,6 +517,36 @@ class Context:
                   "mort_hip_query_radiance_device")
         return sec.value if sync else None
 
+    def probe_bake(self, params, probes, states, dirs=None):
+        """SH9 light probes on the GPU (mort_hip_probe_bake): params PROBE_PARAMS, probes PROBE_DTYPE (n,) or float32 (n, 4) =
+        position, time; states n * D 48-byte XORWOW streams, advanced IN PLACE; dirs None = the library's own set, else float32
+        (D, 3), used as given.  dict(sh float32 (n, 9, 3), seconds)."""
+        probes, dirs = _probe_records(probes), _probe_dirs(dirs, params.directions)
+        st8 = _probe_states(states, probes.shape[0], params.directions)
+        sh = np.zeros((probes.shape[0], 9, 3), dtype=np.float32)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_probe_bake(self._h, C.byref(params), probes.shape[0], probes.ctypes.data, _ptr(dirs), _ptr(st8),
+                                            sh.ctypes.data, C.byref(sec)), "mort_hip_probe_bake")
+        return dict(sh=sh, seconds=sec.value)
+
+    def probe_bake_device(self, params, probes, states, sh, dirs=None, sync=False):
+        """The bake on torch tensors on this context's device, on the current torch stream: probes float32 of 4 n elements, states
+        of 48 n D bytes (advanced in place), sh of 108 n bytes, dirs None or float32 of 3 D elements.  Asynchronous unless sync
+        (then returns the device seconds) or torch runs on its legacy default stream."""
+        import torch
+        if probes.dtype != torch.float32 or not probes.is_contiguous() or probes.numel() % 4 or probes.device.type != "cuda":
+            raise ValueError("expected a contiguous float32 tensor of 4 floats per probe on the GPU")
+        n, D = probes.numel() // 4, params.directions
+        for t, size in ((states, 48 * n * D), (sh, 4 * SH9_FLOATS * n), (dirs, 12 * D)):
+            if t is not None and (not t.is_contiguous() or t.numel() * t.element_size() != size or t.device != probes.device):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {probes.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, probes.device, sync)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._chk(lib().mort_hip_probe_bake_device(self._h, C.byref(params), n, probes.data_ptr(), ptr(dirs), ptr(states), ptr(sh), stream,
+                                                   C.byref(sec) if sync else None), "mort_hip_probe_bake_device")
+        return sec.value if sync else None
+
     def calib_valu(self, waves_per_simd, kind=0):
         """Shader cycles one SIMD needs per wave64 VALU instruction at `waves_per_simd` resident waves (include/mort_hip.h)."""
         r = CalibValu()
@@ -730,6 +784,71 @@ def query_radiance_host(world, params, rays, states, tree=False, nthreads=1):
     if rc != 0:
         raise MortHipError(rc, "mort_hip_query_radiance_host")
     return dict(rgb=rgb, seconds=sec.value)
+
+
+def _probe_records(probes):
+    """probes as a contiguous PROBE_DTYPE (n,) array: PROBE_DTYPE already, or float32 (n, 4) = position, time"""
+    probes = np.asarray(probes)
+    if probes.dtype != PROBE_DTYPE:
+        probes = np.ascontiguousarray(probes, dtype=np.float32).reshape(-1, 4).view(PROBE_DTYPE).reshape(-1)
+    return np.ascontiguousarray(probes).reshape(-1)
+
+
+def _probe_dirs(dirs, D):
+    if dirs is None:
+        return None
+    dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+    if dirs.size != 3 * D:
+        raise ValueError(f"expected {D} directions of 3 floats")
+    return dirs
+
+
+def _probe_states(states, n, D):
+    """the caller's streams as the bytes the library advances in place (no copy)"""
+    if not (isinstance(states, np.ndarray) and states.flags.c_contiguous and states.flags.writeable and states.nbytes == 48 * n * D):
+        raise ValueError(f"expected a contiguous writeable array of {n * D} 48-byte streams")
+    return states
+
+
+def probe_params_from_camera(cam, directions=256, samples=1):
+    """PROBE_PARAMS with the camera's bounce limit, background and light object"""
+    return PROBE_PARAMS(radiance_params_from_camera(cam, samples), directions)
+
+
+def probe_directions(D):
+    """The library's own direction set (mort_hip_probe_directions, needs no GPU): the D spherical Fibonacci points, float32 (D, 3)."""
+    out = np.zeros((max(int(D), 0), 3), dtype=np.float32)
+    rc = lib().mort_hip_probe_directions(D, out.ctypes.data)
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_probe_directions")
+    return out
+
+
+def probe_bake_host(world, params, probes, states, dirs=None, tree=False, nthreads=1):
+    """The bake as a host loop (mort_hip_probe_bake_host), no GPU: arguments and result as Context.probe_bake."""
+    probes, dirs = _probe_records(probes), _probe_dirs(dirs, params.directions)
+    st8 = _probe_states(states, probes.shape[0], params.directions)
+    sh = np.zeros((probes.shape[0], 9, 3), dtype=np.float32)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_probe_bake_host(world.ptr, C.byref(params), probes.shape[0], probes.ctypes.data, _ptr(dirs), _ptr(st8), nthreads,
+                                        HOST_TREE if tree else 0, sh.ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_probe_bake_host")
+    return dict(sh=sh, seconds=sec.value)
+
+
+def sh9_irradiance(sh, normal):
+    """Irradiance at a surface of unit normal `normal` from one probe's coefficients (9, 3) (mort_hip_sh9_irradiance, host only):
+    float32 (3,)."""
+    sh = np.ascontiguousarray(sh, dtype=np.float32)
+    nrm = np.ascontiguousarray(normal, dtype=np.float32)
+    if sh.size != SH9_FLOATS or nrm.size != 3:
+        raise ValueError("expected 27 coefficients and a normal of 3 floats")
+    out = np.zeros(3, dtype=np.float32)
+    rc = lib().mort_hip_sh9_irradiance(sh.ctypes.data, nrm.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_sh9_irradiance")
+    return out
 
 
 def _feature_arrays(W, H):

@@ -11,7 +11,8 @@ graph), waves per SIMD that allocation allows, spilled registers, private (scrat
     touched per-pixel values, read and written in the shade step only), mega_gen_kernel<1024> is a measurement build, or
   * a ray-query kernel (query_closest_kernel, query_occluded_kernel) spills or uses any private memory, or
   * a radiance-query kernel (query_radiance_kernel) spills a vector register or keeps more in private memory than the bounce-stack
-    levels behind its LDS part: MORT_MAX_BOUNCE_LIMIT x 16 B and one 16-byte slot, 1040 B.
+    levels behind its LDS part: MORT_MAX_BOUNCE_LIMIT x 16 B and one 16-byte slot, 1040 B, or
+  * a light-probe kernel (probe_sh_kernel), which runs the same path body, breaks that same rule.
 """
 import os, re, subprocess, sys, tempfile, shutil
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
@@ -40,7 +41,7 @@ finally:
     shutil.rmtree(tmp, ignore_errors=True)
 bad = []
 print(f"{'kernel':58s} {'wg':>5s} {'vgpr':>5s} {'waves/SIMD':>10s} {'v-spill':>7s} {'s-spill':>7s} {'private B':>9s} {'static LDS':>10s}")
-OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_")
+OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_")
 for r in sorted(rows, key=lambda r: r["name"]):
     if not any(o in r["name"] for o in OWN) and "--all" not in sys.argv:
         continue  # rocPRIM's sort kernels (tile_sort.hip): listed with --all
@@ -58,6 +59,8 @@ for r in sorted(rows, key=lambda r: r["name"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the ray queries run without scratch)")
     if r["name"].startswith("query_radiance_") and (r["vspill"] or r["private"] > 1040):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the search loop must not spill; 1040 B for the deep bounce levels)")
+    if r["name"].startswith("probe_") and (r["vspill"] or r["private"] > 1040):
+        bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the radiance body must not spill; 1040 B for the deep bounce levels)")
 if bad:
     print("\n".join("RESOURCE CHECK FAILED: " + b for b in bad), file=sys.stderr)
     sys.exit(1 if check else 0)
