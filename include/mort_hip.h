@@ -459,6 +459,64 @@ int mort_hip_probe_bake_host(const mort_world *world, const mort_probe_params *p
                              mort_rng_state *states, int nthreads, int flags, float *sh_out, double *seconds);
 int mort_hip_sh9_irradiance(const float sh[MORT_SH9_FLOATS], const float normal[3], float rgb_out[3]);
 
+/* ---- irradiance volumes: a regular grid of light probes sampled trilinearly on the device.  The probes of a
+ * grid are baked with mort_hip_probe_bake*, packed into one 128-byte record each, and a kernel gives the irradiance at every
+ * (position, normal) of a batch, blended between the eight surrounding probes under a per-probe weight.  The arithmetic and the
+ * order of the blend below are part of the contract: GPU kernel, host loop and any restatement of it agree to the bit.
+ *
+ * The grid.  Probe (ix, iy, iz) has index p = (iz count[1] + iy) count[0] + ix, position origin[a] + (float)i_a * spacing[a] per
+ * axis (fp32: the product is rounded, then the sum) and time grid.time.  A valid grid has a finite origin, spacing finite and > 0
+ * on every axis (also where count is 1), every count in 1..MORT_VOLUME_MAX_COUNT and at most 2^31 - 1 probes; anything else is
+ * MORT_ERR_INVALID.  mort_hip_volume_probes (plain host code) writes the mort_probe records in index order, ready for the bake.
+ *
+ * A record is MORT_VOLUME_RECORD_FLOATS floats: the probe's 27 SH9 floats as the bake writes them, the weight, four 0.0f.
+ * 128 bytes are one cache line of the device: with records aligned to 128 bytes each corner costs exactly one line (advice; the
+ * _device forms ask for 16 bytes as every other call does).  A record is read as seven 16-byte loads, its last 16 bytes never.
+ * mort_hip_volume_pack* copies the 27 floats bit for bit (NaN payloads included), then the weight as given (weight == NULL:
+ * 1.0f), then the zeros.  The weight is the caller's: 0 masks a probe, no validity rule is built in.
+ *
+ * A point is the first 24 bytes of a record of `stride` bytes: position, then normal -- the head of a mort_hit, so the output of
+ * mort_hip_query_closest_device is sampled with stride 48 and no copy.  stride >= 24 and a multiple of 4, else MORT_ERR_INVALID;
+ * the bytes between the points are not read.
+ *
+ * One sample, everything fp32, nothing contracted, nothing reordered.  Per axis a, with inv[a] = 1.0f / spacing[a] (correctly
+ * rounded, once per call):
+ *   u  = (x[a] - origin[a]) * inv[a];  u = (u > 0) ? u : 0 (NaN goes to 0);  m = (float)(count[a] - 1);  u = (u < m) ? u : m
+ *   i0 = (int)floorf(u);  if (i0 > count[a] - 2) i0 = count[a] - 2;  if (i0 < 0) i0 = 0
+ *   f  = u - (float)i0;  i1 = (i0 + 1 < count[a]) ? i0 + 1 : i0;  w[a][0] = 1.0f - f;  w[a][1] = f
+ * so a point outside the grid takes the boundary's value and an axis with one probe has f = 0.
+ *   B_k  = A_l(k) * Y_k(n): Y_k the nine expressions of the light probes above at the normal AS GIVEN (not normalised),
+ *          A_0 = (float)M_PI, A_1 = (float)(2.0 * M_PI / 3.0), A_2 = (float)(M_PI / 4.0).
+ *   For corner c = cx + 2 cy + 4 cz in ascending c, the probe (i_cx, i_cy, i_cz):
+ *          T_c = (w[0][cx] * w[1][cy]) * w[2][cz],  W_c = T_c * weight_c.
+ *          A corner contributes only if W_c > 0; otherwise its coefficients are not used (a masked probe that holds NaN poisons
+ *          nothing).  For a contributing corner e_c[ch] = ((B_0 sh_c[0][ch] + B_1 sh_c[1][ch]) + ...) + B_8 sh_c[8][ch] (from
+ *          the k = 0 product, no leading 0 +), acc[ch] = acc[ch] + W_c * e_c[ch], wsum = wsum + W_c, both from 0.0f.
+ *   out  = {acc[0] * r, acc[1] * r, acc[2] * r, wsum} with r = 1.0f / wsum correctly rounded where wsum > 0, else {0, 0, 0, 0}:
+ *          the fourth float shows a point that no valid probe covers.
+ *
+ * Forms, `seconds`, streams, n == 0 and alignment as for the queries; the _host forms take `nthreads` and make no HIP call.
+ * Outputs must not overlap inputs (the points count with their span (n - 1) stride + 24).  NULL grid, records, points, sh or
+ * outputs are MORT_ERR_INVALID.  None of these calls needs an uploaded world or an RNG; they ignore the partition and touch
+ * nothing the render keeps. ---- */
+typedef struct mort_volume_grid { float origin[3]; float spacing[3]; int32_t count[3]; float time; } mort_volume_grid; /* 40 B */
+typedef struct mort_volume_point { float p[3], normal[3]; } mort_volume_point; /* 24 B: the head of a mort_hit */
+#define MORT_VOLUME_RECORD_FLOATS 32 /* 128 B per probe: [27 SH9 floats as the bake writes them][weight][4 x 0.0f] */
+#define MORT_VOLUME_MAX_COUNT 4096   /* probes per axis */
+MORT_SA(sizeof(mort_volume_grid) == 40 && sizeof(mort_volume_point) == 24, "irradiance volume layout");
+int mort_hip_volume_probes(const mort_volume_grid *grid, mort_probe *probes_out /* count[0] count[1] count[2] */);
+int mort_hip_volume_pack(mort_ctx *ctx, size_t n, const float *sh /* 27 n */, const float *weight /* n or NULL = 1.0f */,
+                         float *records_out /* 32 n */, double *seconds);
+int mort_hip_volume_pack_device(mort_ctx *ctx, size_t n, const void *d_sh, const void *d_weight /* or NULL */, void *d_records_out,
+                                void *stream, double *seconds);
+int mort_hip_volume_pack_host(size_t n, const float *sh, const float *weight, int nthreads, float *records_out, double *seconds);
+int mort_hip_volume_sample(mort_ctx *ctx, const mort_volume_grid *grid, const float *records, size_t n, const void *points, size_t stride,
+                           float *out /* 4 n */, double *seconds);
+int mort_hip_volume_sample_device(mort_ctx *ctx, const mort_volume_grid *grid, const void *d_records, size_t n, const void *d_points,
+                                  size_t stride, void *d_out, void *stream, double *seconds);
+int mort_hip_volume_sample_host(const mort_volume_grid *grid, const float *records, size_t n, const void *points, size_t stride, int nthreads,
+                                float *out, double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

@@ -15,6 +15,8 @@
  *                   [--pick X,Y]                          no render: the closest-hit record under pixel (X, Y) as one JSON line
  *                   [--probe X,Y[,N]]                     no render: the path-traced colour along the ray through pixel (X, Y) as one JSON line
  *                   [--sh-probe X,Y,Z[,D[,N]]]            no render: the SH9 light probe at world position (X, Y, Z) as one JSON line
+ *                   [--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]]   no render: an irradiance volume over the box, sampled at
+ *                                                          --pick X,Y (one JSON line) or at every pixel (--irradiance-out FILE)
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -54,12 +56,21 @@
  * light object, the streams subsequences 0 .. D - 1 of --seed.  One JSON line: sh (9 x 3), directions, samples, position, mode,
  * seconds.
  *
+ * --sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]] (single GPU / host; with --pick or --irradiance-out, excludes --probe and
+ * --sh-probe): renders nothing; an irradiance volume of NX x NY x NZ probes that spans the box inclusively --
+ * spacing (X1 - X0) / (NX - 1), an axis with one probe sits at X0 with spacing 1 -- baked at time 0.5 as --sh-probe bakes (D
+ * directions, N paths, the scene camera's parameters; the streams are subsequences 0 .. probes D - 1 of --seed, probe-major),
+ * packed with all weights 1.  With --pick X,Y: that pixel's closest-hit query, then the volume sampled at the hit's position and
+ * normal; one JSON line, --pick's fields plus irradiance (3) and weight_sum, zeros for a miss.  With --irradiance-out FILE (and
+ * without --pick): the same chain for every pixel's --pick ray, sqrt(clamp(E / pi, 0, 1)) as an 8-bit PPM, misses black.
+ *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
  * RCCL (`--gather rccl`, the default: xGMI inside a node), or through a shared host mapping (`--gather shm`: for ranks
  * that share one GPU, where RCCL refuses a communicator; used by the tests on a one-GPU box).
  */
 #include <errno.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -96,7 +107,8 @@ static int usage(void) {
     printf("Usage: mort <number_between_1_and_10> [--width W] [--aspect A] [--spp N] [--depth D] [--seed S] [--frames N] "
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
-           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]]\n");
+           "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
+           "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE]\n");
     return -1;
 }
 
@@ -173,6 +185,9 @@ int main(int argc, char **argv) {
     int probe = 0, probe_x = 0, probe_y = 0, probe_n = 1;
     int sh_probe = 0, sh_d = 256, sh_n = 1;
     float sh_pos[3] = {0, 0, 0};
+    int sh_volume = 0, vol_n[3] = {0, 0, 0};
+    float vol_box[6] = {0, 0, 0, 0, 0, 0};
+    const char *irr_out = NULL;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -216,6 +231,12 @@ int main(int argc, char **argv) {
             sh_probe = 1;
             if (sscanf(argv[++i], "%f,%f,%f,%d,%d", &sh_pos[0], &sh_pos[1], &sh_pos[2], &sh_d, &sh_n) < 3 || sh_n < 1) { fprintf(stderr, "--sh-probe X,Y,Z[,D[,N]]\n"); return -1; }
         }
+        else if (ARG("--sh-volume")) {
+            sh_volume = 1;
+            if (sscanf(argv[++i], "%f,%f,%f,%f,%f,%f,%d,%d,%d,%d,%d", &vol_box[0], &vol_box[1], &vol_box[2], &vol_box[3], &vol_box[4], &vol_box[5],
+                       &vol_n[0], &vol_n[1], &vol_n[2], &sh_d, &sh_n) < 9 || sh_n < 1) { fprintf(stderr, "--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]\n"); return -1; }
+        }
+        else if (ARG("--irradiance-out")) irr_out = argv[++i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -230,6 +251,10 @@ int main(int argc, char **argv) {
     if (probe && (gpus > 1 || pick)) { fprintf(stderr, "--probe is a single-GPU option and excludes --pick\n"); return -1; }
     if (sh_probe && (gpus > 1 || pick || probe)) { fprintf(stderr, "--sh-probe is a single-GPU option and excludes --pick and --probe\n"); return -1; }
     if (sh_probe && (sh_d < 64 || sh_d > 4096 || sh_d % 64)) { fprintf(stderr, "--sh-probe: D is a multiple of 64 in 64..4096\n"); return -1; }
+    if (sh_volume && (gpus > 1 || probe || sh_probe)) { fprintf(stderr, "--sh-volume is a single-GPU option and excludes --probe and --sh-probe\n"); return -1; }
+    if (sh_volume && (sh_d < 64 || sh_d > 4096 || sh_d % 64)) { fprintf(stderr, "--sh-volume: D is a multiple of 64 in 64..4096\n"); return -1; }
+    if (sh_volume && !pick == !irr_out) { fprintf(stderr, "--sh-volume needs --pick X,Y or --irradiance-out FILE, not both\n"); return -1; }
+    if (irr_out && !sh_volume) { fprintf(stderr, "--irradiance-out needs --sh-volume\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;
@@ -257,6 +282,94 @@ int main(int argc, char **argv) {
     const int W = cam.image_width, H = cam.image_height;
     const size_t npx = (size_t)W * H;
     const int eff = mort_camera_effective_spp(&cam);
+
+    if (sh_volume) { /* ---- no render: bake a grid of probes, pack it, sample it at the hits of --pick's rays ---- */
+        if (pick && (pick_x < 0 || pick_x >= W || pick_y < 0 || pick_y >= H)) { fprintf(stderr, "--pick %d,%d is outside the %dx%d image\n", pick_x, pick_y, W, H); return -1; }
+        mort_volume_grid grid;
+        for (int k = 0; k < 3; k++) {
+            grid.origin[k] = vol_box[k];
+            grid.count[k] = vol_n[k];
+            grid.spacing[k] = vol_n[k] > 1 ? (vol_box[3 + k] - vol_box[k]) / (float)(vol_n[k] - 1) : 1.0f;
+        }
+        grid.time = 0.5f;
+        int pst;
+        for (int k = 0; k < 3; k++) /* the library's own conditions, before anything is sized by the counts */
+            if (grid.count[k] < 1 || grid.count[k] > MORT_VOLUME_MAX_COUNT || !(grid.spacing[k] > 0.0f) || grid.spacing[k] - grid.spacing[k] != 0.0f ||
+                grid.origin[k] - grid.origin[k] != 0.0f) { fprintf(stderr, "--sh-volume: a box with X1 > X0 (or one probe) per axis and 1..%d probes per axis\n", MORT_VOLUME_MAX_COUNT); return -1; }
+        const size_t probes_n = (size_t)grid.count[0] * (size_t)grid.count[1] * (size_t)grid.count[2];
+        const size_t nq = pick ? 1 : npx;
+        mort_probe_params pp;
+        mort_hip_radiance_params_from_camera(&cam, &pp.rp);
+        pp.rp.samples = sh_n;
+        pp.directions = sh_d;
+        mort_probe *probes = (mort_probe *)malloc(probes_n * sizeof *probes);
+        mort_rng_state *states = (mort_rng_state *)malloc(probes_n * (size_t)sh_d * sizeof *states); /* subsequences 0 .. probes D - 1, probe-major */
+        float *sh = (float *)malloc(probes_n * MORT_SH9_FLOATS * sizeof *sh);
+        float *records = (float *)malloc(probes_n * MORT_VOLUME_RECORD_FLOATS * sizeof *records);
+        mort_ray *rays = (mort_ray *)malloc(nq * sizeof *rays);
+        mort_hit *hits = (mort_hit *)malloc(nq * sizeof *hits);
+        float *irr = (float *)malloc(nq * 4 * sizeof *irr);
+        if (!probes || !states || !sh || !records || !rays || !hits || !irr || probes_n * (size_t)sh_d > 0x7fffffffu) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+        if ((pst = mort_hip_volume_probes(&grid, probes)) != MORT_OK) die(NULL, pst, "mort_hip_volume_probes");
+        if ((pst = mort_hip_rng_seed_host(seed, (int)(probes_n * (size_t)sh_d), 1, states)) != MORT_OK) die(NULL, pst, "mort_hip_rng_seed_host");
+        if (pick) rays[0] = pick_ray(&cam, pick_x, pick_y);
+        else for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) rays[(size_t)y * W + x] = pick_ray(&cam, x, y);
+        double sec = 0, bake_sec = 0, sample_sec = 0;
+        if (host_mode) {
+            const int fl = tree ? MORT_HOST_TREE : 0;
+            if ((pst = mort_hip_probe_bake_host(&world, &pp, probes_n, probes, NULL, states, threads, fl, sh, &bake_sec)) != MORT_OK) die(NULL, pst, "mort_hip_probe_bake_host");
+            if ((pst = mort_hip_volume_pack_host(probes_n, sh, NULL, threads, records, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_volume_pack_host");
+            if ((pst = mort_hip_query_closest_host(&world, nq, rays, NULL, threads, fl, hits, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_closest_host");
+            if ((pst = mort_hip_volume_sample_host(&grid, records, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_host");
+        } else {
+            mort_ctx *pctx = NULL;
+            if ((pst = mort_hip_init(device, &pctx)) != MORT_OK) die(NULL, pst, "mort_hip_init");
+            if ((pst = mort_hip_upload_world(pctx, &world)) != MORT_OK) die(pctx, pst, "mort_hip_upload_world");
+            if ((pst = mort_hip_probe_bake(pctx, &pp, probes_n, probes, NULL, states, sh, &bake_sec)) != MORT_OK) die(pctx, pst, "mort_hip_probe_bake");
+            if ((pst = mort_hip_volume_pack(pctx, probes_n, sh, NULL, records, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_volume_pack");
+            if ((pst = mort_hip_query_closest(pctx, nq, rays, NULL, hits, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_closest");
+            if ((pst = mort_hip_volume_sample(pctx, &grid, records, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample");
+            mort_hip_shutdown(pctx);
+        }
+        for (size_t i = 0; i < nq; i++) /* a miss is an all-zero record: its sample means nothing */
+            if (!(hits[i].flags & MORT_HIT_HIT)) irr[4 * i] = irr[4 * i + 1] = irr[4 * i + 2] = irr[4 * i + 3] = 0.0f;
+        if (pick) {
+            const mort_hit h = hits[0];
+            printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"pick\": [%d, %d], \"hit\": %d, \"t\": ", scene, W, H, pick_x, pick_y, (h.flags & MORT_HIT_HIT) ? 1 : 0);
+            print_f32(h.t);
+            print_v3("p", h.p); print_v3("normal", h.normal);
+            printf(", \"u\": "); print_f32(h.u);
+            printf(", \"v\": "); print_f32(h.v);
+            printf(", \"mat_type\": %d, \"mat_idx\": %d, \"front_face\": %d, \"medium\": %d", (int)h.mat_type, (int)h.mat_idx,
+                   (h.flags & MORT_HIT_FRONT_FACE) ? 1 : 0, (h.flags & MORT_HIT_MEDIUM) ? 1 : 0);
+            print_v3("irradiance", irr);
+            printf(", \"weight_sum\": "); print_f32(irr[3]);
+            printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"samples\": %d, \"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f, \"sample_seconds\": %.6f}\n",
+                   (int)grid.count[0], (int)grid.count[1], (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec, sample_sec);
+        } else {
+            uint8_t *img = (uint8_t *)malloc(npx * 4);
+            if (!img) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+            const float inv_pi = 0.318309886f;
+            for (size_t i = 0; i < npx; i++) {
+                for (int ch = 0; ch < 3; ch++) {
+                    float v = irr[4 * i + ch] * inv_pi;
+                    v = (v > 0.0f) ? v : 0.0f; /* NaN goes to 0 */
+                    v = (v < 1.0f) ? v : 1.0f;
+                    img[4 * i + ch] = (uint8_t)(255.0f * sqrtf(v) + 0.5f);
+                }
+                img[4 * i + 3] = 255;
+            }
+            if (mort_write_ppm(irr_out, img, W, H) != 0) { fprintf(stderr, "cannot write %s\n", irr_out); return EXIT_FAILURE; }
+            free(img);
+            printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"irradiance_out\": \"%s\", \"probes\": [%d, %d, %d], \"directions\": %d, \"samples\": %d, "
+                   "\"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f, \"sample_seconds\": %.6f}\n", scene, W, H, irr_out, (int)grid.count[0], (int)grid.count[1],
+                   (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec, sample_sec);
+        }
+        free(probes); free(states); free(sh); free(records); free(rays); free(hits); free(irr);
+        mort_world_free(&world);
+        free(texels);
+        return 0;
+    }
 
     if (pick) { /* ---- no render: one closest-hit query ---- */
         if (pick_x < 0 || pick_x >= W || pick_y < 0 || pick_y >= H) { fprintf(stderr, "--pick %d,%d is outside the %dx%d image\n", pick_x, pick_y, W, H); return -1; }

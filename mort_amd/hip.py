@@ -37,6 +37,8 @@ EXPORTS = [
     "mort_hip_query_occluded", "mort_hip_query_occluded_device", "mort_hip_query_occluded_host",
     "mort_hip_radiance_params_from_camera", "mort_hip_query_radiance", "mort_hip_query_radiance_device", "mort_hip_query_radiance_host",
     "mort_hip_probe_directions", "mort_hip_probe_bake", "mort_hip_probe_bake_device", "mort_hip_probe_bake_host", "mort_hip_sh9_irradiance",
+    "mort_hip_volume_probes", "mort_hip_volume_pack", "mort_hip_volume_pack_device", "mort_hip_volume_pack_host",
+    "mort_hip_volume_sample", "mort_hip_volume_sample_device", "mort_hip_volume_sample_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -73,6 +75,28 @@ class PROBE_PARAMS(C.Structure):
         if rp is not None:
             C.memmove(C.byref(self.rp), C.byref(rp), C.sizeof(RADIANCE_PARAMS))
         self.directions = directions
+
+
+# irradiance volumes (mort_volume_grid, mort_volume_point of include/mort_hip.h)
+VOLUME_POINT_DTYPE = np.dtype([("p", "<f4", (3,)), ("normal", "<f4", (3,))])
+assert VOLUME_POINT_DTYPE.itemsize == 24
+VOLUME_RECORD_FLOATS = 32
+VOLUME_MAX_COUNT = 4096
+
+
+class VOLUME_GRID(C.Structure):
+    """mort_volume_grid of include/mort_hip.h: probe (ix, iy, iz) sits at origin + i * spacing, index (iz * ny + iy) * nx + ix"""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("count", C.c_int32 * 3), ("time", C.c_float)]
+
+    def __init__(self, origin=(0, 0, 0), spacing=(1, 1, 1), count=(1, 1, 1), time=0.0):
+        super().__init__()
+        for a in range(3):
+            self.origin[a], self.spacing[a], self.count[a] = origin[a], spacing[a], count[a]
+        self.time = time
+
+    @property
+    def probes(self):
+        return self.count[0] * self.count[1] * self.count[2]
 
 
 class Partition(C.Structure):
@@ -251,6 +275,14 @@ def lib():
         L.mort_hip_probe_bake_device.argtypes = [ctx, pp, sz, vp, vp, vp, vp, vp, dp]; L.mort_hip_probe_bake_device.restype = C.c_int
         L.mort_hip_probe_bake_host.argtypes = [wd, pp, sz, vp, vp, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_probe_bake_host.restype = C.c_int
         L.mort_hip_sh9_irradiance.argtypes = [vp, vp, vp]; L.mort_hip_sh9_irradiance.restype = C.c_int
+        gp = C.POINTER(VOLUME_GRID)
+        L.mort_hip_volume_probes.argtypes = [gp, vp]; L.mort_hip_volume_probes.restype = C.c_int
+        L.mort_hip_volume_pack.argtypes = [ctx, sz, vp, vp, vp, dp]; L.mort_hip_volume_pack.restype = C.c_int
+        L.mort_hip_volume_pack_device.argtypes = [ctx, sz, vp, vp, vp, vp, dp]; L.mort_hip_volume_pack_device.restype = C.c_int
+        L.mort_hip_volume_pack_host.argtypes = [sz, vp, vp, C.c_int, vp, dp]; L.mort_hip_volume_pack_host.restype = C.c_int
+        L.mort_hip_volume_sample.argtypes = [ctx, gp, vp, sz, vp, sz, vp, dp]; L.mort_hip_volume_sample.restype = C.c_int
+        L.mort_hip_volume_sample_device.argtypes = [ctx, gp, vp, sz, vp, sz, vp, vp, dp]; L.mort_hip_volume_sample_device.restype = C.c_int
+        L.mort_hip_volume_sample_host.argtypes = [gp, vp, sz, vp, sz, C.c_int, vp, dp]; L.mort_hip_volume_sample_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -545,6 +577,64 @@ class Context:
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         self._chk(lib().mort_hip_probe_bake_device(self._h, C.byref(params), n, probes.data_ptr(), ptr(dirs), ptr(states), ptr(sh), stream,
                                                    C.byref(sec) if sync else None), "mort_hip_probe_bake_device")
+        return sec.value if sync else None
+
+    def volume_pack(self, sh, weight=None):
+        """Probe records of an irradiance volume on the GPU (mort_hip_volume_pack): sh float32 of 27 floats per probe as the bake
+        returns them, weight None = 1.0 or float32 (n,).  dict(records float32 (n, 32), seconds)."""
+        sh, weight = _volume_sh(sh, weight)
+        n = sh.size // SH9_FLOATS
+        rec = np.zeros((n, VOLUME_RECORD_FLOATS), dtype=np.float32)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_volume_pack(self._h, n, sh.ctypes.data, _ptr(weight), rec.ctypes.data, C.byref(sec)), "mort_hip_volume_pack")
+        return dict(records=rec, seconds=sec.value)
+
+    def volume_pack_device(self, sh, records, weight=None, sync=False):
+        """The packing on torch tensors on this context's device, on the current torch stream: sh float32 of 27 n elements,
+        records of 128 n bytes, weight None or float32 of n elements.  Asynchronous unless sync (then returns the device seconds)
+        or torch runs on its legacy default stream."""
+        import torch
+        if sh.dtype != torch.float32 or not sh.is_contiguous() or sh.numel() % SH9_FLOATS or sh.device.type != "cuda":
+            raise ValueError("expected a contiguous float32 tensor of 27 floats per probe on the GPU")
+        n = sh.numel() // SH9_FLOATS
+        for t, size in ((records, 128 * n), (weight, 4 * n)):
+            if t is not None and (not t.is_contiguous() or t.numel() * t.element_size() != size or t.device != sh.device):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {sh.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, sh.device, sync)
+        self._chk(lib().mort_hip_volume_pack_device(self._h, n, sh.data_ptr(), weight.data_ptr() if weight is not None else None,
+                                                    records.data_ptr(), stream, C.byref(sec) if sync else None), "mort_hip_volume_pack_device")
+        return sec.value if sync else None
+
+    def volume_sample(self, grid, records, points, stride=None):
+        """Irradiance at every point on the GPU (mort_hip_volume_sample): grid VOLUME_GRID, records float32 (probes, 32) as
+        volume_pack returns them, points VOLUME_POINT_DTYPE / HIT_DTYPE (n,) or float32 (n, 6) = position, normal, or with
+        `stride` any contiguous array of n records of `stride` bytes that begin with them.  dict(out float32 (n, 4) = E_rgb and
+        the weights' sum, seconds)."""
+        records, points, n, stride = _volume_inputs(grid, records, points, stride)
+        out = np.zeros((n, 4), dtype=np.float32)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_volume_sample(self._h, C.byref(grid), records.ctypes.data, n, points.ctypes.data, stride, out.ctypes.data,
+                                               C.byref(sec)), "mort_hip_volume_sample")
+        return dict(out=out, seconds=sec.value)
+
+    def volume_sample_device(self, grid, records, points, out, stride=24, sync=False):
+        """The sampler on torch tensors on this context's device, on the current torch stream: records of 128 bytes per probe of
+        the grid, points a contiguous tensor of n records of `stride` bytes (24 = packed points, 48 = the hits tensor of
+        query_closest_device, no copy), out of 16 n bytes.  Asynchronous unless sync (then returns the device seconds) or torch
+        runs on its legacy default stream."""
+        import torch
+        nbytes = points.numel() * points.element_size()
+        if not points.is_contiguous() or points.device.type != "cuda" or stride <= 0 or nbytes % stride:
+            raise ValueError(f"expected a contiguous tensor of records of {stride} bytes on the GPU")
+        n = nbytes // stride
+        for t, size in ((records, 128 * grid.probes), (out, 16 * n)):
+            if not t.is_contiguous() or t.numel() * t.element_size() != size or t.device != points.device:
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {points.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, points.device, sync)
+        self._chk(lib().mort_hip_volume_sample_device(self._h, C.byref(grid), records.data_ptr(), n, points.data_ptr(), stride, out.data_ptr(),
+                                                      stream, C.byref(sec) if sync else None), "mort_hip_volume_sample_device")
         return sec.value if sync else None
 
     def calib_valu(self, waves_per_simd, kind=0):
@@ -849,6 +939,69 @@ def sh9_irradiance(sh, normal):
     if rc != 0:
         raise MortHipError(rc, "mort_hip_sh9_irradiance")
     return out
+
+
+def volume_probes(grid):
+    """The probes of a grid in index order (mort_hip_volume_probes, needs no GPU): PROBE_DTYPE (probes,), ready for the bake."""
+    sized = all(0 < c <= VOLUME_MAX_COUNT for c in grid.count) and grid.probes <= 0x7fffffff  # else the library refuses the grid
+    out = np.zeros(grid.probes if sized else 0, dtype=PROBE_DTYPE)
+    rc = lib().mort_hip_volume_probes(C.byref(grid), out.ctypes.data)
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_volume_probes")
+    return out
+
+
+def _volume_sh(sh, weight):
+    sh = np.ascontiguousarray(sh, dtype=np.float32)
+    if sh.size % SH9_FLOATS:
+        raise ValueError("expected 27 coefficients per probe")
+    if weight is not None:
+        weight = np.ascontiguousarray(weight, dtype=np.float32)
+        if weight.size != sh.size // SH9_FLOATS:
+            raise ValueError(f"expected {sh.size // SH9_FLOATS} weights")
+    return sh, weight
+
+
+def _volume_inputs(grid, records, points, stride):
+    """(records, points, n, stride): the records of the whole grid, the points as contiguous memory of n records of stride bytes"""
+    records = np.ascontiguousarray(records, dtype=np.float32)
+    if all(0 < c <= VOLUME_MAX_COUNT for c in grid.count) and records.size != VOLUME_RECORD_FLOATS * grid.probes:
+        raise ValueError(f"expected {grid.probes} records of 32 floats")
+    points = np.asarray(points)
+    if stride is None:
+        if points.dtype.fields is None:
+            points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+            stride = 24
+        else:
+            stride = points.dtype.itemsize
+    points = np.ascontiguousarray(points)
+    if stride <= 0 or points.nbytes % stride:
+        raise ValueError(f"expected records of {stride} bytes")
+    return records, points, points.nbytes // stride, stride
+
+
+def volume_pack_host(sh, weight=None, nthreads=1):
+    """The packing as a host loop (mort_hip_volume_pack_host), no GPU: arguments and result as Context.volume_pack."""
+    sh, weight = _volume_sh(sh, weight)
+    n = sh.size // SH9_FLOATS
+    rec = np.zeros((n, VOLUME_RECORD_FLOATS), dtype=np.float32)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_volume_pack_host(n, sh.ctypes.data, _ptr(weight), nthreads, rec.ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_volume_pack_host")
+    return dict(records=rec, seconds=sec.value)
+
+
+def volume_sample_host(grid, records, points, stride=None, nthreads=1):
+    """The sampler as a host loop (mort_hip_volume_sample_host), no GPU: arguments and result as Context.volume_sample."""
+    records, points, n, stride = _volume_inputs(grid, records, points, stride)
+    out = np.zeros((n, 4), dtype=np.float32)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_volume_sample_host(C.byref(grid), records.ctypes.data, n, points.ctypes.data, stride, nthreads, out.ctypes.data,
+                                           C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_volume_sample_host")
+    return dict(out=out, seconds=sec.value)
 
 
 def _feature_arrays(W, H):

@@ -41,7 +41,7 @@ finally:
     shutil.rmtree(tmp, ignore_errors=True)
 bad = []
 print(f"{'kernel':58s} {'wg':>5s} {'vgpr':>5s} {'waves/SIMD':>10s} {'v-spill':>7s} {'s-spill':>7s} {'private B':>9s} {'static LDS':>10s}")
-OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_")
+OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_", "volume_")
 for r in sorted(rows, key=lambda r: r["name"]):
     if not any(o in r["name"] for o in OWN) and "--all" not in sys.argv:
         continue  # rocPRIM's sort kernels (tile_sort.hip): listed with --all
@@ -61,6 +61,8 @@ for r in sorted(rows, key=lambda r: r["name"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the search loop must not spill; 1040 B for the deep bounce levels)")
     if r["name"].startswith("probe_") and (r["vspill"] or r["private"] > 1040):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the radiance body must not spill; 1040 B for the deep bounce levels)")
+    if r["name"].startswith("volume_") and (r["vspill"] or r["private"]):
+        bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the volume kernels run without scratch)")
 if bad:
     print("\n".join("RESOURCE CHECK FAILED: " + b for b in bad), file=sys.stderr)
     sys.exit(1 if check else 0)
