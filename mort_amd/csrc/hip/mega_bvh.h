@@ -119,6 +119,10 @@ template <typename T> __device__ __forceinline__ T *uni_p(T *p) {
     return (T *)(((unsigned long long)hi << 32) | (unsigned long long)lo);
 }
 
+/* a bounce-stack entry of the HBM part and a pointer to it in the GLOBAL address space (mega_bvh_kernel's stack_deep) */
+typedef float DeepEntry __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) DeepEntry *DeepPtr;
+
 enum { ST_T = 0, ST_L = 1, ST_S = 2, ST_DONE = 3 };
 enum { FL_TIE = 1, FL_REF = 2, FL_MASK = 3 };
 /* bytes 1..3 of `flags`: the segment's byte offsets of the near x / y / z pieces of a four-wide node (own_sign_offset), kept in the
@@ -573,7 +577,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
     int s_ij = 0, iter = 0; /* stratum s_i | s_j << 16; the sample index is s_j * sqrt_spp + s_i */
     uint32_t segments = 0;
     Ray ray; ray.o = mk(0, 0, 0); ray.d = mk(0, 0, 1); ray.tm = 0;
-    float ray_time0 = 0;
+    float ray_time0 = 0; /* always equal to ray.tm (get_ray alone assigns the time); dropping the copy was measured and is slower */
     OwnRay orr; orr.ix = orr.iy = orr.iz = 1; orr.mx = orr.my = orr.mz = 0; orr.band = 0; orr.invlen = 1;
     float ray_a = 1, closest = 0;
     /* the segment's prepared denominator: one reciprocal, set with ray_a in the set-up block, for the up to four divisions of every leaf step of the segment, and
@@ -586,8 +590,13 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
     unsigned short *spa = ts_base; /* pending children: next free entry of the lane's traversal stack */
     int flags = 0;          /* FL_TIE / FL_REF | FL_SIGNS */
     /* bounce-stack levels below the LDS part: [level - DL][lane of the launch] in HBM, one coalesced 1 KB row per wave and level, touched
-     * only by paths deeper than the LDS part (a private array is scratch memory sized for the deepest path in every lane) */
-    float4 *stack_deep = BU_P(L.deep) + ((size_t)blockIdx.x * BLOCK + threadIdx.x);
+     * only by paths deeper than the LDS part (a private array is scratch memory sized for the deepest path in every lane).
+     * Addressed as GLOBAL memory, never through a generic pointer: a pointer read from the argument block is generic to the compiler, the
+     * stack store and the unwind then use FLAT instructions (and the unwind one flat_load for the LDS and the HBM levels alike), and a FLAT
+     * access that may be in flight turns every later wait for an LDS read into s_waitcnt lgkmcnt(0), as FLAT and LDS results return in no
+     * fixed order: get_ray's camera reads and the material reads of the whole shade step then wait for their LAST read before the first
+     * use (measured on Scene 10) */
+    DeepPtr stack_deep = (DeepPtr)BU_P(L.deep) + ((size_t)blockIdx.x * BLOCK + threadIdx.x);
     const size_t deep_stride = (size_t)gridDim.x * BLOCK;
     /* bit i set: bounce level i is a dielectric scatter, whose entry (k = (1,1,1), 1/pdf = 1) unwinds as
      * final = 0 + 1*((1,1,1)*final) = 0 + final exactly -- such levels are neither stored nor loaded */
@@ -905,7 +914,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                             if (!((ident_mask >> iter) & 1ull)) {
                                 float4 e4; e4.x = e.kx; e4.y = e.ky; e4.z = e.kz; e4.w = e.rp;
                                 if (iter < DL) stack_lds[iter * BLOCK + threadIdx.x] = e4;
-                                else stack_deep[(size_t)(iter - DL) * deep_stride] = e4;
+                                else stack_deep[(size_t)(iter - DL) * deep_stride] = DeepEntry{e4.x, e4.y, e4.z, e4.w};
                             }
                             iter++;
                             if (iter >= bounce_limit) { final_value = mk(0, 0, 0); kind = K_FINISH; } /* camera.cuh:161-163 */
@@ -926,8 +935,8 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                             const int lvl = 63 - __builtin_clzll(todo);
                             todo &= ~(1ull << lvl);
                             StackEntry e;
-                            const float4 e4 = (lvl < DL) ? stack_lds[lvl * BLOCK + threadIdx.x] : stack_deep[(size_t)(lvl - DL) * deep_stride];
-                            e.kx = e4.x; e.ky = e4.y; e.kz = e4.z; e.rp = e4.w;
+                            if (lvl < DL) { const float4 e4 = stack_lds[lvl * BLOCK + threadIdx.x]; e.kx = e4.x; e.ky = e4.y; e.kz = e4.z; e.rp = e4.w; }
+                            else { const DeepEntry e4 = stack_deep[(size_t)(lvl - DL) * deep_stride]; e.kx = e4.x; e.ky = e4.y; e.kz = e4.z; e.rp = e4.w; }
                             const V3 t = vmul(mk(e.kx, e.ky, e.kz), final_value);
                             final_value = vadd(mk(0, 0, 0), vscale(e.rp, t));
                         }

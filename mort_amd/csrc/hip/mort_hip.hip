@@ -591,23 +591,31 @@ static void fast_args_base(const mort_ctx *c, const mort_camera *cam, const Rend
     { const char *lc = std::getenv("MORT_LANE_CAP"); if (lc && std::atoi(lc) >= 1 && std::atoi(lc) <= 64) fa.lane_cap = std::atoi(lc); }
 }
 
+/* the bounce-stack levels (at most 12) that fit in LDS beside an image of hot_bytes and the traversal stacks, in FB-thread groups, with
+ * as many groups per CU as keep 12 waves per CU (fewer when their LDS does not fit 160 KB); -1: the image and stacks alone do not fit */
+static int state_lds_levels(uint32_t hot_bytes, int FB, uint32_t tstack_levels, uint32_t static_lds, uint32_t &tstack_off, uint32_t &stack_off) {
+    tstack_off = (hot_bytes + 15u) & ~15u;
+    stack_off = tstack_off + tstack_levels * (uint32_t)FB * 2u;
+    int groups_per_cu = FB >= 768 ? 1 : 768 / FB;
+    while (groups_per_cu > 1 && (long long)(stack_off + static_lds) * groups_per_cu > 160ll * 1024) groups_per_cu--;
+    const long long room = (160ll * 1024 - (long long)static_lds * groups_per_cu) / groups_per_cu - (long long)stack_off;
+    if (room < 0) return -1;
+    const int dl = (int)(room / ((long long)FB * 16));
+    return dl > 12 ? 12 : dl;
+}
+
 /* LDS, grid and HBM scratch of a launch of `kern` in FB-thread groups.  LDS: the image (fa.hot_bytes) | traversal stacks
  * [tstack_levels][FB] u16 | as many bounce-stack levels [dl][FB] float4 as fit next to them, at most 12 and dl_cap, with as many
  * groups per CU as keep 12 waves per CU (fewer when their LDS does not fit 160 KB) and at most per_cu_cap.  The levels below dl
  * go to c->d_deep; MORT_WAVE_LINES (profile builds) sizes the per-wave log. */
 static int state_setup(mort_ctx *c, const mort_camera *cam, FastArgs &fa, const void *kern, int FB, uint32_t tstack_levels, int dl_cap,
                        int per_cu_cap, const char *too_big, hipStream_t s, size_t &lds_bytes, int &grid) {
-    const uint32_t tstack_off = (fa.hot_bytes + 15u) & ~15u;
-    const uint32_t stack_off = tstack_off + tstack_levels * (uint32_t)FB * 2u;
-    fa.off_tstack = tstack_off;
     uint32_t static_lds = 1024; /* the kernel's own __shared__ objects come out of the same 160 KB */
     { hipFuncAttributes fattr; if (hipFuncGetAttributes(&fattr, kern) == hipSuccess) static_lds = (uint32_t)((fattr.sharedSizeBytes + 1023) & ~(size_t)1023); }
-    int groups_per_cu = FB >= 768 ? 1 : 768 / FB;
-    while (groups_per_cu > 1 && (long long)(stack_off + static_lds) * groups_per_cu > 160ll * 1024) groups_per_cu--;
-    const long long room = (160ll * 1024 - (long long)static_lds * groups_per_cu) / groups_per_cu - (long long)stack_off;
-    if (room < 0) { c->last_error = too_big; return MORT_ERR_CAPACITY; }
-    int dl = (int)(room / ((long long)FB * 16));
-    if (dl > 12) dl = 12;
+    uint32_t tstack_off = 0, stack_off = 0;
+    int dl = state_lds_levels(fa.hot_bytes, FB, tstack_levels, static_lds, tstack_off, stack_off);
+    fa.off_tstack = tstack_off;
+    if (dl < 0) { c->last_error = too_big; return MORT_ERR_CAPACITY; }
     if (dl > dl_cap) dl = dl_cap;
     fa.off_stack = stack_off; fa.stack_lds_depth = dl;
     lds_bytes = (size_t)stack_off + (size_t)dl * FB * 16;
@@ -1319,6 +1327,88 @@ extern "C" int mort_hip_debug_exact_forms_device(int device, int what, const flo
     if (d_out) (void)hipFree(d_out);
     if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
     return st;
+}
+
+/* the device side of mort_f2i (mort_math.h: one v_cvt_i32_f32) against mort_f2i_select compiled beside it, over ALL 2^32 bit patterns
+ * (every lane takes every 2^20-th pattern), and its results for a list of patterns (mort_hip_debug_f2i_device) */
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the bounce-stack levels a launch of mega_bvh_kernel keeps in LDS beside
+ * the world's image -- out[0] the image's bytes (0: the world is not served by that kernel, the rest is 0 too), out[1..3] the levels on
+ * 1024-, 768- and 256-thread workgroups (state_lds_levels with the kernel's 1 KB of static LDS); deeper levels go to HBM. */
+extern "C" int mort_hip_debug_bvh_lds_levels(const mort_world *w, int *out) {
+    if (!w || !out) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (!one_sphere_bvh(o) || o.own_nodes.empty() || o.own_nodes4.empty()) return MORT_OK;
+    BvhImages im;
+    build_bvh_images(o, im);
+    if (!im.fits) return MORT_OK;
+    const uint32_t levels = (uint32_t)(o.own4_stack > 1 ? o.own4_stack : 1) + MORT_BVH_TSTACK_SPARE;
+    const int shapes[3] = {1024, 768, 256};
+    out[0] = (int)im.fb.size();
+    for (int k = 0; k < 3; k++) { uint32_t a = 0, b = 0; out[1 + k] = state_lds_levels((uint32_t)im.fb.size(), shapes[k], levels, 1024u, a, b); }
+    return MORT_OK;
+}
+
+/* mort_f2i without a branch or an instruction by name: (int)x of an in-range value, guarded by selects */
+__device__ __forceinline__ int mort_f2i_select(float x) {
+    const bool in_range = (x > -2147483648.0f) && (x < 2147483648.0f);
+    const int t = (int)(in_range ? x : 0.0f);
+    return (x != x) ? 0 : (x >= 2147483648.0f) ? 2147483647 : (x <= -2147483648.0f) ? (-2147483647 - 1) : t;
+}
+static __global__ void __launch_bounds__(256) f2i_all_kernel(unsigned long long *out) {
+    const uint32_t first = blockIdx.x * 256u + threadIdx.x; /* 4096 blocks: 2^20 lanes, 2^12 patterns each */
+    uint32_t differ = 0, lowest = 0xffffffffu;
+    for (uint32_t k = 0; k < 4096u; k++) {
+        const uint32_t bits = first + (k << 20);
+        const float x = __uint_as_float(bits);
+        if (mort_f2i(x) != mort_f2i_select(x)) { differ++; lowest = bits < lowest ? bits : lowest; }
+    }
+    atomicAdd(&out[2], 4096ull);
+    if (differ) { atomicAdd(&out[0], (unsigned long long)differ); atomicMin(&out[1], (unsigned long long)lowest); }
+}
+static __global__ void __launch_bounds__(256) f2i_list_kernel(const uint32_t *bits, size_t n, int *res) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) res[i] = mort_f2i(__uint_as_float(bits[i]));
+}
+
+/* diagnostic (not in include/mort_hip.h): on `device`, out[0] = how many of the 2^32 float bit patterns the device's mort_f2i and
+ * mort_f2i_select convert differently, out[1] = the lowest such pattern (2^32 - 1 if none), out[2] = patterns visited; res[i] = the device's
+ * mort_f2i of bits[i] for the n listed patterns (n may be 0). */
+extern "C" int mort_hip_debug_f2i_device(int device, const uint32_t *bits, size_t n, int *res, unsigned long long *out) {
+    if (!out || (n && (!bits || !res)) || n > ((size_t)1 << 28)) return MORT_ERR_INVALID;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    uint32_t *d_bits = nullptr;
+    int *d_res = nullptr;
+    unsigned long long *d_out = nullptr;
+    const unsigned long long init[3] = {0ull, 0xffffffffull, 0ull};
+    int st = MORT_OK;
+    if (hipMalloc((void **)&d_out, sizeof init) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && n && (hipMalloc((void **)&d_bits, n * 4) != hipSuccess || hipMalloc((void **)&d_res, n * 4) != hipSuccess)) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && (hipMemcpy(d_out, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess ||
+                          (n && hipMemcpy(d_bits, bits, n * 4, hipMemcpyHostToDevice) != hipSuccess))) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        f2i_all_kernel<<<dim3(4096), dim3(256)>>>(d_out);
+        if (n) f2i_list_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(d_bits, n, d_res);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, sizeof init, hipMemcpyDeviceToHost) != hipSuccess ||
+            (n && hipMemcpy(res, d_res, n * 4, hipMemcpyDeviceToHost) != hipSuccess)) st = MORT_ERR_HIP;
+    }
+    if (d_bits) (void)hipFree(d_bits);
+    if (d_res) (void)hipFree(d_res);
+    if (d_out) (void)hipFree(d_out);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+/* host only, no HIP call: the host's mort_f2i of the same patterns (what gcc makes of the same source is tests/test_math.py's business) */
+extern "C" int mort_hip_debug_f2i_host(const uint32_t *bits, size_t n, int *res) {
+    if ((!bits || !res) && n) return MORT_ERR_INVALID;
+    for (size_t i = 0; i < n; i++) res[i] = mort_f2i(__builtin_bit_cast(float, bits[i]));
+    return MORT_OK;
 }
 
 extern "C" int mort_hip_render_device(mort_ctx *c, const mort_camera *cam, int mode, void *d_rgba, void *d_accum,
