@@ -1,0 +1,434 @@
+/*
+ * debug.hip -- the diagnostics behind mort_amd/hip.py's debug_* calls (none is in include/mort_hip.h).  Most are host only:
+ * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Three
+ * launch small kernels of their own (exact_forms_kernel, f2i_all_kernel, f2i_list_kernel) that put the device's short forms
+ * beside its plain operators.  mega_bvh.h is included for those bodies; its kernels are templates and none is instantiated here.
+ */
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "mort_hip.h"
+#include "mega_bvh.h"
+#include "scene_blob.h"
+#include "mort_ctx.h"
+#include "world_images.h"
+
+#pragma clang fp contract(off)
+
+/* diagnostic (not in include/mort_hip.h): the per-wave records of the last frame of a profile build run with MORT_WAVE_LINES=1 */
+extern "C" int mort_hip_debug_wave_log(mort_ctx *c, unsigned long long *out, size_t max_waves) {
+    if (!c || !out || !c->d_wave_log) return 0;
+    hipSetDevice(c->device);
+    quiesce(c);
+    const size_t n = c->wave_log_waves < max_waves ? c->wave_log_waves : max_waves;
+    if (hipMemcpy(out, c->d_wave_log, n * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    return (int)n;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): facts of this build's own trees over a world -- out[0] binary
+ * nodes, [1] leaves, [2] binary depth, [3] four-wide nodes, [4] its pending-children bound, [5] leaf references reached from the
+ * four-wide root, [6] leaves reached more than once or out of range, [7] child slots in use, [8] 1 if every four-wide box and margin
+ * is bit for bit one of the binary tree's for the same child. */
+extern "C" int mort_hip_debug_own_tree(const mort_world *w, int *out) {
+    if (!w || !out) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 9; i++) out[i] = 0;
+    out[0] = (int)o.own_nodes.size(); out[1] = (int)o.own_leaves.size(); out[2] = o.own_depth;
+    out[3] = (int)o.own_nodes4.size(); out[4] = o.own4_stack;
+    if (o.own_nodes4.empty()) return MORT_OK;
+    /* child reference -> (box, margin) in the binary tree */
+    struct Rec { float v[7]; };
+    std::vector<Rec> of_inner(o.own_nodes.size()), of_leaf(o.own_leaves.size());
+    for (const DNode2 &nd : o.own_nodes)
+        for (int k = 0; k < 2; k++) {
+            const uint32_t ref = k ? nd.child1 : nd.child0;
+            Rec r = k ? Rec{{nd.x1min, nd.x1max, nd.y1min, nd.y1max, nd.z1min, nd.z1max, nd.e1}} : Rec{{nd.x0min, nd.x0max, nd.y0min, nd.y0max, nd.z0min, nd.z0max, nd.e0}};
+            if (ref & 0x8000u) of_leaf[ref & 0x7fffu] = r; else of_inner[ref] = r;
+        }
+    std::vector<int> seen(o.own_leaves.size(), 0);
+    std::vector<uint32_t> todo(1, 0u);
+    bool same = true;
+    /* every inner child of a four-wide node stands for one binary node: find which by its box, via the leaves below it */
+    while (!todo.empty()) {
+        const uint32_t n = todo.back(); todo.pop_back();
+        const DNode4 &nd = o.own_nodes4[n];
+        for (int k = 0; k < 4; k++) {
+            const uint32_t ref = nd.child[k];
+            if (ref == 0xffffu) continue;
+            out[7]++;
+            const Rec r{{nd.x[0][k], nd.x[1][k], nd.y[0][k], nd.y[1][k], nd.z[0][k], nd.z[1][k], nd.e[k]}};
+            /* the third piece of each axis repeats the first (dev_scene.h) */
+            if (std::memcmp(&nd.x[2][k], &nd.x[0][k], 4) || std::memcmp(&nd.y[2][k], &nd.y[0][k], 4) || std::memcmp(&nd.z[2][k], &nd.z[0][k], 4)) same = false;
+            if (ref & 0x8000u) {
+                const uint32_t l = (ref & 0x7fffu) / MORT_LEAF2_PIECES;
+                if ((ref & 0x7fffu) % MORT_LEAF2_PIECES || l >= seen.size() || seen[l]++) { out[6]++; continue; }
+                out[5]++;
+                if (std::memcmp(&r, &of_leaf[l], sizeof r) != 0) same = false;
+            } else {
+                if (ref % MORT_NODE4_PIECES || ref / MORT_NODE4_PIECES >= o.own_nodes4.size()) { out[6]++; continue; }
+                bool found = false;
+                for (const Rec &b : of_inner) if (std::memcmp(&r, &b, sizeof r) == 0) { found = true; break; }
+                if (!found) same = false;
+                todo.push_back(ref / MORT_NODE4_PIECES);
+            }
+        }
+    }
+    out[8] = same ? 1 : 0;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): what mort_hip_upload_world and the launch of mega_bvh_kernel decide from
+ * a world's own trees -- out[0] 1 if the world is one reference BVH over spheres, [1] 1 if it has a four-wide tree, [2] bytes of the BVH
+ * megakernel's LDS image (0 without a four-wide tree), [3] bytes of the wavefront traversal kernel's, [4] the limit on either, [5] 1 if mega_bvh_kernel and the wavefront
+ * pipeline serve the world (both images within the limit), [6] the traversal stack levels the launch sizes for, [7] 1 if 1024-thread
+ * groups fit one CU's LDS with that image and stack. */
+extern "C" int mort_hip_debug_bvh_images(const mort_world *w, int *out) {
+    if (!w || !out) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    out[0] = one_sphere_bvh(o) ? 1 : 0; out[1] = (!o.own_nodes.empty() && !o.own_nodes4.empty()) ? 1 : 0; out[4] = MORT_BVH_IMAGE_MAX;
+    if (!out[0] || o.own_nodes.empty()) return MORT_OK;
+    BvhImages im;
+    build_bvh_images(o, im);
+    out[3] = (int)im.tb.size(); /* the binary tree's image exists without a four-wide tree, and tells how big the world is */
+    if (!out[1]) return MORT_OK;
+    out[2] = (int)im.fb.size(); out[5] = im.fits ? 1 : 0;
+    out[6] = o.own4_stack > 1 ? o.own4_stack : 1;
+    out[7] = (im.fits && bvh_wide_block_fits((uint32_t)im.fb.size(), out[6])) ? 1 : 0;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): where the unified tree of a world may be walked from -- out[0] 1 if
+ * the world has a unified tree (else the rest is 0), [1..3] the low corner of its solids' box, [4..6] the high corner, [7] the reach:
+ * a ray origin o is walked iff lo[k] - reach <= o[k] <= hi[k] + reach on every axis (camera_in_reach; per ray in dev_query.h). */
+extern "C" int mort_hip_debug_gen_reach(const mort_world *w, float *out) {
+    if (!w || !out) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    if (!o.g_ok) return MORT_OK;
+    out[0] = 1;
+    for (int k = 0; k < 3; k++) { out[1 + k] = o.g_lo[k]; out[4 + k] = o.g_hi[k]; }
+    out[7] = o.g_reach;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the unified tree of a world and what mort_hip_upload_world decides
+ * from it (build_gen_image, MORT_NO_GEN aside) -- iout[0] 1 if the world has a unified tree (else the rest is 0), [1] nodes, [2] entries,
+ * [3] depth, [4] chain ids (id 0, no transform, included), [5] bytes of the LDS image before the primitives, [6] bytes of the primitives,
+ * [7] 1 if the primitives are in the image, [8] bytes of the LDS part of the image, [9] 1 if that is within MORT_GEN_IMAGE_MAX (the
+ * unified-tree kernels serve the world), [10] MORT_GEN_IMAGE_MAX, [11] the limit on image + primitives for the primitives to be in LDS,
+ * [12] nodes whose split the depth cap chose over the best surface-area split (gen_emit);
+ * fout[0] g_R, [1] g_mnear, [2] g_kmin, [3] g_reach, [4..6] g_c (gen_ray_setup's arguments). */
+extern "C" int mort_hip_debug_gen_tree(const mort_world *w, int *iout, float *fout) {
+    if (!w || !iout || !fout) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 13; i++) iout[i] = 0;
+    for (int i = 0; i < 7; i++) fout[i] = 0;
+    if (!o.g_ok) return MORT_OK;
+    GenImage gi;
+    build_gen_image(o, gi);
+    iout[0] = 1; iout[1] = (int)o.g_nodes.size(); iout[2] = (int)o.g_entries.size(); iout[3] = o.g_depth; iout[4] = gi.g.n_chains;
+    iout[5] = (int)gi.table_bytes; iout[6] = (int)gi.prim_bytes; iout[7] = gi.g.prims_in_lds; iout[8] = (int)gi.lds_part;
+    iout[9] = gi.fits ? 1 : 0; iout[10] = MORT_GEN_IMAGE_MAX; iout[11] = MORT_GEN_PRIMS_LDS_MAX; iout[12] = o.g_capped;
+    fout[0] = gi.g.gR; fout[1] = gi.g.mnear; fout[2] = gi.g.kmin; fout[3] = o.g_reach; fout[4] = gi.g.gx; fout[5] = gi.g.gy; fout[6] = gi.g.gz;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the boxes of the occupied children of the world's four-wide tree, six
+ * floats each (xmin, xmax, ymin, ymax, zmin, zmax), at most max_boxes of them.  Returns how many there are, or a negative status. */
+extern "C" int mort_hip_debug_own_tree4_boxes(const mort_world *w, float *out, size_t max_boxes) {
+    if (!w || (!out && max_boxes)) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    size_t n = 0;
+    for (const DNode4 &nd : sb.comp.own_nodes4)
+        for (int k = 0; k < 4; k++) {
+            if (nd.child[k] == 0xffffu) continue;
+            if (n < max_boxes) { float *o = out + 6 * n; o[0] = nd.x[0][k]; o[1] = nd.x[1][k]; o[2] = nd.y[0][k]; o[3] = nd.y[1][k]; o[4] = nd.z[0][k]; o[5] = nd.z[1][k]; }
+            n++;
+        }
+    return (int)n;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the box step's two forms of the slab test, own_prune on (min, max) and
+ * own_prune_ordered on the sign-chosen (near, far) pieces, over the world's four-wide tree, the pieces chosen by own_sign_offset as in the kernel.
+ * rays: n x 7 floats (origin, direction, closest); ray r meets the nodes r % stride, r % stride + stride, ...  A ray whose reciprocals
+ * are not ordinary never reaches the box step and is only counted.  out[0] (occupied child, ray) pairs compared, [1] pairs whose te differs
+ * in any bit, [2] pairs whose skip decision differs, [3] rays left out, [4] four-wide nodes, [5] unused child slots with a non-zero plane
+ * or margin, [6] pairs skipped by both forms, [8..15] rays compared per sign octant (bit 0: x reciprocal negative, 1: y, 2: z). */
+extern "C" int mort_hip_debug_prune_forms(const mort_world *w, const float *rays, size_t n, int stride, unsigned long long *out) {
+    if (!w || !rays || !out || stride < 1) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const std::vector<DNode4> &nodes = sb.comp.own_nodes4;
+    for (int i = 0; i < 16; i++) out[i] = 0;
+    out[4] = nodes.size();
+    if (nodes.empty()) return MORT_OK;
+    for (const DNode4 &nd : nodes)
+        for (int k = 0; k < 4; k++) {
+            if (nd.child[k] != 0xffffu) continue;
+            const float v[10] = {nd.x[0][k], nd.x[1][k], nd.x[2][k], nd.y[0][k], nd.y[1][k], nd.y[2][k], nd.z[0][k], nd.z[1][k], nd.z[2][k], nd.e[k]};
+            for (float f : v) { uint32_t b; std::memcpy(&b, &f, 4); if (b) { out[5]++; break; } }
+        }
+    unsigned nthreads = std::thread::hardware_concurrency();
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    std::vector<std::array<unsigned long long, 16>> part(nthreads);
+    auto work = [&](unsigned t) {
+        std::array<unsigned long long, 16> &o = part[t];
+        o.fill(0);
+        for (size_t r = t; r < n; r += nthreads) {
+            const float *q = rays + 7 * r;
+            OwnRay orr; /* as the kernel's segment setup (mega_bvh.h) */
+            orr.ix = 1.0f / q[3]; orr.iy = 1.0f / q[4]; orr.iz = 1.0f / q[5];
+            orr.mx = q[0] * orr.ix; orr.my = q[1] * orr.iy; orr.mz = q[2] * orr.iz;
+            const float mm = __builtin_fmaxf(__builtin_fmaxf(mort_fabsf(orr.mx), mort_fabsf(orr.my)), mort_fabsf(orr.mz));
+            orr.band = mm * 4.76837158203125e-07f;
+            orr.invlen = 1.01f / mort_sqrtf(q[3] * q[3] + q[4] * q[4] + q[5] * q[5]);
+            if (!(own_inv_ok(orr.ix) && own_inv_ok(orr.iy) && own_inv_ok(orr.iz) && (mm < 1e30f))) { o[3]++; continue; }
+            const uint32_t sx = own_sign_offset(orr.ix) / 16u, sy = own_sign_offset(orr.iy) / 16u, sz = own_sign_offset(orr.iz) / 16u;
+            o[8 + (sx | sy << 1 | sz << 2)]++;
+            const float closest = q[6];
+            for (size_t ni = r % (size_t)stride; ni < nodes.size(); ni += (size_t)stride) {
+                const DNode4 &nd = nodes[ni];
+                for (int k = 0; k < 4; k++) {
+                    if (nd.child[k] == 0xffffu) continue;
+                    float te_a, te_b;
+                    const bool skip_a = own_prune(nd.x[0][k], nd.x[1][k], nd.y[0][k], nd.y[1][k], nd.z[0][k], nd.z[1][k], nd.e[k], orr, closest, te_a);
+                    const bool skip_b = own_prune_ordered(nd.x[sx][k], nd.x[sx + 1][k], nd.y[sy][k], nd.y[sy + 1][k], nd.z[sz][k], nd.z[sz + 1][k], nd.e[k], orr, closest, te_b);
+                    o[0]++;
+                    if (std::memcmp(&te_a, &te_b, 4) != 0) o[1]++;
+                    if (skip_a != skip_b) o[2]++;
+                    if (skip_a && skip_b) o[6]++;
+                }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < nthreads; t++) pool.emplace_back(work, t);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    for (const auto &o : part) for (int i = 0; i < 16; i++) if (i != 4 && i != 5) out[i] += o[i];
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): dev_math.h's guards of the short forms, per value: bit 0 div_den_ok,
+ * bit 1 div_num_ok, bit 2 sqrt_arg_ok */
+extern "C" int mort_hip_debug_exact_guards(const float *v, size_t n, unsigned char *flags) {
+    if ((!v || !flags) && n) return MORT_ERR_INVALID;
+    for (size_t i = 0; i < n; i++) flags[i] = (unsigned char)((div_den_ok(v[i]) ? 1 : 0) | (div_num_ok(v[i]) ? 2 : 0) | (sqrt_arg_ok(v[i]) ? 4 : 0));
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the MODELS of the short forms (dev_math.h: the fma sequences as plain
+ * C++, the hardware's seed a parameter) against the host's correctly rounded operators.
+ *   what 0: sqrt_ord_model(x[i], seed) against sqrtf(x[i]), seed = sqrtf(x[i]) moved by every offset in [seed_lo, seed_hi] units of its
+ *           last place; `a` is not read;
+ *   what 1: div_by_model(x[i], a[i], div_by_model_prepare(a[i], seed)) against x[i] / a[i], seed = fl(1 / a[i]) moved likewise.
+ * Inputs outside the guards (sqrt_arg_ok; div_den_ok and 2^-85 <= |x| < 2^56) are only counted.  out[0] comparisons, [1] those that
+ * differ in any bit, [2] inputs outside the guards, [8..15] the indices of the first inputs that differ. */
+extern "C" int mort_hip_debug_exact_forms_model(int what, const float *x, const float *a, size_t n, int seed_lo, int seed_hi, unsigned long long *out) {
+    if (!x || !out || (what != 0 && what != 1) || (what == 1 && !a) || seed_lo > seed_hi) return MORT_ERR_INVALID;
+    for (int i = 0; i < 16; i++) out[i] = 0;
+    for (size_t i = 0; i < n; i++) {
+        const bool inside = what == 0 ? sqrt_arg_ok(x[i]) : (div_den_ok(a[i]) && div_num_ok(x[i]) && mort_fabsf(x[i]) >= 0x1p-85f);
+        if (!inside) { out[2]++; continue; }
+        const float want = what == 0 ? mort_sqrtf(x[i]) : x[i] / a[i];
+        const float seed0 = what == 0 ? want : 1.0f / a[i];
+        for (int k = seed_lo; k <= seed_hi; k++) {
+            const float seed = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, seed0) + (uint32_t)k);
+            const float got = what == 0 ? sqrt_ord_model(x[i], seed) : div_by_model(x[i], a[i], div_by_model_prepare(a[i], seed));
+            out[0]++;
+            if (std::memcmp(&got, &want, 4) != 0) { if (out[1] < 8) out[8 + out[1]] = i; out[1]++; }
+        }
+    }
+    return MORT_OK;
+}
+
+/* the device forms against the device's own operators, one element per lane and round (mort_hip_debug_exact_forms_device) */
+__device__ __forceinline__ void exact_forms_count(unsigned long long *slot, bool cond) {
+    const unsigned long long m = __ballot(cond);
+    if (m != 0ull && (int)(threadIdx.x & 63u) == __ffsll((long long)m) - 1) atomicAdd(slot, (unsigned long long)__popcll(m));
+}
+static __global__ void __launch_bounds__(256) exact_forms_kernel(int what, const float *in, size_t n, unsigned long long *out) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    const size_t rounds = (n + stride - 1) / stride; /* every lane runs every round: the ballots see whole waves */
+    for (size_t k = 0; k < rounds; k++) {
+        const size_t i = k * stride + (size_t)blockIdx.x * 256 + threadIdx.x;
+        const bool live = i < n;
+        bool compared = false, differs = false, outside = false, small = false, short_path = false, generic_path = false, short_hit = false, generic_hit = false;
+        if (live && what == 0) {
+            const float x = in[i];
+            if (sqrt_arg_ok(x)) {
+                compared = true;
+                differs = __float_as_uint(sqrt_ord(x)) != __float_as_uint(mort_sqrtf(x));
+            } else outside = true;
+        } else if (live && what == 1) {
+            const float x = in[2 * i], a = in[2 * i + 1];
+            const DivBy dv = div_prepare(a);
+            if (dv.ok && div_num_ok(x)) {
+                const float got = div_by(x, dv), want = x / a;
+                if (mort_fabsf(x) >= 0x1p-85f) { compared = true; differs = __float_as_uint(got) != __float_as_uint(want); }
+                else { small = true; differs = !(mort_fabsf(got) < 0x1p-44f && mort_fabsf(want) < 0x1p-44f); } /* both finite and below any t_min >= 2^-44 */
+            } else outside = true;
+        } else if (live) {
+            const float *q = in + 16 * i;
+            Ray ray; ray.o = mk(q[0], q[1], q[2]); ray.d = mk(q[3], q[4], q[5]); ray.tm = q[6];
+            const float t_max = q[7];
+            DSphere s;
+            s.cx = q[8]; s.cy = q[9]; s.cz = q[10]; s.radius = q[11]; s.vx = q[12]; s.vy = q[13]; s.vz = q[14];
+            s.mat = q[15] != 0.0f ? 0x80000000u : 0u; /* bit 31: the sphere moves (dev_scene.h) */
+            const float a = vlen2(ray.d);
+            const DivBy dv = div_prepare(a);
+            const float got = sphere_hit_root_fast(s, ray, dv, 0.001f, t_max), want = sphere_hit_root(s, ray, a, 0.001f, t_max);
+            compared = true;
+            differs = __float_as_uint(got) != __float_as_uint(want);
+            const SphereQuad sq = sphere_quadratic(s, ray, a);
+            short_path = sphere_short_ok(sq.discriminant, sq.hb2, dv);
+            generic_path = !short_path && !(sq.discriminant < 0);
+            short_hit = short_path && want != -1.0f;
+            generic_hit = generic_path && want != -1.0f;
+        }
+        exact_forms_count(&out[0], compared);
+        exact_forms_count(&out[2], outside);
+        exact_forms_count(&out[3], small);
+        exact_forms_count(&out[4], short_path);
+        exact_forms_count(&out[5], generic_path);
+        exact_forms_count(&out[6], short_hit);
+        exact_forms_count(&out[7], generic_hit);
+        if (differs) { const unsigned long long at = atomicAdd(&out[1], 1ull); if (at < 8ull) out[8 + at] = (unsigned long long)i; }
+    }
+}
+
+/* diagnostic (not in include/mort_hip.h): one launch of the kernel above on `device`, the short forms against the plain operators ON THE DEVICE.
+ *   what 0: in = n values x: sqrt_ord(x) against sqrtf(x) where sqrt_arg_ok(x);
+ *   what 1: in = n pairs (x, a): div_by(x, div_prepare(a)) against x / a where div_den_ok(a) and div_num_ok(x); a numerator below 2^-85 is
+ *           checked for what dev_math.h promises instead: both quotients below 2^-44 in magnitude;
+ *   what 2: in = n records of 16 floats (ray origin, direction, time, t_max; sphere centre, radius, velocity, moves != 0):
+ *           sphere_hit_root_fast against sphere_hit_root with t_min = 0.001, a = the direction's squared length.
+ * out[0] elements compared bit for bit, [1] elements that fail, [2] outside the guards (what 0, 1), [3] small numerators (what 1), what 2:
+ * [4] records on the short branch, [5] on the generic branch past its miss test, [6] / [7] accepted roots of either, [8..15] first failing elements. */
+extern "C" int mort_hip_debug_exact_forms_device(int device, int what, const float *in, size_t n, unsigned long long *out) {
+    if (!in || !out || what < 0 || what > 2 || n == 0) return MORT_ERR_INVALID;
+    const size_t per = what == 0 ? 1 : what == 1 ? 2 : 16;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    float *d_in = nullptr;
+    unsigned long long *d_out = nullptr;
+    int st = MORT_OK;
+    if (hipMalloc((void **)&d_in, n * per * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_out, 16 * sizeof(unsigned long long)) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && (hipMemcpy(d_in, in, n * per * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemset(d_out, 0, 16 * sizeof(unsigned long long)) != hipSuccess)) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        const size_t blocks = (n + 255) / 256;
+        exact_forms_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256)>>>(what, d_in, n, d_out);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the bounce-stack levels a launch of mega_bvh_kernel keeps in LDS beside
+ * the world's image -- out[0] the image's bytes (0: the world is not served by that kernel, the rest is 0 too), out[1..3] the levels on
+ * 1024-, 768- and 256-thread workgroups (state_lds_levels with the kernel's 1 KB of static LDS); deeper levels go to HBM. */
+extern "C" int mort_hip_debug_bvh_lds_levels(const mort_world *w, int *out) {
+    if (!w || !out) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    const int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const mortc::Compiled &o = sb.comp;
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (!one_sphere_bvh(o) || o.own_nodes.empty() || o.own_nodes4.empty()) return MORT_OK;
+    BvhImages im;
+    build_bvh_images(o, im);
+    if (!im.fits) return MORT_OK;
+    const uint32_t levels = (uint32_t)(o.own4_stack > 1 ? o.own4_stack : 1) + MORT_BVH_TSTACK_SPARE;
+    const int shapes[3] = {1024, 768, 256};
+    out[0] = (int)im.fb.size();
+    for (int k = 0; k < 3; k++) { uint32_t a = 0, b = 0; out[1 + k] = state_lds_levels((uint32_t)im.fb.size(), shapes[k], levels, 1024u, a, b); }
+    return MORT_OK;
+}
+
+/* the device side of mort_f2i (mort_math.h: one v_cvt_i32_f32) against mort_f2i_select compiled beside it, over ALL 2^32 bit patterns
+ * (every lane takes every 2^20-th pattern), and its results for a list of patterns (mort_hip_debug_f2i_device) */
+
+/* mort_f2i without a branch or an instruction by name: (int)x of an in-range value, guarded by selects */
+__device__ __forceinline__ int mort_f2i_select(float x) {
+    const bool in_range = (x > -2147483648.0f) && (x < 2147483648.0f);
+    const int t = (int)(in_range ? x : 0.0f);
+    return (x != x) ? 0 : (x >= 2147483648.0f) ? 2147483647 : (x <= -2147483648.0f) ? (-2147483647 - 1) : t;
+}
+static __global__ void __launch_bounds__(256) f2i_all_kernel(unsigned long long *out) {
+    const uint32_t first = blockIdx.x * 256u + threadIdx.x; /* 4096 blocks: 2^20 lanes, 2^12 patterns each */
+    uint32_t differ = 0, lowest = 0xffffffffu;
+    for (uint32_t k = 0; k < 4096u; k++) {
+        const uint32_t bits = first + (k << 20);
+        const float x = __uint_as_float(bits);
+        if (mort_f2i(x) != mort_f2i_select(x)) { differ++; lowest = bits < lowest ? bits : lowest; }
+    }
+    atomicAdd(&out[2], 4096ull);
+    if (differ) { atomicAdd(&out[0], (unsigned long long)differ); atomicMin(&out[1], (unsigned long long)lowest); }
+}
+static __global__ void __launch_bounds__(256) f2i_list_kernel(const uint32_t *bits, size_t n, int *res) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) res[i] = mort_f2i(__uint_as_float(bits[i]));
+}
+
+/* diagnostic (not in include/mort_hip.h): on `device`, out[0] = how many of the 2^32 float bit patterns the device's mort_f2i and
+ * mort_f2i_select convert differently, out[1] = the lowest such pattern (2^32 - 1 if none), out[2] = patterns visited; res[i] = the device's
+ * mort_f2i of bits[i] for the n listed patterns (n may be 0). */
+extern "C" int mort_hip_debug_f2i_device(int device, const uint32_t *bits, size_t n, int *res, unsigned long long *out) {
+    if (!out || (n && (!bits || !res)) || n > ((size_t)1 << 28)) return MORT_ERR_INVALID;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    uint32_t *d_bits = nullptr;
+    int *d_res = nullptr;
+    unsigned long long *d_out = nullptr;
+    const unsigned long long init[3] = {0ull, 0xffffffffull, 0ull};
+    int st = MORT_OK;
+    if (hipMalloc((void **)&d_out, sizeof init) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && n && (hipMalloc((void **)&d_bits, n * 4) != hipSuccess || hipMalloc((void **)&d_res, n * 4) != hipSuccess)) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && (hipMemcpy(d_out, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess ||
+                          (n && hipMemcpy(d_bits, bits, n * 4, hipMemcpyHostToDevice) != hipSuccess))) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        f2i_all_kernel<<<dim3(4096), dim3(256)>>>(d_out);
+        if (n) f2i_list_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(d_bits, n, d_res);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, sizeof init, hipMemcpyDeviceToHost) != hipSuccess ||
+            (n && hipMemcpy(res, d_res, n * 4, hipMemcpyDeviceToHost) != hipSuccess)) st = MORT_ERR_HIP;
+    }
+    if (d_bits) (void)hipFree(d_bits);
+    if (d_res) (void)hipFree(d_res);
+    if (d_out) (void)hipFree(d_out);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+/* host only, no HIP call: the host's mort_f2i of the same patterns (what gcc makes of the same source is tests/test_math.py's business) */
+extern "C" int mort_hip_debug_f2i_host(const uint32_t *bits, size_t n, int *res) {
+    if ((!bits || !res) && n) return MORT_ERR_INVALID;
+    for (size_t i = 0; i < n; i++) res[i] = mort_f2i(__builtin_bit_cast(float, bits[i]));
+    return MORT_OK;
+}

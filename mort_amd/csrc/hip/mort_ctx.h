@@ -16,6 +16,7 @@
 
 #include "mort_hip.h"
 #include "mega_gen.h"
+#include "world_images.h"
 
 /* the kernel families of a render (mort_hip.hip choose_family) */
 enum RenderFamily { FAM_MEGA, FAM_BVH, FAM_GEN, FAM_WAVE, FAM_WAVE_GEN };
@@ -65,10 +66,9 @@ struct mort_ctx {
     bool wave_ok = false; /* wavefront mode: one BVH over spheres as the whole world, hot blob fits LDS */
     /* BVH megakernel: its own LDS image (four-wide own tree, leaf records with their spheres, leaf boxes, material / texture tables) */
     void *d_fast = nullptr;
-    uint32_t f_lambert = 0, f_metal = 0, f_diel = 0, f_dlight = 0, f_iso = 0,
-             f_solid = 0, f_checker = 0, fast_bytes = 0, f_nodes4 = 0, f_leafrecs = 0;
     void *d_trav = nullptr; /* wf_trav's LDS image */
-    uint32_t t_nodes2 = 0, t_leaves = 0, t_spheres = 0, trav_bytes = 0;
+    uint32_t fast_bytes = 0, trav_bytes = 0;
+    BvhOffsets bvh{}; /* where the parts of the two images lie (world_images.h build_bvh_images) */
     int own_nodes = 0, own_leaves = 0, own4_stack = 1;
     bool fast_ok = false;
     /* unified-tree megakernel (mega_gen.hip): its LDS image and launch constants */
@@ -154,6 +154,18 @@ static inline hipError_t switch_stream(mort_ctx *c, hipStream_t s) {
     return e;
 }
 
+/* Wait for everything this context has launched: its own stream and, if a render went to a caller's stream, that one
+ * too -- before any call that reads, overwrites or frees what a render kernel uses (states, scene, counters). */
+static inline hipError_t quiesce(mort_ctx *c) {
+    hipError_t e = hipSuccess;
+    if (c->stream) e = hipStreamSynchronize(c->stream);
+    if (c->last_stream && c->last_stream != c->stream) { hipError_t e2 = hipStreamSynchronize(c->last_stream); if (e == hipSuccess) e = e2; }
+    c->last_stream = nullptr;
+    if (c->dn_stream && c->dn_stream != c->stream) { hipError_t e2 = hipStreamSynchronize(c->dn_stream); if (e == hipSuccess) e = e2; } /* the stages */
+    c->dn_stream = nullptr;
+    return e;
+}
+
 /* rows of `height` that partition p owns: blocks rank, rank + nranks, ... of rows_per_block rows */
 static inline int local_rows_for(const mort_partition &p, int height) {
     int n = 0;
@@ -165,6 +177,12 @@ static inline int local_rows_for(const mort_partition &p, int height) {
         n += r1 - r0;
     }
     return n;
+}
+
+/* the image row of partition p's packed row ly */
+static inline int global_row_host(const mort_partition &p, int ly) {
+    const int lb = ly / p.rows_per_block, within = ly % p.rows_per_block;
+    return (lb * p.nranks + p.rank) * p.rows_per_block + within;
 }
 
 /* the camera must lie where the unified tree's pads were sized for (scene_compile.h build_unified): its centre, widened by

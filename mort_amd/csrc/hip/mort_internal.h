@@ -7,7 +7,31 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include <cstdio>
+#include <cstdlib>
+
 #include "mort_hip.h"
+
+/* ---- tuning variables (MORT_*): read with getenv where they apply, on every call, so a process may change them between renders.
+ * These parse the text getenv gave (null: the variable is not set): each leaves v as it is unless the text is there and accepted,
+ * and says whether it wrote v ---- */
+/* a switch: on iff the text begins with '1' */
+static inline bool knob_flag(const char *e, bool &v) { if (e) v = e[0] == '1'; return e != nullptr; }
+/* any integer, as atoi reads it (text that is no number: 0) */
+static inline bool knob_int(const char *e, int &v) { if (e) v = std::atoi(e); return e != nullptr; }
+/* an integer in [lo, hi] */
+static inline bool knob_int_in(const char *e, int lo, int hi, int &v) { int x = 0; if (!knob_int(e, x) || x < lo || x > hi) return false; v = x; return true; }
+/* "a,b,..": n <= 4 integers, each at least min (text after the n-th is not looked at) */
+static inline bool knob_ints(const char *e, int n, int min, int *v) {
+    int x[4] = {0, 0, 0, 0};
+    if (!e || std::sscanf(e, "%d,%d,%d,%d", &x[0], &x[1], &x[2], &x[3]) < n) return false;
+    for (int k = 0; k < n; k++) if (x[k] < min) return false;
+    for (int k = 0; k < n; k++) v[k] = x[k];
+    return true;
+}
+
+/* context.hip: MORT_MODE_THROUGHPUT's (pixel, stratum row) streams for this image, partition and sqrt_spp, seeded on `s` when they are not yet */
+int mort_ensure_substates(mort_ctx *c, int W, int H, int S, hipStream_t s);
 
 /* tile_sort.hip */
 size_t mort_tile_sort_temp_bytes(int n);

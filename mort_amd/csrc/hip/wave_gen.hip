@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "mort_internal.h"
 #include "wave_gen.h"
 #include "wave_common.h"
 #include "dev_gen.h"
@@ -473,7 +474,7 @@ static int trav_block_for(const GenArgs &ga) { /* the LDS image + per-wave stagi
     int tb = need512 <= 150 * 1024 ? 512 : 256;
     /* a big image (the final scene's 98 KB) admits one workgroup per CU: the kernel needs under 128 VGPRs, so that workgroup can bring four waves per SIMD */
     if (need512 > 75 * 1024 && need1024 <= 158 * 1024) tb = 1024;
-    if (const char *e = std::getenv("MORT_WAVE_TRAV_BLOCK")) { const int v = std::atoi(e); if (v == 256 || v == 512 || (v == 1024 && need1024 <= 158 * 1024)) tb = v; }
+    { int v = 0; if (knob_int(std::getenv("MORT_WAVE_TRAV_BLOCK"), v) && (v == 256 || v == 512 || (v == 1024 && need1024 <= 158 * 1024))) tb = v; }
     return tb;
 }
 int mort_wave_gen_render(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, hipStream_t s, LaunchPlan &plan) {
@@ -484,8 +485,7 @@ int mort_wave_gen_render(mort_ctx *c, const mort_camera *cam, const RenderArgs &
     ga.f.r = a;
     ga.f.hot_src = (const unsigned char *)c->d_gen; ga.f.hot_bytes = c->gen_bytes;
     ga.f.th_s = 32; ga.f.th_l = 24; ga.f.t_keep = 16; /* wf_trav_gen's retire+refill / leaf / box-run thresholds */
-    { const char *th = std::getenv("MORT_WAVE_THRESHOLDS"); /* "f,l,k" */
-      if (th) { int f_ = 0, l_ = 0, k_ = 0; if (std::sscanf(th, "%d,%d,%d", &f_, &l_, &k_) == 3 && f_ >= 1 && l_ >= 1 && k_ >= 1) { ga.f.th_s = f_; ga.f.th_l = l_; ga.f.t_keep = k_; } } }
+    { int th[3]; if (knob_ints(std::getenv("MORT_WAVE_THRESHOLDS"), 3, 1, th)) { ga.f.th_s = th[0]; ga.f.th_l = th[1]; ga.f.t_keep = th[2]; } } /* "f,l,k" */
     const int TB = trav_block_for(ga);
     trav_kernel_t trav = pick_trav(TB, ga.prims_in_lds != 0);
     /* LDS of wf_trav_gen: image | traversal stacks | class staging */

@@ -743,7 +743,7 @@ def render_host(world, cam, states=None, seed=S.DEFAULT_SEED, nthreads=1, tree=F
 
 
 def debug_own_tree(world):
-    """mort_hip_debug_own_tree (host only): dict of the nine facts of this build's own trees over the world (mort_hip.hip)."""
+    """mort_hip_debug_own_tree (host only): dict of the nine facts of this build's own trees over the world (debug.hip)."""
     fn = lib().mort_hip_debug_own_tree
     fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     out = (C.c_int * 9)()
@@ -755,7 +755,7 @@ def debug_own_tree(world):
 
 def debug_bvh_images(world):
     """mort_hip_debug_bvh_images (host only): what mort_hip_upload_world and the launch of mega_bvh_kernel will decide for the world --
-    dict(sphere_bvh, four_wide, fast_bytes, trav_bytes, limit, fits, stack_levels, wide_fits) (mort_hip.hip)."""
+    dict(sphere_bvh, four_wide, fast_bytes, trav_bytes, limit, fits, stack_levels, wide_fits) (debug.hip)."""
     fn = lib().mort_hip_debug_bvh_images
     fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     out = (C.c_int * 8)()

@@ -171,7 +171,7 @@ def _recomposed(ctx, w, cam, nranks, rpb):
 def test_launch_shapes(gpu_ctx, oracle, monkeypatch, env, block):
     """workgroup sizes, a lane cap, the drain mode and a row partition on the entries with the largest LDS images and the deepest
     traversal stacks: none of it reaches the pixels.  A request for 1024 threads is honoured or lowered to 768 as the LDS sum of
-    mort_hip.hip (bvh_wide_block_fits) says for the entry's image and stack bound."""
+    world_images.h (bvh_wide_block_fits) says for the entry's image and stack bound."""
     for name in _shape_cases():
         w, _, _ = bvh_random_case(name)
         p = bvh_random_prediction(name)

@@ -23,7 +23,7 @@ from tests.checker_worlds import nested_checker_world
 
 pytestmark = pytest.mark.gpu
 
-LDS_LEVELS_MAX = 12  # mort_hip.hip: the launch keeps at most twelve bounce-stack levels in LDS
+LDS_LEVELS_MAX = 12  # world_images.h state_lds_levels: the launch keeps at most twelve bounce-stack levels in LDS
 _REF = {}
 
 

@@ -622,7 +622,7 @@ def random_bvh_world(rng, n, family, extras=False, emissive=False):
 
 # The catalogue: name -> (family, spheres, seed, extras, emissive).  Two seeds of every family at 2 .. 7 spheres (2: one leaf
 # node, no own tree), 64, 300, the family's size just below and just above the 72 KB limit on the LDS images
-# (mort_hip.hip build_bvh_images; found on the CPU, tests/test_bvh_random_host.py holds the census) and 1000, the list's
+# (world_images.h build_bvh_images; found on the CPU, tests/test_bvh_random_host.py holds the census) and 1000, the list's
 # capacity; seed 1 of the 64s and 300s with checker and noise textures.
 BVH_LIMIT_SIZES = {"uniform": (650, 660), "cluster": (640, 660), "scales": (640, 650), "line": (670, 680), "shells": (640, 660),
                    "ties": (650, 670)}
@@ -1122,7 +1122,7 @@ def random_gen_world(rng, n, family, seed, far_view=False, tele_view=False):
 
 # The catalogue: name -> (family, tree entries, seed).  Two seeds of every family at 1 (not `ties`: a tie takes two), 2, 3, 5, 47 and
 # 48 (the two sides of the default MORT_GEN_MIN_PRIMS), 150, the family's sizes just below and just above the 48 KB rule that puts
-# the primitives into the LDS image (mort_hip.hip build_gen_image; found on the CPU with hip.debug_gen_tree,
+# the primitives into the LDS image (world_images.h build_gen_image; found on the CPU with hip.debug_gen_tree,
 # tests/test_gen_random_host.py holds the census) and 1000; `mixed` and `quads` once more near the capacity of the reference's
 # sphere and quad tables.
 GEN_LIMIT_SIZES = {"mixed": (300, 310), "scales": (540, 550), "offset": (300, 310), "quads": (260, 270), "line": (390, 410), "ties": (330, 360),
