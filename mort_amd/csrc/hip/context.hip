@@ -58,10 +58,7 @@ seed_kernel(const SeedArgs a) {
             v[0] = r0; v[1] = r1; v[2] = r2; v[3] = r3; v[4] = r4;
         }
     }
-    mort_rng_state st;
-    st.d = a.d0; st.v[0] = v[0]; st.v[1] = v[1]; st.v[2] = v[2]; st.v[3] = v[3]; st.v[4] = v[4];
-    st.boxmuller_flag = 0; st.boxmuller_flag_double = 0; st.boxmuller_extra = 0.f; st.boxmuller_extra_double = 0.;
-    a.states[i] = st;
+    a.states[i] = rng_state(a.d0, v[0], v[1], v[2], v[3], v[4]);
 }
 
 extern "C" const char *mort_hip_strerror(int st) {

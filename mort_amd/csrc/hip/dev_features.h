@@ -135,21 +135,8 @@ DEV float dn_expf(float x) {
     return p * gen_bits_float((uint32_t)(n + 127) << 23); /* n in [-126, 127] */
 }
 
-/* the tail of render_pixel (dev_pixel.h): gamma 2 as sqrt, clamp to [0, 0.999], x256, truncate */
-DEV uchar4 dn_rgba(float r, float g, float b) {
-    const float c[3] = {mort_sqrtf(r), mort_sqrtf(g), mort_sqrtf(b)};
-    unsigned char o[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float v = c[k];
-        if (v < 0.0f) v = 0.0f;
-        if (v > 0.999f) v = 0.999f;
-        o[k] = (unsigned char)mort_f2i(256 * v);
-    }
-    uchar4 out;
-    out.x = o[0]; out.y = o[1]; out.z = o[2]; out.w = 255;
-    return out;
-}
+/* a filtered colour as the render would have written it (dev_render.h pixel_rgba) */
+DEV uchar4 dn_rgba(float r, float g, float b) { uchar4 out; pixel_rgba(out, mk(r, g, b)); return out; }
 
 /* B3-spline taps (1/16, 1/4, 3/8, 1/4, 1/16) */
 DEV float dn_kernel(int i) { return (i == 0 || i == 4) ? 0.0625f : (i == 2 ? 0.375f : 0.25f); }

@@ -29,12 +29,7 @@ DEV PixelTotals render_pixel(const RenderArgs &a, const GenWalk *gw, int x, int 
     const int y = global_row(ly, a.rank, a.nranks, a.rows_per_block);
     const int lofs = x + ly * a.width;
 
-    Rng rng;
-    {
-        const mort_rng_state st = a.states[lofs];
-        rng.d = st.d; rng.v0 = st.v[0]; rng.v1 = st.v[1]; rng.v2 = st.v[2]; rng.v3 = st.v[3]; rng.v4 = st.v[4];
-        rng.draws = 0;
-    }
+    Rng rng = rng_load(a.states[lofs]);
 
     StackEntry stack[MORT_MAX_BOUNCE_LIMIT];
     unsigned long long ident_mask = 0ull; /* levels whose entry is the identity (dielectric): not stored, see mega_bvh.h */
@@ -103,32 +98,11 @@ DEV PixelTotals render_pixel(const RenderArgs &a, const GenWalk *gw, int x, int 
     }
 
     /* camera.cuh:194-207 */
-    pixel_color = vscale(a.pixel_samples_scale, pixel_color);
-    if (pixel_color.x != pixel_color.x) pixel_color.x = 0.0f;
-    if (pixel_color.y != pixel_color.y) pixel_color.y = 0.0f;
-    if (pixel_color.z != pixel_color.z) pixel_color.z = 0.0f;
+    pixel_color = pixel_finish(a.pixel_samples_scale, pixel_color);
     if (a.accum) { a.accum[3 * lofs] = pixel_color.x; a.accum[3 * lofs + 1] = pixel_color.y; a.accum[3 * lofs + 2] = pixel_color.z; }
-    uchar4 out;
-    {
-        float c[3] = {mort_sqrtf(pixel_color.x), mort_sqrtf(pixel_color.y), mort_sqrtf(pixel_color.z)};
-        unsigned char b[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float v = c[k];
-            if (v < 0.0f) v = 0.0f;
-            if (v > 0.999f) v = 0.999f;
-            b[k] = (unsigned char)mort_f2i(256 * v);
-        }
-        out.x = b[0]; out.y = b[1]; out.z = b[2]; out.w = 255;
-    }
-    a.rgba[lofs] = out;
+    pixel_rgba(a.rgba[lofs], pixel_color);
     if (a.seg_px) a.seg_px[lofs] = segments;
-    {
-        mort_rng_state st;
-        st.d = rng.d; st.v[0] = rng.v0; st.v[1] = rng.v1; st.v[2] = rng.v2; st.v[3] = rng.v3; st.v[4] = rng.v4;
-        st.boxmuller_flag = 0; st.boxmuller_flag_double = 0; st.boxmuller_extra = 0.f; st.boxmuller_extra_double = 0.;
-        a.states[lofs] = st;
-    }
+    a.states[lofs] = rng_state(rng.d, rng.v0, rng.v1, rng.v2, rng.v3, rng.v4);
     PixelTotals t; t.segments = segments; t.draws = rng.draws;
     return t;
 }

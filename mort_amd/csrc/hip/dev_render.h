@@ -1,7 +1,8 @@
 /*
  * dev_render.h -- what every render kernel of libmort_hip.so shares: the launch arguments (camera, partition,
- * buffers), Camera::get_ray (camera.cuh:210-242), light-object sampling (pdf.cuh:60-80 over the objects.cuh
- * dispatchers) and the bounce-stack entry of ray_color's unwind (camera.cuh:165-173).
+ * buffers), Camera::get_ray (camera.cuh:210-242), the end of a pixel (camera.cuh:194-207), a stream's load and store,
+ * light-object sampling (pdf.cuh:60-80 over the objects.cuh dispatchers) and the bounce-stack entry of ray_color's
+ * unwind (camera.cuh:165-173).
  */
 #ifndef MORT_DEV_RENDER_H
 #define MORT_DEV_RENDER_H
@@ -68,6 +69,42 @@ DEV Ray get_ray(const CAM &a, int x, int y, Rng &rng, int s_i, int s_j) {
     r.o = origin;
     r.d = vsub(pixel_sample, origin);
     r.tm = random_float(rng);
+    return r;
+}
+
+/* ---- the end of a pixel (camera.cuh:194-207), the one copy every render kernel, the host loop and the filter stages use ---- */
+/* scale * sum, each NaN component 0 */
+DEV V3 pixel_finish(float scale, V3 sum) {
+    V3 c = vscale(scale, sum);
+    if (c.x != c.x) c.x = 0.0f;
+    if (c.y != c.y) c.y = 0.0f;
+    if (c.z != c.z) c.z = 0.0f;
+    return c;
+}
+/* gamma 2 as sqrt, clamp to [0, 0.999], x256, truncate, into the pixel itself (a uchar4 returned by value, or filled in a local and
+ * copied, has its bytes packed by other instructions than the ones the kernels have always run) */
+DEV void pixel_rgba(uchar4 &out, V3 c) {
+    float g[3] = {mort_sqrtf(c.x), mort_sqrtf(c.y), mort_sqrtf(c.z)};
+    unsigned char b[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float v = g[k];
+        if (v < 0.0f) v = 0.0f;
+        if (v > 0.999f) v = 0.999f;
+        b[k] = (unsigned char)mort_f2i(256 * v);
+    }
+    out.x = b[0]; out.y = b[1]; out.z = b[2]; out.w = 255;
+}
+
+/* ---- a stream between its 48-byte record and registers: the Box-Muller fields are never used, and stored as zeros ---- */
+DEV mort_rng_state rng_state(uint32_t d, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t v4) {
+    mort_rng_state st;
+    st.d = d; st.v[0] = v0; st.v[1] = v1; st.v[2] = v2; st.v[3] = v3; st.v[4] = v4;
+    st.boxmuller_flag = 0; st.boxmuller_flag_double = 0; st.boxmuller_extra = 0.f; st.boxmuller_extra_double = 0.;
+    return st;
+}
+DEV Rng rng_load(const mort_rng_state &st) {
+    Rng r; r.d = st.d; r.v0 = st.v[0]; r.v1 = st.v[1]; r.v2 = st.v[2]; r.v3 = st.v[3]; r.v4 = st.v[4]; r.draws = 0;
     return r;
 }
 

@@ -373,19 +373,13 @@ __device__ __attribute__((noinline)) void pixel_write(const FastArgs *fap, float
     const RenderArgs &a = fa.r;
     if (SUB) { /* a stratum row of a pixel: its colour sum goes to the virtual accumulator, the resolve kernel finishes the pixel */
         fa.vaccum[3 * (size_t)lofs] = sx; fa.vaccum[3 * (size_t)lofs + 1] = sy; fa.vaccum[3 * (size_t)lofs + 2] = sz;
-        mort_rng_state st;
-        st.d = d; st.v[0] = v0; st.v[1] = v1; st.v[2] = v2; st.v[3] = v3; st.v[4] = v4;
-        st.boxmuller_flag = 0; st.boxmuller_flag_double = 0; st.boxmuller_extra = 0.f; st.boxmuller_extra_double = 0.;
-        a.states[lofs] = st;
+        a.states[lofs] = rng_state(d, v0, v1, v2, v3, v4);
         const unsigned slot = 32u + 2u * (blockIdx.x & 31u);
         atomicAdd(&a.counters[slot], (unsigned long long)segments);
         atomicAdd(&a.counters[slot + 1u], (unsigned long long)draws);
         return;
     }
-    V3 c = vscale(a.pixel_samples_scale, mk(sx, sy, sz)); /* camera.cuh:194-207 */
-    if (c.x != c.x) c.x = 0.0f;
-    if (c.y != c.y) c.y = 0.0f;
-    if (c.z != c.z) c.z = 0.0f;
+    const V3 c = pixel_finish(a.pixel_samples_scale, mk(sx, sy, sz)); /* camera.cuh:194-207 */
     if (fa.tile_cost) { /* the tile's key in the next frame's order: its LONGEST pixel (a frame with a few pixels per lane ends when its longest chains
                          * do, so those must start first, and a tile with one long pixel among 63 short ones has a small sum), or the tile's sum */
         const int lyl = lofs / a.width, xl = lofs - lyl * a.width;
@@ -394,22 +388,9 @@ __device__ __attribute__((noinline)) void pixel_write(const FastArgs *fap, float
     }
     if (!PROBE) {
         if (a.accum) { a.accum[3 * lofs] = c.x; a.accum[3 * lofs + 1] = c.y; a.accum[3 * lofs + 2] = c.z; }
-        float g[3] = {mort_sqrtf(c.x), mort_sqrtf(c.y), mort_sqrtf(c.z)};
-        unsigned char b[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float v = g[k];
-            if (v < 0.0f) v = 0.0f;
-            if (v > 0.999f) v = 0.999f;
-            b[k] = (unsigned char)mort_f2i(256 * v);
-        }
-        uchar4 out; out.x = b[0]; out.y = b[1]; out.z = b[2]; out.w = 255;
-        a.rgba[lofs] = out;
+        pixel_rgba(a.rgba[lofs], c);
         if (a.seg_px) a.seg_px[lofs] = segments;
-        mort_rng_state st;
-        st.d = d; st.v[0] = v0; st.v[1] = v1; st.v[2] = v2; st.v[3] = v3; st.v[4] = v4;
-        st.boxmuller_flag = 0; st.boxmuller_flag_double = 0; st.boxmuller_extra = 0.f; st.boxmuller_extra_double = 0.;
-        a.states[lofs] = st;
+        a.states[lofs] = rng_state(d, v0, v1, v2, v3, v4);
         /* per-pixel totals: 32 slots each, picked by workgroup (same-address atomics would queue up behind each other) */
         const unsigned slot = 32u + 2u * (blockIdx.x & 31u);
         atomicAdd(&a.counters[slot], (unsigned long long)segments);

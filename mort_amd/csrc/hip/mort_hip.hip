@@ -77,22 +77,9 @@ static __global__ void __launch_bounds__(256) substream_resolve_kernel(const flo
         const size_t v = 3 * ((size_t)(ly * sub + j) * (size_t)width + (size_t)x);
         c = vadd(c, mk(vaccum[v], vaccum[v + 1], vaccum[v + 2]));
     }
-    c = vscale(scale, c);
-    if (c.x != c.x) c.x = 0.0f;
-    if (c.y != c.y) c.y = 0.0f;
-    if (c.z != c.z) c.z = 0.0f;
+    c = pixel_finish(scale, c);
     if (accum) { accum[3 * i] = c.x; accum[3 * i + 1] = c.y; accum[3 * i + 2] = c.z; }
-    float g[3] = {mort_sqrtf(c.x), mort_sqrtf(c.y), mort_sqrtf(c.z)};
-    unsigned char b[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float v = g[k];
-        if (v < 0.0f) v = 0.0f;
-        if (v > 0.999f) v = 0.999f;
-        b[k] = (unsigned char)mort_f2i(256 * v);
-    }
-    uchar4 out; out.x = b[0]; out.y = b[1]; out.z = b[2]; out.w = 255;
-    rgba[i] = out;
+    pixel_rgba(rgba[i], c);
 }
 
 /* ====================================================================== host */

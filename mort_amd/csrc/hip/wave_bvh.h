@@ -26,12 +26,12 @@
  *             to the next front (one atomicAdd per workgroup, coalesced
  *             32-byte ray writes).
  *
- * HBM records: front ray 32 B + id 4 B (two parities), hit 8 B (by position),
- * pixel 48 B (by id: XORWOW words, colour sum, packed counters), bounce stack
- * [depth][id] 16 B.  Algorithmic traffic per segment: trav 32 r + 8 w + 4 q;
+ * This file holds what only this form has: WfArgs, wf_trav (own tree, LDS-DMA
+ * prefetch ring) and the middle of wf_shade (spheres and their materials).
+ * The records, front 0, the shade kernel's head, push, tail and append, and the
+ * traversal kernel's pick / stage / flush are wave_common.h's, shared with
+ * wave_gen.hip.  Algorithmic traffic per segment: trav 32 r + 8 w + 4 q;
  * shade 4 q + 4 + 32 + 8 + 48 r, 4 + 32 + 48 + 16 w = 240 B.
- * Counters are double-buffered by front parity and zeroed by the kernel that
- * runs between their last reader and next writer, so a front needs no memset.
  */
 #ifndef MORT_WAVE_BVH_H
 #define MORT_WAVE_BVH_H
@@ -58,30 +58,9 @@ struct WfArgs {
 };
 
 /* ---- front 0: load streams, first camera ray of every pixel ---- */
-extern "C" __global__ void __launch_bounds__(256) wf_init(const WfArgs w) {
-    const RenderArgs &a = w.r;
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id == 0) {
-        w.cnt->front_count[0] = (unsigned)w.n_paths; w.cnt->front_count[1] = 0;
-        for (int p = 0; p < 2; p++) for (int k = 0; k < 3; k++) w.cnt->cls_count[p][k] = 0;
-        w.cnt->live = (unsigned)w.n_paths;
-    }
-    if (id >= w.n_paths) return;
-    const int ly = id / a.width, x = id - ly * a.width;
-    const int y = global_row(ly, a.rank, a.nranks, a.rows_per_block);
-    const mort_rng_state st = a.states[id];
-    Rng rng; rng.d = st.d; rng.v0 = st.v[0]; rng.v1 = st.v[1]; rng.v2 = st.v[2]; rng.v3 = st.v[3]; rng.v4 = st.v[4]; rng.draws = 0;
-    const Ray ray = get_ray(a, x, y, rng, 0, 0);
-    WfRay rr; rr.ox = ray.o.x; rr.oy = ray.o.y; rr.oz = ray.o.z; rr.tm = ray.tm; rr.dx = ray.d.x; rr.dy = ray.d.y; rr.dz = ray.d.z; rr.time0 = ray.tm;
-    w.q_ray[0][id] = rr;
-    w.q_id[0][id] = (unsigned)id;
-    WfPix p; wf_rng_store(p, rng); p.cr = p.cg = p.cb = 0; p.packed = 0; p.segments = 1; /* the segment this ray is about to trace */
-    w.pix[id] = p;
-}
+extern "C" __global__ void __launch_bounds__(256) wf_init(const WfArgs w) { wf_front0(w, w.r); }
 
 /* ---- traversal of one front ---- */
-enum { W_T = 0, W_L = 1, W_F = 2, W_DONE = 3 };
-
 #ifndef MORT_WF_TH_F
 #define MORT_WF_TH_F 32
 #endif
@@ -94,16 +73,11 @@ enum { W_T = 0, W_L = 1, W_F = 2, W_DONE = 3 };
 #ifndef MORT_WF_BLOCK
 #define MORT_WF_BLOCK 512
 #endif
-#ifndef MORT_WF_STAGE
-#define MORT_WF_STAGE 128 /* positions per class staged in LDS per wave before a flush */
-#endif
 
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK) wf_trav(const WfArgs w) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-#ifdef MORT_PROFILE_STATES
-    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    WPROF_T0;
     {
         const uint4 *src = (const uint4 *)w.trav_src;
         uint4 *dst = (uint4 *)lds;
@@ -158,35 +132,14 @@ __global__ void __launch_bounds__(BLOCK) wf_trav(const WfArgs w) {
     int sp = 0, flags = 0;
     uint32_t bmat = 0;
 
-#define WF_FLUSH(k) do { \
-        if (staged[k] > 0) { \
-            unsigned base_ = 0; \
-            if (lane == 0) base_ = atomicAdd(&w.cnt->cls_count[par][k], (unsigned)staged[k]); \
-            base_ = __shfl(base_, 0); \
-            for (int i_ = lane; i_ < staged[k]; i_ += 64) w.q_cls[k][base_ + (unsigned)i_] = stage[(k) * MORT_WF_STAGE + i_]; \
-            staged[k] = 0; \
-        } } while (0)
-
-#ifdef MORT_PROFILE_STATES
-    unsigned long long pr_steps[3] = {0, 0, 0}, pr_lanes[3] = {0, 0, 0}, pr_cyc[4] = {0, 0, 0, 0};
-    unsigned long long pt0 = __builtin_readcyclecounter(), pt1;
-#define WPROF(i, lanes) do { pr_steps[i] += 1; pr_lanes[i] += (unsigned long long)(lanes); } while (0)
-#define WPROFC(i) do { pt1 = __builtin_readcyclecounter(); pr_cyc[i] += pt1 - pt0; pt0 = pt1; } while (0)
-#else
-#define WPROF(i, lanes) do { } while (0)
-#define WPROFC(i) do { } while (0)
-#endif
-
+    WPROF_BEGIN;
     for (;;) {
         const int nT = __popcll(__ballot(state == W_T));
         const int nL = __popcll(__ballot(state == W_L));
         const int nF = __popcll(__ballot(state == W_F));
         if (nT + nL + nF == 0) break;
         int pick;
-        if (nF >= MORT_WF_TH_F) pick = W_F;
-        else if (nL >= MORT_WF_TH_L) pick = W_L;
-        else if (nT > 0) pick = W_T;
-        else pick = (nL >= nF) ? W_L : W_F;
+        WF_PICK(pick, nT, nL, nF, MORT_WF_TH_F, MORT_WF_TH_L);
         WPROFC(3);
 
         if (pick == W_T) {
@@ -307,32 +260,13 @@ __global__ void __launch_bounds__(BLOCK) wf_trav(const WfArgs w) {
                 else { const int mt = DREF_TYPE(f_bmat); cls = (mt == MORT_MAT_LAMBERTIAN || mt == MORT_MAT_ISOTROPIC) ? WC_LAMB : WC_SPEC; }
             }
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const unsigned long long m = __ballot(cls == k);
-                const int n = __popcll(m);
-                if (n > 0) {
-                    if (staged[k] + n > MORT_WF_STAGE) WF_FLUSH(k);
-                    const int rk = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                    if (cls == k) stage[k * MORT_WF_STAGE + staged[k] + rk] = f_pos;
-                    staged[k] += n;
-                }
-            }
+            for (int k = 0; k < 3; k++) WF_STAGE(w.cnt, par, k, w.q_cls[k], stage, staged, cls, f_pos);
             if (inF && !have && A_head == A_cnt && B_cnt == 0) state = W_DONE; /* slice exhausted */
             WPROFC(2);
         }
     }
-    WF_FLUSH(0); WF_FLUSH(1); WF_FLUSH(2);
-#ifdef MORT_PROFILE_STATES
-    if (lane == 0) {
-        for (int k = 0; k < 3; k++) { atomicAdd(&w.r.counters[4 + k], pr_steps[k]); atomicAdd(&w.r.counters[8 + k], pr_lanes[k]); }
-        for (int k = 0; k < 4; k++) atomicAdd(&w.r.counters[12 + k], pr_cyc[k]);
-        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
-        atomicAdd(&w.r.counters[20], rt1 - rt0);           /* sum of wave lifetimes, 10 ns ticks */
-        atomicAdd(&w.r.counters[21], 1ull);                /* waves */
-        atomicAdd(&w.r.counters[22], pt0 - 0ull > 0 ? (unsigned long long)0 : 0ull);
-    }
-#endif
-#undef WF_FLUSH
+    WF_FLUSH(w.cnt, par, 0, w.q_cls[0], stage, staged); WF_FLUSH(w.cnt, par, 1, w.q_cls[1], stage, staged); WF_FLUSH(w.cnt, par, 2, w.q_cls[2], stage, staged);
+    WPROF_END(w.r.counters);
 #undef WF_DMA
 }
 
@@ -361,42 +295,18 @@ DEV void wf_texture(const DScene &sc, const DLambert &m, V3 outward, V3 p, V3 &c
 extern "C" __global__ void __launch_bounds__(256, MORT_WF_SHADE_WAVES) wf_shade(const WfArgs w) {
     const RenderArgs &a = w.r;
     const DScene &sc = a.sc;
-    const int par = w.parity;
-    const unsigned n0 = w.cnt->cls_count[par][0], n1 = w.cnt->cls_count[par][1], n2 = w.cnt->cls_count[par][2];
-    const unsigned b0 = (n0 + 255u) >> 8, b1 = (n1 + 255u) >> 8, b2 = (n2 + 255u) >> 8;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        /* the other parity's class counters were last read by the previous wf_shade; this front's wf_trav is done */
-        w.cnt->cls_count[par ^ 1][0] = 0; w.cnt->cls_count[par ^ 1][1] = 0; w.cnt->cls_count[par ^ 1][2] = 0;
-    }
-    unsigned b = blockIdx.x;
-    int cls;
-    unsigned n;
-    if (b < b0) { cls = WC_LAMB; n = n0; }
-    else if (b < b0 + b1) { cls = WC_SPEC; n = n1; b -= b0; }
-    else if (b < b0 + b1 + b2) { cls = WC_FIN; n = n2; b -= b0 + b1; }
-    else return;
-    const unsigned i = b * 256u + threadIdx.x;
-    const bool valid = i < n;
-    unsigned id = 0;
-    bool cont = false; /* path continues into the next front */
-    Ray ray; ray.o = mk(0, 0, 0); ray.d = mk(0, 0, 1); ray.tm = 0;
-    float out_time0 = 0;
-    if (valid) {
-        const unsigned pos = w.q_cls[cls][i];
-        id = w.q_id[par][pos];
-        const WfRay rr = w.q_ray[par][pos];
-        const WfHit h = w.hits[pos];
-        WfPix P = w.pix[id];
-        Rng rng = wf_rng_load(P);
-        int s_i = (int)(P.packed & 0xfffu), s_j = (int)((P.packed >> 12) & 0xfffu), iter = (int)(P.packed >> 24);
-        ray.o = mk(rr.ox, rr.oy, rr.oz); ray.d = mk(rr.dx, rr.dy, rr.dz); ray.tm = rr.tm;
-        const float time0 = rr.time0;
-        out_time0 = time0;
+    WfLane l;
+    if (!wf_shade_begin(w, l)) return;
+    if (l.valid) {
+        wf_shade_load(w, l);
+        Ray &ray = l.ray;
+        Rng &rng = l.rng;
+        const int cls = l.cls;
         V3 final_value = a.background; /* WC_FIN from wf_trav: a miss (camera.cuh:154-158) */
         bool terminated = (cls == WC_FIN);
-        if (!terminated) {
-            const DSphere sp = sc.spheres[h.best];
-            const V3 p = ray_at(ray, h.t);
+        if (!terminated) { /* what the ray hit and what the material does: a bounce entry and the scattered ray, or a final value */
+            const DSphere sp = sc.spheres[l.h.best];
+            const V3 p = ray_at(ray, l.h.t);
             const V3 outward = vdiv(vsub(p, sphere_center(sp, ray.tm)), sp.radius);
             const bool front_face = vdot(ray.d, outward) < 0;
             const V3 normal = front_face ? outward : vneg(outward);
@@ -425,7 +335,7 @@ extern "C" __global__ void __launch_bounds__(256, MORT_WF_SHADE_WAVES) wf_shade(
                 }
                 e.x = scattering_pdf * attenuation.x; e.y = scattering_pdf * attenuation.y; e.z = scattering_pdf * attenuation.z;
                 e.w = 1 / mat_pdf;
-                ray.tm = time0; /* ray(rec.p, dir, r.time()) (camera.cuh:119) */
+                ray.tm = l.time0; /* ray(rec.p, dir, r.time()) (camera.cuh:119) */
             } else if (mtype == MORT_MAT_METAL) { /* materials.cuh:73-84 */
                 const DMetal m = sc.metal[midx];
                 const V3 reflected = reflect(ray.d, normal);
@@ -449,89 +359,13 @@ extern "C" __global__ void __launch_bounds__(256, MORT_WF_SHADE_WAVES) wf_shade(
                 terminated = true;
             }
             if (!terminated) {
-                w.stack[(size_t)iter * (size_t)w.n_paths + id] = e;
-                iter++;
                 ray.o = p; ray.d = ndir;
-                if (iter >= a.bounce_limit) { final_value = mk(0, 0, 0); terminated = true; } /* camera.cuh:161-163 */
-                else { P.segments++; cont = true; }
+                wf_shade_push(w, a, l, e, terminated, final_value);
             }
         }
-        if (terminated) { /* unwind + accumulate (camera.cuh:165-173,190), then the next sample or the finished pixel */
-            while (iter > 0) {
-                iter--;
-                const float4 e = w.stack[(size_t)iter * (size_t)w.n_paths + id];
-                const V3 t = vmul(mk(e.x, e.y, e.z), final_value);
-                final_value = vadd(mk(0, 0, 0), vscale(e.w, t));
-            }
-            P.cr += final_value.x; P.cg += final_value.y; P.cb += final_value.z;
-            s_i++;
-            if (s_i >= a.sqrt_spp) { s_i = 0; s_j++; }
-            const int ly = (int)id / a.width, x = (int)id - ly * a.width;
-            if (s_j < a.sqrt_spp) {
-                const int y = global_row(ly, a.rank, a.nranks, a.rows_per_block);
-                ray = get_ray(a, x, y, rng, s_i, s_j);
-                out_time0 = ray.tm;
-                P.segments++;
-                cont = true;
-            } else { /* camera.cuh:194-207 */
-                V3 col = vscale(a.pixel_samples_scale, mk(P.cr, P.cg, P.cb));
-                if (col.x != col.x) col.x = 0.0f;
-                if (col.y != col.y) col.y = 0.0f;
-                if (col.z != col.z) col.z = 0.0f;
-                if (a.accum) { a.accum[3 * id] = col.x; a.accum[3 * id + 1] = col.y; a.accum[3 * id + 2] = col.z; }
-                float g[3] = {mort_sqrtf(col.x), mort_sqrtf(col.y), mort_sqrtf(col.z)};
-                unsigned char bq[3];
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    float v = g[k];
-                    if (v < 0.0f) v = 0.0f;
-                    if (v > 0.999f) v = 0.999f;
-                    bq[k] = (unsigned char)mort_f2i(256 * v);
-                }
-                uchar4 out; out.x = bq[0]; out.y = bq[1]; out.z = bq[2]; out.w = 255;
-                a.rgba[id] = out;
-                if (a.seg_px) a.seg_px[id] = P.segments;
-                mort_rng_state st;
-                st.d = rng.d; st.v[0] = rng.v0; st.v[1] = rng.v1; st.v[2] = rng.v2; st.v[3] = rng.v3; st.v[4] = rng.v4;
-                st.boxmuller_flag = 0; st.boxmuller_flag_double = 0; st.boxmuller_extra = 0.f; st.boxmuller_extra_double = 0.;
-                a.states[id] = st;
-                atomicAdd(&a.counters[0], (unsigned long long)P.segments);
-                atomicAdd(&a.counters[1], (unsigned long long)rng.draws);
-                cont = false;
-            }
-            if (cont) iter = 0;
-        }
-        if (cont) {
-            wf_rng_store(P, rng);
-            P.packed = (uint32_t)s_i | ((uint32_t)s_j << 12) | ((uint32_t)iter << 24);
-            w.pix[id] = P;
-        }
+        wf_shade_tail(w, a, l, terminated, final_value);
     }
-    /* append the survivors to the next front: one global atomicAdd per workgroup, coalesced record writes */
-    {
-        __shared__ unsigned s_cnt[4], s_fin[4], s_base;
-        const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const unsigned long long m = __ballot(cont);
-        const unsigned long long mf = __ballot(valid && !cont);
-        if (lane == 0) { s_cnt[wv] = (unsigned)__popcll(m); s_fin[wv] = (unsigned)__popcll(mf); }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            const unsigned fin = s_fin[0] + s_fin[1] + s_fin[2] + s_fin[3];
-            s_base = tot ? atomicAdd(&w.cnt->front_count[par ^ 1], tot) : 0u;
-            if (fin) atomicSub(&w.cnt->live, fin); /* only finished pixels change the live count */
-        }
-        __syncthreads();
-        unsigned off = s_base;
-        for (int k = 0; k < wv; k++) off += s_cnt[k];
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (cont) {
-            const unsigned np = off + (unsigned)rank;
-            WfRay o; o.ox = ray.o.x; o.oy = ray.o.y; o.oz = ray.o.z; o.tm = ray.tm; o.dx = ray.d.x; o.dy = ray.d.y; o.dz = ray.d.z; o.time0 = out_time0;
-            w.q_ray[par ^ 1][np] = o;
-            w.q_id[par ^ 1][np] = id;
-        }
-    }
+    wf_append(w, l);
 }
 
 #endif

@@ -18,6 +18,9 @@
  *                 then either the next segment's record (appended to the next front: one atomic per workgroup,
  *                 coalesced 32-byte writes) or the unwind, the next sample's camera ray, or the finished pixel.
  *
+ * What the two forms of the mode share is wave_common.h's: the records, front 0 (wf_init_gen is one call), the shade kernel's
+ * head, push, tail and append around the middle written here, and the traversal kernel's pick / stage / flush.
+ *
  * Same streams, same operations, same order per pixel as the megakernels: bit-identical output (tests/test_gpu_gen.py).
  * Algorithmic HBM traffic per segment: trav 32 r + 8 w + 4 q; shade 4 q + 4 + 32 + 8 + 48 r, 4 + 32 + 48 + 16 w = 240 B.
  */
@@ -49,30 +52,8 @@ struct WfGenArgs {
     int parity;               /* front & 1 */
 };
 
-#define WG_STAGE 128 /* positions per class staged in LDS per wave before a flush */
-enum { W_T = 0, W_L = 1, W_F = 2, W_DONE = 3 };
-
 /* ---- front 0: load streams, first camera ray of every pixel ---- */
-__global__ void __launch_bounds__(256) wf_init_gen(const WfGenArgs w) {
-    const RenderArgs &a = w.g.f.r;
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id == 0) {
-        w.cnt->front_count[0] = (unsigned)w.n_paths; w.cnt->front_count[1] = 0;
-        for (int p = 0; p < 2; p++) for (int k = 0; k < 3; k++) w.cnt->cls_count[p][k] = 0;
-        w.cnt->live = (unsigned)w.n_paths;
-    }
-    if (id >= w.n_paths) return;
-    const int ly = id / a.width, x = id - ly * a.width;
-    const int y = global_row(ly, a.rank, a.nranks, a.rows_per_block);
-    const mort_rng_state st = a.states[id];
-    Rng rng; rng.d = st.d; rng.v0 = st.v[0]; rng.v1 = st.v[1]; rng.v2 = st.v[2]; rng.v3 = st.v[3]; rng.v4 = st.v[4]; rng.draws = 0;
-    const Ray ray = get_ray(a, x, y, rng, 0, 0);
-    WfRay rr; rr.ox = ray.o.x; rr.oy = ray.o.y; rr.oz = ray.o.z; rr.tm = ray.tm; rr.dx = ray.d.x; rr.dy = ray.d.y; rr.dz = ray.d.z; rr.time0 = ray.tm;
-    w.q_ray[0][id] = rr;
-    w.q_id[0][id] = (unsigned)id;
-    WfPix p; wf_rng_store(p, rng); p.cr = p.cg = p.cb = 0; p.packed = 0; p.segments = 1; /* the segment this ray is about to trace */
-    w.pix[id] = p;
-}
+__global__ void __launch_bounds__(256) wf_init_gen(const WfGenArgs w) { wf_front0(w, w.g.f.r); }
 
 /* the scan for rays the walk does not decide: out of line, HBM copy of the scene */
 struct WScanHit { uint32_t best; float closest; };
@@ -112,7 +93,7 @@ __global__ void __launch_bounds__(BLOCK) wf_trav_gen(const WfGenArgs) {
     const uint32_t *entries = (const uint32_t *)(lds + uni_u(L.o_entries));
     const int *chains = (const int *)(lds + uni_u(L.o_chains));
     unsigned short *tstack = (unsigned short *)(lds + uni_u(L.f.off_tstack)) + threadIdx.x; /* [level * BLOCK] */
-    unsigned *stage = (unsigned *)(lds + uni_u(W.t_stage)) + (threadIdx.x >> 6) * (3 * WG_STAGE);
+    unsigned *stage = (unsigned *)(lds + uni_u(W.t_stage)) + (threadIdx.x >> 6) * (3 * MORT_WF_STAGE);
     DScene lsc; /* only what the leaf test reads: transform chains and primitives */
     lsc.xforms = (const DXform *)(lds + uni_u(L.o_xforms));
     if (PRIMS_LDS) { lsc.spheres = (const DSphere *)(lds + uni_u(L.o_spheres)); lsc.quads = (const DQuad *)(lds + uni_u(L.o_quads)); }
@@ -146,42 +127,21 @@ __global__ void __launch_bounds__(BLOCK) wf_trav_gen(const WfGenArgs) {
     uint32_t best = GBEST_NONE, node = 0;
     int sp = 0, flags = 0;
 
-#define WG_FLUSH(k) do { \
-        if (staged[k] > 0) { \
-            unsigned base_ = 0; \
-            if (lane == 0) base_ = atomicAdd(&wcnt->cls_count[par][k], (unsigned)staged[k]); \
-            base_ = __shfl(base_, 0); \
-            unsigned *const qc_ = (k) == 0 ? q_cls0 : (k) == 1 ? q_cls1 : q_cls2; \
-            for (int i_ = lane; i_ < staged[k]; i_ += 64) qc_[base_ + (unsigned)i_] = stage[(k) * WG_STAGE + i_]; \
-            staged[k] = 0; \
-        } } while (0)
-
-#ifdef MORT_PROFILE_STATES /* per-state wave-steps, lanes and cycles (scripts/wave_profile.py; printed by mort_hip_render) */
-    unsigned long long pr_steps[3] = {0, 0, 0}, pr_lanes[3] = {0, 0, 0}, pr_cyc[4] = {0, 0, 0, 0};
-    unsigned long long pt0 = __builtin_readcyclecounter(), pt1;
-    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#define WGPROF(i, lanes) do { pr_steps[i] += 1; pr_lanes[i] += (unsigned long long)(lanes); } while (0)
-#define WGPROFC(i) do { pt1 = __builtin_readcyclecounter(); pr_cyc[i] += pt1 - pt0; pt0 = pt1; } while (0)
-#else
-#define WGPROF(i, lanes) do { } while (0)
-#define WGPROFC(i) do { } while (0)
-#endif
+    WPROF_BEGIN;
+    WPROF_T0;
     for (;;) {
         const int nT = __popcll(__ballot(state == W_T));
         const int nL = __popcll(__ballot(state == W_L));
         const int nF = __popcll(__ballot(state == W_F));
         if (nT + nL + nF == 0) break;
         int pick;
-        if (nF >= th_f) pick = W_F;
-        else if (nL >= th_l) pick = W_L;
-        else if (nT > 0) pick = W_T;
-        else pick = (nL >= nF) ? W_L : W_F;
-        WGPROFC(3);
+        WF_PICK(pick, nT, nL, nF, th_f, th_l);
+        WPROFC(3);
 
         if (pick == W_T) {
             int keep;
             do {
-                WGPROF(0, __popcll(__ballot(state == W_T)));
+                WPROF(0, __popcll(__ballot(state == W_T)));
                 if (state == W_T) { /* both child boxes of one node (dev_gen.h gen_prune) */
                     const uint4 *np = (const uint4 *)(nodes2 + node); /* two ds_read_b128: corner + steps, 12 plane offsets + children */
                     const uint4 na = np[0], nb = np[1];
@@ -202,10 +162,10 @@ __global__ void __launch_bounds__(BLOCK) wf_trav_gen(const WfGenArgs) {
                 }
                 keep = __popcll(__ballot(state == W_T));
             } while (keep >= t_keep);
-            WGPROFC(0);
+            WPROFC(0);
         }
         if (pick == W_L) { /* sequential ifs, not a chain: no register copies at a common join (mega_bvh.h) */
-            WGPROF(1, nL);
+            WPROF(1, nL);
             uint32_t lpos = 0;
             int cnt = 0;
             if (state == W_L) { lpos = GLEAF_FIRST(node); cnt = (int)GLEAF_COUNT(node); } /* a leaf reference is a run of entries */
@@ -235,10 +195,10 @@ __global__ void __launch_bounds__(BLOCK) wf_trav_gen(const WfGenArgs) {
                     state = (next & 0x8000u) ? W_L : W_T;
                 } else state = W_F;
             }
-            WGPROFC(1);
+            WPROFC(1);
         }
         if (pick == W_F) {
-            WGPROF(2, nF);
+            WPROF(2, nF);
             /* wave-uniform control flow: every lane runs this block */
             const bool inF = (state == W_F);
             const bool fin = inF && have;
@@ -262,16 +222,7 @@ __global__ void __launch_bounds__(BLOCK) wf_trav_gen(const WfGenArgs) {
             const unsigned f_pos = pos;
             if (inF) have = false;
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const unsigned long long m = __ballot(cls == k);
-                const int n = __popcll(m);
-                if (n > 0) {
-                    if (staged[k] + n > WG_STAGE) WG_FLUSH(k);
-                    const int rk = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                    if (cls == k) stage[k * WG_STAGE + staged[k] + rk] = f_pos;
-                    staged[k] += n;
-                }
-            }
+            for (int k = 0; k < 3; k++) WF_STAGE(wcnt, par, k, k == 0 ? q_cls0 : k == 1 ? q_cls1 : q_cls2, stage, staged, cls, f_pos);
             /* ---- hand the waiting lanes the next records of this wave's batches ---- */
             const unsigned long long need = __ballot(inF);
             const int want = __popcll(need);
@@ -302,20 +253,11 @@ __global__ void __launch_bounds__(BLOCK) wf_trav_gen(const WfGenArgs) {
                 b_off += take; served += take;
             }
             if (inF && !have) state = W_DONE; /* this wave's batches are exhausted */
-            WGPROFC(2);
+            WPROFC(2);
         }
     }
-    WG_FLUSH(0); WG_FLUSH(1); WG_FLUSH(2);
-#ifdef MORT_PROFILE_STATES
-    if (lane == 0) {
-        unsigned long long *const counters = wp->g.f.r.counters;
-        for (int k = 0; k < 3; k++) { atomicAdd(&counters[4 + k], pr_steps[k]); atomicAdd(&counters[8 + k], pr_lanes[k]); }
-        for (int k = 0; k < 4; k++) atomicAdd(&counters[12 + k], pr_cyc[k]);
-        atomicAdd(&counters[20], __builtin_amdgcn_s_memrealtime() - rt0); /* sum of wave lifetimes, 10 ns ticks */
-        atomicAdd(&counters[21], 1ull);
-    }
-#endif
-#undef WG_FLUSH
+    WF_FLUSH(wcnt, par, 0, q_cls0, stage, staged); WF_FLUSH(wcnt, par, 1, q_cls1, stage, staged); WF_FLUSH(wcnt, par, 2, q_cls2, stage, staged);
+    WPROF_END(wp->g.f.r.counters);
 }
 
 /* ---- shading of one front ---- */
@@ -324,44 +266,20 @@ __global__ void __launch_bounds__(256, MORT_WF_SHADE_WAVES) wf_shade_gen(const W
     const RenderArgs &a = ga.f.r;
     const DScene &sc = a.sc;
     const int *chains = (const int *)(ga.f.hot_src + ga.o_chains);
-    const int par = w.parity;
-    const unsigned n0 = w.cnt->cls_count[par][0], n1 = w.cnt->cls_count[par][1], n2 = w.cnt->cls_count[par][2];
-    const unsigned b0 = (n0 + 255u) >> 8, b1 = (n1 + 255u) >> 8, b2 = (n2 + 255u) >> 8;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        /* the other parity's class counters were last read by the previous wf_shade_gen; this front's wf_trav_gen is done */
-        w.cnt->cls_count[par ^ 1][0] = 0; w.cnt->cls_count[par ^ 1][1] = 0; w.cnt->cls_count[par ^ 1][2] = 0;
-    }
-    unsigned b = blockIdx.x;
-    int cls;
-    unsigned n;
-    if (b < b0) { cls = WC_LAMB; n = n0; }
-    else if (b < b0 + b1) { cls = WC_SPEC; n = n1; b -= b0; }
-    else if (b < b0 + b1 + b2) { cls = WC_FIN; n = n2; b -= b0 + b1; }
-    else return;
-    const unsigned i = b * 256u + threadIdx.x;
-    const bool valid = i < n;
-    unsigned id = 0;
-    bool cont = false; /* path continues into the next front */
-    Ray ray; ray.o = mk(0, 0, 0); ray.d = mk(0, 0, 1); ray.tm = 0;
-    float out_time0 = 0;
-    if (valid) {
-        const unsigned pos = w.q_cls[cls][i];
-        id = w.q_id[par][pos];
-        const WfRay rr = w.q_ray[par][pos];
-        const WfHit h = w.hits[pos];
-        WfPix P = w.pix[id];
-        Rng rng = wf_rng_load(P);
-        int s_i = (int)(P.packed & 0xfffu), s_j = (int)((P.packed >> 12) & 0xfffu), iter = (int)(P.packed >> 24);
-        ray.o = mk(rr.ox, rr.oy, rr.oz); ray.d = mk(rr.dx, rr.dy, rr.dz); ray.tm = rr.tm;
-        const float time0 = rr.time0;
-        out_time0 = time0;
+    WfLane l;
+    if (!wf_shade_begin(w, l)) return;
+    if (l.valid) {
+        wf_shade_load(w, l);
+        Ray &ray = l.ray;
+        Rng &rng = l.rng;
+        const float time0 = l.time0;
         /* the constant media come after every solid, with the solids' closest_so_far (world.cuh:154-160) */
-        float closest = h.t;
-        uint32_t best = (uint32_t)h.best;
+        float closest = l.h.t;
+        uint32_t best = (uint32_t)l.h.best;
         gen_media(sc, ga.first_medium, sc.n_items, ray, rng, closest, best);
         V3 final_value = a.background; /* a miss (camera.cuh:154-158) */
         bool terminated = (best == GBEST_NONE);
-        if (!terminated) {
+        if (!terminated) { /* what the ray hit and what the material does: a bounce entry and the scattered ray, or a final value */
             const Best bb = gen_decode_best(sc, chains, best, closest);
             /* inlined: this kernel waits on memory (71 % of its wave cycles), and the out-of-line call's frame -- callee-saved registers and
              * the 22-dword result through scratch -- was half of its memory instructions: 2048x2048x4 spp 223 -> 112 ms.  (The call was a
@@ -376,88 +294,12 @@ __global__ void __launch_bounds__(256, MORT_WF_SHADE_WAVES) wf_shade_gen(const W
             else {
                 float4 e; e.x = so.e.kx; e.y = so.e.ky; e.z = so.e.kz; e.w = so.e.rp; /* dielectric: (1, 1, 1, 1) */
                 if (so.ident) e.x = e.y = e.z = e.w = 1.0f;
-                w.stack[(size_t)iter * (size_t)w.n_paths + id] = e;
-                iter++;
-                if (iter >= a.bounce_limit) { final_value = mk(0, 0, 0); terminated = true; } /* camera.cuh:161-163 */
-                else { P.segments++; cont = true; }
+                wf_shade_push(w, a, l, e, terminated, final_value);
             }
         }
-        if (terminated) { /* unwind + accumulate (camera.cuh:165-173,190), then the next sample or the finished pixel */
-            while (iter > 0) {
-                iter--;
-                const float4 e = w.stack[(size_t)iter * (size_t)w.n_paths + id];
-                const V3 t = vmul(mk(e.x, e.y, e.z), final_value);
-                final_value = vadd(mk(0, 0, 0), vscale(e.w, t));
-            }
-            P.cr += final_value.x; P.cg += final_value.y; P.cb += final_value.z;
-            s_i++;
-            if (s_i >= a.sqrt_spp) { s_i = 0; s_j++; }
-            const int ly = (int)id / a.width, x = (int)id - ly * a.width;
-            if (s_j < a.sqrt_spp) {
-                const int y = global_row(ly, a.rank, a.nranks, a.rows_per_block);
-                ray = get_ray(a, x, y, rng, s_i, s_j);
-                out_time0 = ray.tm;
-                P.segments++;
-                cont = true;
-            } else { /* camera.cuh:194-207 */
-                V3 col = vscale(a.pixel_samples_scale, mk(P.cr, P.cg, P.cb));
-                if (col.x != col.x) col.x = 0.0f;
-                if (col.y != col.y) col.y = 0.0f;
-                if (col.z != col.z) col.z = 0.0f;
-                if (a.accum) { a.accum[3 * id] = col.x; a.accum[3 * id + 1] = col.y; a.accum[3 * id + 2] = col.z; }
-                float g[3] = {mort_sqrtf(col.x), mort_sqrtf(col.y), mort_sqrtf(col.z)};
-                unsigned char bq[3];
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    float v = g[k];
-                    if (v < 0.0f) v = 0.0f;
-                    if (v > 0.999f) v = 0.999f;
-                    bq[k] = (unsigned char)mort_f2i(256 * v);
-                }
-                uchar4 out; out.x = bq[0]; out.y = bq[1]; out.z = bq[2]; out.w = 255;
-                a.rgba[id] = out;
-                if (a.seg_px) a.seg_px[id] = P.segments;
-                mort_rng_state st;
-                st.d = rng.d; st.v[0] = rng.v0; st.v[1] = rng.v1; st.v[2] = rng.v2; st.v[3] = rng.v3; st.v[4] = rng.v4;
-                st.boxmuller_flag = 0; st.boxmuller_flag_double = 0; st.boxmuller_extra = 0.f; st.boxmuller_extra_double = 0.;
-                a.states[id] = st;
-                atomicAdd(&a.counters[0], (unsigned long long)P.segments);
-                atomicAdd(&a.counters[1], (unsigned long long)rng.draws);
-                cont = false;
-            }
-            if (cont) iter = 0;
-        }
-        if (cont) {
-            wf_rng_store(P, rng);
-            P.packed = (uint32_t)s_i | ((uint32_t)s_j << 12) | ((uint32_t)iter << 24);
-            w.pix[id] = P;
-        }
+        wf_shade_tail(w, a, l, terminated, final_value);
     }
-    /* append the survivors to the next front: one global atomicAdd per workgroup, coalesced record writes */
-    {
-        __shared__ unsigned s_cnt[4], s_fin[4], s_base;
-        const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const unsigned long long m = __ballot(cont);
-        const unsigned long long mf = __ballot(valid && !cont);
-        if (lane == 0) { s_cnt[wv] = (unsigned)__popcll(m); s_fin[wv] = (unsigned)__popcll(mf); }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            const unsigned fin = s_fin[0] + s_fin[1] + s_fin[2] + s_fin[3];
-            s_base = tot ? atomicAdd(&w.cnt->front_count[par ^ 1], tot) : 0u;
-            if (fin) atomicSub(&w.cnt->live, fin); /* only finished pixels change the live count */
-        }
-        __syncthreads();
-        unsigned off = s_base;
-        for (int k = 0; k < wv; k++) off += s_cnt[k];
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (cont) {
-            const unsigned np = off + (unsigned)rank;
-            WfRay o; o.ox = ray.o.x; o.oy = ray.o.y; o.oz = ray.o.z; o.tm = ray.tm; o.dx = ray.d.x; o.dy = ray.d.y; o.dz = ray.d.z; o.time0 = out_time0;
-            w.q_ray[par ^ 1][np] = o;
-            w.q_id[par ^ 1][np] = id;
-        }
-    }
+    wf_append(w, l);
 }
 
 /* ---- host side ---- */
@@ -469,8 +311,8 @@ static trav_kernel_t pick_trav(int block, bool prims_in_lds) {
 }
 static int trav_block_for(const GenArgs &ga) { /* the LDS image + per-wave staging must fit one CU's LDS */
     const size_t fixed = (size_t)ga.f.hot_bytes + 32;
-    const size_t need512 = fixed + (size_t)MORT_OWN_STACK * 512 * 2 + (size_t)(512 / 64) * 3 * WG_STAGE * 4;
-    const size_t need1024 = fixed + (size_t)MORT_OWN_STACK * 1024 * 2 + (size_t)(1024 / 64) * 3 * WG_STAGE * 4;
+    const size_t need512 = fixed + (size_t)MORT_OWN_STACK * 512 * 2 + (size_t)(512 / 64) * 3 * MORT_WF_STAGE * 4;
+    const size_t need1024 = fixed + (size_t)MORT_OWN_STACK * 1024 * 2 + (size_t)(1024 / 64) * 3 * MORT_WF_STAGE * 4;
     int tb = need512 <= 150 * 1024 ? 512 : 256;
     /* a big image (the final scene's 98 KB) admits one workgroup per CU: the kernel needs under 128 VGPRs, so that workgroup can bring four waves per SIMD */
     if (need512 > 75 * 1024 && need1024 <= 158 * 1024) tb = 1024;
@@ -491,7 +333,7 @@ int mort_wave_gen_render(mort_ctx *c, const mort_camera *cam, const RenderArgs &
     /* LDS of wf_trav_gen: image | traversal stacks | class staging */
     ga.f.off_tstack = (ga.f.hot_bytes + 15u) & ~15u;
     w.t_stage = ga.f.off_tstack + (uint32_t)MORT_OWN_STACK * (uint32_t)TB * 2u;
-    const size_t trav_lds = (size_t)w.t_stage + (size_t)(TB / 64) * 3 * WG_STAGE * sizeof(unsigned);
+    const size_t trav_lds = (size_t)w.t_stage + (size_t)(TB / 64) * 3 * MORT_WF_STAGE * sizeof(unsigned);
     { /* dynamic + the kernel's own __shared__ objects must fit the CU's 160 KB: refuse here rather than fail at the first launch */
         hipFuncAttributes fattr;
         HIPCHK(c, hipFuncGetAttributes(&fattr, (const void *)trav));
