@@ -11,8 +11,14 @@
  * file, which use only IEEE-754 correctly rounded operations (+ - * / sqrt,
  * conversions) in a fixed order.  Both sides are compiled with
  * -ffp-contract=off.  Each fp32 function evaluates in fp64 and rounds once,
- * which puts it within 1 ULP of the correctly rounded result
- * (tests/test_math.py measures this against glibc).
+ * which puts it within 1 ULP of the correctly rounded result.
+ * tests/test_math.py measures this against mpmath on up to 2^16 inputs per
+ * function: every exponent, denormals, both sides of +-1e5, the 4096 floats
+ * either side of +-1, the neighbours of atan's break points, and a sample of
+ * the floats next to k*pi/2 (every result it sees is the correctly rounded
+ * one).  It compares gcc's compile with hipcc's host compile bit for bit over
+ * 2^22 inputs per function, all floats next to k*pi/2 included, and
+ * tests/test_gpu_math.py compares the gfx950 compile with both over the same.
  *
  * Domains: sin/cos |x| < 1e5 (callers pass phi in [0, 2*pi] and Perlin phases
  * of a few hundred); others full range with IEEE NaN/inf behaviour.

@@ -1,8 +1,8 @@
 /*
  * debug.hip -- the diagnostics behind mort_amd/hip.py's debug_* calls (none is in include/mort_hip.h).  Most are host only:
- * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Three
- * launch small kernels of their own (exact_forms_kernel, f2i_all_kernel, f2i_list_kernel) that put the device's short forms
- * beside its plain operators.  mega_bvh.h is included for those bodies; its kernels are templates and none is instantiated here.
+ * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Five
+ * launch small kernels of their own: exact_forms_kernel, f2i_all_kernel and f2i_list_kernel put the device's short forms
+ * beside its plain operators, math_kernel runs the math layer on a caller's inputs, random_float_all_kernel sweeps random_float.  mega_bvh.h is included for those bodies; its kernels are templates and none is instantiated here.
  */
 #include <hip/hip_runtime.h>
 
@@ -431,4 +431,232 @@ extern "C" int mort_hip_debug_f2i_host(const uint32_t *bits, size_t n, int *res)
     if ((!bits || !res) && n) return MORT_ERR_INVALID;
     for (size_t i = 0; i < n; i++) res[i] = mort_f2i(__builtin_bit_cast(float, bits[i]));
     return MORT_OK;
+}
+
+/* ---- the math layer on a caller's inputs: mort_math.h (group A), the plain operators the contract leans on (P), dev_math.h (B) and
+ * dev_trace.h's uv / texture functions (C), one function number each.  Records are 32-bit words, a double is two (low word first).
+ * math_eval is the one body behind mort_hip_debug_math_host (hipcc's host compile) and math_kernel (the gfx950 compile);
+ * oracle/mort_oracle.c's mort_oracle_math_batch is gcc's compile of group A under the same numbers (tests/test_math.py,
+ * tests/test_gpu_math.py). ---- */
+struct MathShape { unsigned char in, out; };
+static const MathShape MATH_SHAPES[] = {
+    /* A  0 mort_sqrtf x -> f            */ {1, 1},  /*  1 mort_sqrt x -> d               */ {2, 2},
+    /*    2 mort_floorf x -> f           */ {1, 1},  /*  3 mort_fmaxf a b -> f            */ {2, 1},
+    /*    4 mort_fmin a b -> d           */ {4, 2},  /*  5 mort_d2i x -> int              */ {2, 1},
+    /*    6 mort_powi5f a -> f           */ {1, 1},  /*  7 mort_sin x -> d                */ {2, 2},
+    /*    8 mort_cos x -> d              */ {2, 2},  /*  9 mort_sinf x -> f               */ {1, 1},
+    /*   10 mort_cosf x -> f             */ {1, 1},  /* 11 mort_sincosf x -> sin, cos     */ {1, 2},
+    /*   12 mort_atan x -> d             */ {2, 2},  /* 13 mort_atan2f y x -> f           */ {2, 1},
+    /*   14 mort_acosf x -> f            */ {1, 1},  /* 15 mort_logf x -> f               */ {1, 1},
+    /* P 16 fp32 x / a                   */ {2, 1},  /* 17 fp32 1 / a                     */ {1, 1},
+    /*   18 fp64 x / a                   */ {4, 2},  /* 19 (float) of a double            */ {2, 1},
+    /*   20 (float) of a uint32_t        */ {1, 1},  /* 21 __builtin_truncf               */ {1, 1},
+    /* B 22 vlen v -> f                  */ {3, 1},  /* 23 vdiv v t -> v                  */ {4, 3},
+    /*   24 vunit v -> v                 */ {3, 3},  /* 25 vcross u v -> v                */ {6, 3},
+    /*   26 reflect v n -> v             */ {6, 3},  /* 27 refract uv n eta -> v          */ {7, 3},
+    /*   28 reflectance cos idx -> f     */ {2, 1},  /* 29 onb_from_w w, onb_local a -> u v w local */ {6, 12},
+    /*   stream functions: the six XORWOW words (d, v0..v4) lead the record; the value, the six final words and the draw count come back */
+    /*   30 random_float_range mn mx     */ {8, 8},  /* 31 random_int mn mx               */ {8, 8},
+    /*   32 random_in_unit_sphere        */ {6, 10}, /* 33 random_unit_vector             */ {6, 10},
+    /*   34 random_in_unit_disk          */ {6, 10}, /* 35 random_cosine_direction        */ {6, 10},
+    /* C 36 sphere_uv p -> u v           */ {3, 2},  /* 37 noise_value idx p -> rgb       */ {4, 3},
+    /*   38 image_value idx u v -> rgb   */ {3, 3},
+};
+#define MATH_FUNCTIONS ((int)(sizeof MATH_SHAPES / sizeof MATH_SHAPES[0]))
+#define MATH_FN_NOISE 37
+#define MATH_FN_IMAGE 38
+struct MathTables { const float *noise; const DImage *images; const unsigned char *texels; };
+
+DEV float math_f(const uint32_t *w, int k) { return __builtin_bit_cast(float, w[k]); }
+DEV double math_d(const uint32_t *w, int k) { return __builtin_bit_cast(double, (uint64_t)w[k] | ((uint64_t)w[k + 1] << 32)); }
+DEV V3 math_v(const uint32_t *w, int k) { return mk(math_f(w, k), math_f(w, k + 1), math_f(w, k + 2)); }
+DEV void math_pf(uint32_t *w, int k, float x) { w[k] = __builtin_bit_cast(uint32_t, x); }
+DEV void math_pd(uint32_t *w, int k, double x) { const uint64_t u = __builtin_bit_cast(uint64_t, x); w[k] = (uint32_t)u; w[k + 1] = (uint32_t)(u >> 32); }
+DEV void math_pv(uint32_t *w, int k, V3 v) { math_pf(w, k, v.x); math_pf(w, k + 1, v.y); math_pf(w, k + 2, v.z); }
+DEV Rng math_rng(const uint32_t *w) { Rng s; s.d = w[0]; s.v0 = w[1]; s.v1 = w[2]; s.v2 = w[3]; s.v3 = w[4]; s.v4 = w[5]; s.draws = 0; return s; }
+DEV void math_prng(uint32_t *w, int k, const Rng &s) { w[k] = s.d; w[k + 1] = s.v0; w[k + 2] = s.v1; w[k + 3] = s.v2; w[k + 4] = s.v3; w[k + 5] = s.v4; w[k + 6] = s.draws; }
+
+static __host__ __device__ void math_eval(int fn, const uint32_t *in, uint32_t *out, const MathTables &t) {
+    switch (fn) {
+    case 0: math_pf(out, 0, mort_sqrtf(math_f(in, 0))); break;
+    case 1: math_pd(out, 0, mort_sqrt(math_d(in, 0))); break;
+    case 2: math_pf(out, 0, mort_floorf(math_f(in, 0))); break;
+    case 3: math_pf(out, 0, mort_fmaxf(math_f(in, 0), math_f(in, 1))); break;
+    case 4: math_pd(out, 0, mort_fmin(math_d(in, 0), math_d(in, 2))); break;
+    case 5: out[0] = (uint32_t)mort_d2i(math_d(in, 0)); break;
+    case 6: math_pf(out, 0, mort_powi5f(math_f(in, 0))); break;
+    case 7: math_pd(out, 0, mort_sin(math_d(in, 0))); break;
+    case 8: math_pd(out, 0, mort_cos(math_d(in, 0))); break;
+    case 9: math_pf(out, 0, mort_sinf(math_f(in, 0))); break;
+    case 10: math_pf(out, 0, mort_cosf(math_f(in, 0))); break;
+    case 11: { float s, c; mort_sincosf(math_f(in, 0), &s, &c); math_pf(out, 0, s); math_pf(out, 1, c); break; }
+    case 12: math_pd(out, 0, mort_atan(math_d(in, 0))); break;
+    case 13: math_pf(out, 0, mort_atan2f(math_f(in, 0), math_f(in, 1))); break;
+    case 14: math_pf(out, 0, mort_acosf(math_f(in, 0))); break;
+    case 15: math_pf(out, 0, mort_logf(math_f(in, 0))); break;
+    case 16: math_pf(out, 0, math_f(in, 0) / math_f(in, 1)); break;
+    case 17: math_pf(out, 0, 1 / math_f(in, 0)); break;
+    case 18: math_pd(out, 0, math_d(in, 0) / math_d(in, 2)); break;
+    case 19: math_pf(out, 0, (float)math_d(in, 0)); break;
+    case 20: math_pf(out, 0, (float)in[0]); break;
+    case 21: math_pf(out, 0, __builtin_truncf(math_f(in, 0))); break;
+    case 22: math_pf(out, 0, vlen(math_v(in, 0))); break;
+    case 23: math_pv(out, 0, vdiv(math_v(in, 0), math_f(in, 3))); break;
+    case 24: math_pv(out, 0, vunit(math_v(in, 0))); break;
+    case 25: math_pv(out, 0, vcross(math_v(in, 0), math_v(in, 3))); break;
+    case 26: math_pv(out, 0, reflect(math_v(in, 0), math_v(in, 3))); break;
+    case 27: math_pv(out, 0, refract(math_v(in, 0), math_v(in, 3), math_f(in, 6))); break;
+    case 28: math_pf(out, 0, reflectance(math_f(in, 0), math_f(in, 1))); break;
+    case 29: { const Onb o = onb_from_w(math_v(in, 0)); math_pv(out, 0, o.u); math_pv(out, 3, o.v); math_pv(out, 6, o.w); math_pv(out, 9, onb_local(o, math_v(in, 3))); break; }
+    case 30: { Rng s = math_rng(in); math_pf(out, 0, random_float_range(s, math_f(in, 6), math_f(in, 7))); math_prng(out, 1, s); break; }
+    case 31: { Rng s = math_rng(in); out[0] = (uint32_t)random_int(s, (int)in[6], (int)in[7]); math_prng(out, 1, s); break; }
+    case 32: { Rng s = math_rng(in); math_pv(out, 0, random_in_unit_sphere(s)); math_prng(out, 3, s); break; }
+    case 33: { Rng s = math_rng(in); math_pv(out, 0, random_unit_vector(s)); math_prng(out, 3, s); break; }
+    case 34: { Rng s = math_rng(in); math_pv(out, 0, random_in_unit_disk(s)); math_prng(out, 3, s); break; }
+    case 35: { Rng s = math_rng(in); math_pv(out, 0, random_cosine_direction(s)); math_prng(out, 3, s); break; }
+    case 36: { float u, v; sphere_uv(math_v(in, 0), u, v); math_pf(out, 0, u); math_pf(out, 1, v); break; }
+    case MATH_FN_NOISE: math_pv(out, 0, noise_value(t.noise, (int)in[0], math_v(in, 1))); break;
+    case MATH_FN_IMAGE: math_pv(out, 0, image_value(t.images, t.texels, (int)in[0], math_f(in, 1), math_f(in, 2))); break;
+    default: break;
+    }
+}
+
+/* what the table functions may read: every record's index inside its table, every image inside the texels */
+static int math_check_tables(int fn, const uint32_t *in, size_t n, const void *noise, size_t noise_bytes, const DImage *images, size_t n_images,
+                             const void *texels, size_t texel_bytes) {
+    if (fn == MATH_FN_NOISE) {
+        const size_t count = noise_bytes / sizeof(mort_noise_texture);
+        if (!noise || count == 0 || noise_bytes % sizeof(mort_noise_texture)) return MORT_ERR_INVALID;
+        for (size_t k = 0; k < count; k++) { /* the permutations index ranvec */
+            const mort_noise_texture &nt = ((const mort_noise_texture *)noise)[k];
+            for (int j = 0; j < MORT_POINT_COUNT; j++)
+                if ((unsigned)nt.perm_x[j] > 255u || (unsigned)nt.perm_y[j] > 255u || (unsigned)nt.perm_z[j] > 255u) return MORT_ERR_INVALID;
+        }
+        for (size_t i = 0; i < n; i++) if (in[4 * i] >= count) return MORT_ERR_INVALID;
+    } else if (fn == MATH_FN_IMAGE) {
+        if (!images || n_images == 0 || (!texels && texel_bytes)) return MORT_ERR_INVALID;
+        for (size_t k = 0; k < n_images; k++) {
+            const DImage &im = images[k];
+            if (im.height <= 0) continue; /* image_value returns before it reads a texel */
+            if (im.width <= 0 || im.width > 65536 || im.height > 65536) return MORT_ERR_INVALID;
+            if ((size_t)im.offset + (size_t)im.width * 3 * (size_t)im.height > texel_bytes) return MORT_ERR_INVALID;
+        }
+        for (size_t i = 0; i < n; i++) if (in[3 * i] >= n_images) return MORT_ERR_INVALID;
+    }
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the record shape of function fn in 32-bit words; MORT_ERR_INVALID
+ * past the last function */
+extern "C" int mort_hip_debug_math_shape(int fn, int *in_words, int *out_words) {
+    if (fn < 0 || fn >= MATH_FUNCTIONS || !in_words || !out_words) return MORT_ERR_INVALID;
+    *in_words = MATH_SHAPES[fn].in; *out_words = MATH_SHAPES[fn].out;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): function fn over n records, hipcc's host compile of math_eval.
+ * noise: mort_noise_texture records (fn 37); images / texels: DImage records {offset, width, height, 0} and the bytes they index (fn 38);
+ * NULL / 0 for every other function. */
+extern "C" int mort_hip_debug_math_host(int fn, const uint32_t *in, size_t n, uint32_t *out, const void *noise, size_t noise_bytes,
+                                        const void *images, size_t n_images, const void *texels, size_t texel_bytes) {
+    if (fn < 0 || fn >= MATH_FUNCTIONS || ((!in || !out) && n)) return MORT_ERR_INVALID;
+    const int st = math_check_tables(fn, in, n, noise, noise_bytes, (const DImage *)images, n_images, texels, texel_bytes);
+    if (st != MORT_OK) return st;
+    const MathTables t{(const float *)noise, (const DImage *)images, (const unsigned char *)texels};
+    const size_t iw = MATH_SHAPES[fn].in, ow = MATH_SHAPES[fn].out;
+    unsigned nthreads = std::thread::hardware_concurrency();
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    if (n < 4096) nthreads = 1;
+    auto work = [&](unsigned k) {
+        for (size_t i = n * k / nthreads, end = n * (k + 1) / nthreads; i < end; i++) math_eval(fn, in + i * iw, out + i * ow, t);
+    };
+    std::vector<std::thread> pool;
+    for (unsigned k = 1; k < nthreads; k++) pool.emplace_back(work, k);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    return MORT_OK;
+}
+
+/* one lane per record, grid-stride; results leave as raw words */
+static __global__ void __launch_bounds__(256) math_kernel(int fn, int iw, int ow, const uint32_t *in, size_t n, uint32_t *out, MathTables t) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) math_eval(fn, in + i * (size_t)iw, out + i * (size_t)ow, t);
+}
+
+/* diagnostic (not in include/mort_hip.h): one launch of math_kernel on `device`: function fn over n records, arguments as
+ * mort_hip_debug_math_host; the tables are uploaded beside the records.  Writes n records to `out` and nothing after them. */
+extern "C" int mort_hip_debug_math_device(int device, int fn, const uint32_t *in, size_t n, uint32_t *out, const void *noise, size_t noise_bytes,
+                                          const void *images, size_t n_images, const void *texels, size_t texel_bytes) {
+    if (fn < 0 || fn >= MATH_FUNCTIONS || !in || !out || n == 0 || n > ((size_t)1 << 28)) return MORT_ERR_INVALID;
+    int st = math_check_tables(fn, in, n, noise, noise_bytes, (const DImage *)images, n_images, texels, texel_bytes);
+    if (st != MORT_OK) return st;
+    const size_t iw = MATH_SHAPES[fn].in, ow = MATH_SHAPES[fn].out;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    void *d_noise = nullptr, *d_images = nullptr, *d_texels = nullptr;
+    const size_t image_bytes = n_images * sizeof(DImage);
+    const bool want_noise = fn == MATH_FN_NOISE, want_image = fn == MATH_FN_IMAGE;
+    if (hipMalloc((void **)&d_in, n * iw * 4) != hipSuccess || hipMalloc((void **)&d_out, n * ow * 4) != hipSuccess ||
+        (want_noise && hipMalloc(&d_noise, noise_bytes) != hipSuccess) ||
+        (want_image && (hipMalloc(&d_images, image_bytes) != hipSuccess || hipMalloc(&d_texels, texel_bytes ? texel_bytes : 1) != hipSuccess))) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && (hipMemcpy(d_in, in, n * iw * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                          (want_noise && hipMemcpy(d_noise, noise, noise_bytes, hipMemcpyHostToDevice) != hipSuccess) ||
+                          (want_image && (hipMemcpy(d_images, images, image_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                                          (texel_bytes && hipMemcpy(d_texels, texels, texel_bytes, hipMemcpyHostToDevice) != hipSuccess))))) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        const size_t blocks = (n + 255) / 256;
+        const MathTables t{(const float *)d_noise, (const DImage *)d_images, (const unsigned char *)d_texels};
+        math_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256)>>>(fn, (int)iw, (int)ow, d_in, n, d_out, t);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, n * ow * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_noise) (void)hipFree(d_noise);
+    if (d_images) (void)hipFree(d_images);
+    if (d_texels) (void)hipFree(d_texels);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+
+/* the device half of dev_math.h's sentence on random_float: random_float_of(curand_uniform_of(x)), dev_math.h's own two steps, against the
+ * reference's (float)(1.0 - (double)u), for ALL 2^32 generator outputs x (every lane takes every 2^20-th) */
+static __global__ void __launch_bounds__(256) random_float_all_kernel(unsigned long long *out) {
+    const uint32_t first = blockIdx.x * 256u + threadIdx.x; /* 4096 blocks: 2^20 lanes, 2^12 outputs each */
+    uint32_t differ = 0, lowest = 0xffffffffu;
+    for (uint32_t k = 0; k < 4096u; k++) {
+        const uint32_t x = first + (k << 20);
+        const float u = curand_uniform_of(x);
+        double wide = (double)u;
+        __asm__ volatile("" : "+v"(wide)); /* opaque: the compiler would otherwise narrow the fp64 subtraction to the fp32 one and compare nothing */
+        const float got = random_float_of(u), want = (float)(1.0 - wide);
+        if (__float_as_uint(got) != __float_as_uint(want)) { differ++; lowest = x < lowest ? x : lowest; }
+    }
+    atomicAdd(&out[2], 4096ull);
+    if (differ) { atomicAdd(&out[0], (unsigned long long)differ); atomicMin(&out[1], (unsigned long long)lowest); }
+}
+
+/* diagnostic (not in include/mort_hip.h): on `device`, out[0] = how many of the 2^32 generator outputs give a random_float that differs
+ * from the reference's form, out[1] = the lowest such output (2^32 - 1 if none), out[2] = outputs visited */
+extern "C" int mort_hip_debug_random_float_device(int device, unsigned long long *out) {
+    if (!out) return MORT_ERR_INVALID;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    unsigned long long *d_out = nullptr;
+    const unsigned long long init[3] = {0ull, 0xffffffffull, 0ull};
+    int st = MORT_OK;
+    if (hipMalloc((void **)&d_out, sizeof init) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && hipMemcpy(d_out, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        random_float_all_kernel<<<dim3(4096), dim3(256)>>>(d_out);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, sizeof init, hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_out) (void)hipFree(d_out);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
 }

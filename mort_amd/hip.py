@@ -797,6 +797,72 @@ def debug_gen_tree(world):
     return d
 
 
+DIMAGE_DTYPE = np.dtype([("offset", "<u4"), ("width", "<i4"), ("height", "<i4"), ("pad", "<i4")])  # DImage of dev_scene.h
+
+
+def debug_math_shapes():
+    """mort_hip_debug_math_shape (host only) walked to its end: [(in_words, out_words)] per function number of debug.hip's math table."""
+    fn = lib().mort_hip_debug_math_shape
+    fn.restype = C.c_int; fn.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    shapes = []
+    a, b = C.c_int(), C.c_int()
+    while fn(len(shapes), C.byref(a), C.byref(b)) == 0:
+        shapes.append((a.value, b.value))
+    return shapes
+
+
+def _debug_math(name, lead, fnum, records, noise, images, texels, out):
+    shapes = debug_math_shapes()
+    if not 0 <= fnum < len(shapes):
+        raise MortHipError(-1, name, f"no function {fnum}")
+    iw, ow = shapes[fnum]
+    rec = np.ascontiguousarray(records)
+    if rec.dtype.itemsize not in (4, 8) or rec.size * (rec.dtype.itemsize // 4) % iw:
+        raise MortHipError(-1, name, f"function {fnum} takes records of {iw} words")
+    words = rec.reshape(-1).view(np.uint32)
+    n = words.size // iw
+    if out is None:
+        out = np.empty(n * ow, dtype=np.uint32)
+    if out.dtype != np.uint32 or not out.flags.c_contiguous or out.size < n * ow:
+        raise MortHipError(-1, name, f"out: {n * ow} contiguous uint32 words")
+    noise = np.ascontiguousarray(noise).reshape(-1).view(np.uint8) if noise is not None else None
+    images = np.ascontiguousarray(images, dtype=DIMAGE_DTYPE) if images is not None else None
+    texels = np.ascontiguousarray(texels, dtype=np.uint8).reshape(-1) if texels is not None else None
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    fn = getattr(lib(), name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * len(lead) + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    st = fn(*lead, fnum, words.ctypes.data, n, out.ctypes.data, ptr(noise), noise.size if noise is not None else 0,
+            ptr(images), images.size if images is not None else 0, ptr(texels), texels.size if texels is not None else 0)
+    if st != 0:
+        raise MortHipError(st, name)
+    return out
+
+
+def debug_math_host(fnum, records, noise=None, images=None, texels=None, out=None):
+    """mort_hip_debug_math_host (host only): function `fnum` of debug.hip's math table over records (float32, uint32 or float64 array,
+    in_words 32-bit words per record), hipcc's host compile.  noise: the bytes of mort_noise_texture records (noise_value); images
+    (DIMAGE_DTYPE) and texels (uint8) for image_value.  Returns the results as raw uint32 words, out_words per record (`out` if given)."""
+    return _debug_math("mort_hip_debug_math_host", (), fnum, records, noise, images, texels, out)
+
+
+def debug_math_device(fnum, records, noise=None, images=None, texels=None, out=None, device=0):
+    """mort_hip_debug_math_device: the same on `device`, one launch of math_kernel; arguments and result as debug_math_host."""
+    return _debug_math("mort_hip_debug_math_device", (device,), fnum, records, noise, images, texels, out)
+
+
+def debug_random_float_device(device=0):
+    """mort_hip_debug_random_float_device: random_float against (float)(1.0 - (double)u) for all 2^32 generator outputs on `device` --
+    dict(differ, lowest, visited)."""
+    fn = lib().mort_hip_debug_random_float_device
+    fn.restype = C.c_int; fn.argtypes = [C.c_int, C.POINTER(C.c_ulonglong)]
+    out = (C.c_ulonglong * 3)()
+    st = fn(device, out)
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_random_float_device")
+    return dict(differ=out[0], lowest=out[1], visited=out[2])
+
+
 def _query_rays(rays):
     """rays as a contiguous RAY_DTYPE (n,) array: RAY_DTYPE already, or float32 (n, 8) = origin, direction, time, t_max"""
     rays = np.asarray(rays)

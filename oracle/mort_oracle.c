@@ -999,3 +999,47 @@ float mort_oracle_acosf(float x) { return mort_acosf(x); }
 float mort_oracle_atan2f(float y, float x) { return mort_atan2f(y, x); }
 float mort_oracle_logf(float x) { return mort_logf(x); }
 double mort_oracle_sin(double x) { return mort_sin(x); }
+
+/* mort_math.h (0..15) and the plain operators the numerical contract leans on (16..21) over n records of 32-bit words (a double is two,
+ * low word first), function numbers and record shapes as mort_hip_debug_math_shape's groups A and P (mort_amd/csrc/hip/debug.hip):
+ * gcc's compile beside hipcc's two */
+static float mb_f(const uint32_t *w) { float x; memcpy(&x, w, 4); return x; }
+static double mb_d(const uint32_t *w) { double x; memcpy(&x, w, 8); return x; }
+static void mb_pf(uint32_t *w, float x) { memcpy(w, &x, 4); }
+static void mb_pd(uint32_t *w, double x) { memcpy(w, &x, 8); }
+int mort_oracle_math_batch(int fn, const uint32_t *in, size_t n, uint32_t *out) {
+    static const unsigned char shape[22][2] = {{1, 1}, {2, 2}, {1, 1}, {2, 1}, {4, 2}, {2, 1}, {1, 1}, {2, 2},
+                                               {2, 2}, {1, 1}, {1, 1}, {1, 2}, {2, 2}, {2, 1}, {1, 1}, {1, 1},
+                                               {2, 1}, {1, 1}, {4, 2}, {2, 1}, {1, 1}, {1, 1}};
+    if (fn < 0 || fn >= 22 || ((!in || !out) && n)) return MORT_ORACLE_BATCH_BAD_ARGS;
+    const size_t iw = shape[fn][0], ow = shape[fn][1];
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t *a = in + i * iw;
+        uint32_t *o = out + i * ow;
+        switch (fn) {
+        case 0: mb_pf(o, mort_sqrtf(mb_f(a))); break;
+        case 1: mb_pd(o, mort_sqrt(mb_d(a))); break;
+        case 2: mb_pf(o, mort_floorf(mb_f(a))); break;
+        case 3: mb_pf(o, mort_fmaxf(mb_f(a), mb_f(a + 1))); break;
+        case 4: mb_pd(o, mort_fmin(mb_d(a), mb_d(a + 2))); break;
+        case 5: o[0] = (uint32_t)mort_d2i(mb_d(a)); break;
+        case 6: mb_pf(o, mort_powi5f(mb_f(a))); break;
+        case 7: mb_pd(o, mort_sin(mb_d(a))); break;
+        case 8: mb_pd(o, mort_cos(mb_d(a))); break;
+        case 9: mb_pf(o, mort_sinf(mb_f(a))); break;
+        case 10: mb_pf(o, mort_cosf(mb_f(a))); break;
+        case 11: { float s, c; mort_sincosf(mb_f(a), &s, &c); mb_pf(o, s); mb_pf(o + 1, c); break; }
+        case 12: mb_pd(o, mort_atan(mb_d(a))); break;
+        case 13: mb_pf(o, mort_atan2f(mb_f(a), mb_f(a + 1))); break;
+        case 14: mb_pf(o, mort_acosf(mb_f(a))); break;
+        case 15: mb_pf(o, mort_logf(mb_f(a))); break;
+        case 16: mb_pf(o, mb_f(a) / mb_f(a + 1)); break;
+        case 17: mb_pf(o, 1 / mb_f(a)); break;
+        case 18: mb_pd(o, mb_d(a) / mb_d(a + 2)); break;
+        case 19: mb_pf(o, (float)mb_d(a)); break;
+        case 20: mb_pf(o, (float)a[0]); break;
+        default: mb_pf(o, __builtin_truncf(mb_f(a))); break;
+        }
+    }
+    return MORT_ORACLE_BATCH_OK;
+}

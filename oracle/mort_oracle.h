@@ -74,6 +74,11 @@ float mort_oracle_acosf(float x);
 float mort_oracle_atan2f(float y, float x);
 float mort_oracle_logf(float x);
 double mort_oracle_sin(double x);
+/* mort_math.h over n records of 32-bit words: fn 0 mort_sqrtf, 1 mort_sqrt, 2 mort_floorf, 3 mort_fmaxf, 4 mort_fmin, 5 mort_d2i,
+ * 6 mort_powi5f, 7 mort_sin, 8 mort_cos, 9 mort_sinf, 10 mort_cosf, 11 mort_sincosf, 12 mort_atan, 13 mort_atan2f, 14 mort_acosf,
+ * 15 mort_logf; and the plain operators 16 fp32 x / a, 17 fp32 1 / a, 18 fp64 x / a, 19 (float) of a double, 20 (float) of a uint32_t,
+ * 21 __builtin_truncf; a double is two words.  MORT_ORACLE_BATCH_OK or MORT_ORACLE_BATCH_BAD_ARGS. */
+int mort_oracle_math_batch(int fn, const uint32_t *in, size_t n, uint32_t *out);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,8 @@ def lib():
         L.mort_oracle_object_hit_batch.restype = C.c_int
         L.mort_oracle_texture_value_batch.argtypes = [W, C.c_int, vp, vp, vp, vp, vp, vp]
         L.mort_oracle_texture_value_batch.restype = C.c_int
+        L.mort_oracle_math_batch.argtypes = [C.c_int, vp, C.c_size_t, vp]
+        L.mort_oracle_math_batch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -137,6 +139,25 @@ def object_hit_batch(world, obj_type, obj_idx, rays, t_min, t_max, states=None, 
     if rc != 0:
         raise OracleBatchError(rc, "mort_oracle_object_hit_batch")
     return out, hit.astype(bool)
+
+
+# mort_oracle_math_batch: (in_words, out_words) of mort_math.h's functions and the plain operators, numbered as debug.hip's math table numbers them
+MATH_SHAPES = ((1, 1), (2, 2), (1, 1), (2, 1), (4, 2), (2, 1), (1, 1), (2, 2), (2, 2), (1, 1), (1, 1), (1, 2), (2, 2), (2, 1), (1, 1), (1, 1),
+               (2, 1), (1, 1), (4, 2), (2, 1), (1, 1), (1, 1))
+
+
+def math_batch(fn, records):
+    """gcc's compile of include/mort_math.h (fn 0..15) and of the plain operators (16..21), function fn over records (float32, float64 or uint32 array, MATH_SHAPES[fn][0] words each):
+    the results as (n, out_words) uint32 words."""
+    iw, ow = MATH_SHAPES[fn]
+    w = np.ascontiguousarray(records).reshape(-1).view(np.uint32)
+    assert w.size % iw == 0
+    n = w.size // iw
+    out = np.empty((n, ow), dtype=np.uint32)
+    rc = lib().mort_oracle_math_batch(fn, w.ctypes.data, n, out.ctypes.data)
+    if rc != 0:
+        raise OracleBatchError(rc, "mort_oracle_math_batch")
+    return out
 
 
 def texture_value_batch(world, tex_type, tex_idx, u, v, p):
