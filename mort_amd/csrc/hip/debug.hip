@@ -1,8 +1,9 @@
 /*
  * debug.hip -- the diagnostics behind mort_amd/hip.py's debug_* calls (none is in include/mort_hip.h).  Most are host only:
- * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Five
+ * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Six
  * launch small kernels of their own: exact_forms_kernel, f2i_all_kernel and f2i_list_kernel put the device's short forms
- * beside its plain operators, math_kernel runs the math layer on a caller's inputs, random_float_all_kernel sweeps random_float.  mega_bvh.h is included for those bodies; its kernels are templates and none is instantiated here.
+ * beside its plain operators, math_kernel runs the math layer on a caller's inputs, light_kernel the light sampling on a caller's
+ * records over an uploaded world, random_float_all_kernel sweeps random_float.  mega_bvh.h is included for those bodies; its kernels are templates and none is instantiated here.
  */
 #include <hip/hip_runtime.h>
 
@@ -619,6 +620,114 @@ extern "C" int mort_hip_debug_math_device(int device, int fn, const uint32_t *in
     if (d_images) (void)hipFree(d_images);
     if (d_texels) (void)hipFree(d_texels);
     if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+
+/* ---- light sampling on a caller's records against a caller's world: dev_render.h's light_pdf_value and light_random over dev_trace.h's
+ * wsphere_* / wquad_*, reading the world-order tables and the flattened lists of scene_compile.h.  Records are 32-bit words:
+ *   fn 0 light_pdf_value: type, idx, origin[3], direction[3] -> the pdf;
+ *   fn 1 light_random: the six XORWOW words (d, v0..v4), type, idx, origin[3] -> the direction, the six final words, the draw count
+ *        (the math table's stream layout).
+ * light_eval is the one body behind mort_hip_debug_light_host (hipcc's host compile over a world compiled as host_render.hip compiles it)
+ * and light_kernel (the gfx950 compile over a context's uploaded scene); oracle/mort_oracle.c's mort_oracle_light_batch is the oracle's
+ * pdf_value_dispatch / random_dispatch under the same numbers (tests/test_light_host.py, tests/test_gpu_light.py). ---- */
+static const MathShape LIGHT_SHAPES[] = {/* 0 light_pdf_value */ {8, 1}, /* 1 light_random */ {11, 10}};
+#define LIGHT_FUNCTIONS ((int)(sizeof LIGHT_SHAPES / sizeof LIGHT_SHAPES[0]))
+
+static __host__ __device__ void light_eval(int fn, const DScene &sc, const uint32_t *in, uint32_t *out) {
+    if (fn == 0) {
+        math_pf(out, 0, light_pdf_value(sc, (int)in[0], (int)in[1], math_v(in, 2), math_v(in, 5)));
+    } else {
+        Rng s = math_rng(in);
+        math_pv(out, 0, light_random(sc, (int)in[6], (int)in[7], math_v(in, 8), s));
+        math_prng(out, 3, s);
+    }
+}
+
+/* every record names a light object the render would accept: `check` is check_light or check_light_object on (type, idx).  A list's answer
+ * is formed once (it walks the list), a primitive's per record */
+template <typename Check>
+static int light_check_records(int fn, const uint32_t *in, size_t n, Check check) {
+    const size_t iw = LIGHT_SHAPES[fn].in, at = fn == 0 ? 0 : 6;
+    int list_status[MORT_NUM_HITTABLE_LIST];
+    bool list_known[MORT_NUM_HITTABLE_LIST] = {};
+    for (size_t i = 0; i < n; i++) {
+        const int type = (int)in[i * iw + at], idx = (int)in[i * iw + at + 1];
+        int st;
+        if (type == MORT_OBJ_HITTABLE_LIST && idx >= 0 && idx < MORT_NUM_HITTABLE_LIST) {
+            if (!list_known[idx]) { list_status[idx] = check(type, idx); list_known[idx] = true; }
+            st = list_status[idx];
+        } else st = check(type, idx);
+        if (st != MORT_OK) return st;
+    }
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the record shape of light function fn in 32-bit words; MORT_ERR_INVALID
+ * past the last function */
+extern "C" int mort_hip_debug_light_shape(int fn, int *in_words, int *out_words) {
+    if (fn < 0 || fn >= LIGHT_FUNCTIONS || !in_words || !out_words) return MORT_ERR_INVALID;
+    *in_words = LIGHT_SHAPES[fn].in; *out_words = LIGHT_SHAPES[fn].out;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): light function fn over n records against `w`, hipcc's host compile of
+ * light_eval.  The world is compiled as mort_hip_render_host compiles it; a record whose (type, idx) check_light_object refuses as a camera's
+ * light object (index out of range, empty or nested list) fails the whole call with that status, before anything is evaluated. */
+extern "C" int mort_hip_debug_light_host(const mort_world *w, int fn, const uint32_t *in, size_t n, uint32_t *out) {
+    if (!w || fn < 0 || fn >= LIGHT_FUNCTIONS || ((!in || !out) && n)) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const int n_lists = w->objs.num_hittable_list;
+    st = light_check_records(fn, in, n, [&](int type, int idx) { return check_light_object(sb.comp, n_lists, type, idx); });
+    if (st != MORT_OK) return st;
+    DScene sc;
+    scene_view(sb, sb.bytes.data(), sc);
+    const size_t iw = LIGHT_SHAPES[fn].in, ow = LIGHT_SHAPES[fn].out;
+    unsigned nthreads = std::thread::hardware_concurrency();
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    if (n < 4096) nthreads = 1;
+    auto work = [&](unsigned k) {
+        for (size_t i = n * k / nthreads, end = n * (k + 1) / nthreads; i < end; i++) light_eval(fn, sc, in + i * iw, out + i * ow);
+    };
+    std::vector<std::thread> pool;
+    for (unsigned k = 1; k < nthreads; k++) pool.emplace_back(work, k);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    return MORT_OK;
+}
+
+/* one lane per record, grid-stride; results leave as raw words */
+static __global__ void __launch_bounds__(256) light_kernel(int fn, int iw, int ow, DScene sc, const uint32_t *in, size_t n, uint32_t *out) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) light_eval(fn, sc, in + i * (size_t)iw, out + i * (size_t)ow);
+}
+
+/* diagnostic (not in include/mort_hip.h): one launch of light_kernel over the scene of a context whose world has been uploaded: light
+ * function fn over n records.  Every record is checked on the host first, by check_light against the context's copy of the uploaded
+ * world's lists, so every index a lane forms lies inside the uploaded tables; a refused record fails the whole call before the launch.
+ * Writes n records to `out` and nothing after them. */
+extern "C" int mort_hip_debug_light_device(mort_ctx *c, int fn, const uint32_t *in, size_t n, uint32_t *out) {
+    if (!c || fn < 0 || fn >= LIGHT_FUNCTIONS || !in || !out || n == 0 || n > ((size_t)1 << 28)) return MORT_ERR_INVALID;
+    if (!c->have_world) return MORT_ERR_NO_WORLD;
+    int st = light_check_records(fn, in, n, [&](int type, int idx) { return check_light(c, type, idx); });
+    if (st != MORT_OK) return st;
+    const size_t iw = LIGHT_SHAPES[fn].in, ow = LIGHT_SHAPES[fn].out;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, quiesce(c));
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    if (hipMalloc((void **)&d_in, n * iw * 4) != hipSuccess || hipMalloc((void **)&d_out, n * ow * 4) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && hipMemcpy(d_in, in, n * iw * 4, hipMemcpyHostToDevice) != hipSuccess) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        const size_t blocks = (n + 255) / 256;
+        light_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, c->stream>>>(fn, (int)iw, (int)ow, c->sc, d_in, n, d_out);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(out, d_out, n * ow * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
     return st;
 }
 

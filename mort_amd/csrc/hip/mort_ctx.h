@@ -204,7 +204,7 @@ static inline int check_light(const mort_ctx *c, int type, int idx) {
     if (type == MORT_OBJ_HITTABLE_LIST) {
         if (idx < 0 || idx >= c->n_lists || idx >= MORT_NUM_HITTABLE_LIST) return MORT_ERR_INVALID;
         if (c->list_count[idx] <= 0) return MORT_ERR_INVALID;
-        for (int i = 0; i < c->list_count[idx]; i++) {
+        for (int i = 0; i <= c->list_count[idx]; i++) { /* the entry past the members too: random_int(0, n - 1) can give n (scene_compile.h) */
             const int t = c->list_types[c->list_first[idx] + i], k = c->list_idxs[c->list_first[idx] + i];
             if (t == MORT_OBJ_SPHERE) { if (k < 0 || k >= c->n_wspheres) return MORT_ERR_INVALID; }
             else if (t == MORT_OBJ_QUAD) { if (k < 0 || k >= c->n_wquads) return MORT_ERR_INVALID; }

@@ -151,7 +151,7 @@ static inline int check_light_object(const mortc::Compiled &o, int n_lists, int 
     if (type == MORT_OBJ_HITTABLE_LIST) {
         if (idx < 0 || idx >= n_lists || idx >= MORT_NUM_HITTABLE_LIST) return MORT_ERR_INVALID;
         if (o.list_count[idx] <= 0) return MORT_ERR_INVALID;
-        for (int i = 0; i < o.list_count[idx]; i++) {
+        for (int i = 0; i <= o.list_count[idx]; i++) { /* the entry past the members too: random_int(0, n - 1) can give n (scene_compile.h) */
             const int t = o.list_types[o.list_first[idx] + i], k = o.list_idxs[o.list_first[idx] + i];
             if (t == MORT_OBJ_SPHERE) { if (k < 0 || k >= n_wspheres) return MORT_ERR_INVALID; }
             else if (t == MORT_OBJ_QUAD) { if (k < 0 || k >= n_wquads) return MORT_ERR_INVALID; }

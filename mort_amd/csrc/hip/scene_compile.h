@@ -519,6 +519,14 @@ struct Compiler {
             have_all = true;
             return true;
         };
+        /* a quad without a finite plane (u || v or a zero side: n = 0 / 0) is "hit" by EVERY ray in the reference -- its NaN t and NaN
+         * (alpha, beta) pass each test of quad::hit (objects.cuh:190-215) -- which no box bounds: such a world keeps the scan */
+        for (const GPrim &g : pr) {
+            if (g.kind != ITEM_QUADS) continue;
+            const DQuad &q = out.quads[g.idx];
+            for (int k = 0; k < 3; k++) if (!std::isfinite(q.n[k]) || !std::isfinite(q.w[k])) return pi;
+            if (!std::isfinite(q.D)) return pi;
+        }
         for (const GPrim &g : pr) if (!grow(raw_box(g, 0.0))) return pi;
         if (with_boundaries) for (const DItem &it : out.subitems) { /* a medium scatters inside its boundary */
             if (it.kind != ITEM_SPHERES && it.kind != ITEM_QUADS) continue;
@@ -779,6 +787,15 @@ struct Compiler {
             out.list_first[i] = (int)out.list_types.size();
             out.list_count[i] = l.num_objs;
             for (int k = 0; k < l.num_objs; k++) { out.list_types.push_back(l.obj_types[k]); out.list_idxs.push_back(l.obj_idxs[k]); }
+            /* One entry past the members, as the reference's own arrays hold it.  curand_uniform is exactly 1.0f for the highest
+             * generator outputs (2^-25 of all draws), and random_int(0, n - 1) = (int)(float)(u * (n - 1 + 0.999999)) (rng.cuh:31-42) is
+             * then n - 1e-6 rounded to fp32, which is n itself from n = 33 on: list_random (objects.cuh:500-504) reads
+             * obj_types[n], which mort_list_add has left (0, 0), a tag that samples nothing.  Without this
+             * entry light_random would read the next list's first member there.  check_light / check_light_object cover it.  A full
+             * list has no such entry (the reference reads past its array there): it gets the same (0, 0). */
+            const bool room = l.num_objs >= 0 && l.num_objs < MORT_LIST_MAX_OBJS;
+            out.list_types.push_back(room ? l.obj_types[l.num_objs] : 0);
+            out.list_idxs.push_back(room ? l.obj_idxs[l.num_objs] : 0);
         }
         /* materials */
         const mort_world_materials &m = w->mats;

@@ -851,6 +851,45 @@ def debug_math_device(fnum, records, noise=None, images=None, texels=None, out=N
     return _debug_math("mort_hip_debug_math_device", (device,), fnum, records, noise, images, texels, out)
 
 
+LIGHT_SHAPES = ((8, 1), (11, 10))  # mort_hip_debug_light_shape: (in_words, out_words) of light_pdf_value and light_random
+
+
+def _debug_light(name, handle, fnum, records, out):
+    if fnum not in (0, 1):
+        raise MortHipError(-1, name, f"no light function {fnum}")
+    iw, ow = LIGHT_SHAPES[fnum]
+    rec = np.ascontiguousarray(records)
+    if rec.dtype.itemsize != 4 or rec.size % iw:
+        raise MortHipError(-1, name, f"light function {fnum} takes records of {iw} 32-bit words")
+    words = rec.reshape(-1).view(np.uint32)
+    n = words.size // iw
+    if out is None:
+        out = np.empty(n * ow, dtype=np.uint32)
+    if out.dtype != np.uint32 or not out.flags.c_contiguous or out.size < n * ow:
+        raise MortHipError(-1, name, f"out: {n * ow} contiguous uint32 words")
+    fn = getattr(lib(), name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    st = fn(handle, fnum, words.ctypes.data, n, out.ctypes.data)
+    if st != 0:
+        raise MortHipError(st, name)
+    return out
+
+
+def debug_light_host(world, fnum, records, out=None):
+    """mort_hip_debug_light_host (host only): light function `fnum` of debug.hip over records of 32-bit words against `world`, hipcc's
+    host compile.  fnum 0: light_pdf_value over (type, idx, origin[3], direction[3]) -> the pdf; fnum 1: light_random over (six XORWOW
+    words, type, idx, origin[3]) -> direction[3], the six final words, the draw count.  A record that names no acceptable light object
+    fails the call.  Returns the results as raw uint32 words (`out` if given)."""
+    return _debug_light("mort_hip_debug_light_host", C.cast(world.ptr, C.c_void_p), fnum, records, out)
+
+
+def debug_light_device(ctx, fnum, records, out=None):
+    """mort_hip_debug_light_device: the same on the GPU of `ctx`, over the scene of its uploaded world, one launch of light_kernel;
+    arguments and result as debug_light_host."""
+    return _debug_light("mort_hip_debug_light_device", ctx._h, fnum, records, out)
+
+
 def debug_random_float_device(device=0):
     """mort_hip_debug_random_float_device: random_float against (float)(1.0 - (double)u) for all 2^32 generator outputs on `device` --
     dict(differ, lowest, visited)."""

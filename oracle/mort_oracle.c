@@ -895,6 +895,64 @@ void mort_oracle_light_random(const mort_world *w, int type, int idx, const floa
 /* ---- batched, threaded forms of the entry points above (tests/feature_ref.py): loops, no arithmetic of their own ---- */
 enum { MORT_ORACLE_BATCH_OK = 0, MORT_ORACLE_BATCH_BAD_ARGS = -1, MORT_ORACLE_BATCH_NO_STREAM = -3 };
 
+/* pdf_value_dispatch (fn 0) and random_dispatch (fn 1) over n records of 32-bit words, function numbers and record shapes as
+ * mort_hip_debug_light_shape (mort_amd/csrc/hip/debug.hip): fn 0 type, idx, origin[3], direction[3] -> the pdf; fn 1 the six stream words
+ * (d, v[0..4]), type, idx, origin[3] -> the direction, the six final words, the draw count.  A sphere, quad or list index outside the
+ * world's tables is refused for the whole batch; what a list holds is the caller's business, as it is pdf_value_dispatch's */
+typedef struct { const mort_world *w; int fn, tid, nthreads; size_t n; const uint32_t *in; uint32_t *out; } light_job_t;
+static void *light_job(void *arg) {
+    light_job_t *j = arg;
+    const size_t iw = j->fn == 0 ? 8 : 11, ow = j->fn == 0 ? 1 : 10;
+    for (size_t i = j->n * (size_t)j->tid / (size_t)j->nthreads, end = j->n * ((size_t)j->tid + 1) / (size_t)j->nthreads; i < end; i++) {
+        const uint32_t *a = j->in + i * iw;
+        uint32_t *o = j->out + i * ow;
+        float f[6];
+        if (j->fn == 0) {
+            memcpy(f, a + 2, sizeof f);
+            ctx_t c = {j->w, NULL, 0};
+            float pdf = pdf_value_dispatch(&c, (int)a[0], (int)a[1], V(f[0], f[1], f[2]), V(f[3], f[4], f[5]));
+            memcpy(o, &pdf, 4);
+        } else {
+            mort_rng_state st;
+            memset(&st, 0, sizeof st);
+            st.d = a[0];
+            for (int k = 0; k < 5; k++) st.v[k] = a[1 + k];
+            memcpy(f, a + 8, 3 * sizeof(float));
+            rng_t g = {&st, 0};
+            ctx_t c = {j->w, &g, 0};
+            vec3 d = random_dispatch(&c, (int)a[6], (int)a[7], V(f[0], f[1], f[2]));
+            memcpy(o, d.e, 3 * sizeof(float));
+            o[3] = st.d;
+            for (int k = 0; k < 5; k++) o[4 + k] = st.v[k];
+            o[9] = (uint32_t)g.draws;
+        }
+    }
+    return NULL;
+}
+int mort_oracle_light_batch(const mort_world *w, int fn, const uint32_t *in, size_t n, uint32_t *out, int nthreads) {
+    if (!w || (fn != 0 && fn != 1) || ((!in || !out) && n)) return MORT_ORACLE_BATCH_BAD_ARGS;
+    const mort_world_objects *o = &w->objs;
+    const size_t iw = fn == 0 ? 8 : 11, at = fn == 0 ? 0 : 6;
+    for (size_t i = 0; i < n; i++) {
+        const int type = (int)in[i * iw + at], idx = (int)in[i * iw + at + 1];
+        const int count = type == MORT_OBJ_SPHERE ? o->num_spheres : type == MORT_OBJ_QUAD ? o->num_quads :
+                          type == MORT_OBJ_HITTABLE_LIST ? o->num_hittable_list : -1;
+        if (count >= 0 && (idx < 0 || idx >= count)) return MORT_ORACLE_BATCH_BAD_ARGS;
+    }
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 64) nthreads = 64;
+    if (n < 4096) nthreads = 1;
+    light_job_t jobs[64];
+    pthread_t th[64];
+    for (int t = 0; t < nthreads; t++) {
+        jobs[t] = (light_job_t){w, fn, t, nthreads, n, in, out};
+        if (t > 0) pthread_create(&th[t], NULL, light_job, &jobs[t]);
+    }
+    light_job(&jobs[0]);
+    for (int t = 1; t < nthreads; t++) pthread_join(th[t], NULL);
+    return MORT_ORACLE_BATCH_OK;
+}
+
 /* would hit_dispatch on this object reach constant_medium_hit's random_float()? */
 static bool object_draws(const mort_world *w, int type, int idx, int depth) {
     const mort_world_objects *o = &w->objs;

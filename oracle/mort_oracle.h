@@ -79,6 +79,11 @@ double mort_oracle_sin(double x);
  * 15 mort_logf; and the plain operators 16 fp32 x / a, 17 fp32 1 / a, 18 fp64 x / a, 19 (float) of a double, 20 (float) of a uint32_t,
  * 21 __builtin_truncf; a double is two words.  MORT_ORACLE_BATCH_OK or MORT_ORACLE_BATCH_BAD_ARGS. */
 int mort_oracle_math_batch(int fn, const uint32_t *in, size_t n, uint32_t *out);
+/* pdf_value_dispatch (fn 0) and random_dispatch (fn 1) over n records of 32-bit words against `w`, over `nthreads` host threads:
+ * fn 0 type, idx, origin[3], direction[3] -> the pdf; fn 1 the six stream words (d, v[0..4]), type, idx, origin[3] -> the direction,
+ * the six final stream words, the draw count.  A sphere, quad or list index outside the world's tables gives MORT_ORACLE_BATCH_BAD_ARGS
+ * and computes nothing. */
+int mort_oracle_light_batch(const mort_world *w, int fn, const uint32_t *in, size_t n, uint32_t *out, int nthreads);
 
 #ifdef __cplusplus
 }

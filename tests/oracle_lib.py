@@ -62,6 +62,8 @@ def lib():
         L.mort_oracle_texture_value_batch.restype = C.c_int
         L.mort_oracle_math_batch.argtypes = [C.c_int, vp, C.c_size_t, vp]
         L.mort_oracle_math_batch.restype = C.c_int
+        L.mort_oracle_light_batch.argtypes = [W, C.c_int, vp, C.c_size_t, vp, C.c_int]
+        L.mort_oracle_light_batch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -157,6 +159,23 @@ def math_batch(fn, records):
     rc = lib().mort_oracle_math_batch(fn, w.ctypes.data, n, out.ctypes.data)
     if rc != 0:
         raise OracleBatchError(rc, "mort_oracle_math_batch")
+    return out
+
+
+LIGHT_SHAPES = ((8, 1), (11, 10))  # mort_oracle_light_batch: (in_words, out_words) of pdf_value_dispatch and random_dispatch
+
+
+def light_batch(world, fn, records, nthreads=8):
+    """pdf_value_dispatch (fn 0) or random_dispatch (fn 1) over records of 32-bit words (LIGHT_SHAPES[fn][0] each, the layout of
+    debug.hip's light table): the results as (n, out_words) uint32 words."""
+    iw, ow = LIGHT_SHAPES[fn]
+    w = np.ascontiguousarray(records).reshape(-1).view(np.uint32)
+    assert w.size % iw == 0
+    n = w.size // iw
+    out = np.empty((n, ow), dtype=np.uint32)
+    rc = lib().mort_oracle_light_batch(world.ptr, fn, w.ctypes.data, n, out.ctypes.data, nthreads)
+    if rc != 0:
+        raise OracleBatchError(rc, "mort_oracle_light_batch")
     return out
 
 

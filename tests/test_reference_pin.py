@@ -383,6 +383,43 @@ def test_reference_build_matches_its_record(ref, name):
     COUNTS["2d recorded cases"] += 1
 
 
+@pytest.mark.parametrize("world_name", ["bvh", "flat"])
+def test_light_sampling_records(ref, world_name):
+    """pdfValueDispatch / randomDispatch over the light sweep's worlds (tests/light_cases.py): 2^14 records per function from the same
+    builder as the 2^20 the kernels run, so every family is there whole -- origins inside a sphere, in a quad's plane, at the centre, at
+    Q; degenerate primitives; lists of 1, 3, 40 and 500 members with members that sample nothing; random_int one past the list -- where
+    the oracle's restatement could have drifted from the reference unnoticed.  The pdf, the direction and the final stream words."""
+    from tests import light_cases as LC
+    world, _ = LC.WORLDS[world_name]()
+    R.load(world)
+    rec, lab = LC.pin_records(world_name, 0)
+    want = O.light_batch(world, 0, rec)[:, 0]
+    got = np.empty(len(rec), np.float32)
+    f = rec[:, 2:].view(np.float32)
+    for i in range(len(rec)):
+        got[i] = ref.mort_ref_pdf_value(int(lab["type"][i]), int(lab["idx"][i]), (C.c_float * 3)(*f[i, :3]), (C.c_float * 3)(*f[i, 3:]))
+    assert np.isnan(got).sum() > 1000 and np.isinf(got).sum() > 100 and (got == 0).sum() > 1000  # the edges are in the sample
+    LC.assert_same(0, rec, dict(oracle=want.reshape(-1, 1), reference=got.view(np.uint32).reshape(-1, 1)))
+    rec, lab = LC.pin_records(world_name, 1)
+    want = O.light_batch(world, 1, rec)
+    got = np.zeros((len(rec), 10), np.uint32)
+    got[:, 9] = want[:, 9]  # the reference does not count its draws: the stream words tell
+    st, d = S.RngState(), (C.c_float * 3)()
+    f = rec[:, 8:].view(np.float32)
+    for i in range(len(rec)):
+        st.d = int(rec[i, 0])
+        for k in range(5):
+            st.v[k] = int(rec[i, 1 + k])
+        assert ref.mort_ref_light_random(int(lab["type"][i]), int(lab["idx"][i]), (C.c_float * 3)(*f[i]), st, d) == 0
+        got[i, :3] = np.array(list(d), np.float32).view(np.uint32)
+        got[i, 3] = st.d
+        got[i, 4:9] = list(st.v)
+    past = [int((want[(lab["type"] == S.OBJ_HITTABLE_LIST) & (lab["idx"] == li), 9] == 1).sum()) for li in (0, 1)]
+    LC.assert_same(1, rec, dict(oracle=want, reference=got))
+    COUNTS["2b light sweep records"] += 2 * len(rec)
+    COUNTS["2b of them random_int one past a list of primitives"] += past[0] if world_name == "bvh" else 0
+
+
 def test_entry_points_refuse_without_a_loaded_world(ref):
     """a BVH build leaves the reference's host arrays unlike the uploaded world: until the next load the per-ray entry
     points answer with an error and touch nothing"""
