@@ -517,6 +517,73 @@ int mort_hip_volume_sample_device(mort_ctx *ctx, const mort_volume_grid *grid, c
 int mort_hip_volume_sample_host(const mort_volume_grid *grid, const float *records, size_t n, const void *points, size_t stride, int nthreads,
                                 float *out, double *seconds);
 
+/* ---- visibility-weighted irradiance volumes: per-probe depth maps and a Chebyshev test in the sampler.  The
+ * blend above weighs the eight probes round a point by trilinear weight alone, so a probe behind a wall lights a surface it
+ * cannot see.  Here every probe also gets an octahedral map of the first two moments of the distance to the nearest solid, baked
+ * on the device, and the sampler multiplies each corner's weight by the Chebyshev bound on the probability that the probe sees the
+ * point.  Everything is fp32, nothing contracted or reordered, every / and square root correctly rounded: GPU kernel, host loop
+ * and any restatement agree to the bit.
+ *
+ * A depth map is MORT_DEPTH_FLOATS floats: (R + 2) x (R + 2) texels of two floats (m1, m2), R = MORT_DEPTH_RES = 8, row-major;
+ * texel (i, j) sits at float 2 (j 10 + i): 800 bytes per probe.  Interior texels are i, j in 1..8; the one-texel border holds
+ * copies so that the sampler's bilinear taps never wrap, in bordered coordinates:
+ *   (0, j) <- (1, 9 - j), (9, j) <- (8, 9 - j) for j in 1..8;  (i, 0) <- (9 - i, 1), (i, 9) <- (9 - i, 8) for i in 1..8;
+ *   (0, 0) <- (8, 8), (9, 9) <- (1, 1), (0, 9) <- (8, 1), (9, 0) <- (1, 8).
+ *
+ * The bake.  params->subsamples = s in 1..8, params->max_distance finite and > 0, else MORT_ERR_INVALID.  For probe p and interior
+ * texel (i + 1, j + 1), i, j in 0..7, the sub-samples (a, b) in ascending b and within b in ascending a, with
+ * step = 2.0f / (float)(8 s) and inv = 1.0f / (float)(s s), each rounded once on the host:
+ *   u = ((float)(i s + a) + 0.5f) * step - 1.0f, v the same from (j, b);  z = (1.0f - |u|) - |v|;
+ *   z < 0: x = (1.0f - |v|) * (u >= 0 ? 1.0f : -1.0f), y = (1.0f - |u|) * (v >= 0 ? 1.0f : -1.0f);  else x = u, y = v.
+ *   ray    origin position_p, direction (x, y, z) as computed (NOT normalised), time time_p, t_max = +inf; searched as
+ *          mort_hip_query_closest searches with states == NULL: media are passed over and nothing is drawn.
+ *   len = sqrt((x x + y y) + z z);  d = hit ? t * len : max_distance;  d = (d < max_distance) ? d : max_distance (a NaN goes to
+ *   the cap);  m1 = m1 + d, m2 = m2 + d * d, both from 0.0f.
+ * The texel is (m1 * inv, m2 * inv); the border copies follow the table above.
+ * Forms, alignment, overlap, `seconds`, n == 0 (MORT_OK, nothing launched), MORT_ERR_NO_WORLD and MORT_HOST_TREE as for
+ * mort_hip_probe_bake*; there is no RNG and no light object.  NULL params, probes or depth_out are MORT_ERR_INVALID.
+ *
+ * The sampler takes mort_hip_volume_sample*'s arguments, the maps (`depth`, MORT_DEPTH_FLOATS per probe in grid index order) and
+ * mort_volume_vis_params: normal_bias and min_visibility finite and >= 0, min_visibility <= 1, else MORT_ERR_INVALID (as are a
+ * NULL depth or params, and maps that overlap the output).  One sample is the plain sampler's, word for word, but for the corner
+ * weight.  For corner c with W0_c = T_c * weight_c: if !(W0_c > 0) the corner is skipped as there -- neither its map nor its
+ * coefficients influence the result.  Otherwise, per axis a,
+ *   q[a] = x[a] + normal_bias * n[a];  pos[a] = origin[a] + (float)i_a * spacing[a] (product rounded, then the sum);
+ *   v[a] = q[a] - pos[a];  r = sqrt((v0 v0 + v1 v1) + v2 v2);  s1 = (|v0| + |v1|) + |v2|.
+ *   !(s1 > 0) || !(s1 < +inf): V = 1.0f.  Otherwise
+ *   ox = v0 / s1, oy = v1 / s1;  v2 < 0: (ox, oy) = ((1.0f - |oy|) * (ox >= 0 ? 1 : -1), (1.0f - |ox|) * (oy >= 0 ? 1 : -1)), both
+ *   from the old values;
+ *   tx = (ox * 0.5f + 0.5f) * 8.0f + 0.5f, i0 = (int)floorf(tx) clamped to 0..8, fx = tx - (float)i0; ty, j0, fy the same;
+ *   per moment, with t(i, j) the map's texel:  top = t(i0, j0) * (1.0f - fx) + t(i0 + 1, j0) * fx,
+ *   bot = t(i0, j0 + 1) * (1.0f - fx) + t(i0 + 1, j0 + 1) * fx,  m = top * (1.0f - fy) + bot * fy;
+ *   r > m1: var = |m2 - m1 m1|, dl = r - m1, den = var + dl dl, k = (den > 0) ? var / den : 0.0f, V = (k k) k,
+ *   V = (V > min_visibility) ? V : min_visibility;  else (also for a NaN on either side) V = 1.0f.
+ *   W_c = W0_c * V; the corner contributes only if W_c > 0, and from there the nine-term sums, the accumulation from 0.0f, wsum
+ *   and 1.0f / wsum are the plain sampler's.
+ * So with V = 1 at every corner the output equals mort_hip_volume_sample's bit for bit, and with min_visibility = 0 a fully
+ * occluded probe drops out of the blend and cannot poison the sum.  None of the sampler's forms needs an uploaded world. ---- */
+#define MORT_DEPTH_RES 8
+#define MORT_DEPTH_FLOATS 200 /* (8 + 2) x (8 + 2) texels x (m1, m2): 800 B per probe */
+typedef struct mort_depth_params { int subsamples; float max_distance; } mort_depth_params;
+typedef struct mort_volume_vis_params { float normal_bias; float min_visibility; } mort_volume_vis_params;
+MORT_SA(sizeof(mort_depth_params) == 8 && sizeof(mort_volume_vis_params) == 8 && MORT_DEPTH_FLOATS * sizeof(float) == 800,
+        "depth map layout");
+int mort_hip_probe_depth_bake(mort_ctx *ctx, const mort_depth_params *params, size_t n, const mort_probe *probes, float *depth_out /* 200 n */,
+                              double *seconds);
+int mort_hip_probe_depth_bake_device(mort_ctx *ctx, const mort_depth_params *params, size_t n, const void *d_probes, void *d_depth_out,
+                                     void *stream, double *seconds);
+int mort_hip_probe_depth_bake_host(const mort_world *world, const mort_depth_params *params, size_t n, const mort_probe *probes, int nthreads,
+                                   int flags, float *depth_out, double *seconds);
+int mort_hip_volume_sample_visible(mort_ctx *ctx, const mort_volume_grid *grid, const float *records, const float *depth,
+                                   const mort_volume_vis_params *params, size_t n, const void *points, size_t stride, float *out /* 4 n */,
+                                   double *seconds);
+int mort_hip_volume_sample_visible_device(mort_ctx *ctx, const mort_volume_grid *grid, const void *d_records, const void *d_depth,
+                                          const mort_volume_vis_params *params, size_t n, const void *d_points, size_t stride, void *d_out,
+                                          void *stream, double *seconds);
+int mort_hip_volume_sample_visible_host(const mort_volume_grid *grid, const float *records, const float *depth,
+                                        const mort_volume_vis_params *params, size_t n, const void *points, size_t stride, int nthreads,
+                                        float *out, double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

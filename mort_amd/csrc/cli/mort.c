@@ -17,6 +17,7 @@
  *                   [--sh-probe X,Y,Z[,D[,N]]]            no render: the SH9 light probe at world position (X, Y, Z) as one JSON line
  *                   [--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]]   no render: an irradiance volume over the box, sampled at
  *                                                          --pick X,Y (one JSON line) or at every pixel (--irradiance-out FILE)
+ *                   [--visibility BIAS[,MINVIS[,S]]]      with --sh-volume: depth maps per probe and the visibility-weighted sampler
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -64,6 +65,13 @@
  * normal; one JSON line, --pick's fields plus irradiance (3) and weight_sum, zeros for a miss.  With --irradiance-out FILE (and
  * without --pick): the same chain for every pixel's --pick ray, sqrt(clamp(E / pi, 0, 1)) as an 8-bit PPM, misses black.
  *
+ * --visibility BIAS[,MINVIS[,S]] (with --sh-volume only): after the SH bake, one depth map per probe (DESIGN.md 4.18;
+ * mort_hip_probe_depth_bake, or its _host form) with S x S rays per texel (default 2, 1..8) and
+ * max_distance = (float)(1.5 sqrt(sx^2 + sy^2 + sz^2)) over the grid's spacing, computed in double; the volume is then sampled with
+ * mort_hip_volume_sample_visible: normal_bias = BIAS (finite, >= 0), min_visibility = MINVIS (default 0.05, in 0..1).  --pick's JSON
+ * line gains normal_bias, min_visibility, depth_subsamples and max_distance, --irradiance-out's the same.  Without the
+ * option every byte of the output is what it was.
+ *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
  * RCCL (`--gather rccl`, the default: xGMI inside a node), or through a shared host mapping (`--gather shm`: for ranks
@@ -108,7 +116,7 @@ static int usage(void) {
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
            "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
-           "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE]\n");
+           "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]]\n");
     return -1;
 }
 
@@ -188,6 +196,8 @@ int main(int argc, char **argv) {
     int sh_volume = 0, vol_n[3] = {0, 0, 0};
     float vol_box[6] = {0, 0, 0, 0, 0, 0};
     const char *irr_out = NULL;
+    int visibility = 0, vis_s = 2;
+    float vis_bias = 0.0f, vis_min = 0.05f;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -237,6 +247,10 @@ int main(int argc, char **argv) {
                        &vol_n[0], &vol_n[1], &vol_n[2], &sh_d, &sh_n) < 9 || sh_n < 1) { fprintf(stderr, "--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]\n"); return -1; }
         }
         else if (ARG("--irradiance-out")) irr_out = argv[++i];
+        else if (ARG("--visibility")) {
+            visibility = 1;
+            if (sscanf(argv[++i], "%f,%f,%d", &vis_bias, &vis_min, &vis_s) < 1) { fprintf(stderr, "--visibility BIAS[,MINVIS[,S]]\n"); return -1; }
+        }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -254,6 +268,10 @@ int main(int argc, char **argv) {
     if (sh_volume && (gpus > 1 || probe || sh_probe)) { fprintf(stderr, "--sh-volume is a single-GPU option and excludes --probe and --sh-probe\n"); return -1; }
     if (sh_volume && (sh_d < 64 || sh_d > 4096 || sh_d % 64)) { fprintf(stderr, "--sh-volume: D is a multiple of 64 in 64..4096\n"); return -1; }
     if (sh_volume && !pick == !irr_out) { fprintf(stderr, "--sh-volume needs --pick X,Y or --irradiance-out FILE, not both\n"); return -1; }
+    if (visibility && !sh_volume) { fprintf(stderr, "--visibility needs --sh-volume\n"); return -1; }
+    if (visibility && (!(vis_bias >= 0.0f) || vis_bias - vis_bias != 0.0f || !(vis_min >= 0.0f) || !(vis_min <= 1.0f) || vis_s < 1 || vis_s > MORT_DEPTH_RES)) {
+        fprintf(stderr, "--visibility: BIAS finite and >= 0, MINVIS in 0..1, S in 1..%d\n", MORT_DEPTH_RES); return -1;
+    }
     if (irr_out && !sh_volume) { fprintf(stderr, "--irradiance-out needs --sh-volume\n"); return -1; }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
@@ -309,6 +327,14 @@ int main(int argc, char **argv) {
         mort_ray *rays = (mort_ray *)malloc(nq * sizeof *rays);
         mort_hit *hits = (mort_hit *)malloc(nq * sizeof *hits);
         float *irr = (float *)malloc(nq * 4 * sizeof *irr);
+        float *depth = visibility ? (float *)malloc(probes_n * MORT_DEPTH_FLOATS * sizeof *depth) : NULL;
+        mort_depth_params dp;
+        dp.subsamples = vis_s;
+        dp.max_distance = (float)(1.5 * sqrt((double)grid.spacing[0] * (double)grid.spacing[0] + (double)grid.spacing[1] * (double)grid.spacing[1] +
+                                             (double)grid.spacing[2] * (double)grid.spacing[2]));
+        mort_volume_vis_params vp;
+        vp.normal_bias = vis_bias; vp.min_visibility = vis_min;
+        if (visibility && !depth) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
         if (!probes || !states || !sh || !records || !rays || !hits || !irr || probes_n * (size_t)sh_d > 0x7fffffffu) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
         if ((pst = mort_hip_volume_probes(&grid, probes)) != MORT_OK) die(NULL, pst, "mort_hip_volume_probes");
         if ((pst = mort_hip_rng_seed_host(seed, (int)(probes_n * (size_t)sh_d), 1, states)) != MORT_OK) die(NULL, pst, "mort_hip_rng_seed_host");
@@ -320,6 +346,10 @@ int main(int argc, char **argv) {
             if ((pst = mort_hip_probe_bake_host(&world, &pp, probes_n, probes, NULL, states, threads, fl, sh, &bake_sec)) != MORT_OK) die(NULL, pst, "mort_hip_probe_bake_host");
             if ((pst = mort_hip_volume_pack_host(probes_n, sh, NULL, threads, records, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_volume_pack_host");
             if ((pst = mort_hip_query_closest_host(&world, nq, rays, NULL, threads, fl, hits, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_closest_host");
+            if (visibility) {
+                if ((pst = mort_hip_probe_depth_bake_host(&world, &dp, probes_n, probes, threads, fl, depth, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_probe_depth_bake_host");
+                if ((pst = mort_hip_volume_sample_visible_host(&grid, records, depth, &vp, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_visible_host");
+            } else
             if ((pst = mort_hip_volume_sample_host(&grid, records, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_host");
         } else {
             mort_ctx *pctx = NULL;
@@ -328,6 +358,10 @@ int main(int argc, char **argv) {
             if ((pst = mort_hip_probe_bake(pctx, &pp, probes_n, probes, NULL, states, sh, &bake_sec)) != MORT_OK) die(pctx, pst, "mort_hip_probe_bake");
             if ((pst = mort_hip_volume_pack(pctx, probes_n, sh, NULL, records, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_volume_pack");
             if ((pst = mort_hip_query_closest(pctx, nq, rays, NULL, hits, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_closest");
+            if (visibility) {
+                if ((pst = mort_hip_probe_depth_bake(pctx, &dp, probes_n, probes, depth, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_probe_depth_bake");
+                if ((pst = mort_hip_volume_sample_visible(pctx, &grid, records, depth, &vp, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample_visible");
+            } else
             if ((pst = mort_hip_volume_sample(pctx, &grid, records, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample");
             mort_hip_shutdown(pctx);
         }
@@ -344,6 +378,11 @@ int main(int argc, char **argv) {
                    (h.flags & MORT_HIT_FRONT_FACE) ? 1 : 0, (h.flags & MORT_HIT_MEDIUM) ? 1 : 0);
             print_v3("irradiance", irr);
             printf(", \"weight_sum\": "); print_f32(irr[3]);
+            if (visibility) {
+                printf(", \"normal_bias\": "); print_f32(vp.normal_bias);
+                printf(", \"min_visibility\": "); print_f32(vp.min_visibility);
+                printf(", \"depth_subsamples\": %d, \"max_distance\": ", dp.subsamples); print_f32(dp.max_distance);
+            }
             printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"samples\": %d, \"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f, \"sample_seconds\": %.6f}\n",
                    (int)grid.count[0], (int)grid.count[1], (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec, sample_sec);
         } else {
@@ -362,10 +401,16 @@ int main(int argc, char **argv) {
             if (mort_write_ppm(irr_out, img, W, H) != 0) { fprintf(stderr, "cannot write %s\n", irr_out); return EXIT_FAILURE; }
             free(img);
             printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"irradiance_out\": \"%s\", \"probes\": [%d, %d, %d], \"directions\": %d, \"samples\": %d, "
-                   "\"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f, \"sample_seconds\": %.6f}\n", scene, W, H, irr_out, (int)grid.count[0], (int)grid.count[1],
+                   "\"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f, \"sample_seconds\": %.6f", scene, W, H, irr_out, (int)grid.count[0], (int)grid.count[1],
                    (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec, sample_sec);
+            if (visibility) {
+                printf(", \"normal_bias\": "); print_f32(vp.normal_bias);
+                printf(", \"min_visibility\": "); print_f32(vp.min_visibility);
+                printf(", \"depth_subsamples\": %d, \"max_distance\": ", dp.subsamples); print_f32(dp.max_distance);
+            }
+            printf("}\n");
         }
-        free(probes); free(states); free(sh); free(records); free(rays); free(hits); free(irr);
+        free(probes); free(states); free(sh); free(records); free(rays); free(hits); free(irr); free(depth);
         mort_world_free(&world);
         free(texels);
         return 0;

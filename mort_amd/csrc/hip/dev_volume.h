@@ -143,25 +143,38 @@ DEV float4 volume_sample_point(const VolumeArgs &a, float px, float py, float pz
     return o;
 }
 
-/* point i of the batch: its 24 bytes in, its 16 bytes out */
-DEV void volume_sample_one(const VolumeArgs &a, size_t i) {
+/* point i of the batch: its 24 bytes in ... */
+struct VolumePointIn { float p[6]; };
+DEV VolumePointIn volume_load_point(const VolumeArgs &a, size_t i) {
     const unsigned char *src = a.points + i * a.stride;
-    float p[6];
+    VolumePointIn r;
 #if defined(__HIP_DEVICE_COMPILE__)
     if ((a.stride & 15u) == 0) { /* wave-uniform; the points' base is 16-byte aligned: 16 + 8 bytes */
         const float4 lo = *(const float4 *)src;
         const float2 hi = *(const float2 *)(src + 16);
-        p[0] = lo.x; p[1] = lo.y; p[2] = lo.z; p[3] = lo.w; p[4] = hi.x; p[5] = hi.y;
+        r.p[0] = lo.x; r.p[1] = lo.y; r.p[2] = lo.z; r.p[3] = lo.w; r.p[4] = hi.x; r.p[5] = hi.y;
     } else {
 #pragma unroll
-        for (int k = 0; k < 6; k++) p[k] = ((const float *)src)[k];
+        for (int k = 0; k < 6; k++) r.p[k] = ((const float *)src)[k];
     }
-    *(float4 *)(a.out + 4 * i) = volume_sample_point(a, p[0], p[1], p[2], p[3], p[4], p[5]);
 #else
-    std::memcpy(p, src, sizeof p);
-    const float4 o = volume_sample_point(a, p[0], p[1], p[2], p[3], p[4], p[5]);
+    std::memcpy(r.p, src, sizeof r.p);
+#endif
+    return r;
+}
+
+/* ... and its 16 bytes out */
+DEV void volume_store_sample(const VolumeArgs &a, size_t i, float4 o) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(float4 *)(a.out + 4 * i) = o;
+#else
     std::memcpy(a.out + 4 * i, &o, sizeof o);
 #endif
+}
+
+DEV void volume_sample_one(const VolumeArgs &a, size_t i) {
+    const VolumePointIn r = volume_load_point(a, i);
+    volume_store_sample(a, i, volume_sample_point(a, r.p[0], r.p[1], r.p[2], r.p[3], r.p[4], r.p[5]));
 }
 
 /* 16 bytes t of the packed records: quarter t & 7 of record t >> 3 */

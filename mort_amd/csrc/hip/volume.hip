@@ -9,6 +9,12 @@
  *                          corners are taken two at a time (the x neighbours of one grid row) in a loop that is not unrolled, so
  *                          at most two records are in registers; of a corner first the quarter with the weight is loaded, the
  *                          other six only if the corner contributes, none if its trilinear weight is 0; one 16-byte store.
+ *   volume_sample_visible_kernel   the same with every corner's weight multiplied by the Chebyshev visibility read from the
+ *                          probe's depth map (dev_depth.h): normal_bias and min_visibility ride in the argument
+ *                          struct; once a corner's T * weight is known to be > 0 the corner is straight-line code (selects, no
+ *                          branch), so that its four map taps (8-byte loads in the source, merged pairwise into two 16-byte
+ *                          loads by the compiler) are issued in one block with its six coefficient loads and nothing is
+ *                          loaded after that block's first wait (checked in the disassembly).
  *   volume_pack_kernel     one lane per 16 bytes of the records: dword loads (a probe's 108 bytes are only 4-byte aligned), one
  *                          16-byte store.
  *
@@ -22,6 +28,7 @@
 
 #include "mort_hip.h"
 #include "dev_volume.h"
+#include "dev_depth.h"
 #include "mort_ctx.h"
 #include "mort_internal.h"
 #include "stage_common.h"
@@ -35,6 +42,12 @@ __global__ void __launch_bounds__(QUERY_BLOCK) volume_sample_kernel(const Volume
     const size_t i = (size_t)blockIdx.x * QUERY_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     volume_sample_one(a, i);
+}
+
+__global__ void __launch_bounds__(QUERY_BLOCK) volume_sample_visible_kernel(const VolumeVisArgs a) {
+    const size_t i = (size_t)blockIdx.x * QUERY_BLOCK + threadIdx.x;
+    if (i >= a.v.n) return;
+    volume_vis_sample_one(a, i);
 }
 
 __global__ void __launch_bounds__(QUERY_BLOCK) volume_pack_kernel(const VolumePackArgs a) {
@@ -76,6 +89,17 @@ int sample_check(const mort_volume_grid *g, const void *records, size_t n, const
     return buffers_disjoint(ins, in_bytes, 2, outs, out_bytes, 1) ? MORT_OK : MORT_ERR_INVALID;
 }
 
+/* what the three visible forms check on top of that */
+int visible_check(const mort_volume_grid *g, const void *records, const void *depth, const mort_volume_vis_params *vp, size_t n, const void *points,
+                  size_t stride, void *out, size_t *span) {
+    if (!depth || !vp) return MORT_ERR_INVALID;
+    const int st = sample_check(g, records, n, points, stride, out, span);
+    if (st != MORT_OK) return st;
+    if (!std::isfinite(vp->normal_bias) || !(vp->normal_bias >= 0.0f)) return MORT_ERR_INVALID;
+    if (!std::isfinite(vp->min_visibility) || !(vp->min_visibility >= 0.0f) || !(vp->min_visibility <= 1.0f)) return MORT_ERR_INVALID;
+    return overlap(out, n * 4 * sizeof(float), depth, grid_probes(g) * MORT_DEPTH_FLOATS * sizeof(float)) ? MORT_ERR_INVALID : MORT_OK;
+}
+
 int pack_check(size_t n, const void *sh, const void *weight, void *records) {
     if (!sh || !records || n > kMaxPack) return MORT_ERR_INVALID;
     const void *ins[2] = {sh, weight};
@@ -105,6 +129,18 @@ void pack_host_chunk(void *p, int chunk) {
     const VolumePackArgs *a = (const VolumePackArgs *)p;
     const size_t i0 = (size_t)chunk * kHostChunk, i1 = i0 + kHostChunk < a->n ? i0 + kHostChunk : a->n;
     for (size_t t = 8 * i0; t < 8 * i1; t++) volume_pack_quad(*a, t);
+}
+
+void visible_args(VolumeVisArgs &a, const mort_volume_grid *g, const void *records, const void *depth, const mort_volume_vis_params *vp, size_t n,
+                  const void *points, size_t stride, void *out) {
+    sample_args(a.v, g, records, n, points, stride, out);
+    a.depth = (const float *)depth; a.normal_bias = vp->normal_bias; a.min_visibility = vp->min_visibility;
+}
+
+void visible_host_chunk(void *p, int chunk) {
+    const VolumeVisArgs *a = (const VolumeVisArgs *)p;
+    const size_t i0 = (size_t)chunk * kHostChunk, i1 = i0 + kHostChunk < a->v.n ? i0 + kHostChunk : a->v.n;
+    for (size_t i = i0; i < i1; i++) volume_vis_sample_one(*a, i);
 }
 
 } // namespace
@@ -218,4 +254,58 @@ extern "C" int mort_hip_volume_sample(mort_ctx *c, const mort_volume_grid *g, co
     if ((st = mort_hip_volume_sample_device(c, g, pl[0].dev, n, pl[1].dev, stride, pl[2].dev, c->stream, &sec)) != MORT_OK) return st;
     if (seconds) *seconds = sec;
     return stage_download(c, pl, 3);
+}
+
+extern "C" int mort_hip_volume_sample_visible_host(const mort_volume_grid *g, const float *records, const float *depth,
+                                                   const mort_volume_vis_params *vp, size_t n, const void *points, size_t stride, int nthreads,
+                                                   float *out, double *seconds) {
+    size_t span = 0;
+    const int st = visible_check(g, records, depth, vp, n, points, stride, out, &span);
+    if (st != MORT_OK) return st;
+    if (seconds) *seconds = 0;
+    if (n == 0) return MORT_OK;
+    VolumeVisArgs a;
+    visible_args(a, g, records, depth, vp, n, points, stride, out);
+    const double t0 = now_s();
+    run_rows((int)((n + kHostChunk - 1) / kHostChunk), nthreads, visible_host_chunk, &a);
+    if (seconds) *seconds = now_s() - t0;
+    return MORT_OK;
+}
+
+extern "C" int mort_hip_volume_sample_visible_device(mort_ctx *c, const mort_volume_grid *g, const void *d_records, const void *d_depth,
+                                                     const mort_volume_vis_params *vp, size_t n, const void *d_points, size_t stride, void *d_out,
+                                                     void *stream, double *seconds) {
+    if (!c) return MORT_ERR_INVALID;
+    size_t span = 0;
+    int st = visible_check(g, d_records, d_depth, vp, n, d_points, stride, d_out, &span);
+    if (st != MORT_OK) return st;
+    if (!aligned16(d_records) || !aligned16(d_depth) || !aligned16(d_points) || !aligned16(d_out)) return MORT_ERR_INVALID;
+    if (n == 0) { if (seconds) *seconds = 0; return MORT_OK; }
+    VolumeVisArgs a;
+    visible_args(a, g, d_records, d_depth, vp, n, d_points, stride, d_out);
+    hipStream_t s;
+    if ((st = stage_begin(c, stream, 0, seconds, &s)) != MORT_OK) return st;
+    const dim3 grid((unsigned)((n + QUERY_BLOCK - 1) / QUERY_BLOCK)), block(QUERY_BLOCK);
+    hipLaunchKernelGGL(volume_sample_visible_kernel, grid, block, 0, s, a);
+    HIPCHK(c, hipGetLastError());
+    return stage_end(c, s, seconds);
+}
+
+extern "C" int mort_hip_volume_sample_visible(mort_ctx *c, const mort_volume_grid *g, const float *records, const float *depth,
+                                              const mort_volume_vis_params *vp, size_t n, const void *points, size_t stride, float *out,
+                                              double *seconds) {
+    if (!c) return MORT_ERR_INVALID;
+    size_t span = 0;
+    int st = visible_check(g, records, depth, vp, n, points, stride, out, &span);
+    if (st != MORT_OK) return st;
+    if (n == 0) { if (seconds) *seconds = 0; return MORT_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, switch_stream(c, c->stream));
+    StagePlane pl[4] = {{records, nullptr, grid_probes(g) * kRecordBytes}, {depth, nullptr, grid_probes(g) * MORT_DEPTH_FLOATS * sizeof(float)},
+                        {points, nullptr, span}, {nullptr, out, n * 4 * sizeof(float)}};
+    if ((st = stage_upload(c, pl, 4)) != MORT_OK) return st;
+    double sec = 0;
+    if ((st = mort_hip_volume_sample_visible_device(c, g, pl[0].dev, pl[1].dev, vp, n, pl[2].dev, stride, pl[3].dev, c->stream, &sec)) != MORT_OK) return st;
+    if (seconds) *seconds = sec;
+    return stage_download(c, pl, 4);
 }

@@ -39,6 +39,8 @@ EXPORTS = [
     "mort_hip_probe_directions", "mort_hip_probe_bake", "mort_hip_probe_bake_device", "mort_hip_probe_bake_host", "mort_hip_sh9_irradiance",
     "mort_hip_volume_probes", "mort_hip_volume_pack", "mort_hip_volume_pack_device", "mort_hip_volume_pack_host",
     "mort_hip_volume_sample", "mort_hip_volume_sample_device", "mort_hip_volume_sample_host",
+    "mort_hip_probe_depth_bake", "mort_hip_probe_depth_bake_device", "mort_hip_probe_depth_bake_host",
+    "mort_hip_volume_sample_visible", "mort_hip_volume_sample_visible_device", "mort_hip_volume_sample_visible_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -97,6 +99,29 @@ class VOLUME_GRID(C.Structure):
     @property
     def probes(self):
         return self.count[0] * self.count[1] * self.count[2]
+
+
+# visibility-weighted irradiance volumes (mort_depth_params, mort_volume_vis_params of include/mort_hip.h)
+DEPTH_RES = 8
+DEPTH_FLOATS = 200
+
+
+class DEPTH_PARAMS(C.Structure):
+    """mort_depth_params of include/mort_hip.h: s x s rays per texel, distances capped at max_distance"""
+    _fields_ = [("subsamples", C.c_int), ("max_distance", C.c_float)]
+
+    def __init__(self, subsamples=2, max_distance=1.0):
+        super().__init__()
+        self.subsamples, self.max_distance = subsamples, max_distance
+
+
+class VOLUME_VIS_PARAMS(C.Structure):
+    """mort_volume_vis_params of include/mort_hip.h"""
+    _fields_ = [("normal_bias", C.c_float), ("min_visibility", C.c_float)]
+
+    def __init__(self, normal_bias=0.0, min_visibility=0.05):
+        super().__init__()
+        self.normal_bias, self.min_visibility = normal_bias, min_visibility
 
 
 class Partition(C.Structure):
@@ -283,6 +308,15 @@ def lib():
         L.mort_hip_volume_sample.argtypes = [ctx, gp, vp, sz, vp, sz, vp, dp]; L.mort_hip_volume_sample.restype = C.c_int
         L.mort_hip_volume_sample_device.argtypes = [ctx, gp, vp, sz, vp, sz, vp, vp, dp]; L.mort_hip_volume_sample_device.restype = C.c_int
         L.mort_hip_volume_sample_host.argtypes = [gp, vp, sz, vp, sz, C.c_int, vp, dp]; L.mort_hip_volume_sample_host.restype = C.c_int
+        kp, qp = C.POINTER(DEPTH_PARAMS), C.POINTER(VOLUME_VIS_PARAMS)
+        L.mort_hip_probe_depth_bake.argtypes = [ctx, kp, sz, vp, vp, dp]; L.mort_hip_probe_depth_bake.restype = C.c_int
+        L.mort_hip_probe_depth_bake_device.argtypes = [ctx, kp, sz, vp, vp, vp, dp]; L.mort_hip_probe_depth_bake_device.restype = C.c_int
+        L.mort_hip_probe_depth_bake_host.argtypes = [wd, kp, sz, vp, C.c_int, C.c_int, vp, dp]; L.mort_hip_probe_depth_bake_host.restype = C.c_int
+        L.mort_hip_volume_sample_visible.argtypes = [ctx, gp, vp, vp, qp, sz, vp, sz, vp, dp]; L.mort_hip_volume_sample_visible.restype = C.c_int
+        L.mort_hip_volume_sample_visible_device.argtypes = [ctx, gp, vp, vp, qp, sz, vp, sz, vp, vp, dp]
+        L.mort_hip_volume_sample_visible_device.restype = C.c_int
+        L.mort_hip_volume_sample_visible_host.argtypes = [gp, vp, vp, qp, sz, vp, sz, C.c_int, vp, dp]
+        L.mort_hip_volume_sample_visible_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -635,6 +669,61 @@ class Context:
         stream, sync = _torch_stream(torch, points.device, sync)
         self._chk(lib().mort_hip_volume_sample_device(self._h, C.byref(grid), records.data_ptr(), n, points.data_ptr(), stride, out.data_ptr(),
                                                       stream, C.byref(sec) if sync else None), "mort_hip_volume_sample_device")
+        return sec.value if sync else None
+
+    def probe_depth_bake(self, params, probes):
+        """Depth maps of light probes on the GPU (mort_hip_probe_depth_bake): params DEPTH_PARAMS, probes as for probe_bake.
+        dict(depth float32 (n, 200) = 10 x 10 texels of (m1, m2), seconds)."""
+        probes = _probe_records(probes)
+        depth = np.zeros((probes.shape[0], DEPTH_FLOATS), dtype=np.float32)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_probe_depth_bake(self._h, C.byref(params), probes.shape[0], probes.ctypes.data, depth.ctypes.data, C.byref(sec)),
+                  "mort_hip_probe_depth_bake")
+        return dict(depth=depth, seconds=sec.value)
+
+    def probe_depth_bake_device(self, params, probes, depth, sync=False):
+        """The depth bake on torch tensors on this context's device, on the current torch stream: probes float32 of 4 n elements,
+        depth of 800 n bytes.  Asynchronous unless sync (then returns the device seconds) or torch runs on its legacy default
+        stream."""
+        import torch
+        if probes.dtype != torch.float32 or not probes.is_contiguous() or probes.numel() % 4 or probes.device.type != "cuda":
+            raise ValueError("expected a contiguous float32 tensor of 4 floats per probe on the GPU")
+        n = probes.numel() // 4
+        if not depth.is_contiguous() or depth.numel() * depth.element_size() != 4 * DEPTH_FLOATS * n or depth.device != probes.device:
+            raise ValueError(f"expected a contiguous tensor of {4 * DEPTH_FLOATS * n} bytes on {probes.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, probes.device, sync)
+        self._chk(lib().mort_hip_probe_depth_bake_device(self._h, C.byref(params), n, probes.data_ptr(), depth.data_ptr(),
+                                                         stream, C.byref(sec) if sync else None), "mort_hip_probe_depth_bake_device")
+        return sec.value if sync else None
+
+    def volume_sample_visible(self, grid, records, depth, params, points, stride=None):
+        """The visibility-weighted sampler on the GPU (mort_hip_volume_sample_visible): volume_sample's arguments, depth float32
+        (probes, 200) as probe_depth_bake returns it for the grid's probes, params VOLUME_VIS_PARAMS.  dict(out, seconds)."""
+        records, points, n, stride = _volume_inputs(grid, records, points, stride)
+        depth = _volume_depth(grid, depth)
+        out = np.zeros((n, 4), dtype=np.float32)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_volume_sample_visible(self._h, C.byref(grid), records.ctypes.data, depth.ctypes.data, C.byref(params), n,
+                                                       points.ctypes.data, stride, out.ctypes.data, C.byref(sec)), "mort_hip_volume_sample_visible")
+        return dict(out=out, seconds=sec.value)
+
+    def volume_sample_visible_device(self, grid, records, depth, params, points, out, stride=24, sync=False):
+        """The visibility-weighted sampler on torch tensors: volume_sample_device's arguments and depth of 800 bytes per probe of
+        the grid.  Asynchronous unless sync (then returns the device seconds) or torch runs on its legacy default stream."""
+        import torch
+        nbytes = points.numel() * points.element_size()
+        if not points.is_contiguous() or points.device.type != "cuda" or stride <= 0 or nbytes % stride:
+            raise ValueError(f"expected a contiguous tensor of records of {stride} bytes on the GPU")
+        n = nbytes // stride
+        for t, size in ((records, 128 * grid.probes), (depth, 4 * DEPTH_FLOATS * grid.probes), (out, 16 * n)):
+            if not t.is_contiguous() or t.numel() * t.element_size() != size or t.device != points.device:
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {points.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, points.device, sync)
+        self._chk(lib().mort_hip_volume_sample_visible_device(self._h, C.byref(grid), records.data_ptr(), depth.data_ptr(), C.byref(params), n,
+                                                              points.data_ptr(), stride, out.data_ptr(), stream, C.byref(sec) if sync else None),
+                  "mort_hip_volume_sample_visible_device")
         return sec.value if sync else None
 
     def calib_valu(self, waves_per_simd, kind=0):
@@ -1106,6 +1195,39 @@ def volume_sample_host(grid, records, points, stride=None, nthreads=1):
                                            C.byref(sec))
     if rc != 0:
         raise MortHipError(rc, "mort_hip_volume_sample_host")
+    return dict(out=out, seconds=sec.value)
+
+
+def _volume_depth(grid, depth):
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if all(0 < c <= VOLUME_MAX_COUNT for c in grid.count) and depth.size != DEPTH_FLOATS * grid.probes:
+        raise ValueError(f"expected {grid.probes} depth maps of 200 floats")
+    return depth
+
+
+def probe_depth_bake_host(world, params, probes, tree=False, nthreads=1):
+    """The depth bake as a host loop (mort_hip_probe_depth_bake_host), no GPU: arguments and result as Context.probe_depth_bake."""
+    probes = _probe_records(probes)
+    depth = np.zeros((probes.shape[0], DEPTH_FLOATS), dtype=np.float32)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_probe_depth_bake_host(world.ptr, C.byref(params), probes.shape[0], probes.ctypes.data, nthreads, HOST_TREE if tree else 0,
+                                              depth.ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_probe_depth_bake_host")
+    return dict(depth=depth, seconds=sec.value)
+
+
+def volume_sample_visible_host(grid, records, depth, params, points, stride=None, nthreads=1):
+    """The visibility-weighted sampler as a host loop (mort_hip_volume_sample_visible_host), no GPU: arguments and result as
+    Context.volume_sample_visible."""
+    records, points, n, stride = _volume_inputs(grid, records, points, stride)
+    depth = _volume_depth(grid, depth)
+    out = np.zeros((n, 4), dtype=np.float32)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_volume_sample_visible_host(C.byref(grid), records.ctypes.data, depth.ctypes.data, C.byref(params), n, points.ctypes.data,
+                                                   stride, nthreads, out.ctypes.data, C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_volume_sample_visible_host")
     return dict(out=out, seconds=sec.value)
 
 

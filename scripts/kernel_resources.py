@@ -12,7 +12,9 @@ graph), waves per SIMD that allocation allows, spilled registers, private (scrat
   * a ray-query kernel (query_closest_kernel, query_occluded_kernel) spills or uses any private memory, or
   * a radiance-query kernel (query_radiance_kernel) spills a vector register or keeps more in private memory than the bounce-stack
     levels behind its LDS part: MORT_MAX_BOUNCE_LIMIT x 16 B and one 16-byte slot, 1040 B, or
-  * a light-probe kernel (probe_sh_kernel), which runs the same path body, breaks that same rule.
+  * a light-probe kernel (probe_sh_kernel), which runs the same path body, breaks that same rule, or
+  * an irradiance-volume kernel (volume_*, the visible sampler among them) or the depth bake
+    (probe_depth_kernel, which runs the ray queries' search) spills or uses any private memory.
 """
 import os, re, subprocess, sys, tempfile, shutil
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
@@ -59,7 +61,9 @@ for r in sorted(rows, key=lambda r: r["name"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the ray queries run without scratch)")
     if r["name"].startswith("query_radiance_") and (r["vspill"] or r["private"] > 1040):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the search loop must not spill; 1040 B for the deep bounce levels)")
-    if r["name"].startswith("probe_") and (r["vspill"] or r["private"] > 1040):
+    if r["name"].startswith("probe_depth_") and (r["vspill"] or r["private"]):
+        bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the depth bake runs without scratch)")
+    if r["name"].startswith("probe_") and not r["name"].startswith("probe_depth_") and (r["vspill"] or r["private"] > 1040):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the radiance body must not spill; 1040 B for the deep bounce levels)")
     if r["name"].startswith("volume_") and (r["vspill"] or r["private"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the volume kernels run without scratch)")

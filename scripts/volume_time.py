@@ -14,6 +14,11 @@ There is nothing in the parent to compare with, so each batch's time is reported
 once, every probe record read once -- and that traffic's rate as a share of Context.calib_hbm_copy measured in the same process.
 Nothing is gated.  One JSON line per batch.
 
+The visibility-weighted sampler is timed beside the plain one in the same process, on the same two batches: the
+depth maps of the same grid are baked first (s = 2, max_distance 1.5 cell diagonals, reported in rays per second: 64 s^2 per
+probe), then volume_sample_visible_kernel runs with normal_bias 5 and min_visibility 0.05.  Each batch's line gains the visible
+sampler's times under "visible", its ratio to the plain sampler and its extra minimum traffic, 800 bytes per probe.
+
   --reps N   --warmup N   --probes-per-axis K   --width W"""
 import argparse
 import json
@@ -73,6 +78,12 @@ def main(a):
         records = torch.zeros(grid.probes * 32, dtype=torch.float32, device=dev)
         bake_s = ctx.probe_bake_device(hip.probe_params_from_camera(cam, D), probes_t, streams, sh, sync=True)
         pack_s = ctx.volume_pack_device(sh, records, sync=True)
+        # the depth maps of the same probes
+        dparams = hip.DEPTH_PARAMS(2, float(F(1.5 * np.sqrt(3.0) * float(grid.spacing[0]))))
+        depth = torch.zeros(grid.probes * hip.DEPTH_FLOATS, dtype=torch.float32, device=dev)
+        db = med(lambda: ctx.probe_depth_bake_device(dparams, probes_t, depth, sync=True), a.reps, a.warmup)
+        depth_rays = grid.probes * 64 * dparams.subsamples ** 2
+        vparams = hip.VOLUME_VIS_PARAMS(5.0, 0.05)
         # coherent: the frame's hits, never copied
         rays = pick_rays(cam)
         n = len(rays)
@@ -88,13 +99,22 @@ def main(a):
         pts_t = torch.from_numpy(pts.reshape(-1)).to(dev)
         out = torch.zeros(n * 4, dtype=torch.float32, device=dev)
         base = dict(probes=grid.probes, record_bytes=grid.probes * 128, points=n, reps=a.reps, warmup=a.warmup, calib_hbm_copy_gbs=copy_gbs,
-                    bake_ms=bake_s * 1e3, pack_ms=pack_s * 1e3, query_closest_ms=query_s * 1e3)
+                    bake_ms=bake_s * 1e3, pack_ms=pack_s * 1e3, query_closest_ms=query_s * 1e3,
+                    depth_bake=dict(subsamples=dparams.subsamples, max_distance=dparams.max_distance, rays=depth_rays, ms=db["ms"], ms_min=db["ms_min"],
+                                    ms_max=db["ms_max"], mrays_per_s=depth_rays / db["ms"] / 1e3, map_bytes=grid.probes * 800))
         for name, t, stride in (("coherent", hits_t, 48), ("incoherent", pts_t, 24)):
             r = med(lambda: ctx.volume_sample_device(grid, records, t, out, stride=stride, sync=True), a.reps, a.warmup)
             o = out.view(n, 4)
+            plain_out = out.clone()
+            v = med(lambda: ctx.volume_sample_visible_device(grid, records, depth, vparams, t, out, stride=stride, sync=True), a.reps, a.warmup)
+            changed = float((out.view(n, 4) != plain_out.view(n, 4)).any(1).float().mean())
+            visible = dict(ms=v["ms"], ms_min=v["ms_min"], ms_max=v["ms_max"], spread=v["spread"], runs_ms=v["runs_ms"], ratio_to_plain=v["ms"] / r["ms"],
+                           extra_min_traffic_bytes=800 * grid.probes, points_changed=changed, normal_bias=vparams.normal_bias,
+                           min_visibility=vparams.min_visibility)
+            o = plain_out.view(n, 4)
             traffic = n * (stride + 16) + 128 * grid.probes
             gbs = traffic / (r["ms"] * 1e-3) / 1e9
-            print(json.dumps(dict(base, batch=name, stride=stride, **r, min_traffic_bytes=traffic, min_traffic_gbs=gbs, share_of_copy=gbs / copy_gbs,
+            print(json.dumps(dict(base, batch=name, stride=stride, **r, min_traffic_bytes=traffic, min_traffic_gbs=gbs, share_of_copy=gbs / copy_gbs, visible=visible,
                                   mpoints_per_s=n / r["ms"] / 1e3, covered=float((o[:, 3] > 0).float().mean()),
                                   mean_irradiance=[float(v) for v in o[:, :3].nanmean(0)])), flush=True)
 
