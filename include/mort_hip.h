@@ -346,7 +346,8 @@ int mort_hip_view_read(mort_view *v, int what, void *host_out);
  * states != NULL: one 48-byte XORWOW stream per ray; media are evaluated exactly as world::hit does, drawing from that ray's
  * stream, which is advanced in place (only d and v[] are written; a ray that draws nothing leaves its stream's bits as they were).
  *
- * The record: a miss is all zero.  A sphere's (u, v) are sphere_uv of its outward normal; a medium hit has normal (1, 0, 0),
+ * The record: a miss is all zero.  mat_type / mat_idx are the hit's material reference as the world was compiled: a tag outside
+ * MORT_MAT_LAMBERTIAN .. MORT_MAT_ISOTROPIC is reported as (0x7fff, 0), whatever its index.  A sphere's (u, v) are sphere_uv of its outward normal; a medium hit has normal (1, 0, 0),
  * MORT_HIT_FRONT_FACE and u = v = 0 (the reference leaves u, v indeterminate there).
  * Occlusion: out[i] = 1 iff a solid is hit in [0.001, t_max]; media never occlude and nothing is drawn: the MORT_HIT_HIT flag of
  * the closest-hit query with states == NULL.

@@ -1,9 +1,9 @@
 /*
  * debug.hip -- the diagnostics behind mort_amd/hip.py's debug_* calls (none is in include/mort_hip.h).  Most are host only:
- * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Six
+ * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Seven
  * launch small kernels of their own: exact_forms_kernel, f2i_all_kernel and f2i_list_kernel put the device's short forms
  * beside its plain operators, math_kernel runs the math layer on a caller's inputs, light_kernel the light sampling on a caller's
- * records over an uploaded world, random_float_all_kernel sweeps random_float.  mega_bvh.h is included for those bodies; its kernels are templates and none is instantiated here.
+ * records over an uploaded world, shade_kernel the shade step (search + shade_hit) on a caller's records over an uploaded world, random_float_all_kernel sweeps random_float.  mega_bvh.h is included for those bodies; its kernels are templates and none is instantiated here.
  */
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,8 @@
 #include "scene_blob.h"
 #include "mort_ctx.h"
 #include "world_images.h"
+#include "dev_radiance.h"
+#include "query_common.h"
 
 #pragma clang fp contract(off)
 
@@ -647,8 +649,7 @@ static __host__ __device__ void light_eval(int fn, const DScene &sc, const uint3
 /* every record names a light object the render would accept: `check` is check_light or check_light_object on (type, idx).  A list's answer
  * is formed once (it walks the list), a primitive's per record */
 template <typename Check>
-static int light_check_records(int fn, const uint32_t *in, size_t n, Check check) {
-    const size_t iw = LIGHT_SHAPES[fn].in, at = fn == 0 ? 0 : 6;
+static int light_check_records(size_t iw, size_t at, const uint32_t *in, size_t n, Check check) { /* (type, idx) at words at, at + 1 of iw */
     int list_status[MORT_NUM_HITTABLE_LIST];
     bool list_known[MORT_NUM_HITTABLE_LIST] = {};
     for (size_t i = 0; i < n; i++) {
@@ -680,7 +681,7 @@ extern "C" int mort_hip_debug_light_host(const mort_world *w, int fn, const uint
     int st = build_scene_blob(w, sb);
     if (st != MORT_OK) return st;
     const int n_lists = w->objs.num_hittable_list;
-    st = light_check_records(fn, in, n, [&](int type, int idx) { return check_light_object(sb.comp, n_lists, type, idx); });
+    st = light_check_records(LIGHT_SHAPES[fn].in, fn == 0 ? 0 : 6, in, n, [&](int type, int idx) { return check_light_object(sb.comp, n_lists, type, idx); });
     if (st != MORT_OK) return st;
     DScene sc;
     scene_view(sb, sb.bytes.data(), sc);
@@ -712,7 +713,7 @@ static __global__ void __launch_bounds__(256) light_kernel(int fn, int iw, int o
 extern "C" int mort_hip_debug_light_device(mort_ctx *c, int fn, const uint32_t *in, size_t n, uint32_t *out) {
     if (!c || fn < 0 || fn >= LIGHT_FUNCTIONS || !in || !out || n == 0 || n > ((size_t)1 << 28)) return MORT_ERR_INVALID;
     if (!c->have_world) return MORT_ERR_NO_WORLD;
-    int st = light_check_records(fn, in, n, [&](int type, int idx) { return check_light(c, type, idx); });
+    int st = light_check_records(LIGHT_SHAPES[fn].in, fn == 0 ? 0 : 6, in, n, [&](int type, int idx) { return check_light(c, type, idx); });
     if (st != MORT_OK) return st;
     const size_t iw = LIGHT_SHAPES[fn].in, ow = LIGHT_SHAPES[fn].out;
     HIPCHK(c, hipSetDevice(c->device));
@@ -725,6 +726,124 @@ extern "C" int mort_hip_debug_light_device(mort_ctx *c, int fn, const uint32_t *
         light_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, c->stream>>>(fn, (int)iw, (int)ow, c->sc, d_in, n, d_out);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
             hipMemcpy(out, d_out, n * ow * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return st;
+}
+
+/* ---- the shade step on a caller's records against a caller's world: one iteration of ray_color's loop body (camera.cuh:96-159) -- the
+ * closest-hit search of a radiance query's segment (dev_radiance.h radiance_world_hit: [0.001, inf), the unified tree where the world has
+ * one, else the item scan) and dev_shade.h's shade_hit on what it finds.  One record, in 32-bit words:
+ *   in  (16): the six XORWOW words (d, v0..v4), ray origin[3], direction[3], time, ray_time0 (the time a Lambertian or isotropic scatter
+ *             gives its ray), light_type, light_idx (the camera's light object; -1 = none);
+ *   out (22): status (0 miss, 1 the path ends, 2 scatter, 3 scatter whose stack entry is the identity), k[3] = scattering_pdf x attenuation,
+ *             rp = 1 / pdf, final_value[3], the ray afterwards (7; the scattered ray of a scatter, else the ray as given), the six final
+ *             stream words, the draw count.  k and rp are 0 where nothing scatters, (1, 1, 1) and 1 for status 3; final_value is 0 for a
+ *             miss (the background is the caller's) and for a scatter.
+ * shade_eval is the one body behind mort_hip_debug_shade_host (hipcc's host compile over a world compiled as host_render.hip compiles it)
+ * and shade_kernel (the gfx950 compile over a context's uploaded scene); oracle/mort_oracle.c's mort_oracle_shade_batch is the oracle's
+ * loop body under the same layout (tests/test_shade_host.py, tests/test_gpu_shade.py). ---- */
+#define SHADE_IN_WORDS 16
+#define SHADE_OUT_WORDS 22
+
+template <bool TREE>
+static __host__ __device__ void shade_eval(const QueryArgs &q, const uint32_t *in, uint32_t *out, unsigned short *walk, int walk_stride) {
+    Rng s = math_rng(in);
+    Ray ray;
+    ray.o = math_v(in, 6); ray.d = math_v(in, 9); ray.tm = math_f(in, 12);
+    const float ray_time0 = math_f(in, 13);
+    uint32_t status = 0;
+    StackEntry e;
+    e.kx = e.ky = e.kz = e.rp = 0.0f;
+    V3 final_value = mk(0, 0, 0);
+    Best best;
+    if (radiance_world_hit<TREE>(q, ray, s, best, walk, walk_stride)) {
+        const ShadeOut so = shade_hit(q.sc, (int)in[14], (int)in[15], ray, ray_time0, best, s);
+        if (so.done) { status = 1; final_value = so.final_value; }
+        else if (so.ident) { status = 3; e.kx = e.ky = e.kz = e.rp = 1.0f; }
+        else { status = 2; e = so.e; }
+    }
+    out[0] = status;
+    math_pf(out, 1, e.kx); math_pf(out, 2, e.ky); math_pf(out, 3, e.kz); math_pf(out, 4, e.rp);
+    math_pv(out, 5, final_value);
+    math_pv(out, 8, ray.o); math_pv(out, 11, ray.d); math_pf(out, 14, ray.tm);
+    math_prng(out, 15, s);
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the record shape of shade function fn in 32-bit words (fn 0, the shade
+ * step, is the only one); MORT_ERR_INVALID past the last function */
+#define SHADE_FUNCTIONS 1
+extern "C" int mort_hip_debug_shade_shape(int fn, int *in_words, int *out_words) {
+    if (fn < 0 || fn >= SHADE_FUNCTIONS || !in_words || !out_words) return MORT_ERR_INVALID;
+    *in_words = SHADE_IN_WORDS; *out_words = SHADE_OUT_WORDS;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the shade step over n records against `w`, hipcc's host compile of
+ * shade_eval.  The world is compiled as mort_hip_render_host compiles it; flags: MORT_HOST_TREE searches the unified tree where the world
+ * has one.  A record whose light object check_light_object refuses fails the whole call with that status, before anything is evaluated. */
+extern "C" int mort_hip_debug_shade_host(const mort_world *w, int fn, int flags, const uint32_t *in, size_t n, uint32_t *out) {
+    if (!w || fn < 0 || fn >= SHADE_FUNCTIONS || ((!in || !out) && n)) return MORT_ERR_INVALID;
+    SceneBlob sb;
+    int st = build_scene_blob(w, sb);
+    if (st != MORT_OK) return st;
+    const int n_lists = w->objs.num_hittable_list;
+    st = light_check_records(SHADE_IN_WORDS, 14, in, n, [&](int type, int idx) { return check_light_object(sb.comp, n_lists, type, idx); });
+    if (st != MORT_OK) return st;
+    const bool tree = (flags & MORT_HOST_TREE) && sb.comp.g_ok;
+    QueryArgs q;
+    query_args_host(sb, tree, q);
+    unsigned nthreads = std::thread::hardware_concurrency();
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    if (n < 4096) nthreads = 1;
+    auto work = [&](unsigned k) {
+        unsigned short walk[MORT_OWN_STACK];
+        for (size_t i = n * k / nthreads, end = n * (k + 1) / nthreads; i < end; i++) {
+            if (tree) shade_eval<true>(q, in + i * SHADE_IN_WORDS, out + i * SHADE_OUT_WORDS, walk, 1);
+            else shade_eval<false>(q, in + i * SHADE_IN_WORDS, out + i * SHADE_OUT_WORDS, walk, 1);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned k = 1; k < nthreads; k++) pool.emplace_back(work, k);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    return MORT_OK;
+}
+
+/* one lane per record, grid-stride; the walk's pending children in LDS as query_radiance_kernel keeps them; results leave as raw words */
+template <bool TREE>
+static __global__ void __launch_bounds__(QUERY_BLOCK) shade_kernel(QueryArgs q, const uint32_t *in, size_t n, uint32_t *out) {
+    __shared__ unsigned short walk_stack[TREE ? MORT_OWN_STACK * QUERY_BLOCK : 1];
+    const size_t stride = (size_t)gridDim.x * QUERY_BLOCK;
+    for (size_t i = (size_t)blockIdx.x * QUERY_BLOCK + threadIdx.x; i < n; i += stride)
+        shade_eval<TREE>(q, in + i * SHADE_IN_WORDS, out + i * SHADE_OUT_WORDS, &walk_stack[TREE ? threadIdx.x : 0], QUERY_BLOCK);
+}
+
+/* diagnostic (not in include/mort_hip.h): one launch of shade_kernel over the scene of a context whose world has been uploaded, the
+ * search a radiance query makes there (the unified tree where the world has one).  Every record's light object is checked on the host
+ * first, by check_light against the context's copy of the uploaded world's lists; a refused record fails the whole call before the
+ * launch.  Writes n records to `out` and nothing after them. */
+extern "C" int mort_hip_debug_shade_device(mort_ctx *c, int fn, const uint32_t *in, size_t n, uint32_t *out) {
+    if (!c || fn < 0 || fn >= SHADE_FUNCTIONS || !in || !out || n == 0 || n > ((size_t)1 << 26)) return MORT_ERR_INVALID;
+    if (!c->have_world) return MORT_ERR_NO_WORLD;
+    int st = light_check_records(SHADE_IN_WORDS, 14, in, n, [&](int type, int idx) { return check_light(c, type, idx); });
+    if (st != MORT_OK) return st;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, quiesce(c));
+    QueryArgs q;
+    query_args_device(c, q);
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    if (hipMalloc((void **)&d_in, n * SHADE_IN_WORDS * 4) != hipSuccess || hipMalloc((void **)&d_out, n * SHADE_OUT_WORDS * 4) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && hipMemcpy(d_in, in, n * SHADE_IN_WORDS * 4, hipMemcpyHostToDevice) != hipSuccess) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        const size_t blocks = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
+        const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096)), block(QUERY_BLOCK);
+        if (c->gen_ok) shade_kernel<true><<<grid, block, 0, c->stream>>>(q, d_in, n, d_out);
+        else shade_kernel<false><<<grid, block, 0, c->stream>>>(q, d_in, n, d_out);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipMemcpy(out, d_out, n * SHADE_OUT_WORDS * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
     }
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);

@@ -26,6 +26,11 @@
 #define DREF(type, idx) (((uint32_t)(type) << 16) | (uint32_t)(idx))
 #define DREF_TYPE(r) ((int)((r) >> 16) & 0x7fff)
 #define DREF_IDX(r) ((int)((r) & 0xffffu))
+/* Every tag outside the known set compiles to this one reference (scene_compile.h mat_ref / tex_ref): it decodes to a tag no
+ * dispatch knows (a material that does not scatter, a texture's error pattern), leaves bit 31 (a sphere's "moves") clear, differs
+ * from a DLambert's "colour inlined" 0 and carries no index, so nothing is read from a table for it. */
+#define DREF_UNKNOWN_TYPE 0x7fff
+#define DREF_UNKNOWN DREF(DREF_UNKNOWN_TYPE, 0)
 
 struct __attribute__((aligned(16))) DSphere { /* 32 B */
     float cx, cy, cz, radius;

@@ -25,7 +25,7 @@ static inline bool tex_ok(const mort_world *w, int type, int idx, int depth) {
     case MORT_TEXTURE_IMAGE: return idx >= 0 && idx < w->texs.num_image_textures;
     case MORT_TEXTURE_NOISE: return idx >= 0 && idx < w->texs.num_noise_textures;
     }
-    return true; /* unknown tag: the error pattern, no table access */
+    return true; /* unknown tag: compiles to DREF_UNKNOWN (scene_compile.h tex_ref) -- the error pattern, no table access */
 }
 static inline bool mat_ok(const mort_world *w, int type, int idx) {
     const mort_world_materials &m = w->mats;
@@ -36,7 +36,7 @@ static inline bool mat_ok(const mort_world *w, int type, int idx) {
     case MORT_MAT_DIFFUSE_LIGHT: return idx >= 0 && idx < m.num_diffuse_lights && tex_ok(w, m.host_diffuse_light[idx].texType, m.host_diffuse_light[idx].texIdx, 0);
     case MORT_MAT_ISOTROPIC: return idx >= 0 && idx < m.num_isotropics && tex_ok(w, m.host_isotropic[idx].texType, m.host_isotropic[idx].texIdx, 0);
     }
-    return true; /* unknown tag: treated as "does not scatter", no table access */
+    return true; /* unknown tag: compiles to DREF_UNKNOWN (scene_compile.h mat_ref) -- does not scatter, no table access */
 }
 static inline int validate_world(const mort_world *w) {
     const mort_world_objects &o = w->objs;

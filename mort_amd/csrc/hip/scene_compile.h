@@ -67,6 +67,18 @@ struct Compiled {
     float g_c[3] = {0, 0, 0}, g_R = 0, g_mnear = 0, g_kmin = 0;
 };
 
+/* Material and texture references as the kernels decode them (dev_scene.h DREF_TYPE: 15 bits of tag, DREF_IDX: 16 bits of index).
+ * A known tag keeps its index, which validate_world (scene_blob.h) has checked against its table; every other tag -- zero, negative,
+ * or with bits the 15-bit field would drop, so that it would decode as a known one -- becomes DREF_UNKNOWN, whatever its index. */
+static inline uint32_t mat_ref(int type, int idx) {
+    if (type < MORT_MAT_LAMBERTIAN || type > MORT_MAT_ISOTROPIC) return DREF_UNKNOWN;
+    return DREF(type, idx & 0xffff);
+}
+static inline uint32_t tex_ref(int type, int idx) {
+    if (type < MORT_TEXTURE_SOLID || type > MORT_TEXTURE_NOISE) return DREF_UNKNOWN;
+    return DREF(type, idx & 0xffff);
+}
+
 /* A sphere that does not move gets a ZERO velocity: the BVH megakernel's leaf step computes every centre as c + tm * v without looking at the
  * moves bit (mega_bvh.h sphere_quadratic); the hit record still selects by the bit. */
 static inline DSphere to_dsphere(const mort_sphere &s) {
@@ -75,7 +87,7 @@ static inline DSphere to_dsphere(const mort_sphere &s) {
     d.vx = s.moves ? s.center_vec.e[0] : 0.0f;
     d.vy = s.moves ? s.center_vec.e[1] : 0.0f;
     d.vz = s.moves ? s.center_vec.e[2] : 0.0f;
-    d.mat = DREF(s.mat_type, s.mat_idx) | (s.moves ? 0x80000000u : 0u);
+    d.mat = mat_ref(s.mat_type, s.mat_idx) | (s.moves ? 0x80000000u : 0u);
     return d;
 }
 static inline DQuad to_dquad(const mort_quad &q) {
@@ -84,7 +96,7 @@ static inline DQuad to_dquad(const mort_quad &q) {
     for (int k = 0; k < 3; k++) {
         d.Q[k] = q.Q.e[k]; d.u[k] = q.u.e[k]; d.v[k] = q.v.e[k]; d.n[k] = q.normal.e[k]; d.w[k] = q.w.e[k];
     }
-    d.D = q.D; d.area = q.area; d.mat = DREF(q.mat_type, q.mat_idx);
+    d.D = q.D; d.area = q.area; d.mat = mat_ref(q.mat_type, q.mat_idx);
     return d;
 }
 
@@ -162,7 +174,7 @@ struct Compiler {
                 it.first = (int)out.subitems.size();
                 emit_items(b, out.subitems, false);
                 it.count = (int)out.subitems.size() - it.first;
-                it.mat = DREF(m.mat_type, m.mat_idx);
+                it.mat = mat_ref(m.mat_type, m.mat_idx);
                 it.medium = (int)out.media.size();
                 out.media.push_back(m.neg_inv_density);
                 items.push_back(it);
@@ -741,8 +753,6 @@ struct Compiler {
         }
         out.g_ok = true;
     }
-
-    static uint32_t tex_ref(int type, int idx) { return DREF(type & 0x7fff, idx & 0xffff); }
 
     DLambert tex_material(int tex_type, int tex_idx) {
         DLambert d;

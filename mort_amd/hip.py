@@ -979,6 +979,44 @@ def debug_light_device(ctx, fnum, records, out=None):
     return _debug_light("mort_hip_debug_light_device", ctx._h, fnum, records, out)
 
 
+SHADE_SHAPE = (16, 22)  # mort_hip_debug_shade_shape: (in_words, out_words) of the shade step (fn 0)
+
+
+def _debug_shade(name, args, fnum, records, out):
+    iw, ow = SHADE_SHAPE
+    rec = np.ascontiguousarray(records)
+    if rec.dtype.itemsize != 4 or rec.size % iw:
+        raise MortHipError(-1, name, f"the shade step takes records of {iw} 32-bit words")
+    words = rec.reshape(-1).view(np.uint32)
+    n = words.size // iw
+    if out is None:
+        out = np.empty(n * ow, dtype=np.uint32)
+    if out.dtype != np.uint32 or not out.flags.c_contiguous or out.size < n * ow:
+        raise MortHipError(-1, name, f"out: {n * ow} contiguous uint32 words")
+    fn = getattr(lib(), name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int] + [C.c_int] * (len(args) - 1) + [C.c_void_p, C.c_size_t, C.c_void_p]
+    st = fn(args[0], fnum, *args[1:], words.ctypes.data, n, out.ctypes.data)
+    if st != 0:
+        raise MortHipError(st, name)
+    return out
+
+
+def debug_shade_host(world, records, tree=False, fnum=0, out=None):
+    """mort_hip_debug_shade_host (host only): one iteration of ray_color's loop body -- the closest-hit search of a radiance query's
+    segment (tree: over the unified tree where the world has one) and shade_hit -- over records of 16 32-bit words (six XORWOW words, ray
+    origin[3], direction[3], time, ray_time0, light_type, light_idx) against `world`, hipcc's host compile.  22 words per record come
+    back: status (0 miss, 1 the path ends, 2 scatter, 3 identity scatter), k[3], rp, final_value[3], the ray afterwards (7), the six final
+    stream words, the draw count.  A record that names no acceptable light object fails the call.  Returns raw uint32 words (`out` if given)."""
+    return _debug_shade("mort_hip_debug_shade_host", (C.cast(world.ptr, C.c_void_p), HOST_TREE if tree else 0), fnum, records, out)
+
+
+def debug_shade_device(ctx, records, fnum=0, out=None):
+    """mort_hip_debug_shade_device: the same on the GPU of `ctx`, over the scene of its uploaded world, one launch of shade_kernel (the
+    search is the radiance queries': the unified tree where the world has one); arguments and result as debug_shade_host."""
+    return _debug_shade("mort_hip_debug_shade_device", (ctx._h,), fnum, records, out)
+
+
 def debug_random_float_device(device=0):
     """mort_hip_debug_random_float_device: random_float against (float)(1.0 - (double)u) for all 2^32 generator outputs on `device` --
     dict(differ, lowest, visited)."""

@@ -615,7 +615,7 @@ static vec3 value_dispatch(const mort_world *w, int type, int idx, float u, floa
 /* ------------------------------------------------------------------ materials + pdfs (materials.cuh, pdf.cuh) */
 
 enum { PDF_NONE = 0, PDF_COSINE = 1, PDF_SPHERE = 2 };
-typedef struct { vec3 attenuation; int pdf_kind; onb uvw; bool skip_pdf; ray skip_pdf_ray; } scatter_record;
+typedef struct { vec3 attenuation; int pdf_kind; onb uvw; bool skip_pdf; ray skip_pdf_ray; bool cant_refract, reflected; /* census only */ } scatter_record;
 
 static bool scatter_dispatch(ctx_t *c, const ray *r_in, const hit_record *rec, scatter_record *srec) {
     const mort_world *w = c->w; /* materials.cuh:272-296 */
@@ -649,10 +649,14 @@ static bool scatter_dispatch(ctx_t *c, const ray *r_in, const hit_record *rec, s
         float sin_theta = (float)mort_sqrt(1.0 - cos_theta * cos_theta);
         bool cant_refract = (refraction_ratio * sin_theta) > 1.0;
         vec3 direction;
-        if (cant_refract || reflectance(cos_theta, refraction_ratio) > random_float(c->g))
+        srec->cant_refract = cant_refract;
+        if (cant_refract || reflectance(cos_theta, refraction_ratio) > random_float(c->g)) {
             direction = reflect(unit_direction, rec->normal);
-        else
+            srec->reflected = true;
+        } else {
             direction = refract(unit_direction, rec->normal, refraction_ratio);
+            srec->reflected = false;
+        }
         srec->skip_pdf_ray = (ray){rec->p, direction, r_in->t};
         return true;
     }
@@ -699,6 +703,78 @@ static vec3 srec_pdf_generate(const scatter_record *s, rng_t *g) {
 
 /* ------------------------------------------------------------------ camera (camera.cuh) */
 
+/* one iteration of ray_color's loop body (camera.cuh:96-159): the closest hit of *current_ray and what its material does.  ray_color
+ * and mort_oracle_shade_batch both call it, so the batch cannot drift from the loop the goldens and the reference pin hold in place.
+ * time0 is r.time() of the ray ray_color was called with (camera.cuh:119).  STEP_SCATTER: *current_ray is the scattered ray and
+ * att / emi / spdf / pdf are what the loop pushes.  STEP_END: emi is the emission the path ends with.  `branch`: see SHADE_BR_*. */
+enum { STEP_MISS = 0, STEP_END = 1, STEP_SCATTER = 2 };
+enum { SHADE_BR_TAG = 0 /* 8 bits: mat_type + 2, 0xff = outside -1 .. 252 */, SHADE_BR_TEX = 8 /* 8 bits: the material's texType + 2 likewise, 0 = no texture */,
+       SHADE_BR_FRONT = 1 << 16, SHADE_BR_CANT_REFRACT = 1 << 17, SHADE_BR_REFLECTED = 1 << 18, SHADE_BR_REFRACTED = 1 << 19,
+       SHADE_BR_FROM_LIGHT = 1 << 20, SHADE_BR_FROM_MATERIAL = 1 << 21, SHADE_BR_MAT_PDF_ZERO = 1 << 22, SHADE_BR_NORMAL_NONFINITE = 1 << 23,
+       SHADE_BR_RATIO_ONE = 1 << 24, SHADE_BR_SKIP_PDF = 1 << 25 };
+typedef struct { vec3 att, emi; float spdf, pdf; unsigned branch; } step_out;
+
+static unsigned branch_tag(int tag) { return (tag >= -1 && tag <= 252) ? (unsigned)(tag + 2) : 0xffu; }
+
+static int bounce_step(ctx_t *c, int light_obj_type, int light_obj_idx, float time0, ray *current_ray, hit_record *rec, step_out *o) {
+    o->att = V(0, 0, 0); o->emi = V(0, 0, 0); o->spdf = 0; o->pdf = 0; o->branch = 0;
+    if (!world_hit(c, current_ray, 0.001f, INFINITY, rec)) return STEP_MISS;
+    {
+        const mort_world_materials *m = &c->w->mats;
+        int tex = -2; /* the material's own texture tag, for the census */
+        if (rec->mat_type == MORT_MAT_LAMBERTIAN) tex = m->host_lambertian[rec->mat_idx].texType;
+        else if (rec->mat_type == MORT_MAT_DIFFUSE_LIGHT) tex = m->host_diffuse_light[rec->mat_idx].texType;
+        else if (rec->mat_type == MORT_MAT_ISOTROPIC) tex = m->host_isotropic[rec->mat_idx].texType;
+        o->branch = branch_tag(rec->mat_type) << SHADE_BR_TAG | (tex == -2 ? 0u : branch_tag(tex) << SHADE_BR_TEX) | (rec->front_face ? SHADE_BR_FRONT : 0);
+        if (!isfinite(rec->normal.e[0]) || !isfinite(rec->normal.e[1]) || !isfinite(rec->normal.e[2])) o->branch |= SHADE_BR_NORMAL_NONFINITE;
+        if (rec->mat_type == MORT_MAT_DIELECTRIC) { /* the decisions scatter_dispatch is about to take, restated for the census only */
+            const mort_dielectric *d = &m->host_dielectric[rec->mat_idx];
+            const float ratio = rec->front_face ? d->inv_ior : d->ior;
+            if (ratio == 1.0f) o->branch |= SHADE_BR_RATIO_ONE;
+        }
+    }
+    ray scattered;
+    vec3 emission = emit_dispatch(c->w, rec);
+    float pdf, scattering_pdf;
+    scatter_record srec;
+    srec.cant_refract = false; srec.reflected = false;
+    if (!scatter_dispatch(c, current_ray, rec, &srec)) {
+        o->emi = emission;
+        return STEP_END;
+    }
+    if (srec.skip_pdf) {
+        *current_ray = srec.skip_pdf_ray;
+        o->att = srec.attenuation; o->emi = V(0, 0, 0); o->spdf = 1.0f; o->pdf = 1.0f;
+        o->branch |= SHADE_BR_SKIP_PDF;
+        if (rec->mat_type == MORT_MAT_DIELECTRIC)
+            o->branch |= (srec.cant_refract ? SHADE_BR_CANT_REFRACT : 0) | (srec.reflected ? SHADE_BR_REFLECTED : SHADE_BR_REFRACTED);
+        return STEP_SCATTER;
+    }
+    if (light_obj_type == -1) {
+        scattered = (ray){rec->p, srec_pdf_generate(&srec, c->g), time0};
+        pdf = srec_pdf_value(&srec, scattered.dir);
+        scattering_pdf = scatter_pdf_dispatch(rec, &scattered);
+    } else {
+        /* mixture_pdf(hittable_pdf(light), srec.pdf), pdf.cuh:60-107 */
+        vec3 dir;
+        if (random_float(c->g) < 0.5) {
+            dir = random_dispatch(c, light_obj_type, light_obj_idx, rec->p);
+            o->branch |= SHADE_BR_FROM_LIGHT;
+        } else {
+            dir = srec_pdf_generate(&srec, c->g);
+            o->branch |= SHADE_BR_FROM_MATERIAL;
+        }
+        scattered = (ray){rec->p, dir, time0};
+        pdf = (float)(0.5 * pdf_value_dispatch(c, light_obj_type, light_obj_idx, rec->p, scattered.dir) +
+                      0.5 * srec_pdf_value(&srec, scattered.dir));
+        scattering_pdf = scatter_pdf_dispatch(rec, &scattered);
+    }
+    if (srec_pdf_value(&srec, scattered.dir) == 0.0f) o->branch |= SHADE_BR_MAT_PDF_ZERO; /* census only: pure, draws nothing */
+    *current_ray = scattered;
+    o->att = srec.attenuation; o->emi = emission; o->spdf = scattering_pdf; o->pdf = pdf;
+    return STEP_SCATTER;
+}
+
 static vec3 ray_color(ctx_t *c, const mort_camera *cam, const ray *r) { /* camera.cuh:86-176 */
     hit_record rec;
     memset(&rec, 0, sizeof rec);
@@ -709,47 +785,17 @@ static vec3 ray_color(ctx_t *c, const mort_camera *cam, const ray *r) { /* camer
     vec3 final_value = V(0, 0, 0);
 
     while (iter < cam->bounce_limit) {
-        if (world_hit(c, &current_ray, 0.001f, INFINITY, &rec)) {
-            ray scattered;
-            vec3 emission = emit_dispatch(c->w, &rec);
-            float pdf, scattering_pdf;
-            scatter_record srec;
-            if (scatter_dispatch(c, &current_ray, &rec, &srec)) {
-                if (srec.skip_pdf) {
-                    current_ray = srec.skip_pdf_ray;
-                    st_att[iter] = srec.attenuation;
-                    st_emi[iter] = V(0, 0, 0);
-                    st_spdf[iter] = 1.0f;
-                    st_pdf[iter] = 1.0f;
-                    iter++;
-                    continue;
-                }
-                if (cam->light_obj_type == -1) {
-                    scattered = (ray){rec.p, srec_pdf_generate(&srec, c->g), r->t};
-                    pdf = srec_pdf_value(&srec, scattered.dir);
-                    scattering_pdf = scatter_pdf_dispatch(&rec, &scattered);
-                } else {
-                    /* mixture_pdf(hittable_pdf(light), srec.pdf), pdf.cuh:60-107 */
-                    vec3 dir;
-                    if (random_float(c->g) < 0.5)
-                        dir = random_dispatch(c, cam->light_obj_type, cam->light_obj_idx, rec.p);
-                    else
-                        dir = srec_pdf_generate(&srec, c->g);
-                    scattered = (ray){rec.p, dir, r->t};
-                    pdf = (float)(0.5 * pdf_value_dispatch(c, cam->light_obj_type, cam->light_obj_idx, rec.p, scattered.dir) +
-                                  0.5 * srec_pdf_value(&srec, scattered.dir));
-                    scattering_pdf = scatter_pdf_dispatch(&rec, &scattered);
-                }
-                current_ray = scattered;
-                st_att[iter] = srec.attenuation;
-                st_emi[iter] = emission;
-                st_spdf[iter] = scattering_pdf;
-                st_pdf[iter] = pdf;
-                iter++;
-            } else {
-                final_value = emission;
-                break;
-            }
+        step_out so;
+        const int what = bounce_step(c, cam->light_obj_type, cam->light_obj_idx, r->t, &current_ray, &rec, &so);
+        if (what == STEP_SCATTER) {
+            st_att[iter] = so.att;
+            st_emi[iter] = so.emi;
+            st_spdf[iter] = so.spdf;
+            st_pdf[iter] = so.pdf;
+            iter++;
+        } else if (what == STEP_END) {
+            final_value = so.emi;
+            break;
         } else {
             final_value = cam->background;
             break;
@@ -949,6 +995,71 @@ int mort_oracle_light_batch(const mort_world *w, int fn, const uint32_t *in, siz
         if (t > 0) pthread_create(&th[t], NULL, light_job, &jobs[t]);
     }
     light_job(&jobs[0]);
+    for (int t = 1; t < nthreads; t++) pthread_join(th[t], NULL);
+    return MORT_ORACLE_BATCH_OK;
+}
+
+/* one iteration of ray_color's loop body (bounce_step) over n records of 32-bit words, the layout of mort_hip_debug_shade_shape
+ * (mort_amd/csrc/hip/debug.hip): in (16) the six stream words (d, v[0..4]), ray origin[3], direction[3], time, the time of the ray
+ * ray_color was called with, the camera's light object (type, idx); out (22) status (0 miss, 1 the path ends, 2 scatter, 3 a dielectric's
+ * scatter), k[3] = scattering_pdf x attenuation, rp = the fp32 1 / pdf (1 for a skip-pdf scatter), final_value[3] (the emission a path
+ * ends with), the ray afterwards (7), the six final words, the draw count.  branch (may be NULL): one SHADE_BR_* word per record, for a
+ * census; no kernel produces it.  A light object whose sphere, quad or list index lies outside the world's tables is refused for the
+ * whole batch. */
+typedef struct { const mort_world *w; int tid, nthreads; size_t n; const uint32_t *in; uint32_t *out, *branch; } shade_job_t;
+static void *shade_job(void *arg) {
+    shade_job_t *j = arg;
+    for (size_t i = j->n * (size_t)j->tid / (size_t)j->nthreads, end = j->n * ((size_t)j->tid + 1) / (size_t)j->nthreads; i < end; i++) {
+        const uint32_t *a = j->in + i * 16;
+        uint32_t *o = j->out + i * 22;
+        float f[8];
+        mort_rng_state st;
+        memset(&st, 0, sizeof st);
+        st.d = a[0];
+        for (int k = 0; k < 5; k++) st.v[k] = a[1 + k];
+        memcpy(f, a + 6, sizeof f);
+        rng_t g = {&st, 0};
+        ctx_t c = {j->w, &g, 0};
+        ray r = {V(f[0], f[1], f[2]), V(f[3], f[4], f[5]), f[6]};
+        hit_record rec;
+        memset(&rec, 0, sizeof rec);
+        step_out so;
+        const int what = bounce_step(&c, (int)a[14], (int)a[15], f[7], &r, &rec, &so);
+        vec3 kk = V(0, 0, 0), fin = V(0, 0, 0);
+        float rp = 0;
+        if (what == STEP_SCATTER) {
+            kk = vscale(so.spdf, so.att);
+            rp = (so.branch & SHADE_BR_SKIP_PDF) ? 1.0f : 1 / so.pdf;
+        } else if (what == STEP_END) fin = so.emi;
+        o[0] = what == STEP_SCATTER && rec.mat_type == MORT_MAT_DIELECTRIC ? 3u : (uint32_t)what;
+        memcpy(o + 1, kk.e, 12); memcpy(o + 4, &rp, 4); memcpy(o + 5, fin.e, 12);
+        memcpy(o + 8, r.orig.e, 12); memcpy(o + 11, r.dir.e, 12); memcpy(o + 14, &r.t, 4);
+        o[15] = st.d;
+        for (int k = 0; k < 5; k++) o[16 + k] = st.v[k];
+        o[21] = (uint32_t)g.draws;
+        if (j->branch) j->branch[i] = so.branch;
+    }
+    return NULL;
+}
+int mort_oracle_shade_batch(const mort_world *w, const uint32_t *in, size_t n, uint32_t *out, uint32_t *branch, int nthreads) {
+    if (!w || ((!in || !out) && n)) return MORT_ORACLE_BATCH_BAD_ARGS;
+    const mort_world_objects *ob = &w->objs;
+    for (size_t i = 0; i < n; i++) {
+        const int type = (int)in[i * 16 + 14], idx = (int)in[i * 16 + 15];
+        const int count = type == MORT_OBJ_SPHERE ? ob->num_spheres : type == MORT_OBJ_QUAD ? ob->num_quads :
+                          type == MORT_OBJ_HITTABLE_LIST ? ob->num_hittable_list : -1;
+        if (count >= 0 && (idx < 0 || idx >= count)) return MORT_ORACLE_BATCH_BAD_ARGS;
+    }
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 64) nthreads = 64;
+    if (n < 4096) nthreads = 1;
+    shade_job_t jobs[64];
+    pthread_t th[64];
+    for (int t = 0; t < nthreads; t++) {
+        jobs[t] = (shade_job_t){w, t, nthreads, n, in, out, branch};
+        if (t > 0) pthread_create(&th[t], NULL, shade_job, &jobs[t]);
+    }
+    shade_job(&jobs[0]);
     for (int t = 1; t < nthreads; t++) pthread_join(th[t], NULL);
     return MORT_ORACLE_BATCH_OK;
 }

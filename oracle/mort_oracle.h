@@ -85,6 +85,13 @@ int mort_oracle_math_batch(int fn, const uint32_t *in, size_t n, uint32_t *out);
  * and computes nothing. */
 int mort_oracle_light_batch(const mort_world *w, int fn, const uint32_t *in, size_t n, uint32_t *out, int nthreads);
 
+/* one iteration of ray_color's loop body -- world::hit over [0.001, inf), then emission, scatter and the pdf mixture -- over n records of
+ * 32-bit words, the layout of mort_hip_debug_shade_shape (debug.hip): 16 words in, 22 out (mort_oracle.c has the fields).  ray_color runs
+ * the same function.  branch: NULL, or n words that name the branches each record took (material and texture tag, front face, the
+ * dielectric's decisions, which half of the mixture was sampled, a zero material pdf, a non-finite normal), for a census.  A light
+ * object outside the world's tables gives MORT_ORACLE_BATCH_BAD_ARGS and computes nothing. */
+int mort_oracle_shade_batch(const mort_world *w, const uint32_t *in, size_t n, uint32_t *out, uint32_t *branch, int nthreads);
+
 #ifdef __cplusplus
 }
 #endif

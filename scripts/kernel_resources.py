@@ -43,7 +43,7 @@ finally:
     shutil.rmtree(tmp, ignore_errors=True)
 bad = []
 print(f"{'kernel':58s} {'wg':>5s} {'vgpr':>5s} {'waves/SIMD':>10s} {'v-spill':>7s} {'s-spill':>7s} {'private B':>9s} {'static LDS':>10s}")
-OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_", "volume_", "math_kernel", "random_float_all_kernel")
+OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_", "volume_", "math_kernel", "light_kernel", "shade_kernel", "random_float_all_kernel")
 for r in sorted(rows, key=lambda r: r["name"]):
     if not any(o in r["name"] for o in OWN) and "--all" not in sys.argv:
         continue  # rocPRIM's sort kernels (tile_sort.hip): listed with --all

@@ -179,6 +179,41 @@ def light_batch(world, fn, records, nthreads=8):
     return out
 
 
+SHADE_SHAPE = (16, 22)  # mort_oracle_shade_batch: (in_words, out_words), the layout of debug.hip's shade table
+# the branch word of mort_oracle_shade_batch (mort_oracle.c SHADE_BR_*)
+BR_FRONT, BR_CANT_REFRACT, BR_REFLECTED, BR_REFRACTED, BR_FROM_LIGHT, BR_FROM_MATERIAL, BR_MAT_PDF_ZERO, BR_NORMAL_NONFINITE, BR_RATIO_ONE, BR_SKIP_PDF = \
+    (1 << k for k in range(16, 26))
+
+
+def br_tag(branch):
+    """the hit's material tag as decoded (-2: no hit; a large negative number: a tag outside -1 .. 252)"""
+    t = (np.asarray(branch) & 0xff).astype(np.int64)
+    return np.where(t == 255, -(1 << 40), t - 2)
+
+
+def br_tex(branch):
+    """the texture tag of the hit's material; -2 where the material has no texture"""
+    t = ((np.asarray(branch) >> 8) & 0xff).astype(np.int64)
+    return np.where(t == 255, -(1 << 40), t - 2)
+
+
+def shade_batch(world, records, nthreads=16):
+    """one iteration of ray_color's loop body over records of SHADE_SHAPE[0] words: ((n, 22) uint32 results, (n,) uint32 branch words)"""
+    iw, ow = SHADE_SHAPE
+    w = np.ascontiguousarray(records).reshape(-1).view(np.uint32)
+    assert w.size % iw == 0
+    n = w.size // iw
+    out = np.empty((n, ow), dtype=np.uint32)
+    branch = np.empty(n, dtype=np.uint32)
+    fn = lib().mort_oracle_shade_batch
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+    rc = fn(C.cast(world.ptr, C.c_void_p), w.ctypes.data, n, out.ctypes.data, branch.ctypes.data, nthreads)
+    if rc != 0:
+        raise OracleBatchError(rc, "mort_oracle_shade_batch")
+    return out, branch
+
+
 def texture_value_batch(world, tex_type, tex_idx, u, v, p):
     """texture value_dispatch for n points: tex_type / tex_idx / u / v (n,), p (n, 3) -> rgb (n, 3) float32."""
     p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)

@@ -325,6 +325,92 @@ def test_camera_rays_and_ray_color(ref):
     COUNTS["2b camera rays"] += n
 
 
+def _shade_cases():
+    from tests import shade_cases as SC
+    return [(w, s) for w in SC.WORLDS for s in SC.LIGHT_SETTINGS]
+
+
+def _undefined_int_conversion(world, rays7, streams):
+    """per ray: does the closest hit evaluate a texture whose (int)floorf(...) is out of int's range or a NaN?  The reference converts with a
+    plain cast (textures.cuh:54-56,183-185,347), which the device defines (saturation, NaN -> 0: mort_f2i, the oracle's form) and C++ on
+    the host leaves undefined: there the reference compiled for the CPU is not the reference.  True for a hit on a textured material at a
+    non-finite point, or on a checker whose 1 / scale carries every finite point out of range (scale 0, 1e-30 or NaN)."""
+    st = streams.copy()
+    h, hit = O.world_hit_batch(world, rays7, 0.001, np.inf, states=st)
+    m, t = world.c.mats, world.c.texs
+    tables = {S.MAT_LAMBERTIAN: m.host_lambertian, S.MAT_DIFFUSE_LIGHT: m.host_diffuse_light, S.MAT_ISOTROPIC: m.host_isotropic}
+    out = np.zeros(len(rays7), bool)
+    for i in np.flatnonzero(hit):
+        tab = tables.get(int(h["mat_type"][i]))
+        if tab is None:
+            continue
+        tex = tab[int(h["mat_idx"][i])]
+        wild = tex.texType == S.TEXTURE_CHECKER and not abs(t.host_checker_texture[tex.texIdx].inv_scale) < 1e6
+        out[i] = wild or not np.isfinite(h["p"][i]).all() or (tex.texType not in (S.TEXTURE_SOLID, S.TEXTURE_CHECKER, S.TEXTURE_NOISE) and not np.isfinite((h["u"][i], h["v"][i])).all())
+    return out
+
+
+@pytest.mark.parametrize("world_name,setting", _shade_cases())
+def test_shade_sweep_records_as_two_segment_paths(ref, world_name, setting):
+    """the records of the shade-step sweep (tests/shade_cases.py: edge refraction indices, fuzz and albedos, unknown tags, zero and negative
+    radii, rays at the critical angle, non-finite rays) as two-segment paths through the reference's own ray_color, bounce limit 2: colour
+    and final stream words against the oracle's ray_color, whose loop body is the function mort_oracle_shade_batch runs.  2048 records
+    of each of the nine (world, light setting) pairs, so that more than 2^14 are compared.  A path whose first or second hit converts a float outside int's range with a plain cast
+    (_undefined_int_conversion) is left out of the comparison: at least 85 % of the records remain."""
+    from tests import radiance_ref as RR
+    from tests import shade_cases as SC
+    from tests.query_rays import _words
+    sw = SC.shade_world(world_name)
+    rec, _ = SC.records(world_name, setting)
+    n = 2048
+    rec = np.array(rec[np.sort(np.random.default_rng(14).choice(len(rec), n, replace=False))])
+    rec[:, 13] = rec[:, 12]  # ray_color scatters with the time of the ray it is given
+    _, cam = host.build_scene(2, width=8, spp=1, depth=2)
+    cam.background.e[0], cam.background.e[1], cam.background.e[2] = 0.30, 0.35, 0.45
+    cam.light_obj_type, cam.light_obj_idx = sw.lights[setting]
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, :7] = rec[:, 6:13].view(np.float32); rays[:, 7] = np.inf
+    streams0 = np.zeros(n, O.STATE_DTYPE)
+    streams0["d"] = rec[:, 0]; streams0["v"] = rec[:, 1:6]
+    streams = streams0.copy()
+    want = RR.oracle_radiance(sw.world, cam, rays, streams, 1)
+    first, _ = O.shade_batch(sw.world, rec)
+    mid = np.zeros(n, O.STATE_DTYPE)
+    mid["d"] = first[:, 15]; mid["v"] = first[:, 16:21]
+    left_out = _undefined_int_conversion(sw.world, rays[:, :7], streams0) | \
+        ((first[:, 0] >= 2) & _undefined_int_conversion(sw.world, np.ascontiguousarray(first[:, 8:15].view(np.float32)), mid))
+    assert left_out.mean() <= 0.15, float(left_out.mean())
+    R.load(sw.world)
+    r7, cr, sr = (C.c_float * 7)(), (C.c_float * 3)(), S.RngState()
+    got = np.zeros((n, 3), np.float32)
+    for i in np.flatnonzero(~left_out):
+        r7[:] = rays[i, :7].tolist()
+        sr.d = int(rec[i, 0])
+        for k in range(5):
+            sr.v[k] = int(rec[i, 1 + k])
+        assert ref.mort_ref_ray_color(C.byref(cam), r7, sr, cr) == 0
+        got[i] = list(cr)
+        assert sr.d == streams["d"][i] and list(sr.v) == streams["v"][i].tolist(), (world_name, setting, i)
+    bad = np.flatnonzero((_words(got) != _words(want)).any(1) & ~left_out)
+    assert bad.size == 0, f"{world_name} {setting}: {bad.size} of {n} colours differ, first {bad[0]}: reference {got[bad[0]]} oracle {want[bad[0]]}"
+    COUNTS["2b shade sweep records"] += int((~left_out).sum())
+    COUNTS["2b of them left out: an int conversion C++ leaves undefined"] += int(left_out.sum())
+
+
+MATERIAL_PINS = [("ior_edges", "flat", 12), ("unknown_tags", "bvh", 12), ("mirror_hall", "bvh", 64)]
+
+
+@pytest.mark.parametrize("key", MATERIAL_PINS, ids=["-".join(map(str, k)) for k in MATERIAL_PINS])
+def test_material_worlds_render_as_the_reference(ref, key):
+    """three of MATERIAL_WORLDS (tests/material_worlds.py), small: the edge refraction indices, the tags outside the known set, and the
+    closed hall of mirrors at the bounce limit's maximum"""
+    from tests import material_worlds as M
+    cam = M.camera(key[0], key[2])
+    small = M._camera(dict(M.MATERIAL_WORLDS[key[0]], width=32), key[2])
+    assert small.image_width < cam.image_width
+    pin_render(M.material_world(key[0], key[1]), small, frames=1)
+
+
 # ---------------------------------------------------------------- c. the host scene layer: BVH build
 
 @pytest.mark.parametrize("hierarchy", [0, 1])
