@@ -850,6 +850,126 @@ extern "C" int mort_hip_debug_shade_device(mort_ctx *c, int fn, const uint32_t *
     return st;
 }
 
+/* ---- the two ends of Camera::render on a caller's records: dev_render.h's get_ray in both of its instantiations, and the pixel's finish.
+ * Records are 32-bit words:
+ *   fn 0 get_ray<RenderArgs> (the one-lane kernel, the wave mode's front, the host loop): in (30) the six XORWOW words (d, v0..v4), x, y,
+ *        s_i, s_j, recip_sqrt_spp, defocus_angle, center, pixel00, du, dv, defocus_u, defocus_v; out (14) origin[3], direction[3], time, the
+ *        six final words, the draw count;
+ *   fn 1 get_ray<CamView>, the same records: on the device a record's CamView is written into the workgroup's LDS (256 x 80 B) by the
+ *        NEIGHBOURING lane, and after a barrier get_ray reads the LDS copy, as mega_bvh.h and mega_gen.hip read theirs after theirs (the
+ *        build checks camera_kernel's 20480 B of static LDS: scripts/kernel_resources.py);
+ *   fn 2 pixel_finish and pixel_rgba: in (4) scale, sum[3]; out (4) the accumulator[3] and the uchar4, written as the pixel itself.
+ * camera_eval is the one body behind mort_hip_debug_camera_host (hipcc's host compile) and camera_kernel (the gfx950 compile);
+ * oracle/mort_oracle.c's mort_oracle_camera_batch is the oracle's get_ray and render_pixel's tail under the same numbers
+ * (tests/test_camera_host.py, tests/test_gpu_camera.py). ---- */
+static const MathShape CAMERA_SHAPES[] = {/* 0 get_ray<RenderArgs> */ {30, 14}, /* 1 get_ray<CamView> */ {30, 14}, /* 2 pixel finish */ {4, 4}};
+#define CAMERA_FUNCTIONS ((int)(sizeof CAMERA_SHAPES / sizeof CAMERA_SHAPES[0]))
+static_assert(sizeof(CamView) == 80, "CamView: 20 words");
+
+DEV void camera_put_ray(uint32_t *out, const Ray &r, const Rng &s) {
+    math_pv(out, 0, r.o); math_pv(out, 3, r.d); math_pf(out, 6, r.tm);
+    math_prng(out, 7, s);
+}
+
+/* the CamView of a record, for fn 1 */
+DEV void camera_view_fill(CamView &view, const uint32_t *in) {
+    view.recip_sqrt_spp = math_f(in, 10); view.defocus_angle = math_f(in, 11);
+    view.center = math_v(in, 12); view.pixel00 = math_v(in, 15); view.du = math_v(in, 18); view.dv = math_v(in, 21);
+    view.defocus_u = math_v(in, 24); view.defocus_v = math_v(in, 27);
+}
+
+/* `view` (fn 1 only): the record's CamView, filled before the call (camera_view_fill): in LDS on the device */
+static __host__ __device__ void camera_eval(int fn, const uint32_t *in, uint32_t *out, const CamView *view) {
+    if (fn == 2) {
+        const V3 c = pixel_finish(math_f(in, 0), math_v(in, 1));
+        math_pv(out, 0, c);
+        pixel_rgba(*reinterpret_cast<uchar4 *>(out + 3), c);
+        return;
+    }
+    Rng s = math_rng(in);
+    const int x = (int)in[6], y = (int)in[7], s_i = (int)in[8], s_j = (int)in[9];
+    if (fn == 0) {
+        RenderArgs a;
+        a.recip_sqrt_spp = math_f(in, 10); a.defocus_angle = math_f(in, 11);
+        a.center = math_v(in, 12); a.pixel00 = math_v(in, 15); a.du = math_v(in, 18); a.dv = math_v(in, 21);
+        a.defocus_u = math_v(in, 24); a.defocus_v = math_v(in, 27);
+        camera_put_ray(out, get_ray(a, x, y, s, s_i, s_j), s);
+    } else {
+        camera_put_ray(out, get_ray(*view, x, y, s, s_i, s_j), s);
+    }
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): the record shape of camera function fn in 32-bit words; MORT_ERR_INVALID
+ * past the last function */
+extern "C" int mort_hip_debug_camera_shape(int fn, int *in_words, int *out_words) {
+    if (fn < 0 || fn >= CAMERA_FUNCTIONS || !in_words || !out_words) return MORT_ERR_INVALID;
+    *in_words = CAMERA_SHAPES[fn].in; *out_words = CAMERA_SHAPES[fn].out;
+    return MORT_OK;
+}
+
+/* diagnostic (not in include/mort_hip.h; host only, no HIP call): camera function fn over n records, hipcc's host compile of camera_eval */
+extern "C" int mort_hip_debug_camera_host(int fn, const uint32_t *in, size_t n, uint32_t *out) {
+    if (fn < 0 || fn >= CAMERA_FUNCTIONS || ((!in || !out) && n)) return MORT_ERR_INVALID;
+    const size_t iw = CAMERA_SHAPES[fn].in, ow = CAMERA_SHAPES[fn].out;
+    unsigned nthreads = std::thread::hardware_concurrency();
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 16) nthreads = 16;
+    if (n < 4096) nthreads = 1;
+    auto work = [&](unsigned k) {
+        CamView view;
+        for (size_t i = n * k / nthreads, end = n * (k + 1) / nthreads; i < end; i++) {
+            if (fn == 1) camera_view_fill(view, in + i * iw);
+            camera_eval(fn, in + i * iw, out + i * ow, &view);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned k = 1; k < nthreads; k++) pool.emplace_back(work, k);
+    work(0);
+    for (std::thread &th : pool) th.join();
+    return MORT_OK;
+}
+
+/* one lane per record, grid-stride with the same trip count in every lane, so that the barriers are reached by all.  fn 1: lane t writes the
+ * CamView of its neighbour's record (lane t ^ 1 of the same workgroup: record i ^ 1) into slot t ^ 1 of the workgroup's LDS; after the
+ * barrier every lane hands get_ray the slot of its own record, which another lane wrote; the second barrier keeps the next trip's writes
+ * behind this trip's reads.  Results leave as raw words */
+static __global__ void __launch_bounds__(256) camera_kernel(int fn, int iw, int ow, const uint32_t *in, size_t n, uint32_t *out) {
+    __shared__ CamView s_view[256];
+    const size_t stride = (size_t)gridDim.x * 256;
+    const size_t trips = (n + stride - 1) / stride;
+    for (size_t k = 0; k < trips; k++) {
+        const size_t i = k * stride + (size_t)blockIdx.x * 256 + threadIdx.x, j = i ^ 1;
+        if (fn == 1 && j < n) camera_view_fill(s_view[threadIdx.x ^ 1], in + j * (size_t)iw);
+        __syncthreads();
+        if (i < n) camera_eval(fn, in + i * (size_t)iw, out + i * (size_t)ow, &s_view[threadIdx.x]);
+        __syncthreads();
+    }
+}
+
+/* diagnostic (not in include/mort_hip.h): one launch of camera_kernel on `device`: camera function fn over n records.  Writes n records
+ * to `out` and nothing after them. */
+extern "C" int mort_hip_debug_camera_device(int device, int fn, const uint32_t *in, size_t n, uint32_t *out) {
+    if (fn < 0 || fn >= CAMERA_FUNCTIONS || !in || !out || n == 0 || n > ((size_t)1 << 26)) return MORT_ERR_INVALID;
+    const size_t iw = CAMERA_SHAPES[fn].in, ow = CAMERA_SHAPES[fn].out;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    int st = MORT_OK;
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    if (hipMalloc((void **)&d_in, n * iw * 4) != hipSuccess || hipMalloc((void **)&d_out, n * ow * 4) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && hipMemcpy(d_in, in, n * iw * 4, hipMemcpyHostToDevice) != hipSuccess) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        const size_t blocks = (n + 255) / 256;
+        camera_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256)>>>(fn, (int)iw, (int)ow, d_in, n, d_out);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, n * ow * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+
 /* the device half of dev_math.h's sentence on random_float: random_float_of(curand_uniform_of(x)), dev_math.h's own two steps, against the
  * reference's (float)(1.0 - (double)u), for ALL 2^32 generator outputs x (every lane takes every 2^20-th) */
 static __global__ void __launch_bounds__(256) random_float_all_kernel(unsigned long long *out) {

@@ -515,7 +515,9 @@ static float degrees_to_radians(float degrees) { /* utils.h:21,25-27: float pi *
     const float pi = 3.1415926535897932385f;
     return (float)(degrees * pi / 180.0);
 }
-static float host_tanf(float x) { return (float)(mort_sin((double)x) / mort_cos((double)x)); }
+/* tan(+-0) is +-0 in every libm; mort_sin(-0.0) is +0 (include/mort_math.h), which would turn a defocus_angle of -0 into disk vectors of
+ * the opposite zero sign to the reference's */
+static float host_tanf(float x) { return x == 0 ? x : (float)(mort_sin((double)x) / mort_cos((double)x)); }
 
 void mort_camera_initialize(mort_camera *c);
 

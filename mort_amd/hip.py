@@ -1017,6 +1017,45 @@ def debug_shade_device(ctx, records, fnum=0, out=None):
     return _debug_shade("mort_hip_debug_shade_device", (ctx._h,), fnum, records, out)
 
 
+CAMERA_SHAPES = ((30, 14), (30, 14), (4, 4))  # mort_hip_debug_camera_shape: (in_words, out_words) of get_ray<RenderArgs>, get_ray<CamView>, the pixel finish
+
+
+def _debug_camera(name, lead, fnum, records, out):
+    if fnum not in (0, 1, 2):
+        raise MortHipError(-1, name, f"no camera function {fnum}")
+    iw, ow = CAMERA_SHAPES[fnum]
+    rec = np.ascontiguousarray(records)
+    if rec.dtype.itemsize != 4 or rec.size % iw:
+        raise MortHipError(-1, name, f"camera function {fnum} takes records of {iw} 32-bit words")
+    words = rec.reshape(-1).view(np.uint32)
+    n = words.size // iw
+    if out is None:
+        out = np.empty(n * ow, dtype=np.uint32)
+    if out.dtype != np.uint32 or not out.flags.c_contiguous or out.size < n * ow:
+        raise MortHipError(-1, name, f"out: {n * ow} contiguous uint32 words")
+    fn = getattr(lib(), name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * len(lead) + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    st = fn(*lead, fnum, words.ctypes.data, n, out.ctypes.data)
+    if st != 0:
+        raise MortHipError(st, name)
+    return out
+
+
+def debug_camera_host(fnum, records, out=None):
+    """mort_hip_debug_camera_host (host only): camera function `fnum` of debug.hip over records of 32-bit words, hipcc's host compile.
+    fnum 0 / 1: get_ray<RenderArgs> / get_ray<CamView> over (six XORWOW words, x, y, s_i, s_j, recip_sqrt_spp, defocus_angle, center,
+    pixel00, du, dv, defocus_u, defocus_v) -> origin[3], direction[3], time, the six final words, the draw count; fnum 2: pixel_finish and
+    pixel_rgba over (scale, sum[3]) -> the accumulator[3] and the uchar4 as one word.  Returns raw uint32 words (`out` if given)."""
+    return _debug_camera("mort_hip_debug_camera_host", (), fnum, records, out)
+
+
+def debug_camera_device(fnum, records, out=None, device=0):
+    """mort_hip_debug_camera_device: the same on `device`, one launch of camera_kernel (fnum 1: a record's CamView is written into LDS by the neighbouring lane and read by get_ray after a barrier); arguments and
+    result as debug_camera_host."""
+    return _debug_camera("mort_hip_debug_camera_device", (device,), fnum, records, out)
+
+
 def debug_random_float_device(device=0):
     """mort_hip_debug_random_float_device: random_float against (float)(1.0 - (double)u) for all 2^32 generator outputs on `device` --
     dict(differ, lowest, visited)."""

@@ -829,6 +829,20 @@ static ray get_ray(const mort_camera *cam, double u, double v, rng_t *g, int s_i
 
 static float clampf(float x, float mn, float mx) { if (x < mn) return mn; if (x > mx) return mx; return x; } /* utils.h:35-39 */
 
+/* the end of Camera::render (camera.cuh:194-207) on a pixel's sum: the mean with each NaN component 0 (returned: the accumulator), and
+ * its gamma-2, clamped, truncated bytes with alpha 255 into rgba4 */
+static vec3 pixel_tail(float pixel_samples_scale, vec3 pixel_color, uint8_t *rgba4) {
+    pixel_color = vscale(pixel_samples_scale, pixel_color);
+    for (int k = 0; k < 3; k++)
+        if (pixel_color.e[k] != pixel_color.e[k]) pixel_color.e[k] = 0.0f;
+    for (int k = 0; k < 3; k++) {
+        float gch = mort_sqrtf(pixel_color.e[k]);
+        rgba4[k] = (uint8_t)mort_f2i(256 * clampf(gch, 0.0f, 0.999f));
+    }
+    rgba4[3] = 255;
+    return pixel_color;
+}
+
 static void render_pixel(const mort_world *w, const mort_camera *cam, mort_rng_state *states, int x, int y,
                          uint8_t *rgba, float *accum, uint32_t *seg_px, uint64_t *segs, uint64_t *draws) {
     int offset = x + y * cam->image_width; /* camera.cuh:178-208 */
@@ -840,15 +854,8 @@ static void render_pixel(const mort_world *w, const mort_camera *cam, mort_rng_s
             ray r = get_ray(cam, x, y, &g, s_i, s_j);
             pixel_color = vadd(pixel_color, ray_color(&c, cam, &r));
         }
-    pixel_color = vscale(cam->pixel_samples_scale, pixel_color);
-    for (int k = 0; k < 3; k++)
-        if (pixel_color.e[k] != pixel_color.e[k]) pixel_color.e[k] = 0.0f;
+    pixel_color = pixel_tail(cam->pixel_samples_scale, pixel_color, rgba + 4 * (size_t)offset);
     if (accum) { accum[3 * offset] = pixel_color.e[0]; accum[3 * offset + 1] = pixel_color.e[1]; accum[3 * offset + 2] = pixel_color.e[2]; }
-    for (int k = 0; k < 3; k++) {
-        float gch = mort_sqrtf(pixel_color.e[k]);
-        rgba[4 * offset + k] = (uint8_t)mort_f2i(256 * clampf(gch, 0.0f, 0.999f));
-    }
-    rgba[4 * offset + 3] = 255;
     if (seg_px) seg_px[offset] = (uint32_t)c.segments;
     *segs += c.segments;
     *draws += g.draws;
@@ -1060,6 +1067,68 @@ int mort_oracle_shade_batch(const mort_world *w, const uint32_t *in, size_t n, u
         if (t > 0) pthread_create(&th[t], NULL, shade_job, &jobs[t]);
     }
     shade_job(&jobs[0]);
+    for (int t = 1; t < nthreads; t++) pthread_join(th[t], NULL);
+    return MORT_ORACLE_BATCH_OK;
+}
+
+/* the two ends of Camera::render over n records of 32-bit words, function numbers and record shapes as mort_hip_debug_camera_shape
+ * (mort_amd/csrc/hip/debug.hip).  fn 0 and fn 1 (one function here; the kernels have two instantiations), get_ray: in (30) the six stream
+ * words (d, v[0..4]), x, y, s_i, s_j, recip_sqrt_spp, defocus_angle, center, pixel00_loc, pixel_delta_u, pixel_delta_v, defocus_disk_u,
+ * defocus_disk_v; out (14) origin[3], direction[3], time, the six final words, the draw count.  fn 2, render_pixel's tail: in (4)
+ * pixel_samples_scale, the pixel's sum[3]; out (4) the accumulator[3] and the four bytes of the pixel as one word (red lowest). */
+typedef struct { int fn, tid, nthreads; size_t n; const uint32_t *in; uint32_t *out; } camera_job_t;
+static void *camera_job(void *arg) {
+    camera_job_t *j = arg;
+    const size_t iw = j->fn == 2 ? 4 : 30, ow = j->fn == 2 ? 4 : 14;
+    for (size_t i = j->n * (size_t)j->tid / (size_t)j->nthreads, end = j->n * ((size_t)j->tid + 1) / (size_t)j->nthreads; i < end; i++) {
+        const uint32_t *a = j->in + i * iw;
+        uint32_t *o = j->out + i * ow;
+        if (j->fn == 2) {
+            float f[4];
+            uint8_t px[4];
+            memcpy(f, a, sizeof f);
+            vec3 acc = pixel_tail(f[0], V(f[1], f[2], f[3]), px);
+            memcpy(o, acc.e, sizeof acc.e);
+            o[3] = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16) | ((uint32_t)px[3] << 24);
+        } else {
+            mort_rng_state st;
+            memset(&st, 0, sizeof st);
+            st.d = a[0];
+            for (int k = 0; k < 5; k++) st.v[k] = a[1 + k];
+            mort_camera cam;
+            memset(&cam, 0, sizeof cam);
+            float f[20];
+            memcpy(f, a + 10, sizeof f);
+            cam.recip_sqrt_spp = f[0];
+            cam.defocus_angle = f[1];
+            cam.center = V(f[2], f[3], f[4]);
+            cam.pixel00_loc = V(f[5], f[6], f[7]);
+            cam.pixel_delta_u = V(f[8], f[9], f[10]);
+            cam.pixel_delta_v = V(f[11], f[12], f[13]);
+            cam.defocus_disk_u = V(f[14], f[15], f[16]);
+            cam.defocus_disk_v = V(f[17], f[18], f[19]);
+            rng_t g = {&st, 0};
+            ray r = get_ray(&cam, (int)a[6], (int)a[7], &g, (int)a[8], (int)a[9]);
+            memcpy(o, &r, 7 * sizeof(float));
+            o[7] = st.d;
+            for (int k = 0; k < 5; k++) o[8 + k] = st.v[k];
+            o[13] = (uint32_t)g.draws;
+        }
+    }
+    return NULL;
+}
+int mort_oracle_camera_batch(int fn, const uint32_t *in, size_t n, uint32_t *out, int nthreads) {
+    if (fn < 0 || fn > 2 || ((!in || !out) && n)) return MORT_ORACLE_BATCH_BAD_ARGS;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 64) nthreads = 64;
+    if (n < 4096) nthreads = 1;
+    camera_job_t jobs[64];
+    pthread_t th[64];
+    for (int t = 0; t < nthreads; t++) {
+        jobs[t] = (camera_job_t){fn, t, nthreads, n, in, out};
+        if (t > 0) pthread_create(&th[t], NULL, camera_job, &jobs[t]);
+    }
+    camera_job(&jobs[0]);
     for (int t = 1; t < nthreads; t++) pthread_join(th[t], NULL);
     return MORT_ORACLE_BATCH_OK;
 }

@@ -92,6 +92,11 @@ int mort_oracle_light_batch(const mort_world *w, int fn, const uint32_t *in, siz
  * object outside the world's tables gives MORT_ORACLE_BATCH_BAD_ARGS and computes nothing. */
 int mort_oracle_shade_batch(const mort_world *w, const uint32_t *in, size_t n, uint32_t *out, uint32_t *branch, int nthreads);
 
+/* the two ends of Camera::render over n records of 32-bit words, the layouts of mort_hip_debug_camera_shape (debug.hip): fn 0 and fn 1
+ * get_ray (30 words in: the six stream words, x, y, s_i, s_j, recip_sqrt_spp, defocus_angle and the six camera vectors; 14 out: the ray,
+ * the six final words, the draw count), fn 2 the pixel's tail (scale, sum[3] -> accumulator[3], the pixel's four bytes as one word). */
+int mort_oracle_camera_batch(int fn, const uint32_t *in, size_t n, uint32_t *out, int nthreads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -288,6 +288,48 @@ void mort_ref_get_ray(const mort_camera *mc, int x, int y, int s_i, int s_j, mor
     ray_to(c.get_ray(x, y, reinterpret_cast<curandState *>(state), 0, s_i, s_j), ray7);
 }
 
+/* Camera::initialize (camera.cuh:47-84) on the camera's input fields; every field comes back */
+void mort_ref_camera_initialize(mort_camera *mc) {
+    Camera c = camera_from(mc);
+    c.initialize();
+    memcpy(mc, static_cast<const void *>(&c), sizeof c);
+}
+
+/* rotate_around (vec3.cuh:215-227) */
+void mort_ref_rotate_around(const float vec[3], const float axis[3], float theta, float out[3]) {
+    const vec3 r = rotate_around(vec3(vec[0], vec[1], vec[2]), vec3(axis[0], axis[1], axis[2]), theta);
+    memcpy(out, &r, 3 * sizeof(float));
+}
+
+/* One tick of mort.cu's input() (lines 51-90), which polls Win32 and cannot be compiled: its statements restated over the reference's
+ * own vec3 operators, rotate_around and initialize(), with the polls replaced by their results (keys: 1 W, 2 S, 4 A, 8 D). */
+void mort_ref_camera_input(mort_camera *mc, int keys, int mouseDeltaX, int mouseDeltaY, int left) {
+    Camera cam = camera_from(mc);
+    if (keys & 1) { cam.lookat += -(cam.w); cam.lookfrom += -(cam.w); }
+    if (keys & 2) { cam.lookat += cam.w; cam.lookfrom += cam.w; }
+    if (keys & 4) { cam.lookat += -(cam.u); cam.lookfrom += -(cam.u); }
+    if (keys & 8) { cam.lookat += cam.u; cam.lookfrom += cam.u; }
+    if (left) {
+        if (mouseDeltaX != 0) {
+            vec3 cam_direction = cam.lookat - cam.lookfrom;
+            vec3 rotated = rotate_around(cam_direction, cam.vup, -mouseDeltaX / 500.0);
+            cam.lookat = cam.lookfrom + rotated;
+        }
+        if (mouseDeltaY != 0) {
+            vec3 cam_direction = cam.lookat - cam.lookfrom;
+            vec3 rotated = rotate_around(cam_direction, cam.u, -mouseDeltaY / 500.0);
+            cam.lookat = cam.lookfrom + rotated;
+        }
+    }
+    cam.initialize();
+    memcpy(mc, static_cast<const void *>(&cam), sizeof cam);
+}
+
+/* the tan (fn 0), cos (1) and sin (2) of a float as this translation unit resolves them: the overloads initialize() and rotate_around call */
+float mort_ref_libm(int fn, float x) {
+    return fn == 0 ? tan(x) : fn == 1 ? cos(x) : sin(x);
+}
+
 /* Camera::ray_color for one ray of pixel (0, 0) */
 int mort_ref_ray_color(const mort_camera *mc, const float ray7[7], mort_rng_state *state, float rgb[3]) {
     if (!g_loaded || !camera_ok(mc)) return -1;

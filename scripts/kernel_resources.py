@@ -14,7 +14,9 @@ graph), waves per SIMD that allocation allows, spilled registers, private (scrat
     levels behind its LDS part: MORT_MAX_BOUNCE_LIMIT x 16 B and one 16-byte slot, 1040 B, or
   * a light-probe kernel (probe_sh_kernel), which runs the same path body, breaks that same rule, or
   * an irradiance-volume kernel (volume_*, the visible sampler among them) or the depth bake
-    (probe_depth_kernel, which runs the ray queries' search) spills or uses any private memory.
+    (probe_depth_kernel, which runs the ray queries' search) spills or uses any private memory, or
+  * the camera sweep's kernel (camera_kernel, debug.hip) does not hold its 256 CamViews in static LDS: its fn 1 exists to run
+    get_ray<CamView> on an LDS copy, as the megakernels do.
 """
 import os, re, subprocess, sys, tempfile, shutil
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
@@ -43,7 +45,7 @@ finally:
     shutil.rmtree(tmp, ignore_errors=True)
 bad = []
 print(f"{'kernel':58s} {'wg':>5s} {'vgpr':>5s} {'waves/SIMD':>10s} {'v-spill':>7s} {'s-spill':>7s} {'private B':>9s} {'static LDS':>10s}")
-OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_", "volume_", "math_kernel", "light_kernel", "shade_kernel", "random_float_all_kernel")
+OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_", "volume_", "math_kernel", "light_kernel", "shade_kernel", "camera_kernel", "random_float_all_kernel")
 for r in sorted(rows, key=lambda r: r["name"]):
     if not any(o in r["name"] for o in OWN) and "--all" not in sys.argv:
         continue  # rocPRIM's sort kernels (tile_sort.hip): listed with --all
@@ -67,6 +69,8 @@ for r in sorted(rows, key=lambda r: r["name"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the radiance body must not spill; 1040 B for the deep bounce levels)")
     if r["name"].startswith("volume_") and (r["vspill"] or r["private"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the volume kernels run without scratch)")
+    if r["name"].startswith("camera_kernel") and r["lds"] != 256 * 80:
+        bad.append(f"{r['name']}: {r['lds']} B of static LDS, not the 256 CamViews (20480 B) its get_ray<CamView> is to read: the compiler has removed the LDS round trip")
 if bad:
     print("\n".join("RESOURCE CHECK FAILED: " + b for b in bad), file=sys.stderr)
     sys.exit(1 if check else 0)

@@ -179,6 +179,26 @@ def light_batch(world, fn, records, nthreads=8):
     return out
 
 
+CAMERA_SHAPES = ((30, 14), (30, 14), (4, 4))  # mort_oracle_camera_batch: (in_words, out_words) of get_ray (fn 0 and 1) and the pixel's tail (fn 2)
+
+
+def camera_batch(fn, records, nthreads=16):
+    """get_ray (fn 0, 1) or render_pixel's tail (fn 2) over records of 32-bit words (CAMERA_SHAPES[fn][0] each, the layout of debug.hip's
+    camera table): the results as (n, out_words) uint32 words."""
+    iw, ow = CAMERA_SHAPES[fn]
+    w = np.ascontiguousarray(records).reshape(-1).view(np.uint32)
+    assert w.size % iw == 0
+    n = w.size // iw
+    out = np.empty((n, ow), dtype=np.uint32)
+    f = lib().mort_oracle_camera_batch
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+    rc = f(fn, w.ctypes.data, n, out.ctypes.data, nthreads)
+    if rc != 0:
+        raise OracleBatchError(rc, "mort_oracle_camera_batch")
+    return out
+
+
 SHADE_SHAPE = (16, 22)  # mort_oracle_shade_batch: (in_words, out_words), the layout of debug.hip's shade table
 # the branch word of mort_oracle_shade_batch (mort_oracle.c SHADE_BR_*)
 BR_FRONT, BR_CANT_REFRACT, BR_REFLECTED, BR_REFRACTED, BR_FROM_LIGHT, BR_FROM_MATERIAL, BR_MAT_PDF_ZERO, BR_NORMAL_NONFINITE, BR_RATIO_ONE, BR_SKIP_PDF = \

@@ -56,6 +56,10 @@ def lib(mode="pinned"):
         L.mort_ref_pdf_value.argtypes = [C.c_int, C.c_int, fp, fp]; L.mort_ref_pdf_value.restype = C.c_float
         L.mort_ref_light_random.argtypes = [C.c_int, C.c_int, fp, St, fp]; L.mort_ref_light_random.restype = C.c_int
         L.mort_ref_add_bvh.argtypes = [W, C.c_int, C.c_bool, C.c_int]; L.mort_ref_add_bvh.restype = C.c_int
+        L.mort_ref_camera_initialize.argtypes = [Cam]; L.mort_ref_camera_initialize.restype = None
+        L.mort_ref_rotate_around.argtypes = [fp, fp, C.c_float, fp]; L.mort_ref_rotate_around.restype = None
+        L.mort_ref_camera_input.argtypes = [Cam, C.c_int, C.c_int, C.c_int, C.c_int]; L.mort_ref_camera_input.restype = None
+        L.mort_ref_libm.argtypes = [C.c_int, C.c_float]; L.mort_ref_libm.restype = C.c_float
         _libs[mode] = L
     return _libs[mode]
 

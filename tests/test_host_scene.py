@@ -80,6 +80,63 @@ def test_camera_initialize_against_float64_math():
     np.testing.assert_allclose(cam.pixel_delta_v.tolist(), dv, rtol=2e-6, atol=1e-9)
     np.testing.assert_allclose(cam.pixel00_loc.tolist(), p00, rtol=2e-6)
     assert cam.pixel_delta_v.e[1] > 0  # row 0 is the bottom row
+    _float64_math_on_every_camera()
+
+
+def _float64_math_on_every_camera():
+    """the check of scene 1 above (rtol 2e-6 per component, atol 1e-9 on the deltas) over every camera of tests/camera_cases.py whose fields
+    are finite.  Every component checked is a sum of products -- a cross product's two, pixel00_loc's c - f w - (vw / 2) u - (vh / 2) v
+    + ... -- and fp32 rounds such a sum with an error proportional to the magnitude M of its terms, not to the sum: no fp32 evaluation,
+    the reference's included, meets a bound relative to a sum that cancels.  The bound is therefore 2e-6 x max(|sum|, M / 2): the check's
+    own wherever a component is at least half its terms, and about 8 ulp of M (the roundings of the terms, of the sums and of the unit
+    vectors they are formed from) where it cancels.  M of u = unit(vup x w) is (|vup_a w_b| + |vup_b w_a|) / |vup x w|; v = w x u inherits
+    u's error, so its M is |w_a| M(u_b) + |w_b| M(u_a); pixel00_loc's M adds the terms of its sum with these in place of |u| and |v|."""
+    from tests import camera_cases as CC
+    F, D = np.float32, np.float64
+    cams, fam = CC.cameras()
+    got = CC.initialized()
+    finite = np.ones(len(cams), bool)
+    for name in CC.FLOAT_FIELDS:
+        finite &= np.isfinite(got[name].reshape(len(cams), -1)).all(1)
+    finite &= (got["sqrt_spp"] > 0)
+    assert finite[fam["scenes"]].all() and finite.sum() >= 2500, int(finite.sum())
+    c = cams[finite]; g = got[finite]
+    lookfrom, lookat, vup = (c[k].astype(D) for k in ("lookfrom", "lookat", "vup"))
+    focus = c["focus_dist"].astype(D)[:, None]
+    W, H = g["image_width"].astype(D)[:, None], g["image_height"].astype(D)[:, None]
+    norm = lambda a: a / np.linalg.norm(a, axis=1)[:, None]
+    wv = norm(lookfrom - lookat)
+    u = norm(np.cross(vup, wv))
+    v = np.cross(wv, u)
+    theta = (c["vfov"].astype(F) * F(3.1415926535897932385)).astype(D) / 180.0      # degrees_to_radians is fp32 by definition (utils.h:21,25-27): near
+    h = np.tan(theta.astype(F).astype(D) / 2)[:, None]                              # 180 degrees tan magnifies that rounding far beyond any tolerance
+    vh = 2 * h * focus
+    vw = vh * (W / H)
+    du = vw * u / W
+    dv = vh * v / H
+    ul = lookfrom - focus * wv - vw * u / 2 - vh * v / 2
+    p00 = ul + 0.5 * (du + dv)
+    ia, ib = [1, 2, 0], [2, 0, 1]
+    Mu = (np.abs(vup[:, ia] * wv[:, ib]) + np.abs(vup[:, ib] * wv[:, ia])) / np.linalg.norm(np.cross(vup, wv), axis=1)[:, None]
+    Mv = np.abs(wv[:, ia]) * Mu[:, ib] + np.abs(wv[:, ib]) * Mu[:, ia]
+    Mdu, Mdv = vw / W * Mu, vh / H * Mv
+    S_terms = np.abs(lookfrom) + np.abs(focus * wv) + vw / 2 * Mu + vh / 2 * Mv + 0.5 * (Mdu + Mdv)
+    for name, want, M in (("pixel_delta_u", du, Mdu), ("pixel_delta_v", dv, Mdv)):
+        e = np.abs(g[name] - want)
+        bad = e > 1e-9 + 2e-6 * np.maximum(np.abs(want), M / 2)
+        assert not bad.any(), (name, int(bad.any(1).sum()), np.flatnonzero(finite)[np.flatnonzero(bad.any(1))[:5]])
+        assert not ((e > 1e-9 + 2e-6 * np.abs(want)) & (np.abs(want) >= M / 2)).any(), name   # the check's own bound wherever nothing cancels
+    tol = 2e-6 * np.maximum(np.abs(p00), S_terms / 2)
+    err = np.abs(g["pixel00_loc"] - p00)
+    bad = err > tol
+    strict = int((err > 2e-6 * np.abs(p00)).any(1).sum())
+    print(f"{int(finite.sum())} finite cameras; pixel00_loc components beyond 2e-6 of a cancelling sum itself: {strict} cameras; largest error / bound {float((err / np.maximum(tol, 1e-300)).max()):.3f}")
+    assert not bad.any(), (int(bad.any(1).sum()), np.flatnonzero(finite)[np.flatnonzero(bad.any(1))[:5]])
+    strict_bad = err > 2e-6 * np.abs(p00)
+    assert not (strict_bad & (np.abs(p00) >= S_terms / 2)).any()       # the check's own bound on every component that is at least half its terms:
+    assert strict <= len(c) // 50                                      # what exceeds it is confined to cancelling sums, and those stay few (measured: 46)
+    assert (g["sqrt_spp"] == np.floor(np.sqrt(c["samples_per_pixel"].astype(D)))).all()
+    assert (g["pixel_samples_scale"] == (1.0 / (g["sqrt_spp"].astype(D) ** 2)).astype(F)).all()
 
 
 def test_bvh_builder_invariants():

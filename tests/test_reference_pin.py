@@ -325,6 +325,78 @@ def test_camera_rays_and_ray_color(ref):
     COUNTS["2b camera rays"] += n
 
 
+def test_get_ray_records_as_the_reference(ref):
+    """2^12 of the camera sweep's get_ray records (tests/camera_cases.py: offsets of exactly 0 and 1, disk points on the unit circle, pixels
+    past 2^24, sqrt_spp of 0 and 32768, defocus angles of -0, inf and NaN, non-finite cameras) through the reference's own get_ray: the ray
+    and the stream it leaves equal the oracle's, bit for bit"""
+    from tests import camera_cases as CC
+    rec = CC.pin_ray_records()
+    want = O.camera_batch(0, rec)
+    got = np.zeros_like(want)
+    got[:, 13] = want[:, 13]  # the reference does not count its draws: the stream words tell
+    cam, st, r7 = S.Camera(), S.RngState(), (C.c_float * 7)()
+    f = rec[:, 10:].view(np.float32)
+    for i in range(len(rec)):
+        st.d = int(rec[i, 0])
+        for k in range(5):
+            st.v[k] = int(rec[i, 1 + k])
+        cam.recip_sqrt_spp, cam.defocus_angle = f[i, 0], f[i, 1]
+        for j, name in enumerate(("center", "pixel00_loc", "pixel_delta_u", "pixel_delta_v", "defocus_disk_u", "defocus_disk_v")):
+            getattr(cam, name).e[:] = f[i, 2 + 3 * j: 5 + 3 * j].tolist()
+        x, y, s_i, s_j = (int(v) for v in rec[i, 6:10].view(np.int32))
+        ref.mort_ref_get_ray(C.byref(cam), x, y, s_i, s_j, st, r7)
+        got[i, 0:7] = np.array(list(r7), np.float32).view(np.uint32)
+        got[i, 7] = st.d
+        got[i, 8:13] = list(st.v)
+    cen = CC.ray_census(rec, want)
+    assert min(cen["no_disk"], cen["accepted_first"], cen["rejected_once"], cen["rejected_more"]) >= 50 and cen["nonfinite"] >= 40, cen
+    assert min(cen["px_zero"], cen["px_one"], cen["py_zero"], cen["py_one"]) >= 1, cen
+    CC.assert_same(0, rec, dict(oracle=want, reference=got))
+    COUNTS["2b get_ray records"] += len(rec)
+
+
+def test_pixel_tail_records_as_the_reference(ref):
+    """The end of Camera::render is not callable alone: 1 x 1 frames of an empty world, whose every sample returns the background, hand it
+    sqrt_spp^2 x background.  2048 cases (tests/camera_cases.py pin_pixel_cases) with sqrt_spp in 1, 2, 3; a case is kept where the fp32
+    additions of the background reproduce the intended sum exactly, which at least half must; the kept ones equal the oracle's tail over
+    (pixel_samples_scale, sum): the uchar4 of the reference's own render, and the accumulator."""
+    from tests import camera_cases as CC
+    rows = CC.pin_pixel_cases()
+    empty = host.World()
+    R.load(empty)
+    _, cam = host.build_scene(2, width=1, spp=1, aspect=1.0)
+    assert cam.image_width == 1 and cam.image_height == 1
+    rec = np.zeros((len(rows), 4), np.float32)
+    got = np.zeros((len(rows), 4), np.uint32)
+    keep = np.zeros(len(rows), bool)
+    rgba, accum = np.zeros(4, np.uint8), np.zeros(3, np.float32)
+    with np.errstate(all="ignore"):
+        for i, (n, *b) in enumerate(rows):
+            n = int(n)
+            b = np.array(b, np.float32)
+            total = np.zeros(3, np.float32)
+            for _ in range(n * n):
+                total = total + b
+            intended = (b.astype(np.float64) * (n * n)).astype(np.float32)
+            keep[i] = bool(((total.view(np.uint32) == intended.view(np.uint32)) & ((b.astype(np.float64) * (n * n)) == intended)).all())
+            cam.samples_per_pixel = n * n
+            host.lib().mort_camera_initialize(C.byref(cam))
+            cam.background.e[:] = b.tolist()
+            rec[i, 0] = cam.pixel_samples_scale
+            rec[i, 1:4] = total
+            st = O.seed_states(S.DEFAULT_SEED, 1, 1)
+            assert ref.mort_ref_render(C.byref(cam), st.ctypes.data, 0, 1, rgba.ctypes.data, accum.ctypes.data, 1) == 0
+            got[i, 0:3] = accum.view(np.uint32)
+            got[i, 3] = rgba.view(np.uint32)[0]
+    assert keep.sum() * 2 >= len(rows), int(keep.sum())
+    rec, got = rec[keep], got[keep]
+    want = O.camera_batch(2, rec.view(np.uint32))
+    prod = rec[:, 0:1] * rec[:, 1:4]
+    assert (prod < 0).any() and (prod == np.float32(-0.5)).any() and np.isinf(prod).any() and len(np.unique(want[:, 3] & 0xff)) >= 200
+    CC.assert_same(2, rec.view(np.uint32), dict(oracle=want, reference=got))
+    COUNTS["2b pixel tails"] += len(rec)
+
+
 def _shade_cases():
     from tests import shade_cases as SC
     return [(w, s) for w in SC.WORLDS for s in SC.LIGHT_SETTINGS]
