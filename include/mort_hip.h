@@ -585,6 +585,51 @@ int mort_hip_volume_sample_visible_host(const mort_volume_grid *grid, const floa
                                         const mort_volume_vis_params *params, size_t n, const void *points, size_t stride, int nthreads,
                                         float *out, double *seconds);
 
+/* ---- cached radiance queries: paths that end in an irradiance volume.  The final-gather use of a probe grid: a
+ * path runs its first K = cache_depth bounces as a radiance query runs them, and at the first Lambertian surface after that it
+ * returns albedo * E(p, n) / pi from the volume instead of tracing on.
+ *
+ * The calls take the radiance queries' arguments (rays, streams advanced in place, rgb_out 3 n), and in addition `records`
+ * (MORT_VOLUME_RECORD_FLOATS per probe of params->grid, as mort_hip_volume_pack* writes them), `depth` (MORT_DEPTH_FLOATS per
+ * probe: required with MORT_CACHED_VISIBLE, NULL without) and an optional ends_out (n words or NULL): per ray, how many of its
+ * `samples` paths ended in the volume.
+ *
+ * The path is the radiance query's with one addition.  At iteration `iter` of a path (0 = the caller's ray's own hit), when the
+ * segment's search has found a hit and before its emission or scatter is evaluated:
+ *   1. if iter >= K and the hit's material tag is MORT_MAT_LAMBERTIAN (isotropic, metal, dielectric, lights and unknown tags
+ *      never), the volume is sampled at the hit's point and its facing normal, by mort_hip_volume_sample*'s arithmetic, or with
+ *      MORT_CACHED_VISIBLE by mort_hip_volume_sample_visible*'s under params->vis, word for word;
+ *   2. if the returned weight sum is > 0 the path ends here: its final value per channel is (albedo_c * E_c) * INV_PI, albedo the
+ *      material's texture value at the hit, INV_PI = (float)(1.0 / 3.14159265358979323846); no random number is drawn for this hit
+ *      and the ray's count goes up by one; the unwind and the sum over the samples are the radiance query's;
+ *   3. otherwise (a weight sum of 0 or NaN: no probe contributes) the iteration goes on exactly as in a radiance query.
+ * Everything else is the radiance queries': the reach test per origin, the media after the solids with their draws, the bounce
+ * limit, no NaN guard (a NaN coefficient reaches the colour).  So with K >= bounce_limit, or with every weight 0, the call is a
+ * radiance query to the bit, streams included.
+ *
+ * Forms, `seconds`, n == 0, alignment (the _device form: every buffer 16 bytes) and overlap as for the radiance queries; the
+ * streams and the counts are outputs, the records and maps inputs.  The radiance calls' checks apply to params->path and the
+ * volume calls' to params->grid and, with the flag, params->vis.  cache_depth outside 0..MORT_MAX_BOUNCE_LIMIT, an unknown flag
+ * bit, a NULL records, and depth present without MORT_CACHED_VISIBLE or absent with it are MORT_ERR_INVALID. ---- */
+#define MORT_CACHED_VISIBLE 1u
+typedef struct mort_cached_params {
+    mort_radiance_params path;  /* bounce limit, samples, background, light object: as a radiance query */
+    int32_t cache_depth;        /* K, 0 .. MORT_MAX_BOUNCE_LIMIT */
+    uint32_t flags;             /* 0 or MORT_CACHED_VISIBLE */
+    mort_volume_grid grid;
+    mort_volume_vis_params vis; /* read only with MORT_CACHED_VISIBLE */
+} mort_cached_params;
+MORT_SA(sizeof(mort_cached_params) == 84, "cached radiance query layout");
+int mort_hip_query_radiance_cached(mort_ctx *ctx, const mort_cached_params *params, size_t n, const mort_ray *rays, mort_rng_state *states,
+                                   const float *records, const float *depth /* or NULL */, float *rgb_out, uint32_t *ends_out /* n or NULL */,
+                                   double *seconds);
+int mort_hip_query_radiance_cached_device(mort_ctx *ctx, const mort_cached_params *params, size_t n, const void *d_rays, void *d_states,
+                                          const void *d_records, const void *d_depth, void *d_rgb_out, void *d_ends_out, void *stream,
+                                          double *seconds);
+int mort_hip_query_radiance_cached_host(const mort_world *world, const mort_cached_params *params, size_t n, const mort_ray *rays,
+                                        mort_rng_state *states, const float *records, const float *depth, int nthreads, int flags,
+                                        float *rgb_out, uint32_t *ends_out, double *seconds);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

@@ -18,6 +18,8 @@
  *                   [--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]]   no render: an irradiance volume over the box, sampled at
  *                                                          --pick X,Y (one JSON line) or at every pixel (--irradiance-out FILE)
  *                   [--visibility BIAS[,MINVIS[,S]]]      with --sh-volume: depth maps per probe and the visibility-weighted sampler
+ *                   [--cache-depth K]                     with --sh-volume: paths that end in the volume from bounce K on, along
+ *                                                          --probe X,Y[,N] (one JSON line) or every pixel's ray (--radiance-out FILE)
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -72,6 +74,15 @@
  * line gains normal_bias, min_visibility, depth_subsamples and max_distance, --irradiance-out's the same.  Without the
  * option every byte of the output is what it was.
  *
+ * --cache-depth K (with --sh-volume only, and then with --probe or --radiance-out instead of --pick / --irradiance-out): the
+ * volume is baked as above (with --visibility its depth maps too) and used inside the path: a cached radiance
+ * query (mort_hip_query_radiance_cached, or its _host form) with cache_depth = K in 0..MORT_MAX_BOUNCE_LIMIT and the scene
+ * camera's parameters.  With --probe X,Y[,N]: --probe's ray, stream and N paths; one JSON line, --probe's fields plus
+ * cache_depth, ends (how many of the N paths ended in the volume) and the volume's parameters.  With --radiance-out FILE: every
+ * pixel's --pick ray gets N = --spp paths (default 1) from that pixel's stream (subsequence X + Y * W of --seed), and
+ * sqrt(clamp(sum / N, 0, 1)), NaN as 0, is written as an 8-bit PPM.  That is a PREVIEW from pixel-centre rays (no jitter, no lens,
+ * time 0.5), not a render.  Without --cache-depth every accepted and refused combination and every output byte is what it was.
+ *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
  * RCCL (`--gather rccl`, the default: xGMI inside a node), or through a shared host mapping (`--gather shm`: for ranks
@@ -116,7 +127,10 @@ static int usage(void) {
            "[--mode mega|wave|host|throughput] [--threads T] [--tree] [--gpus N] [--devices a,b,..] [--gather rccl|shm] "
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
            "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
-           "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]]\n");
+           "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]] "
+           "[--cache-depth K] [--radiance-out FILE]\n"
+           "  --cache-depth K with --sh-volume: paths end in the volume from bounce K on; --probe X,Y[,N] prints one pixel's colour,\n"
+           "  --radiance-out FILE writes a preview from pixel-centre rays (--spp paths each; no jitter, no lens), not a render\n");
     return -1;
 }
 
@@ -198,6 +212,8 @@ int main(int argc, char **argv) {
     const char *irr_out = NULL;
     int visibility = 0, vis_s = 2;
     float vis_bias = 0.0f, vis_min = 0.05f;
+    int cached = 0, cache_depth = 0;
+    const char *rad_out = NULL;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -251,6 +267,8 @@ int main(int argc, char **argv) {
             visibility = 1;
             if (sscanf(argv[++i], "%f,%f,%d", &vis_bias, &vis_min, &vis_s) < 1) { fprintf(stderr, "--visibility BIAS[,MINVIS[,S]]\n"); return -1; }
         }
+        else if (ARG("--cache-depth")) { cached = 1; if (sscanf(argv[++i], "%d", &cache_depth) != 1) { fprintf(stderr, "--cache-depth K\n"); return -1; } }
+        else if (ARG("--radiance-out")) rad_out = argv[++i];
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -265,9 +283,15 @@ int main(int argc, char **argv) {
     if (probe && (gpus > 1 || pick)) { fprintf(stderr, "--probe is a single-GPU option and excludes --pick\n"); return -1; }
     if (sh_probe && (gpus > 1 || pick || probe)) { fprintf(stderr, "--sh-probe is a single-GPU option and excludes --pick and --probe\n"); return -1; }
     if (sh_probe && (sh_d < 64 || sh_d > 4096 || sh_d % 64)) { fprintf(stderr, "--sh-probe: D is a multiple of 64 in 64..4096\n"); return -1; }
-    if (sh_volume && (gpus > 1 || probe || sh_probe)) { fprintf(stderr, "--sh-volume is a single-GPU option and excludes --probe and --sh-probe\n"); return -1; }
+    if (cached && !sh_volume) { fprintf(stderr, "--cache-depth needs --sh-volume\n"); return -1; }
+    if (rad_out && !cached) { fprintf(stderr, "--radiance-out needs --cache-depth\n"); return -1; }
+    if (cached && (cache_depth < 0 || cache_depth > MORT_MAX_BOUNCE_LIMIT)) { fprintf(stderr, "--cache-depth: K in 0..%d\n", MORT_MAX_BOUNCE_LIMIT); return -1; }
+    if (cached && (pick || irr_out || !probe == !rad_out)) {
+        fprintf(stderr, "--cache-depth needs --probe X,Y[,N] or --radiance-out FILE, not both, and excludes --pick and --irradiance-out\n"); return -1;
+    }
+    if (sh_volume && (gpus > 1 || (probe && !cached) || sh_probe)) { fprintf(stderr, "--sh-volume is a single-GPU option and excludes --probe and --sh-probe\n"); return -1; }
     if (sh_volume && (sh_d < 64 || sh_d > 4096 || sh_d % 64)) { fprintf(stderr, "--sh-volume: D is a multiple of 64 in 64..4096\n"); return -1; }
-    if (sh_volume && !pick == !irr_out) { fprintf(stderr, "--sh-volume needs --pick X,Y or --irradiance-out FILE, not both\n"); return -1; }
+    if (sh_volume && !cached && !pick == !irr_out) { fprintf(stderr, "--sh-volume needs --pick X,Y or --irradiance-out FILE, not both\n"); return -1; }
     if (visibility && !sh_volume) { fprintf(stderr, "--visibility needs --sh-volume\n"); return -1; }
     if (visibility && (!(vis_bias >= 0.0f) || vis_bias - vis_bias != 0.0f || !(vis_min >= 0.0f) || !(vis_min <= 1.0f) || vis_s < 1 || vis_s > MORT_DEPTH_RES)) {
         fprintf(stderr, "--visibility: BIAS finite and >= 0, MINVIS in 0..1, S in 1..%d\n", MORT_DEPTH_RES); return -1;
@@ -303,6 +327,7 @@ int main(int argc, char **argv) {
 
     if (sh_volume) { /* ---- no render: bake a grid of probes, pack it, sample it at the hits of --pick's rays ---- */
         if (pick && (pick_x < 0 || pick_x >= W || pick_y < 0 || pick_y >= H)) { fprintf(stderr, "--pick %d,%d is outside the %dx%d image\n", pick_x, pick_y, W, H); return -1; }
+        if (probe && (probe_x < 0 || probe_x >= W || probe_y < 0 || probe_y >= H)) { fprintf(stderr, "--probe %d,%d is outside the %dx%d image\n", probe_x, probe_y, W, H); return -1; }
         mort_volume_grid grid;
         for (int k = 0; k < 3; k++) {
             grid.origin[k] = vol_box[k];
@@ -315,7 +340,7 @@ int main(int argc, char **argv) {
             if (grid.count[k] < 1 || grid.count[k] > MORT_VOLUME_MAX_COUNT || !(grid.spacing[k] > 0.0f) || grid.spacing[k] - grid.spacing[k] != 0.0f ||
                 grid.origin[k] - grid.origin[k] != 0.0f) { fprintf(stderr, "--sh-volume: a box with X1 > X0 (or one probe) per axis and 1..%d probes per axis\n", MORT_VOLUME_MAX_COUNT); return -1; }
         const size_t probes_n = (size_t)grid.count[0] * (size_t)grid.count[1] * (size_t)grid.count[2];
-        const size_t nq = pick ? 1 : npx;
+        const size_t nq = (pick || probe) ? 1 : npx;
         mort_probe_params pp;
         mort_hip_radiance_params_from_camera(&cam, &pp.rp);
         pp.rp.samples = sh_n;
@@ -338,16 +363,39 @@ int main(int argc, char **argv) {
         if (!probes || !states || !sh || !records || !rays || !hits || !irr || probes_n * (size_t)sh_d > 0x7fffffffu) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
         if ((pst = mort_hip_volume_probes(&grid, probes)) != MORT_OK) die(NULL, pst, "mort_hip_volume_probes");
         if ((pst = mort_hip_rng_seed_host(seed, (int)(probes_n * (size_t)sh_d), 1, states)) != MORT_OK) die(NULL, pst, "mort_hip_rng_seed_host");
+        /* --cache-depth: the volume inside the path.  The query's parameters, one pixel stream per ray, the colours and the counts */
+        mort_cached_params cp;
+        memset(&cp, 0, sizeof cp);
+        mort_hip_radiance_params_from_camera(&cam, &cp.path);
+        cp.path.samples = probe ? probe_n : (spp > 0 ? spp : 1);
+        cp.cache_depth = cache_depth; cp.flags = visibility ? MORT_CACHED_VISIBLE : 0u; cp.grid = grid; cp.vis = vp;
+        mort_rng_state *qstates = NULL;
+        float *rgb = NULL;
+        uint32_t *ends = NULL;
+        if (cached) {
+            mort_rng_state *pixels = (mort_rng_state *)malloc(npx * sizeof *pixels); /* the run's pixel streams */
+            qstates = (mort_rng_state *)malloc(nq * sizeof *qstates);
+            rgb = (float *)malloc(nq * 3 * sizeof *rgb);
+            ends = (uint32_t *)malloc(nq * sizeof *ends);
+            if (!pixels || !qstates || !rgb || !ends) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+            if ((pst = mort_hip_rng_seed_host(seed, W, H, pixels)) != MORT_OK) die(NULL, pst, "mort_hip_rng_seed_host");
+            if (probe) qstates[0] = pixels[(size_t)probe_x + (size_t)probe_y * W];
+            else memcpy(qstates, pixels, npx * sizeof *pixels);
+            free(pixels);
+        }
         if (pick) rays[0] = pick_ray(&cam, pick_x, pick_y);
+        else if (probe) rays[0] = pick_ray(&cam, probe_x, probe_y);
         else for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) rays[(size_t)y * W + x] = pick_ray(&cam, x, y);
         double sec = 0, bake_sec = 0, sample_sec = 0;
         if (host_mode) {
             const int fl = tree ? MORT_HOST_TREE : 0;
             if ((pst = mort_hip_probe_bake_host(&world, &pp, probes_n, probes, NULL, states, threads, fl, sh, &bake_sec)) != MORT_OK) die(NULL, pst, "mort_hip_probe_bake_host");
             if ((pst = mort_hip_volume_pack_host(probes_n, sh, NULL, threads, records, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_volume_pack_host");
-            if ((pst = mort_hip_query_closest_host(&world, nq, rays, NULL, threads, fl, hits, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_closest_host");
-            if (visibility) {
-                if ((pst = mort_hip_probe_depth_bake_host(&world, &dp, probes_n, probes, threads, fl, depth, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_probe_depth_bake_host");
+            if (!cached && (pst = mort_hip_query_closest_host(&world, nq, rays, NULL, threads, fl, hits, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_closest_host");
+            if (visibility && (pst = mort_hip_probe_depth_bake_host(&world, &dp, probes_n, probes, threads, fl, depth, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_probe_depth_bake_host");
+            if (cached) {
+                if ((pst = mort_hip_query_radiance_cached_host(&world, &cp, nq, rays, qstates, records, depth, threads, fl, rgb, ends, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_radiance_cached_host");
+            } else if (visibility) {
                 if ((pst = mort_hip_volume_sample_visible_host(&grid, records, depth, &vp, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_visible_host");
             } else
             if ((pst = mort_hip_volume_sample_host(&grid, records, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_host");
@@ -357,14 +405,52 @@ int main(int argc, char **argv) {
             if ((pst = mort_hip_upload_world(pctx, &world)) != MORT_OK) die(pctx, pst, "mort_hip_upload_world");
             if ((pst = mort_hip_probe_bake(pctx, &pp, probes_n, probes, NULL, states, sh, &bake_sec)) != MORT_OK) die(pctx, pst, "mort_hip_probe_bake");
             if ((pst = mort_hip_volume_pack(pctx, probes_n, sh, NULL, records, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_volume_pack");
-            if ((pst = mort_hip_query_closest(pctx, nq, rays, NULL, hits, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_closest");
-            if (visibility) {
-                if ((pst = mort_hip_probe_depth_bake(pctx, &dp, probes_n, probes, depth, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_probe_depth_bake");
+            if (!cached && (pst = mort_hip_query_closest(pctx, nq, rays, NULL, hits, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_closest");
+            if (visibility && (pst = mort_hip_probe_depth_bake(pctx, &dp, probes_n, probes, depth, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_probe_depth_bake");
+            if (cached) {
+                if ((pst = mort_hip_query_radiance_cached(pctx, &cp, nq, rays, qstates, records, depth, rgb, ends, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_radiance_cached");
+            } else if (visibility) {
                 if ((pst = mort_hip_volume_sample_visible(pctx, &grid, records, depth, &vp, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample_visible");
             } else
             if ((pst = mort_hip_volume_sample(pctx, &grid, records, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample");
             mort_hip_shutdown(pctx);
         }
+        if (cached) {
+            if (probe) {
+                printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"probe\": [%d, %d], \"samples\": %d", scene, W, H, probe_x, probe_y, probe_n);
+                print_v3("origin", rays[0].origin); print_v3("dir", rays[0].dir);
+                printf(", \"time\": "); print_f32(rays[0].time);
+                print_v3("rgb", rgb);
+                printf(", \"cache_depth\": %d, \"ends\": %u", cache_depth, (unsigned)ends[0]);
+            } else {
+                uint8_t *img = (uint8_t *)malloc(npx * 4);
+                if (!img) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+                const float paths = (float)cp.path.samples;
+                unsigned long long ended = 0;
+                for (size_t i = 0; i < npx; i++) {
+                    for (int ch = 0; ch < 3; ch++) {
+                        float v = rgb[3 * i + ch] / paths;
+                        v = (v > 0.0f) ? v : 0.0f; /* NaN goes to 0 */
+                        v = (v < 1.0f) ? v : 1.0f;
+                        img[4 * i + ch] = (uint8_t)(255.0f * sqrtf(v) + 0.5f);
+                    }
+                    img[4 * i + 3] = 255;
+                    ended += ends[i];
+                }
+                if (mort_write_ppm(rad_out, img, W, H) != 0) { fprintf(stderr, "cannot write %s\n", rad_out); return EXIT_FAILURE; }
+                free(img);
+                printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"radiance_out\": \"%s\", \"samples\": %d, \"cache_depth\": %d, \"ends\": %llu", scene, W, H,
+                       rad_out, cp.path.samples, cache_depth, ended);
+            }
+            if (visibility) {
+                printf(", \"normal_bias\": "); print_f32(vp.normal_bias);
+                printf(", \"min_visibility\": "); print_f32(vp.min_visibility);
+                printf(", \"depth_subsamples\": %d, \"max_distance\": ", dp.subsamples); print_f32(dp.max_distance);
+            }
+            printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"probe_samples\": %d, \"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f}\n",
+                   (int)grid.count[0], (int)grid.count[1], (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec);
+            free(qstates); free(rgb); free(ends);
+        } else {
         for (size_t i = 0; i < nq; i++) /* a miss is an all-zero record: its sample means nothing */
             if (!(hits[i].flags & MORT_HIT_HIT)) irr[4 * i] = irr[4 * i + 1] = irr[4 * i + 2] = irr[4 * i + 3] = 0.0f;
         if (pick) {
@@ -409,6 +495,7 @@ int main(int argc, char **argv) {
                 printf(", \"depth_subsamples\": %d, \"max_distance\": ", dp.subsamples); print_f32(dp.max_distance);
             }
             printf("}\n");
+        }
         }
         free(probes); free(states); free(sh); free(records); free(rays); free(hits); free(irr); free(depth);
         mort_world_free(&world);

@@ -45,6 +45,14 @@ bool mort_denoise_params_ok(const mort_denoise_params *p);
 bool mort_temporal_params_ok(const mort_temporal_params *p);
 bool mort_svgf_params_ok(const mort_svgf_params *p);
 
+/* radiance.hip, volume.hip: the checks and the launch parameters of the radiance and volume calls, for the cached radiance queries
+ * (cached.hip) */
+struct RadianceArgs;
+int mort_radiance_check(const mort_radiance_params *p, size_t n, const void *rays, void *states, void *rgb);
+void mort_radiance_args_params(RadianceArgs &a, const mort_radiance_params *p);
+bool mort_volume_grid_ok(const mort_volume_grid *g);
+bool mort_volume_vis_params_ok(const mort_volume_vis_params *p);
+
 /* view.hip: mort_hip_shutdown frees the views still alive on the context */
 void mort_views_free(mort_ctx *c);
 

@@ -1,7 +1,7 @@
 /*
- * query_common.h -- host scaffolding that the ray queries (query.hip) and the radiance queries (radiance.hip) share: the one
- * workgroup shape and its limits, the alignment the _device forms ask for, and the launch arguments over the context's scene.
- * The per-ray bodies are in dev_query.h and dev_radiance.h.
+ * query_common.h -- host scaffolding that the ray queries (query.hip), the radiance queries (radiance.hip) and the cached radiance
+ * queries (cached.hip) share: the one workgroup shape and its limits, the alignment the _device forms ask for, and the launch
+ * arguments over the context's scene.  The per-ray bodies are in dev_query.h, dev_radiance.h and dev_cached.h.
  */
 #ifndef MORT_QUERY_COMMON_H
 #define MORT_QUERY_COMMON_H

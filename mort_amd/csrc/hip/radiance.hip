@@ -85,6 +85,9 @@ int radiance_check(const mort_radiance_params *p, size_t n, const void *rays, vo
 
 } // namespace
 
+int mort_radiance_check(const mort_radiance_params *p, size_t n, const void *rays, void *states, void *rgb) { return radiance_check(p, n, rays, states, rgb); }
+void mort_radiance_args_params(RadianceArgs &a, const mort_radiance_params *p) { radiance_args_params(a, p); }
+
 /* for the tests: the bounce-stack levels the kernels keep in LDS; needs no device */
 extern "C" int mort_hip_debug_radiance_lds_levels(void) { return MORT_RADIANCE_LDS_LEVELS; }
 

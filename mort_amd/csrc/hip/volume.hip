@@ -89,14 +89,18 @@ int sample_check(const mort_volume_grid *g, const void *records, size_t n, const
     return buffers_disjoint(ins, in_bytes, 2, outs, out_bytes, 1) ? MORT_OK : MORT_ERR_INVALID;
 }
 
+bool vis_params_ok(const mort_volume_vis_params *vp) {
+    if (!std::isfinite(vp->normal_bias) || !(vp->normal_bias >= 0.0f)) return false;
+    return std::isfinite(vp->min_visibility) && vp->min_visibility >= 0.0f && vp->min_visibility <= 1.0f;
+}
+
 /* what the three visible forms check on top of that */
 int visible_check(const mort_volume_grid *g, const void *records, const void *depth, const mort_volume_vis_params *vp, size_t n, const void *points,
                   size_t stride, void *out, size_t *span) {
     if (!depth || !vp) return MORT_ERR_INVALID;
     const int st = sample_check(g, records, n, points, stride, out, span);
     if (st != MORT_OK) return st;
-    if (!std::isfinite(vp->normal_bias) || !(vp->normal_bias >= 0.0f)) return MORT_ERR_INVALID;
-    if (!std::isfinite(vp->min_visibility) || !(vp->min_visibility >= 0.0f) || !(vp->min_visibility <= 1.0f)) return MORT_ERR_INVALID;
+    if (!vis_params_ok(vp)) return MORT_ERR_INVALID;
     return overlap(out, n * 4 * sizeof(float), depth, grid_probes(g) * MORT_DEPTH_FLOATS * sizeof(float)) ? MORT_ERR_INVALID : MORT_OK;
 }
 
@@ -144,6 +148,9 @@ void visible_host_chunk(void *p, int chunk) {
 }
 
 } // namespace
+
+bool mort_volume_grid_ok(const mort_volume_grid *g) { return grid_ok(g); }
+bool mort_volume_vis_params_ok(const mort_volume_vis_params *p) { return vis_params_ok(p); }
 
 extern "C" int mort_hip_volume_probes(const mort_volume_grid *g, mort_probe *probes_out) {
     if (!g || !probes_out || !grid_ok(g)) return MORT_ERR_INVALID;

@@ -41,6 +41,7 @@ EXPORTS = [
     "mort_hip_volume_sample", "mort_hip_volume_sample_device", "mort_hip_volume_sample_host",
     "mort_hip_probe_depth_bake", "mort_hip_probe_depth_bake_device", "mort_hip_probe_depth_bake_host",
     "mort_hip_volume_sample_visible", "mort_hip_volume_sample_visible_device", "mort_hip_volume_sample_visible_host",
+    "mort_hip_query_radiance_cached", "mort_hip_query_radiance_cached_device", "mort_hip_query_radiance_cached_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -122,6 +123,27 @@ class VOLUME_VIS_PARAMS(C.Structure):
     def __init__(self, normal_bias=0.0, min_visibility=0.05):
         super().__init__()
         self.normal_bias, self.min_visibility = normal_bias, min_visibility
+
+
+# cached radiance queries (mort_cached_params of include/mort_hip.h)
+CACHED_VISIBLE = 1
+
+
+class CACHED_PARAMS(C.Structure):
+    """mort_cached_params of include/mort_hip.h: a radiance query whose paths end in the volume `grid` from bounce cache_depth on;
+    vis (VOLUME_VIS_PARAMS) sets MORT_CACHED_VISIBLE"""
+    _fields_ = [("path", RADIANCE_PARAMS), ("cache_depth", C.c_int32), ("flags", C.c_uint32), ("grid", VOLUME_GRID),
+                ("vis", VOLUME_VIS_PARAMS)]
+
+    def __init__(self, path=None, cache_depth=1, grid=None, vis=None):
+        super().__init__()
+        if path is not None:
+            C.memmove(C.byref(self.path), C.byref(path), C.sizeof(RADIANCE_PARAMS))
+        if grid is not None:
+            C.memmove(C.byref(self.grid), C.byref(grid), C.sizeof(VOLUME_GRID))
+        self.cache_depth = cache_depth
+        self.vis.normal_bias, self.vis.min_visibility = (vis.normal_bias, vis.min_visibility) if vis is not None else (0.0, 0.0)
+        self.flags = CACHED_VISIBLE if vis is not None else 0
 
 
 class Partition(C.Structure):
@@ -317,6 +339,12 @@ def lib():
         L.mort_hip_volume_sample_visible_device.restype = C.c_int
         L.mort_hip_volume_sample_visible_host.argtypes = [gp, vp, vp, qp, sz, vp, sz, C.c_int, vp, dp]
         L.mort_hip_volume_sample_visible_host.restype = C.c_int
+        cp = C.POINTER(CACHED_PARAMS)
+        L.mort_hip_query_radiance_cached.argtypes = [ctx, cp, sz, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_query_radiance_cached.restype = C.c_int
+        L.mort_hip_query_radiance_cached_device.argtypes = [ctx, cp, sz, vp, vp, vp, vp, vp, vp, vp, dp]
+        L.mort_hip_query_radiance_cached_device.restype = C.c_int
+        L.mort_hip_query_radiance_cached_host.argtypes = [wd, cp, sz, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, dp]
+        L.mort_hip_query_radiance_cached_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -581,6 +609,33 @@ class Context:
         self._chk(lib().mort_hip_query_radiance_device(self._h, C.byref(params), n, rays.data_ptr(), states.data_ptr() if states is not None else None,
                                                        rgb.data_ptr() if rgb is not None else None, stream, C.byref(sec) if sync else None),
                   "mort_hip_query_radiance_device")
+        return sec.value if sync else None
+
+    def query_radiance_cached(self, params, rays, states, records, depth=None, want_ends=True):
+        """The cached radiance query on the GPU (mort_hip_query_radiance_cached): params CACHED_PARAMS, rays and states as for
+        query_radiance (the streams advanced IN PLACE), records float32 (probes, 32) of params.grid, depth float32 (probes, 200) with
+        CACHED_VISIBLE and None without.  dict(rgb float32 (n, 3), ends uint32 (n,) or None, seconds): ends counts the paths of a
+        ray that ended in the volume."""
+        rays, st8, records, depth, rgb, ends = _cached_arrays(params, rays, states, records, depth, want_ends)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_query_radiance_cached(self._h, C.byref(params), rays.shape[0], rays.ctypes.data, _ptr(st8), _ptr(records),
+                                                       _ptr(depth), rgb.ctypes.data, _ptr(ends), C.byref(sec)), "mort_hip_query_radiance_cached")
+        return dict(rgb=rgb, ends=ends, seconds=sec.value)
+
+    def query_radiance_cached_device(self, params, rays, states, records, depth, rgb, ends=None, sync=False):
+        """The cached radiance query on torch tensors: rays, states and rgb as for query_radiance_device, records of 128 bytes and
+        depth (or None) of 800 bytes per probe of params.grid, ends None or 4 n bytes."""
+        import torch
+        n = _check_query_tensors(torch, rays, ((states, 48), (rgb, 12), (ends, 4)))
+        for t, size in ((records, 128 * params.grid.probes), (depth, 4 * DEPTH_FLOATS * params.grid.probes)):
+            if t is not None and (not t.is_contiguous() or t.numel() * t.element_size() != size or t.device != rays.device):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {rays.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, rays.device, sync)
+        dptr = lambda t: t.data_ptr() if t is not None else None
+        self._chk(lib().mort_hip_query_radiance_cached_device(self._h, C.byref(params), n, rays.data_ptr(), dptr(states), dptr(records), dptr(depth),
+                                                              dptr(rgb), dptr(ends), stream, C.byref(sec) if sync else None),
+                  "mort_hip_query_radiance_cached_device")
         return sec.value if sync else None
 
     def probe_bake(self, params, probes, states, dirs=None):
@@ -1145,6 +1200,36 @@ def query_radiance_host(world, params, rays, states, tree=False, nthreads=1):
     if rc != 0:
         raise MortHipError(rc, "mort_hip_query_radiance_host")
     return dict(rgb=rgb, seconds=sec.value)
+
+
+def _cached_arrays(params, rays, states, records, depth, want_ends):
+    """the arrays of a cached radiance query: inputs as contiguous float32, the outputs new"""
+    rays = _query_rays(rays)
+    st8 = _query_states(states, rays)
+    probes = params.grid.probes if all(0 < c <= VOLUME_MAX_COUNT for c in params.grid.count) else None
+    if records is not None:
+        records = np.ascontiguousarray(records, dtype=np.float32)
+        if probes is not None and records.size != VOLUME_RECORD_FLOATS * probes:
+            raise ValueError(f"expected {probes} records of 32 floats")
+    if depth is not None:
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if probes is not None and depth.size != DEPTH_FLOATS * probes:
+            raise ValueError(f"expected {probes} depth maps of 200 floats")
+    rgb = np.zeros((rays.shape[0], 3), dtype=np.float32)
+    ends = np.zeros(rays.shape[0], dtype=np.uint32) if want_ends else None
+    return rays, st8, records, depth, rgb, ends
+
+
+def query_radiance_cached_host(world, params, rays, states, records, depth=None, want_ends=True, tree=False, nthreads=1):
+    """The cached radiance query as a host loop (mort_hip_query_radiance_cached_host), no GPU: arguments and result as
+    Context.query_radiance_cached."""
+    rays, st8, records, depth, rgb, ends = _cached_arrays(params, rays, states, records, depth, want_ends)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_query_radiance_cached_host(world.ptr, C.byref(params), rays.shape[0], rays.ctypes.data, _ptr(st8), _ptr(records),
+                                                   _ptr(depth), nthreads, HOST_TREE if tree else 0, rgb.ctypes.data, _ptr(ends), C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_query_radiance_cached_host")
+    return dict(rgb=rgb, ends=ends, seconds=sec.value)
 
 
 def _probe_records(probes):
