@@ -311,6 +311,7 @@ typedef struct mort_view_stats {
 #define MORT_VIEW_NORMAL 5    /* [3] */
 #define MORT_VIEW_DEPTH 6     /* [1] */
 #define MORT_VIEW_HISTORY 7   /* [MORT_TEMPORAL_HISTORY_FLOATS] the history the last frame wrote, three float4 planes; needs temporal */
+#define MORT_VIEW_ENDS 8      /* [1, uint32] the last cached frame's paths per pixel that ended in the volume; needs a cache attached */
 /* the three stages' own defaults; temporal 1, filter SVGF; width = height = 0 */
 int mort_hip_view_defaults(mort_view_params *p);
 /* MORT_OK or MORT_ERR_INVALID: sizes > 0, temporal 0 / 1, a known filter, and the stages' own checks of the parameters in use
@@ -629,6 +630,52 @@ int mort_hip_query_radiance_cached_device(mort_ctx *ctx, const mort_cached_param
 int mort_hip_query_radiance_cached_host(const mort_world *world, const mort_cached_params *params, size_t n, const mort_ray *rays,
                                         mort_rng_state *states, const float *records, const float *depth, int nthreads, int flags,
                                         float *rgb_out, uint32_t *ends_out, double *seconds);
+
+/* ---- cached frames: renders whose paths end in an irradiance volume.  Camera::render for every pixel, as
+ * mort_hip_render runs it -- the pixel's stream from the context (or `states`), get_ray per stratum drawn from that stream, the flat
+ * sample x bounce loop with one segment counted per search, the unwind, the pixel's finish and its uchar4, the stream stored back
+ * -- with the cached radiance queries' one shortcut inside the bounce loop: after a search that found a hit and before that hit is
+ * shaded, at iteration iter >= K = cache_depth, steps 1-3 above; a path that ends so makes no draw for that hit, its segment is
+ * counted as any other, and the pixel's count in ends_px_out goes up by one.  The bounce limit, the background, the light object
+ * and the samples are the camera's.  So with K >= cam->bounce_limit, or with every weight 0, a cached frame is
+ * mort_hip_render(..., MORT_MODE_MEGA, ...) to the bit: uchar4, accumulators, per-pixel segments, final streams, stats.segments
+ * and stats.rng_draws.
+ *
+ * `records`, `depth` and the flag as for the cached queries.  ends_px_out (one uint32 per pixel, or NULL): how many of the pixel's
+ * sqrt_spp^2 paths ended in the volume.  The three forms mirror mort_hip_render / _render_device / _render_host: host buffers
+ * (records and maps go up, results come down); caller's DEVICE buffers, every one 16-byte aligned, on `stream`, asynchronous
+ * when stats is NULL; and the host loop of the same body, which needs no GPU (MORT_HOST_TREE as elsewhere).
+ *
+ * Checks: the render's (camera, world, seeded states of the frame's size) and the cached queries' (cache_depth, flags, grid, vis,
+ * records, depth with and without the flag); an output that overlaps an input or another output is MORT_ERR_INVALID.  Only the
+ * whole-image partition is supported, else MORT_ERR_UNSUPPORTED, as for a view.  mort_stats as the render fills it: kernel_name
+ * the kernel with its template arguments, scene_in_lds 0, reference_walks 0, algorithmic_hbm_bytes the render's plus 4 B per
+ * pixel when ends is written. ---- */
+typedef struct mort_cached_frame_params {
+    int32_t cache_depth;        /* K, 0 .. MORT_MAX_BOUNCE_LIMIT */
+    uint32_t flags;             /* 0 or MORT_CACHED_VISIBLE */
+    mort_volume_grid grid;
+    mort_volume_vis_params vis; /* read only with MORT_CACHED_VISIBLE */
+} mort_cached_frame_params;
+MORT_SA(sizeof(mort_cached_frame_params) == 56, "cached frame layout");
+int mort_hip_render_cached(mort_ctx *ctx, const mort_camera *cam, const mort_cached_frame_params *params, const float *records,
+                           const float *depth /* or NULL */, uint8_t *rgba_out, float *accum_out /* or NULL */,
+                           uint32_t *segments_px_out /* or NULL */, uint32_t *ends_px_out /* or NULL */, mort_stats *stats);
+int mort_hip_render_cached_device(mort_ctx *ctx, const mort_camera *cam, const mort_cached_frame_params *params, const void *d_records,
+                                  const void *d_depth, void *d_rgba, void *d_accum /* or NULL */, void *d_ends /* or NULL */, void *stream,
+                                  mort_stats *stats);
+int mort_hip_render_cached_host(const mort_world *world, const mort_camera *cam, mort_rng_state *states, int nthreads, int flags,
+                                const mort_cached_frame_params *params, const float *records, const float *depth, uint8_t *rgba_out,
+                                float *accum_out, uint32_t *segments_px_out, uint32_t *ends_px_out, mort_stats *stats);
+/* a view's frames as cached frames (NULL params: plain renders again).  The caller owns d_records and d_depth, which must outlive
+ * the view's frames; the checks are mort_hip_render_cached_device's for them.  Attaching or detaching forgets the history, as
+ * mort_hip_view_reset does: the estimator changes and its variance with it.  With a cache attached a frame must use
+ * MORT_MODE_MEGA, any other mode is MORT_ERR_UNSUPPORTED.  mort_hip_view_read(MORT_VIEW_ENDS) gives the last frame's counts of
+ * paths that ended in the volume, which the view keeps in a buffer of its own. */
+int mort_hip_view_set_cache(mort_view *v, const mort_cached_frame_params *params, const void *d_records, const void *d_depth);
+/* the same for a caller without device buffers (the CLI): records and depth (or NULL) are host arrays, which the view copies into
+ * device buffers of its own; those live until the next attach or detach by either form, or the view's end */
+int mort_hip_view_set_cache_host(mort_view *v, const mort_cached_frame_params *params, const float *records, const float *depth);
 
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);

@@ -20,6 +20,8 @@
  *                   [--visibility BIAS[,MINVIS[,S]]]      with --sh-volume: depth maps per probe and the visibility-weighted sampler
  *                   [--cache-depth K]                     with --sh-volume: paths that end in the volume from bounce K on, along
  *                                                          --probe X,Y[,N] (one JSON line) or every pixel's ray (--radiance-out FILE)
+ *                   [--cache-render]                      with --sh-volume and --cache-depth: the frames are cached frames, renders
+ *                                                          whose paths end in the volume (single GPU / host)
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -83,6 +85,14 @@
  * sqrt(clamp(sum / N, 0, 1)), NaN as 0, is written as an 8-bit PPM.  That is a PREVIEW from pixel-centre rays (no jitter, no lens,
  * time 0.5), not a render.  Without --cache-depth every accepted and refused combination and every output byte is what it was.
  *
+ * --cache-render (with --sh-volume ... --cache-depth K, --visibility optional; excludes --probe, --radiance-out, --pick and
+ * --irradiance-out; one GPU in the default mode, or --mode host): the volume is baked as above, then the ordinary frame loop runs
+ * -- --spp, --frames, --keys / --mouse, --out, --temporal, --denoise, --svgf, --features-out, --variance-out, --dump-f32 and the
+ * states files as for a render -- with cached frames in the renders' place: on a GPU every frame goes through a
+ * view with the cache attached (mort_hip_view_set_cache_host), under --mode host through mort_hip_render_cached_host.  The JSON line is
+ * the render's own plus cache_depth, ends (the paths of the last frame that ended in the volume) and the volume's parameters.
+ * Without --cache-render every accepted and refused combination and every output byte is what it was.
+ *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
  * RCCL (`--gather rccl`, the default: xGMI inside a node), or through a shared host mapping (`--gather shm`: for ranks
@@ -128,9 +138,10 @@ static int usage(void) {
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
            "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
            "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]] "
-           "[--cache-depth K] [--radiance-out FILE]\n"
+           "[--cache-depth K] [--radiance-out FILE] [--cache-render]\n"
            "  --cache-depth K with --sh-volume: paths end in the volume from bounce K on; --probe X,Y[,N] prints one pixel's colour,\n"
-           "  --radiance-out FILE writes a preview from pixel-centre rays (--spp paths each; no jitter, no lens), not a render\n");
+           "  --radiance-out FILE writes a preview from pixel-centre rays (--spp paths each; no jitter, no lens), not a render,\n"
+           "  --cache-render renders: the ordinary frame loop (--frames, --out, --temporal, --svgf, ...) over cached frames\n");
     return -1;
 }
 
@@ -183,6 +194,64 @@ static mort_ray pick_ray(const mort_camera *cam, int x, int y) {
     return r;
 }
 
+/* --sh-volume's grid: NX x NY x NZ probes that span the box inclusively, at time 0.5; -1 (and a message) where the library's own
+ * conditions fail, before anything is sized by the counts */
+static int volume_grid(const float box[6], const int n[3], mort_volume_grid *grid) {
+    for (int k = 0; k < 3; k++) {
+        grid->origin[k] = box[k];
+        grid->count[k] = n[k];
+        grid->spacing[k] = n[k] > 1 ? (box[3 + k] - box[k]) / (float)(n[k] - 1) : 1.0f;
+    }
+    grid->time = 0.5f;
+    for (int k = 0; k < 3; k++)
+        if (grid->count[k] < 1 || grid->count[k] > MORT_VOLUME_MAX_COUNT || !(grid->spacing[k] > 0.0f) || grid->spacing[k] - grid->spacing[k] != 0.0f ||
+            grid->origin[k] - grid->origin[k] != 0.0f) { fprintf(stderr, "--sh-volume: a box with X1 > X0 (or one probe) per axis and 1..%d probes per axis\n", MORT_VOLUME_MAX_COUNT); return -1; }
+    return 0;
+}
+
+/* --cache-render: the volume a cached frame ends its paths in, baked as the no-render uses of --sh-volume bake it (D directions, N
+ * paths, the scene camera's parameters, the streams subsequences 0 .. probes D - 1 of the seed; all weights 1; with --visibility
+ * the depth maps, S x S rays per texel, max_distance 1.5 cell diagonals) */
+typedef struct {
+    mort_cached_frame_params p;
+    mort_depth_params dp;
+    float *records, *depth; /* host; depth NULL without --visibility */
+    size_t probes;
+    double bake_sec;
+} cache_volume;
+static void bake_cache_volume(cache_volume *v, mort_ctx *ctx /* NULL: the host forms */, const mort_world *world, const mort_camera *cam,
+                              unsigned long long seed, int sh_d, int sh_n, int vis_s, int threads, int host_flags) {
+    const mort_volume_grid *g = &v->p.grid;
+    const int visible = (v->p.flags & MORT_CACHED_VISIBLE) != 0;
+    const size_t n = v->probes = (size_t)g->count[0] * (size_t)g->count[1] * (size_t)g->count[2];
+    mort_probe_params pp;
+    mort_hip_radiance_params_from_camera(cam, &pp.rp);
+    pp.rp.samples = sh_n;
+    pp.directions = sh_d;
+    v->dp.subsamples = vis_s;
+    v->dp.max_distance = (float)(1.5 * sqrt((double)g->spacing[0] * (double)g->spacing[0] + (double)g->spacing[1] * (double)g->spacing[1] +
+                                            (double)g->spacing[2] * (double)g->spacing[2]));
+    mort_probe *probes = (mort_probe *)malloc(n * sizeof *probes);
+    mort_rng_state *states = (mort_rng_state *)malloc(n * (size_t)sh_d * sizeof *states);
+    float *sh = (float *)malloc(n * MORT_SH9_FLOATS * sizeof *sh);
+    v->records = (float *)malloc(n * MORT_VOLUME_RECORD_FLOATS * sizeof(float));
+    v->depth = visible ? (float *)malloc(n * MORT_DEPTH_FLOATS * sizeof(float)) : NULL;
+    if (!probes || !states || !sh || !v->records || (visible && !v->depth) || n * (size_t)sh_d > 0x7fffffffu) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    int st;
+    if ((st = mort_hip_volume_probes(g, probes)) != MORT_OK) die(NULL, st, "mort_hip_volume_probes");
+    if ((st = mort_hip_rng_seed_host(seed, (int)(n * (size_t)sh_d), 1, states)) != MORT_OK) die(NULL, st, "mort_hip_rng_seed_host");
+    if (!ctx) {
+        if ((st = mort_hip_probe_bake_host(world, &pp, n, probes, NULL, states, threads, host_flags, sh, &v->bake_sec)) != MORT_OK) die(NULL, st, "mort_hip_probe_bake_host");
+        if ((st = mort_hip_volume_pack_host(n, sh, NULL, threads, v->records, NULL)) != MORT_OK) die(NULL, st, "mort_hip_volume_pack_host");
+        if (visible && (st = mort_hip_probe_depth_bake_host(world, &v->dp, n, probes, threads, host_flags, v->depth, NULL)) != MORT_OK) die(NULL, st, "mort_hip_probe_depth_bake_host");
+    } else {
+        if ((st = mort_hip_probe_bake(ctx, &pp, n, probes, NULL, states, sh, &v->bake_sec)) != MORT_OK) die(ctx, st, "mort_hip_probe_bake");
+        if ((st = mort_hip_volume_pack(ctx, n, sh, NULL, v->records, NULL)) != MORT_OK) die(ctx, st, "mort_hip_volume_pack");
+        if (visible && (st = mort_hip_probe_depth_bake(ctx, &v->dp, n, probes, v->depth, NULL)) != MORT_OK) die(ctx, st, "mort_hip_probe_depth_bake");
+    }
+    free(probes); free(states); free(sh);
+}
+
 /* input() before frame f (mort.cu:49-91,94): the f-th character of --keys held down, the --mouse delta dragged */
 static void frame_input(mort_camera *cam, const char *keys, int f, int mdx, int mdy) {
     int k = 0;
@@ -214,6 +283,7 @@ int main(int argc, char **argv) {
     float vis_bias = 0.0f, vis_min = 0.05f;
     int cached = 0, cache_depth = 0;
     const char *rad_out = NULL;
+    int cache_render = 0;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -269,6 +339,7 @@ int main(int argc, char **argv) {
         }
         else if (ARG("--cache-depth")) { cached = 1; if (sscanf(argv[++i], "%d", &cache_depth) != 1) { fprintf(stderr, "--cache-depth K\n"); return -1; } }
         else if (ARG("--radiance-out")) rad_out = argv[++i];
+        else if (strcmp(argv[i], "--cache-render") == 0) cache_render = 1;
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -286,7 +357,10 @@ int main(int argc, char **argv) {
     if (cached && !sh_volume) { fprintf(stderr, "--cache-depth needs --sh-volume\n"); return -1; }
     if (rad_out && !cached) { fprintf(stderr, "--radiance-out needs --cache-depth\n"); return -1; }
     if (cached && (cache_depth < 0 || cache_depth > MORT_MAX_BOUNCE_LIMIT)) { fprintf(stderr, "--cache-depth: K in 0..%d\n", MORT_MAX_BOUNCE_LIMIT); return -1; }
-    if (cached && (pick || irr_out || !probe == !rad_out)) {
+    if (cache_render && (!sh_volume || !cached)) { fprintf(stderr, "--cache-render needs --sh-volume and --cache-depth\n"); return -1; }
+    if (cache_render && (probe || rad_out || pick || irr_out)) { fprintf(stderr, "--cache-render excludes --probe, --radiance-out, --pick and --irradiance-out\n"); return -1; }
+    if (cache_render && (gpus > 1 || mode != MORT_MODE_MEGA)) { fprintf(stderr, "--cache-render is a single-GPU option of the default mode and of --mode host\n"); return -1; }
+    if (cached && !cache_render && (pick || irr_out || !probe == !rad_out)) {
         fprintf(stderr, "--cache-depth needs --probe X,Y[,N] or --radiance-out FILE, not both, and excludes --pick and --irradiance-out\n"); return -1;
     }
     if (sh_volume && (gpus > 1 || (probe && !cached) || sh_probe)) { fprintf(stderr, "--sh-volume is a single-GPU option and excludes --probe and --sh-probe\n"); return -1; }
@@ -325,20 +399,12 @@ int main(int argc, char **argv) {
     const size_t npx = (size_t)W * H;
     const int eff = mort_camera_effective_spp(&cam);
 
-    if (sh_volume) { /* ---- no render: bake a grid of probes, pack it, sample it at the hits of --pick's rays ---- */
+    if (sh_volume && !cache_render) { /* ---- no render: bake a grid of probes, pack it, sample it at the hits of --pick's rays ---- */
         if (pick && (pick_x < 0 || pick_x >= W || pick_y < 0 || pick_y >= H)) { fprintf(stderr, "--pick %d,%d is outside the %dx%d image\n", pick_x, pick_y, W, H); return -1; }
         if (probe && (probe_x < 0 || probe_x >= W || probe_y < 0 || probe_y >= H)) { fprintf(stderr, "--probe %d,%d is outside the %dx%d image\n", probe_x, probe_y, W, H); return -1; }
         mort_volume_grid grid;
-        for (int k = 0; k < 3; k++) {
-            grid.origin[k] = vol_box[k];
-            grid.count[k] = vol_n[k];
-            grid.spacing[k] = vol_n[k] > 1 ? (vol_box[3 + k] - vol_box[k]) / (float)(vol_n[k] - 1) : 1.0f;
-        }
-        grid.time = 0.5f;
         int pst;
-        for (int k = 0; k < 3; k++) /* the library's own conditions, before anything is sized by the counts */
-            if (grid.count[k] < 1 || grid.count[k] > MORT_VOLUME_MAX_COUNT || !(grid.spacing[k] > 0.0f) || grid.spacing[k] - grid.spacing[k] != 0.0f ||
-                grid.origin[k] - grid.origin[k] != 0.0f) { fprintf(stderr, "--sh-volume: a box with X1 > X0 (or one probe) per axis and 1..%d probes per axis\n", MORT_VOLUME_MAX_COUNT); return -1; }
+        if (volume_grid(vol_box, vol_n, &grid) != 0) return -1;
         const size_t probes_n = (size_t)grid.count[0] * (size_t)grid.count[1] * (size_t)grid.count[2];
         const size_t nq = (pick || probe) ? 1 : npx;
         mort_probe_params pp;
@@ -635,9 +701,20 @@ int main(int argc, char **argv) {
         if (tf && rank != 0) { sleep(60); _exit(3); } /* a healthy peer that would wait in ncclSend: must be killed, not waited for */
     }
 
+    cache_volume cv; /* --cache-render */
+    memset(&cv, 0, sizeof cv);
+    uint32_t *ends_px = NULL;
+    if (cache_render) {
+        cv.p.cache_depth = cache_depth; cv.p.flags = visibility ? MORT_CACHED_VISIBLE : 0u;
+        cv.p.vis.normal_bias = vis_bias; cv.p.vis.min_visibility = vis_min;
+        if (volume_grid(vol_box, vol_n, &cv.p.grid) != 0) return -1;
+        ends_px = calloc(npx, sizeof *ends_px);
+        if (!ends_px) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+    }
+
     uint8_t *rgba = calloc(npx, 4);
     /* a single GPU keeps the chain on the device (a view): only --dump-f32 brings the accumulators back */
-    const int use_view = !host_mode && gpus == 1 && (temporal || denoise || svgf || feat_out || dump);
+    const int use_view = !host_mode && gpus == 1 && (temporal || denoise || svgf || feat_out || dump || cache_render);
     const int want_accum = dump || (host_mode && (denoise || temporal || svgf));
     float *accum = want_accum ? calloc(npx * 3, sizeof(float)) : NULL;
     if (!rgba || (want_accum && !accum)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
@@ -670,8 +747,13 @@ int main(int argc, char **argv) {
             if (!f || fread(hstates, sizeof *hstates, npx, f) != npx) { fprintf(stderr, "cannot read %zu states from %s\n", npx, sin); return EXIT_FAILURE; }
             fclose(f);
         } else if ((st = mort_hip_rng_seed_host(seed, W, H, hstates)) != MORT_OK) die(NULL, st, "mort_hip_rng_seed_host");
+        if (cache_render) bake_cache_volume(&cv, NULL, &world, &cam, seed, sh_d, sh_n, vis_s, threads, tree ? MORT_HOST_TREE : 0);
         for (int f = 0; f < frames; f++) {
             if (f > 0) frame_input(&cam, keys, f, mouse_dx, mouse_dy);
+            if (cache_render) {
+                if ((st = mort_hip_render_cached_host(&world, &cam, hstates, threads, tree ? MORT_HOST_TREE : 0, &cv.p, cv.records, cv.depth, rgba, accum, NULL,
+                                                      ends_px, &stats)) != MORT_OK) die(NULL, st, "mort_hip_render_cached_host");
+            } else
             if ((st = mort_hip_render_host(&world, &cam, hstates, threads, tree ? MORT_HOST_TREE : 0, rgba, accum, NULL, &stats)) != MORT_OK) die(NULL, st, "mort_hip_render_host");
             total_ms += stats.seconds * 1e3;
             printf("Avg. time per frame: %3.1f ms\n", total_ms / (f + 1)); /* mort.cu:119 */
@@ -718,10 +800,14 @@ int main(int argc, char **argv) {
             vp.filter = denoise ? MORT_VIEW_FILTER_DENOISE : svgf ? MORT_VIEW_FILTER_SVGF : MORT_VIEW_FILTER_NONE;
             if ((st = mort_hip_view_create(ctx, &vp, &view)) != MORT_OK) die(ctx, st, "mort_hip_view_create");
         }
+        if (cache_render) { /* the volume baked on this context; the view keeps its own device copies of the records and maps */
+            bake_cache_volume(&cv, ctx, &world, &cam, seed, sh_d, sh_n, vis_s, threads, 0);
+            if ((st = mort_hip_view_set_cache_host(view, &cv.p, cv.records, cv.depth)) != MORT_OK) die(ctx, st, "mort_hip_view_set_cache_host");
+        }
         for (int f = 0; f < frames; f++) {
             if (f > 0) frame_input(&cam, keys, f, mouse_dx, mouse_dy);
             const double t0 = now_s();
-            if (view && (temporal || f == frames - 1)) { /* render, features, temporal step and filter on the device; the frame's uchar4
+            if (view && (temporal || cache_render || f == frames - 1)) { /* render, features, temporal step and filter on the device; the frame's uchar4
                                                           * comes back.  Without --temporal only the last frame is filtered or written:
                                                           * the frames before it are plain renders, as they always were */
                 mort_view_stats vs;
@@ -748,6 +834,7 @@ int main(int argc, char **argv) {
             if (rank == 0) printf("Avg. time per frame: %3.1f ms\n", total_ms / (f + 1)); /* mort.cu:119 */
         }
         if (view) { /* what the files need of the last frame */
+            if (cache_render && (st = mort_hip_view_read(view, MORT_VIEW_ENDS, ends_px)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
             if (dump && (st = mort_hip_view_read(view, MORT_VIEW_RAW_ACCUM, accum)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
             if (feat_out) {
                 alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
@@ -838,6 +925,18 @@ int main(int argc, char **argv) {
     if (denoise) printf(", \"denoise_seconds\": %.6f", denoise_sec); /* feature pass + denoise, device time (host loops: wall time) */
     if (svgf) printf(", \"svgf_seconds\": %.6f", svgf_sec); /* feature pass + SVGF filter, likewise */
     if (temporal) printf(", \"temporal_seconds\": %.6f", temporal_sec); /* feature passes + temporal steps over all frames, likewise */
+    if (cache_render) { /* the last frame's paths that ended in the volume, and the volume as the no-render uses report it */
+        unsigned long long ended = 0;
+        for (size_t i = 0; i < npx; i++) ended += ends_px[i];
+        printf(", \"cache_depth\": %d, \"ends\": %llu", cache_depth, ended);
+        if (visibility) {
+            printf(", \"normal_bias\": "); print_f32(cv.p.vis.normal_bias);
+            printf(", \"min_visibility\": "); print_f32(cv.p.vis.min_visibility);
+            printf(", \"depth_subsamples\": %d, \"max_distance\": ", cv.dp.subsamples); print_f32(cv.dp.max_distance);
+        }
+        printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"probe_samples\": %d, \"bake_seconds\": %.6f", (int)cv.p.grid.count[0], (int)cv.p.grid.count[1],
+               (int)cv.p.grid.count[2], sh_d, sh_n, cv.bake_sec);
+    }
     printf("}\n");
     if (out && mort_write_ppm(out, rgba, W, H) != 0) { fprintf(stderr, "cannot write %s\n", out); return EXIT_FAILURE; }
     if (dump) {
@@ -855,6 +954,6 @@ int main(int argc, char **argv) {
     }
     if (ctx) mort_hip_shutdown(ctx);
     mort_world_free(&world);
-    free(texels); free(rgba); free(accum); free(hstates);
+    free(texels); free(rgba); free(accum); free(hstates); free(ends_px); free(cv.records); free(cv.depth);
     return 0;
 }

@@ -41,6 +41,27 @@ __global__ void __launch_bounds__(QUERY_BLOCK, 3) query_radiance_cached_kernel(c
 
 /* ====================================================================== host */
 
+/* ---- what the cached frames (cached_frame.hip) share with the queries: the checks of the new fields and the volume by value ---- */
+
+bool mort_cached_volume_ok(int32_t cache_depth, uint32_t flags, const mort_volume_grid *grid, const mort_volume_vis_params *vis, const void *records,
+                           const void *depth) {
+    if (!records || cache_depth < 0 || cache_depth > MORT_MAX_BOUNCE_LIMIT || (flags & ~MORT_CACHED_VISIBLE)) return false;
+    const bool visible = (flags & MORT_CACHED_VISIBLE) != 0;
+    if (visible != (depth != nullptr)) return false;
+    return mort_volume_grid_ok(grid) && (!visible || mort_volume_vis_params_ok(vis));
+}
+
+void mort_cached_volume(VolumeArgs &v, const mort_volume_grid &grid, const void *records) {
+    std::memset(&v, 0, sizeof v);
+    v.g = grid;
+    for (int k = 0; k < 3; k++) v.inv[k] = 1.0f / grid.spacing[k];
+    v.records = (const float *)records;
+}
+void mort_cached_volume(VolumeVisArgs &v, const mort_volume_grid &grid, const mort_volume_vis_params &vis, const void *records, const void *depth) {
+    mort_cached_volume(v.v, grid, records);
+    v.depth = (const float *)depth; v.normal_bias = vis.normal_bias; v.min_visibility = vis.min_visibility;
+}
+
 namespace {
 
 constexpr size_t kRecordBytes = MORT_VOLUME_RECORD_FLOATS * sizeof(float);
@@ -53,10 +74,7 @@ int cached_check(const mort_cached_params *p, size_t n, const void *rays, void *
     if (!p || !records) return MORT_ERR_INVALID;
     const int st = mort_radiance_check(&p->path, n, rays, states, rgb);
     if (st != MORT_OK) return st;
-    if (p->cache_depth < 0 || p->cache_depth > MORT_MAX_BOUNCE_LIMIT || (p->flags & ~MORT_CACHED_VISIBLE)) return MORT_ERR_INVALID;
-    const bool visible = (p->flags & MORT_CACHED_VISIBLE) != 0;
-    if (visible != (depth != nullptr)) return MORT_ERR_INVALID;
-    if (!mort_volume_grid_ok(&p->grid) || (visible && !mort_volume_vis_params_ok(&p->vis))) return MORT_ERR_INVALID;
+    if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, records, depth)) return MORT_ERR_INVALID;
     const size_t probes = cached_probes(p);
     const void *ins[3] = {rays, records, depth};
     const size_t in_bytes[3] = {n * sizeof(mort_ray), probes * kRecordBytes, probes * kDepthBytes};
@@ -65,16 +83,6 @@ int cached_check(const mort_cached_params *p, size_t n, const void *rays, void *
     return buffers_disjoint(ins, in_bytes, 3, outs, out_bytes, 3) ? MORT_OK : MORT_ERR_INVALID;
 }
 
-void cached_volume(VolumeArgs &v, const mort_cached_params *p, const void *records) {
-    std::memset(&v, 0, sizeof v);
-    v.g = p->grid;
-    for (int k = 0; k < 3; k++) v.inv[k] = 1.0f / p->grid.spacing[k];
-    v.records = (const float *)records;
-}
-void cached_volume(VolumeVisArgs &v, const mort_cached_params *p, const void *records, const void *depth) {
-    cached_volume(v.v, p, records);
-    v.depth = (const float *)depth; v.normal_bias = p->vis.normal_bias; v.min_visibility = p->vis.min_visibility;
-}
 
 /* everything of the arguments but the scene (c.r.q: query_args_device / query_args_host come first, they clear it) */
 template <bool VISIBLE>
@@ -83,8 +91,8 @@ void cached_args(CachedArgs<VISIBLE> &c, const mort_cached_params *p, size_t n, 
     mort_radiance_args_params(c.r, &p->path);
     c.r.q.n = n; c.r.q.rays = (const mort_ray *)rays; c.r.q.states = (mort_rng_state *)states; c.r.rgb = (float *)rgb;
     c.cache_depth = p->cache_depth; c.ends = (uint32_t *)ends;
-    if constexpr (VISIBLE) cached_volume(c.vol.v, p, records, depth);
-    else cached_volume(c.vol.v, p, records);
+    if constexpr (VISIBLE) mort_cached_volume(c.vol.v, p->grid, p->vis, records, depth);
+    else mort_cached_volume(c.vol.v, p->grid, records);
 }
 
 template <bool VISIBLE>

@@ -53,6 +53,15 @@ void mort_radiance_args_params(RadianceArgs &a, const mort_radiance_params *p);
 bool mort_volume_grid_ok(const mort_volume_grid *g);
 bool mort_volume_vis_params_ok(const mort_volume_vis_params *p);
 
+/* cached.hip: the checks of the cached queries' own fields (cache_depth, flags, grid, vis, records, depth with and without the flag)
+ * and their volume as the kernels take it by value, for the cached frames (cached_frame.hip) */
+struct VolumeArgs;
+struct VolumeVisArgs;
+bool mort_cached_volume_ok(int32_t cache_depth, uint32_t flags, const mort_volume_grid *grid, const mort_volume_vis_params *vis, const void *records,
+                           const void *depth);
+void mort_cached_volume(VolumeArgs &v, const mort_volume_grid &grid, const void *records);
+void mort_cached_volume(VolumeVisArgs &v, const mort_volume_grid &grid, const mort_volume_vis_params &vis, const void *records, const void *depth);
+
 /* view.hip: mort_hip_shutdown frees the views still alive on the context */
 void mort_views_free(mort_ctx *c);
 

@@ -1,7 +1,7 @@
 /*
  * view.hip -- the view: a frame's whole chain kept on the device across frames.
  *
- *   render -> first-hit features -> [temporal step] -> [a-trous denoiser | SVGF filter] -> uchar4
+ *   render (or cached frame, mort_hip_view_set_cache) -> first-hit features -> [temporal step] -> [a-trous denoiser | SVGF filter] -> uchar4
  *
  * No kernel lives here and no arithmetic: a frame is the existing _device entry points (mort_hip.hip, denoise.hip, temporal.hip,
  * svgf.hip) called back to back on one stream with their `seconds` / `stats` waits left out, so its bits are those of the calls
@@ -49,6 +49,12 @@ struct mort_view {
     bool have_feat = false;     /* d_feat belongs to feat_cam and world feat_serial */
     mort_camera prev_cam{}, feat_cam{};
     unsigned feat_serial = 0, hist_serial = 0;
+    /* mort_hip_view_set_cache: the frames are cached frames over the caller's device buffers */
+    bool cached = false;
+    mort_cached_frame_params cache{};
+    const void *d_records = nullptr, *d_cache_depth = nullptr;
+    uint32_t *d_ends = nullptr; /* per pixel, the last frame's paths that ended in the volume (allocated when a cache is first attached) */
+    void *own_records = nullptr, *own_depth = nullptr; /* mort_hip_view_set_cache_host: the view's own copies of the caller's host arrays */
 
     float *albedo() const { return d_feat; }
     float *normal() const { return d_feat + 3 * npx; }
@@ -66,7 +72,8 @@ bool same_feature_camera(const mort_camera &a, const mort_camera &b) {
 
 void free_buffers(mort_view *v) {
     (void)hipFree(v->d_rgba); (void)hipFree(v->d_accum); (void)hipFree(v->d_feat); (void)hipFree(v->d_hist[0]); (void)hipFree(v->d_hist[1]);
-    (void)hipFree(v->d_tacc); (void)hipFree(v->d_var); (void)hipFree(v->d_facc); (void)hipFree(v->d_out);
+    (void)hipFree(v->d_tacc); (void)hipFree(v->d_var); (void)hipFree(v->d_facc); (void)hipFree(v->d_out); (void)hipFree(v->d_ends);
+    (void)hipFree(v->own_records); (void)hipFree(v->own_depth);
     if (v->h_out) (void)hipHostFree(v->h_out);
     for (hipEvent_t e : v->ev) if (e) (void)hipEventDestroy(e);
 }
@@ -104,7 +111,10 @@ int view_frame(mort_view *v, const mort_camera *cam, int mode, void *d_dst, uint
     mort_stats local;
     std::memset(&local, 0, sizeof local);
     c->defer_stats = timed; c->pending_stats = nullptr;
-    int st = mort_hip_render_device(c, cam, mode, v->d_rgba, v->d_accum, s, timed ? &local : nullptr);
+    int st;
+    if (!v->cached) st = mort_hip_render_device(c, cam, mode, v->d_rgba, v->d_accum, s, timed ? &local : nullptr);
+    else if (mode != MORT_MODE_MEGA) st = MORT_ERR_UNSUPPORTED;
+    else st = mort_hip_render_cached_device(c, cam, &v->cache, v->d_records, v->d_cache_depth, v->d_rgba, v->d_accum, v->d_ends, s, timed ? &local : nullptr);
     c->defer_stats = false;
     if (st != MORT_OK) {
         c->pending_stats = nullptr;
@@ -269,6 +279,60 @@ extern "C" int mort_hip_view_reset(mort_view *v) {
     return MORT_OK;
 }
 
+namespace {
+/* the volume copies of an earlier mort_hip_view_set_cache_host, once no frame in flight reads them */
+int free_own_cache(mort_view *v) {
+    if (!v->own_records && !v->own_depth) return MORT_OK;
+    mort_ctx *c = v->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (v->last_stream) HIPCHK(c, hipStreamSynchronize(v->last_stream));
+    (void)hipFree(v->own_records); (void)hipFree(v->own_depth);
+    v->own_records = v->own_depth = nullptr;
+    return MORT_OK;
+}
+} // namespace
+
+extern "C" int mort_hip_view_set_cache_host(mort_view *v, const mort_cached_frame_params *p, const float *records, const float *depth) {
+    if (!v || !p) return MORT_ERR_INVALID;
+    if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, records, depth)) return MORT_ERR_INVALID;
+    mort_ctx *c = v->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t probes = (size_t)p->grid.count[0] * (size_t)p->grid.count[1] * (size_t)p->grid.count[2];
+    const size_t rb = probes * MORT_VOLUME_RECORD_FLOATS * sizeof(float), db = probes * MORT_DEPTH_FLOATS * sizeof(float);
+    void *d_rec = nullptr, *d_dep = nullptr;
+    hipError_t e = hipMalloc(&d_rec, rb);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, records, rb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && depth) e = hipMalloc(&d_dep, db);
+    if (e == hipSuccess && depth) e = hipMemcpy(d_dep, depth, db, hipMemcpyHostToDevice);
+    int st = e == hipSuccess ? MORT_OK : e == hipErrorOutOfMemory ? ((void)hipGetLastError(), MORT_ERR_NOMEM) : hip_fail(c, e, "mort_hip_view_set_cache_host");
+    if (st == MORT_OK) st = mort_hip_view_set_cache(v, p, d_rec, d_dep); /* frees the copies of an earlier call */
+    if (st != MORT_OK) { (void)hipFree(d_rec); (void)hipFree(d_dep); return st; }
+    v->own_records = d_rec; v->own_depth = d_dep;
+    return MORT_OK;
+}
+
+extern "C" int mort_hip_view_set_cache(mort_view *v, const mort_cached_frame_params *p, const void *d_records, const void *d_depth) {
+    if (!v) return MORT_ERR_INVALID;
+    if (p) { /* what mort_hip_render_cached_device will ask of them at every frame */
+        if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, d_records, d_depth)) return MORT_ERR_INVALID;
+        if (((uintptr_t)d_records & 15u) || ((uintptr_t)d_depth & 15u)) return MORT_ERR_INVALID;
+        if (!v->d_ends) {
+            mort_ctx *c = v->ctx;
+            HIPCHK(c, hipSetDevice(c->device));
+            const hipError_t e = hipMalloc((void **)&v->d_ends, v->npx * sizeof(uint32_t));
+            if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return MORT_ERR_NOMEM; }
+            HIPCHK(c, e);
+        }
+    }
+    const int st = free_own_cache(v); /* whatever is attached now replaces them */
+    if (st != MORT_OK) return st;
+    if (p) v->cache = *p;
+    v->cached = p != nullptr;
+    v->d_records = p ? d_records : nullptr; v->d_cache_depth = p ? d_depth : nullptr;
+    v->frame = 0; /* another estimator: its history does not continue */
+    return MORT_OK;
+}
+
 extern "C" int mort_hip_view_frame_device(mort_view *v, const mort_camera *cam, int mode, void *d_rgba_out, void *stream, mort_view_stats *stats) {
     if (!v || !cam || !d_rgba_out) return MORT_ERR_INVALID;
     return view_frame(v, cam, mode, d_rgba_out, nullptr, stream, stats);
@@ -288,7 +352,7 @@ extern "C" int mort_hip_view_read(mort_view *v, int what, void *host_out) {
     if (!v || !host_out || !v->have_frame) return MORT_ERR_INVALID;
     mort_ctx *c = v->ctx;
     const size_t npx = v->npx;
-    const float *src = nullptr;
+    const void *src = nullptr; /* 32-bit words: floats, but for MORT_VIEW_ENDS */
     size_t floats = 0;
     switch (what) {
     case MORT_VIEW_RAW_ACCUM: src = v->d_accum; floats = 3 * npx; break;
@@ -298,7 +362,8 @@ extern "C" int mort_hip_view_read(mort_view *v, int what, void *host_out) {
     case MORT_VIEW_ALBEDO: src = v->albedo(); floats = 3 * npx; break;
     case MORT_VIEW_NORMAL: src = v->normal(); floats = 3 * npx; break;
     case MORT_VIEW_DEPTH: src = v->depth(); floats = npx; break;
-    case MORT_VIEW_HISTORY: src = v->p.temporal ? v->d_hist[v->hist_cur] : nullptr; floats = MORT_TEMPORAL_HISTORY_FLOATS * npx; break;
+    case MORT_VIEW_ENDS: src = v->cached ? v->d_ends : nullptr; floats = npx; break;
+    case MORT_VIEW_HISTORY: src = v->p.temporal ? v->d_hist[v->hist_cur] : (const void *)nullptr; floats = MORT_TEMPORAL_HISTORY_FLOATS * npx; break;
     default: return MORT_ERR_INVALID;
     }
     if (!src) return MORT_ERR_INVALID; /* a buffer this configuration does not produce */

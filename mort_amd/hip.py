@@ -42,12 +42,14 @@ EXPORTS = [
     "mort_hip_probe_depth_bake", "mort_hip_probe_depth_bake_device", "mort_hip_probe_depth_bake_host",
     "mort_hip_volume_sample_visible", "mort_hip_volume_sample_visible_device", "mort_hip_volume_sample_visible_host",
     "mort_hip_query_radiance_cached", "mort_hip_query_radiance_cached_device", "mort_hip_query_radiance_cached_host",
+    "mort_hip_render_cached", "mort_hip_render_cached_device", "mort_hip_render_cached_host", "mort_hip_view_set_cache",
+    "mort_hip_view_set_cache_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
 # mort_hip_view_read: name -> (MORT_VIEW_* code, floats per pixel)
 VIEW_BUFFERS = {"raw_accum": (0, 3), "accum": (1, 3), "filtered": (2, 3), "variance": (3, 1), "albedo": (4, 3), "normal": (5, 3),
-                "depth": (6, 1), "history": (7, TEMPORAL_HISTORY_FLOATS)}
+                "depth": (6, 1), "history": (7, TEMPORAL_HISTORY_FLOATS), "ends": (8, 1)}
 HOST_TREE = 1
 # ray queries (mort_ray, mort_hit of include/mort_hip.h)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("dir", "<f4", (3,)), ("time", "<f4"), ("t_max", "<f4")])
@@ -139,6 +141,20 @@ class CACHED_PARAMS(C.Structure):
         super().__init__()
         if path is not None:
             C.memmove(C.byref(self.path), C.byref(path), C.sizeof(RADIANCE_PARAMS))
+        if grid is not None:
+            C.memmove(C.byref(self.grid), C.byref(grid), C.sizeof(VOLUME_GRID))
+        self.cache_depth = cache_depth
+        self.vis.normal_bias, self.vis.min_visibility = (vis.normal_bias, vis.min_visibility) if vis is not None else (0.0, 0.0)
+        self.flags = CACHED_VISIBLE if vis is not None else 0
+
+
+class CACHED_FRAME_PARAMS(C.Structure):
+    """mort_cached_frame_params of include/mort_hip.h: a render whose paths end in the volume `grid` from bounce cache_depth on;
+    vis (VOLUME_VIS_PARAMS) sets MORT_CACHED_VISIBLE.  Bounce limit, background, light object and samples are the camera's."""
+    _fields_ = [("cache_depth", C.c_int32), ("flags", C.c_uint32), ("grid", VOLUME_GRID), ("vis", VOLUME_VIS_PARAMS)]
+
+    def __init__(self, cache_depth=1, grid=None, vis=None):
+        super().__init__()
         if grid is not None:
             C.memmove(C.byref(self.grid), C.byref(grid), C.sizeof(VOLUME_GRID))
         self.cache_depth = cache_depth
@@ -345,6 +361,15 @@ def lib():
         L.mort_hip_query_radiance_cached_device.restype = C.c_int
         L.mort_hip_query_radiance_cached_host.argtypes = [wd, cp, sz, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, dp]
         L.mort_hip_query_radiance_cached_host.restype = C.c_int
+        fp = C.POINTER(CACHED_FRAME_PARAMS)
+        L.mort_hip_render_cached.argtypes = [ctx, C.POINTER(S.Camera), fp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.mort_hip_render_cached.restype = C.c_int
+        L.mort_hip_render_cached_device.argtypes = [ctx, C.POINTER(S.Camera), fp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.mort_hip_render_cached_device.restype = C.c_int
+        L.mort_hip_render_cached_host.argtypes = [wd, C.POINTER(S.Camera), vp, C.c_int, C.c_int, fp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.mort_hip_render_cached_host.restype = C.c_int
+        L.mort_hip_view_set_cache.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache.restype = C.c_int
+        L.mort_hip_view_set_cache_host.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -638,6 +663,41 @@ class Context:
                   "mort_hip_query_radiance_cached_device")
         return sec.value if sync else None
 
+    def render_cached(self, cam, params, records, depth=None, want_accum=True, want_segments=False, want_ends=True):
+        """A cached frame on the GPU (mort_hip_render_cached): Context.render in MODE_MEGA whose paths end in the volume.  params
+        CACHED_FRAME_PARAMS, records and depth as for query_radiance_cached.  Context.render's dict plus ends_px uint32 (H, W) or
+        None: the paths of a pixel that ended in the volume."""
+        W, H = cam.image_width, cam.image_height
+        records, depth = _cached_volume_arrays(params, records, depth)
+        rgba = np.zeros((H, W, 4), dtype=np.uint8)
+        accum = np.zeros((H, W, 3), dtype=np.float32) if want_accum else None
+        seg = np.zeros((H, W), dtype=np.uint32) if want_segments else None
+        ends = np.zeros((H, W), dtype=np.uint32) if want_ends else None
+        st = Stats()
+        self._chk(lib().mort_hip_render_cached(self._h, C.byref(cam), C.byref(params), _ptr(records), _ptr(depth), rgba.ctypes.data, _ptr(accum),
+                                               _ptr(seg), _ptr(ends), C.byref(st)), "mort_hip_render_cached")
+        return dict(rgba=rgba, accum=accum, segments_px=seg, ends_px=ends, stats=st.asdict())
+
+    def render_cached_device(self, cam, params, records, depth, rgba, accum=None, ends=None, sync=False):
+        """The cached frame on torch tensors, on the current torch stream: records of 128 bytes and depth (or None) of 800 bytes per
+        probe of params.grid; rgba of at least 4, accum (or None) of at least 12 and ends (or None) of at least 4 bytes per pixel,
+        written from their heads.  Asynchronous (returns None) unless sync (then returns the stats)."""
+        import torch
+        npx = cam.image_width * cam.image_height
+        for t, size, exact in ((records, 128 * params.grid.probes, True), (depth, 4 * DEPTH_FLOATS * params.grid.probes, True),
+                               (rgba, 4 * npx, False), (accum, 12 * npx, False), (ends, 4 * npx, False)):
+            if t is None:
+                continue
+            have = t.numel() * t.element_size()
+            if not t.is_contiguous() or t.device != rgba.device or (have != size if exact else have < size):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {rgba.device}")
+        stream, sync = _torch_stream(torch, rgba.device, sync)
+        dptr = lambda t: t.data_ptr() if t is not None else None
+        st = Stats()
+        self._chk(lib().mort_hip_render_cached_device(self._h, C.byref(cam), C.byref(params), dptr(records), dptr(depth), dptr(rgba), dptr(accum),
+                                                      dptr(ends), stream, C.byref(st) if sync else None), "mort_hip_render_cached_device")
+        return st.asdict() if sync else None
+
     def probe_bake(self, params, probes, states, dirs=None):
         """SH9 light probes on the GPU (mort_hip_probe_bake): params PROBE_PARAMS, probes PROBE_DTYPE (n,) or float32 (n, 4) =
         position, time; states n * D 48-byte XORWOW streams, advanced IN PLACE; dirs None = the library's own set, else float32
@@ -831,6 +891,21 @@ class View:
         """Forget the history: the next frame starts over.  RNG states are not touched."""
         self.ctx._chk(lib().mort_hip_view_reset(self._handle()), "mort_hip_view_reset")
 
+    def set_cache(self, params=None, records=None, depth=None):
+        """The view's frames become cached frames: params CACHED_FRAME_PARAMS; records and depth (or None) either torch tensors on
+        the GPU as for Context.render_cached_device, kept alive by the view (mort_hip_view_set_cache), or numpy arrays, which the
+        view copies to the device (mort_hip_view_set_cache_host).  params None detaches the cache.  Either way the history is
+        forgotten, as by reset()."""
+        if params is not None and isinstance(records, np.ndarray):
+            records, depth = _cached_volume_arrays(params, records, depth)
+            self.ctx._chk(lib().mort_hip_view_set_cache_host(self._handle(), C.byref(params), _ptr(records), _ptr(depth)), "mort_hip_view_set_cache_host")
+            self._cache = None
+            return
+        dptr = lambda t: t.data_ptr() if t is not None else None
+        self.ctx._chk(lib().mort_hip_view_set_cache(self._handle(), C.byref(params) if params is not None else None, dptr(records), dptr(depth)),
+                      "mort_hip_view_set_cache")
+        self._cache = (records, depth) if params is not None else None
+
     def frame(self, cam, mode=MODE_MEGA):
         """One frame, one host wait: dict(rgba (H, W, 4) u8, stats)."""
         rgba = np.zeros((self.height, self.width, 4), dtype=np.uint8)
@@ -852,12 +927,12 @@ class View:
 
     def read(self, name):
         """One buffer of the last frame as a numpy array (VIEW_BUFFERS): raw_accum / accum / filtered / albedo / normal (H, W, 3),
-        variance / depth (H, W), history (3, H, W, 4)."""
+        variance / depth (H, W), history (3, H, W, 4); "ends" (uint32 (H, W)) with a cache attached."""
         code, ch = VIEW_BUFFERS[name]
         shape = (3, self.height, self.width, 4) if name == "history" else (self.height, self.width, ch) if ch > 1 else (self.height, self.width)
         out = np.zeros(shape, dtype=np.float32)
         self.ctx._chk(lib().mort_hip_view_read(self._handle(), code, out.ctypes.data), f"mort_hip_view_read({name})")
-        return out
+        return out.view(np.uint32) if name == "ends" else out  # MORT_VIEW_ENDS holds counts
 
 
 def seed_states_host(seed, width, height, dtype=None):
@@ -884,6 +959,40 @@ def render_host(world, cam, states=None, seed=S.DEFAULT_SEED, nthreads=1, tree=F
     if rc != 0:
         raise MortHipError(rc, "mort_hip_render_host")
     return dict(rgba=rgba, accum=accum, segments_px=seg, stats=stt.asdict(), states=st8)
+
+
+def _cached_volume_arrays(params, records, depth):
+    """records and depth maps of a cached call as contiguous float32, their sizes checked against params.grid where that is legal"""
+    probes = params.grid.probes if all(0 < c <= VOLUME_MAX_COUNT for c in params.grid.count) else None
+    if records is not None:
+        records = np.ascontiguousarray(records, dtype=np.float32)
+        if probes is not None and records.size != VOLUME_RECORD_FLOATS * probes:
+            raise ValueError(f"expected {probes} records of 32 floats")
+    if depth is not None:
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if probes is not None and depth.size != DEPTH_FLOATS * probes:
+            raise ValueError(f"expected {probes} depth maps of 200 floats")
+    return records, depth
+
+
+def render_cached_host(world, cam, params, records, depth=None, states=None, seed=S.DEFAULT_SEED, nthreads=1, tree=False, want_accum=True,
+                       want_segments=True, want_ends=True):
+    """The cached frame as a host loop (mort_hip_render_cached_host), no GPU: render_host's arguments and dict (final states
+    included) with Context.render_cached's params, records, depth and ends_px."""
+    W, H = cam.image_width, cam.image_height
+    st8 = seed_states_host(seed, W, H) if states is None else np.ascontiguousarray(states).view(np.uint8).reshape(-1).copy()
+    assert st8.nbytes == W * H * 48
+    records, depth = _cached_volume_arrays(params, records, depth)
+    rgba = np.zeros((H, W, 4), dtype=np.uint8)
+    accum = np.zeros((H, W, 3), dtype=np.float32) if want_accum else None
+    seg = np.zeros((H, W), dtype=np.uint32) if want_segments else None
+    ends = np.zeros((H, W), dtype=np.uint32) if want_ends else None
+    stt = Stats()
+    rc = lib().mort_hip_render_cached_host(world.ptr, C.byref(cam), st8.ctypes.data, nthreads, HOST_TREE if tree else 0, C.byref(params),
+                                           _ptr(records), _ptr(depth), rgba.ctypes.data, _ptr(accum), _ptr(seg), _ptr(ends), C.byref(stt))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_render_cached_host")
+    return dict(rgba=rgba, accum=accum, segments_px=seg, ends_px=ends, stats=stt.asdict(), states=st8)
 
 
 def debug_own_tree(world):
@@ -1206,15 +1315,7 @@ def _cached_arrays(params, rays, states, records, depth, want_ends):
     """the arrays of a cached radiance query: inputs as contiguous float32, the outputs new"""
     rays = _query_rays(rays)
     st8 = _query_states(states, rays)
-    probes = params.grid.probes if all(0 < c <= VOLUME_MAX_COUNT for c in params.grid.count) else None
-    if records is not None:
-        records = np.ascontiguousarray(records, dtype=np.float32)
-        if probes is not None and records.size != VOLUME_RECORD_FLOATS * probes:
-            raise ValueError(f"expected {probes} records of 32 floats")
-    if depth is not None:
-        depth = np.ascontiguousarray(depth, dtype=np.float32)
-        if probes is not None and depth.size != DEPTH_FLOATS * probes:
-            raise ValueError(f"expected {probes} depth maps of 200 floats")
+    records, depth = _cached_volume_arrays(params, records, depth)
     rgb = np.zeros((rays.shape[0], 3), dtype=np.float32)
     ends = np.zeros(rays.shape[0], dtype=np.uint32) if want_ends else None
     return rays, st8, records, depth, rgb, ends

@@ -12,6 +12,7 @@ graph), waves per SIMD that allocation allows, spilled registers, private (scrat
   * a ray-query kernel (query_closest_kernel, query_occluded_kernel) spills or uses any private memory, or
   * a radiance-query kernel (query_radiance_kernel) spills a vector register or keeps more in private memory than the bounce-stack
     levels behind its LDS part: MORT_MAX_BOUNCE_LIMIT x 16 B and one 16-byte slot, 1040 B, or
+  * a cached-frame kernel (cached_frame_kernel), the same body behind a camera, breaks that same rule, or
   * a light-probe kernel (probe_sh_kernel), which runs the same path body, breaks that same rule, or
   * an irradiance-volume kernel (volume_*, the visible sampler among them) or the depth bake
     (probe_depth_kernel, which runs the ray queries' search) spills or uses any private memory, or
@@ -45,7 +46,7 @@ finally:
     shutil.rmtree(tmp, ignore_errors=True)
 bad = []
 print(f"{'kernel':58s} {'wg':>5s} {'vgpr':>5s} {'waves/SIMD':>10s} {'v-spill':>7s} {'s-spill':>7s} {'private B':>9s} {'static LDS':>10s}")
-OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "probe_", "volume_", "math_kernel", "light_kernel", "shade_kernel", "camera_kernel", "random_float_all_kernel")
+OWN = ("mega_", "wf_", "seed_kernel", "calib_", "deinterleave", "substream", "iota_kernel", "feat_kernel", "atrous_", "tacc_", "svgf_", "query_", "cached_frame_", "probe_", "volume_", "math_kernel", "light_kernel", "shade_kernel", "camera_kernel", "random_float_all_kernel")
 for r in sorted(rows, key=lambda r: r["name"]):
     if not any(o in r["name"] for o in OWN) and "--all" not in sys.argv:
         continue  # rocPRIM's sort kernels (tile_sort.hip): listed with --all
@@ -63,6 +64,8 @@ for r in sorted(rows, key=lambda r: r["name"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the ray queries run without scratch)")
     if r["name"].startswith("query_radiance_") and (r["vspill"] or r["private"] > 1040):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the search loop must not spill; 1040 B for the deep bounce levels)")
+    if r["name"].startswith("cached_frame_") and (r["vspill"] or r["private"] > 1040):
+        bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the radiance body must not spill; 1040 B for the deep bounce levels)")
     if r["name"].startswith("probe_depth_") and (r["vspill"] or r["private"]):
         bad.append(f"{r['name']}: {r['vspill']} spilled VGPRs, {r['private']} B of private memory per lane (the depth bake runs without scratch)")
     if r["name"].startswith("probe_") and not r["name"].startswith("probe_depth_") and (r["vspill"] or r["private"] > 1040):
