@@ -677,6 +677,86 @@ int mort_hip_view_set_cache(mort_view *v, const mort_cached_frame_params *params
  * device buffers of its own; those live until the next attach or detach by either form, or the view's end */
 int mort_hip_view_set_cache_host(mort_view *v, const mort_cached_frame_params *params, const float *records, const float *depth);
 
+/* ---- volume refresh: probes re-baked through the volume and blended into their records.  The producer that uses
+ * the cache: a probe's rays are traced as cached paths that end in the volume as it stands, projected as the bake projects them,
+ * and blended into the probe's record under a hysteresis, so each round carries light one bounce further at the cost of a cached
+ * query per direction, and any subset of the probes can be refreshed between two frames.  Kernel, host loop and any restatement
+ * agree to the bit.
+ *
+ * Let P be the probes of params->cached.grid, D = params->directions, m the call's number of selected probes
+ * p_i = first + i step, i = 0 .. m - 1.
+ *   states       P D streams for the WHOLE grid, probe p direction j uses states[p D + j]; only the selected probes' streams move,
+ *                so a partial refresh leaves every other probe's streams where its last refresh left them.
+ *   records_in, records_out   P records each (MORT_VOLUME_RECORD_FLOATS floats); the call writes the m selected records of
+ *                records_out and no other byte of it.
+ *   depth        the maps, P x MORT_DEPTH_FLOATS: required with MORT_CACHED_VISIBLE in cached.flags, NULL without.
+ *   ends_out     P words or NULL, written for the selected probes only: how many of the probe's D samples paths ended in the volume.
+ *   dirs         3 D floats or NULL = mort_hip_probe_directions' set, as for the bake.
+ *
+ * For a selected probe p = (iz ny + iy) nx + ix, everything fp32 and nothing contracted:
+ *   1. if the weight records_in[p][27] is not > 0 (0, negative, NaN) the record is copied to records_out[p] bit for bit; no path
+ *      runs, no stream moves, ends_out[p] = 0.  Masking is the caller's rule, and a masked probe is usually one inside geometry.
+ *   2. position origin[a] + (float)i_a * spacing[a] per axis (the product rounded, then the sum), time grid.time:
+ *      mort_hip_volume_probes' arithmetic, computed where the probe is refreshed.
+ *   3. for direction j the ray is (position, dirs[j] exactly as given, time) and the stream states[p D + j] is advanced in place as
+ *      the bake advances it; the paths are the cached query's over records_in and depth under params->cached, word for word (its
+ *      steps 1-3 with K = cached.cache_depth, samples = cached.path.samples paths per direction, MORT_CACHED_VISIBLE honoured).
+ *   4. the projection is the light probes': the NaN guard on the direction's sum, the nine basis expressions,
+ *      term[k][ch] = Y_k * g[ch], batches of 64 summed by the balanced tree, the batch sums added in ascending order from batch 0's
+ *      sum, new[k][ch] = scale * acc with scale = (float)(4 pi / (double)(D samples)).
+ *   5. the blend, for each of the 27 floats with old = records_in[p][i]: if hysteresis == 0.0f, out = new bit for bit; otherwise
+ *      out = (h * old) + (om * new) with om = 1.0f - h rounded once per call.  Nothing is guarded: a NaN in old stays NaN for
+ *      h > 0.  Float 27, the weight, is copied bit for bit; floats 28..31 are 0.0f.
+ *   6. ends_out[p] is the sum of the directions' counts.
+ * So with hysteresis 0, K >= bounce_limit and records_in = mort_hip_volume_pack(zeros, weight) with every weight > 0, the first 27
+ * floats of every selected record and all streams equal mort_hip_probe_bake* over mort_hip_volume_probes(grid) to the bit, and
+ * the record equals mort_hip_volume_pack* of that bake; and the selected records never depend on the unselected bytes of
+ * records_out.
+ *
+ * mort_hip_probe_directions_round (plain host code) gives a direction set per refresh round: with K = 0 in a diffuse world a
+ * refresh draws no random number, so the set is the only sampling and an unrotated set would repeat its aliasing every round.
+ * Round 0 is mort_hip_probe_directions bit for bit.  Round r >= 1 is that set rotated, in double, rounded once: with v_j the
+ * library's D-point direction j in double before rounding, k = (k0, k1, k2) direction r mod 64 of the 64-point set in double before
+ * rounding, theta = (double)r * (pi * (3.0 - sqrt(5.0))), c = cos theta, s = sin theta, t = 1.0 - c, the Rodrigues matrix
+ *   R = { c + (t k0) k0,      (t k0) k1 - s k2,   (t k0) k2 + s k1 }
+ *       { (t k0) k1 + s k2,   c + (t k1) k1,      (t k1) k2 - s k0 }
+ *       { (t k0) k2 - s k1,   (t k1) k2 + s k0,   c + (t k2) k2    }
+ * and out[j][a] = (float)((R[a][0] v_j[0] + R[a][1] v_j[1]) + R[a][2] v_j[2]).
+ *
+ * Checks, in this order: NULL params, states, records_in or records_out; directions outside 64..4096 or not a multiple of 64,
+ * samples < 1; the cached calls' checks of cache_depth, flags, grid, vis and depth against the flag; hysteresis NaN, < 0 or >= 1;
+ * step == 0, or (m > 0) first + (m - 1) step >= P computed without overflow; P D above the queries' ray limit -- all
+ * MORT_ERR_INVALID.  records_out, states and ends_out are outputs, dirs, records_in and depth inputs: an output that overlaps an
+ * input or another output is MORT_ERR_INVALID -- an in-place refresh is refused on purpose, the paths of one probe would read
+ * records another workgroup is writing.  Then the bounce limit (MORT_ERR_CAPACITY), for the _device form every buffer 16-byte
+ * aligned, an uploaded world (MORT_ERR_NO_WORLD) and the light object, as for the bake.  m == 0 is MORT_OK and touches nothing.
+ * Forms, `seconds` and MORT_HOST_TREE as for the bake; the host-buffer form sends records_out up as well, so its unselected records
+ * come back as they went.  The calls ignore the partition, need no pixel RNG and touch nothing the render keeps. ---- */
+typedef struct mort_refresh_params {
+    mort_cached_params cached; /* path (samples = paths per direction), cache_depth K, flags, grid, vis: as a cached query */
+    int32_t directions;        /* D: a multiple of 64 in 64..4096, as a probe bake */
+    float hysteresis;          /* h, finite, 0 <= h < 1 */
+    uint32_t first, step;      /* the selected probes: p_i = first + i * step, i = 0 .. m - 1 */
+} mort_refresh_params;
+MORT_SA(sizeof(mort_refresh_params) == 100, "volume refresh layout");
+int mort_hip_volume_refresh(mort_ctx *ctx, const mort_refresh_params *params, size_t m, const float *dirs /* 3 D or NULL */,
+                            mort_rng_state *states /* P D */, const float *records_in, const float *depth /* or NULL */, float *records_out,
+                            uint32_t *ends_out /* P or NULL */, double *seconds);
+int mort_hip_volume_refresh_device(mort_ctx *ctx, const mort_refresh_params *params, size_t m, const void *d_dirs /* or NULL */, void *d_states,
+                                   const void *d_records_in, const void *d_depth, void *d_records_out, void *d_ends_out, void *stream,
+                                   double *seconds);
+int mort_hip_volume_refresh_host(const mort_world *world, const mort_refresh_params *params, size_t m, const float *dirs, mort_rng_state *states,
+                                 const float *records_in, const float *depth, int nthreads, int flags, float *records_out, uint32_t *ends_out,
+                                 double *seconds);
+int mort_hip_probe_directions_round(int directions, uint32_t round, float *dirs_out /* 3 D */);
+/* new records (and maps) for a view that has a cache attached: the params stay, the checks are mort_hip_view_set_cache's, the
+ * presence of depth must match the attached flag, and a view without a cache is MORT_ERR_INVALID.  The history is KEPT: set_cache
+ * forgets it because the estimator changes; a refreshed volume is the same estimator with a better cache.  The caller runs the
+ * refresh on the frames' stream into a back buffer of its own and hands the view the pointer; the _host form copies the arrays
+ * into device buffers of the view's own, as mort_hip_view_set_cache_host does. */
+int mort_hip_view_update_cache(mort_view *v, const void *d_records, const void *d_depth);
+int mort_hip_view_update_cache_host(mort_view *v, const float *records, const float *depth);
+
 /* Number of rows owned for an image of `height` rows under the current partition. */
 int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */

@@ -22,6 +22,8 @@
  *                                                          --probe X,Y[,N] (one JSON line) or every pixel's ray (--radiance-out FILE)
  *                   [--cache-render]                      with --sh-volume and --cache-depth: the frames are cached frames, renders
  *                                                          whose paths end in the volume (single GPU / host)
+ *                   [--refresh R[,H[,KR[,S]]]]            with --sh-volume: R rounds re-bake every probe through the volume and blend;
+ *                                                          with --cache-render and S > 0 every S-th probe again before each frame
  *
  * --frames N re-renders like the reference's idle loop (mort.cu:93-120): RNG streams continue from frame to frame; before each
  * frame after the first, input() runs (mort.cu:49-91) with the frame's character of --keys held down ('.' = none) and the
@@ -93,6 +95,16 @@
  * the render's own plus cache_depth, ends (the paths of the last frame that ended in the volume) and the volume's parameters.
  * Without --cache-render every accepted and refused combination and every output byte is what it was.
  *
+ * --refresh R[,H[,KR[,S]]] (with --sh-volume only, under every use it has): after the bake (and the maps), R rounds of
+ * mort_hip_volume_refresh (or its _host form) follow.  Round r = 1 .. R refreshes every probe (first 0, step 1)
+ * with hysteresis H (default 0.9, 0 <= H < 1), refresh depth KR (default 0, in 0..MORT_MAX_BOUNCE_LIMIT), --sh-volume's D and N, and
+ * the direction set mort_hip_probe_directions_round(D, r); the bake's streams are carried on and the records ping-pong between two
+ * buffers.  With --cache-render and S > 0 (default 0; S > 0 needs --cache-render), before every frame f >= 1 one more round runs
+ * over the probes first = f mod S, step = S with the set of round R + f, and the view takes the records by
+ * mort_hip_view_update_cache_host (its history goes on).  The JSON line gains refresh_rounds, hysteresis, refresh_depth,
+ * refresh_stride and refresh_ends (the paths of the last full round that ended in the volume; 0 for R = 0).  Without --refresh
+ * every accepted and refused combination and every output byte is what it was.
+ *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
  * RCCL (`--gather rccl`, the default: xGMI inside a node), or through a shared host mapping (`--gather shm`: for ranks
@@ -138,10 +150,12 @@ static int usage(void) {
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
            "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
            "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]] "
-           "[--cache-depth K] [--radiance-out FILE] [--cache-render]\n"
+           "[--cache-depth K] [--radiance-out FILE] [--cache-render] [--refresh R[,H[,KR[,S]]]]\n"
            "  --cache-depth K with --sh-volume: paths end in the volume from bounce K on; --probe X,Y[,N] prints one pixel's colour,\n"
            "  --radiance-out FILE writes a preview from pixel-centre rays (--spp paths each; no jitter, no lens), not a render,\n"
-           "  --cache-render renders: the ordinary frame loop (--frames, --out, --temporal, --svgf, ...) over cached frames\n");
+           "  --cache-render renders: the ordinary frame loop (--frames, --out, --temporal, --svgf, ...) over cached frames\n"
+           "  --refresh R[,H[,KR[,S]]] with --sh-volume: R rounds re-bake every probe through the volume (hysteresis H, refresh depth KR);\n"
+           "  with --cache-render and S > 0 every S-th probe is refreshed again before each frame\n");
     return -1;
 }
 
@@ -209,6 +223,56 @@ static int volume_grid(const float box[6], const int n[3], mort_volume_grid *gri
     return 0;
 }
 
+/* --refresh R[,H[,KR[,S]]]: rounds of the volume refresh over a baked volume */
+typedef struct {
+    int on, rounds, depth, stride;
+    float h;
+    unsigned long long ends; /* the paths of the last full round that ended in the volume */
+} refresh_opts;
+
+/* one round over the probes first, first + step, ... with the direction set of round `round`: from `in` into `out`, the streams
+ * carried on; ctx NULL: the host form.  *ends_sum (or NULL): the selected probes' counts */
+static void refresh_round(mort_ctx *ctx, const mort_world *world, const mort_camera *cam, const refresh_opts *ro, const mort_volume_grid *grid,
+                          uint32_t flags, const mort_volume_vis_params *vis, int sh_d, int sh_n, uint32_t round, uint32_t first, uint32_t step,
+                          mort_rng_state *states, const float *in, const float *depth, float *out, int threads, int host_flags,
+                          unsigned long long *ends_sum) {
+    const size_t n = (size_t)grid->count[0] * (size_t)grid->count[1] * (size_t)grid->count[2];
+    const size_t m = first < n ? (n - 1 - first) / step + 1 : 0;
+    mort_refresh_params rp;
+    memset(&rp, 0, sizeof rp);
+    mort_hip_radiance_params_from_camera(cam, &rp.cached.path);
+    rp.cached.path.samples = sh_n;
+    rp.cached.cache_depth = ro->depth; rp.cached.flags = flags; rp.cached.grid = *grid; rp.cached.vis = *vis;
+    rp.directions = sh_d; rp.hysteresis = ro->h; rp.first = first; rp.step = step;
+    float *dirs = (float *)malloc(3 * (size_t)sh_d * sizeof *dirs);
+    uint32_t *ends = (uint32_t *)calloc(n, sizeof *ends);
+    if (!dirs || !ends) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    int st;
+    if ((st = mort_hip_probe_directions_round(sh_d, round, dirs)) != MORT_OK) die(NULL, st, "mort_hip_probe_directions_round");
+    if (!ctx) {
+        if ((st = mort_hip_volume_refresh_host(world, &rp, m, dirs, states, in, depth, threads, host_flags, out, ends, NULL)) != MORT_OK) die(NULL, st, "mort_hip_volume_refresh_host");
+    } else if ((st = mort_hip_volume_refresh(ctx, &rp, m, dirs, states, in, depth, out, ends, NULL)) != MORT_OK) die(ctx, st, "mort_hip_volume_refresh");
+    if (ends_sum) { *ends_sum = 0; for (size_t i = 0; i < m; i++) *ends_sum += ends[first + i * step]; }
+    free(dirs); free(ends);
+}
+
+/* rounds 1 .. R over every probe; the records ping-pong between `a` (the bake's) and `b`: returns the one that holds the last round's */
+static float *refresh_all(mort_ctx *ctx, const mort_world *world, const mort_camera *cam, refresh_opts *ro, const mort_volume_grid *grid, uint32_t flags,
+                          const mort_volume_vis_params *vis, int sh_d, int sh_n, mort_rng_state *states, float *a, float *b, const float *depth,
+                          int threads, int host_flags) {
+    for (int r = 1; r <= ro->rounds; r++) {
+        refresh_round(ctx, world, cam, ro, grid, flags, vis, sh_d, sh_n, (uint32_t)r, 0, 1, states, a, depth, b, threads, host_flags, &ro->ends);
+        float *t = a; a = b; b = t;
+    }
+    return a;
+}
+
+static void print_refresh(const refresh_opts *ro) {
+    if (!ro->on) return;
+    printf(", \"refresh_rounds\": %d, \"hysteresis\": ", ro->rounds); print_f32(ro->h);
+    printf(", \"refresh_depth\": %d, \"refresh_stride\": %d, \"refresh_ends\": %llu", ro->depth, ro->stride, ro->ends);
+}
+
 /* --cache-render: the volume a cached frame ends its paths in, baked as the no-render uses of --sh-volume bake it (D directions, N
  * paths, the scene camera's parameters, the streams subsequences 0 .. probes D - 1 of the seed; all weights 1; with --visibility
  * the depth maps, S x S rays per texel, max_distance 1.5 cell diagonals) */
@@ -218,9 +282,11 @@ typedef struct {
     float *records, *depth; /* host; depth NULL without --visibility */
     size_t probes;
     double bake_sec;
+    float *back;            /* --refresh: the buffer the next round writes, and the bake's streams carried on; else NULL */
+    mort_rng_state *states;
 } cache_volume;
 static void bake_cache_volume(cache_volume *v, mort_ctx *ctx /* NULL: the host forms */, const mort_world *world, const mort_camera *cam,
-                              unsigned long long seed, int sh_d, int sh_n, int vis_s, int threads, int host_flags) {
+                              unsigned long long seed, int sh_d, int sh_n, int vis_s, int threads, int host_flags, refresh_opts *ro) {
     const mort_volume_grid *g = &v->p.grid;
     const int visible = (v->p.flags & MORT_CACHED_VISIBLE) != 0;
     const size_t n = v->probes = (size_t)g->count[0] * (size_t)g->count[1] * (size_t)g->count[2];
@@ -249,7 +315,24 @@ static void bake_cache_volume(cache_volume *v, mort_ctx *ctx /* NULL: the host f
         if ((st = mort_hip_volume_pack(ctx, n, sh, NULL, v->records, NULL)) != MORT_OK) die(ctx, st, "mort_hip_volume_pack");
         if (visible && (st = mort_hip_probe_depth_bake(ctx, &v->dp, n, probes, v->depth, NULL)) != MORT_OK) die(ctx, st, "mort_hip_probe_depth_bake");
     }
-    free(probes); free(states); free(sh);
+    free(probes); free(sh);
+    if (!ro->on) { free(states); return; }
+    v->states = states;
+    float *second = (float *)malloc(n * MORT_VOLUME_RECORD_FLOATS * sizeof(float));
+    if (!second) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    float *now = refresh_all(ctx, world, cam, ro, g, v->p.flags, &v->p.vis, sh_d, sh_n, states, v->records, second, v->depth, threads, host_flags);
+    v->back = now == v->records ? second : v->records;
+    v->records = now;
+}
+
+/* --refresh ...,S with --cache-render, before frame f >= 1: the probes f mod S, f mod S + S, ... once more, into the back buffer (which
+ * first takes the other records as they stand), and the buffers change places */
+static void refresh_before_frame(cache_volume *v, mort_ctx *ctx, const mort_world *world, const mort_camera *cam, const refresh_opts *ro, int sh_d,
+                                 int sh_n, int f, int threads, int host_flags) {
+    memcpy(v->back, v->records, v->probes * MORT_VOLUME_RECORD_FLOATS * sizeof(float));
+    refresh_round(ctx, world, cam, ro, &v->p.grid, v->p.flags, &v->p.vis, sh_d, sh_n, (uint32_t)(ro->rounds + f), (uint32_t)(f % ro->stride),
+                  (uint32_t)ro->stride, v->states, v->records, v->depth, v->back, threads, host_flags, NULL);
+    float *t = v->records; v->records = v->back; v->back = t;
 }
 
 /* input() before frame f (mort.cu:49-91,94): the f-th character of --keys held down, the --mouse delta dragged */
@@ -284,6 +367,9 @@ int main(int argc, char **argv) {
     int cached = 0, cache_depth = 0;
     const char *rad_out = NULL;
     int cache_render = 0;
+    refresh_opts refresh;
+    memset(&refresh, 0, sizeof refresh);
+    refresh.h = 0.9f;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -340,6 +426,10 @@ int main(int argc, char **argv) {
         else if (ARG("--cache-depth")) { cached = 1; if (sscanf(argv[++i], "%d", &cache_depth) != 1) { fprintf(stderr, "--cache-depth K\n"); return -1; } }
         else if (ARG("--radiance-out")) rad_out = argv[++i];
         else if (strcmp(argv[i], "--cache-render") == 0) cache_render = 1;
+        else if (ARG("--refresh")) {
+            refresh.on = 1;
+            if (sscanf(argv[++i], "%d,%f,%d,%d", &refresh.rounds, &refresh.h, &refresh.depth, &refresh.stride) < 1) { fprintf(stderr, "--refresh R[,H[,KR[,S]]]\n"); return -1; }
+        }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return usage(); }
     }
     if (gpus < 1 || gpus > 64 || frames < 1 || threads < 1) { fprintf(stderr, "bad --gpus / --frames / --threads\n"); return -1; }
@@ -371,6 +461,11 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--visibility: BIAS finite and >= 0, MINVIS in 0..1, S in 1..%d\n", MORT_DEPTH_RES); return -1;
     }
     if (irr_out && !sh_volume) { fprintf(stderr, "--irradiance-out needs --sh-volume\n"); return -1; }
+    if (refresh.on && !sh_volume) { fprintf(stderr, "--refresh needs --sh-volume\n"); return -1; }
+    if (refresh.on && (refresh.rounds < 0 || refresh.rounds > 65535 || !(refresh.h >= 0.0f) || !(refresh.h < 1.0f) || refresh.depth < 0 ||
+                       refresh.depth > MORT_MAX_BOUNCE_LIMIT || refresh.stride < 0 || (refresh.stride > 0 && !cache_render))) {
+        fprintf(stderr, "--refresh: R in 0..65535, H in [0, 1), KR in 0..%d, S >= 0 and S > 0 only with --cache-render\n", MORT_MAX_BOUNCE_LIMIT); return -1;
+    }
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;
@@ -415,6 +510,8 @@ int main(int argc, char **argv) {
         mort_rng_state *states = (mort_rng_state *)malloc(probes_n * (size_t)sh_d * sizeof *states); /* subsequences 0 .. probes D - 1, probe-major */
         float *sh = (float *)malloc(probes_n * MORT_SH9_FLOATS * sizeof *sh);
         float *records = (float *)malloc(probes_n * MORT_VOLUME_RECORD_FLOATS * sizeof *records);
+        float *records2 = refresh.on ? (float *)malloc(probes_n * MORT_VOLUME_RECORD_FLOATS * sizeof *records2) : NULL; /* --refresh: the other buffer */
+        float *volume = records; /* the records that are sampled: the bake's, or the last round's */
         mort_ray *rays = (mort_ray *)malloc(nq * sizeof *rays);
         mort_hit *hits = (mort_hit *)malloc(nq * sizeof *hits);
         float *irr = (float *)malloc(nq * 4 * sizeof *irr);
@@ -425,7 +522,7 @@ int main(int argc, char **argv) {
                                              (double)grid.spacing[2] * (double)grid.spacing[2]));
         mort_volume_vis_params vp;
         vp.normal_bias = vis_bias; vp.min_visibility = vis_min;
-        if (visibility && !depth) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+        if ((visibility && !depth) || (refresh.on && !records2)) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
         if (!probes || !states || !sh || !records || !rays || !hits || !irr || probes_n * (size_t)sh_d > 0x7fffffffu) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
         if ((pst = mort_hip_volume_probes(&grid, probes)) != MORT_OK) die(NULL, pst, "mort_hip_volume_probes");
         if ((pst = mort_hip_rng_seed_host(seed, (int)(probes_n * (size_t)sh_d), 1, states)) != MORT_OK) die(NULL, pst, "mort_hip_rng_seed_host");
@@ -459,12 +556,13 @@ int main(int argc, char **argv) {
             if ((pst = mort_hip_volume_pack_host(probes_n, sh, NULL, threads, records, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_volume_pack_host");
             if (!cached && (pst = mort_hip_query_closest_host(&world, nq, rays, NULL, threads, fl, hits, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_closest_host");
             if (visibility && (pst = mort_hip_probe_depth_bake_host(&world, &dp, probes_n, probes, threads, fl, depth, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_probe_depth_bake_host");
+            if (refresh.on) volume = refresh_all(NULL, &world, &cam, &refresh, &grid, cp.flags, &vp, sh_d, sh_n, states, records, records2, depth, threads, fl);
             if (cached) {
-                if ((pst = mort_hip_query_radiance_cached_host(&world, &cp, nq, rays, qstates, records, depth, threads, fl, rgb, ends, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_radiance_cached_host");
+                if ((pst = mort_hip_query_radiance_cached_host(&world, &cp, nq, rays, qstates, volume, depth, threads, fl, rgb, ends, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_radiance_cached_host");
             } else if (visibility) {
-                if ((pst = mort_hip_volume_sample_visible_host(&grid, records, depth, &vp, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_visible_host");
+                if ((pst = mort_hip_volume_sample_visible_host(&grid, volume, depth, &vp, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_visible_host");
             } else
-            if ((pst = mort_hip_volume_sample_host(&grid, records, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_host");
+            if ((pst = mort_hip_volume_sample_host(&grid, volume, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_host");
         } else {
             mort_ctx *pctx = NULL;
             if ((pst = mort_hip_init(device, &pctx)) != MORT_OK) die(NULL, pst, "mort_hip_init");
@@ -473,12 +571,13 @@ int main(int argc, char **argv) {
             if ((pst = mort_hip_volume_pack(pctx, probes_n, sh, NULL, records, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_volume_pack");
             if (!cached && (pst = mort_hip_query_closest(pctx, nq, rays, NULL, hits, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_closest");
             if (visibility && (pst = mort_hip_probe_depth_bake(pctx, &dp, probes_n, probes, depth, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_probe_depth_bake");
+            if (refresh.on) volume = refresh_all(pctx, &world, &cam, &refresh, &grid, cp.flags, &vp, sh_d, sh_n, states, records, records2, depth, threads, 0);
             if (cached) {
-                if ((pst = mort_hip_query_radiance_cached(pctx, &cp, nq, rays, qstates, records, depth, rgb, ends, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_radiance_cached");
+                if ((pst = mort_hip_query_radiance_cached(pctx, &cp, nq, rays, qstates, volume, depth, rgb, ends, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_radiance_cached");
             } else if (visibility) {
-                if ((pst = mort_hip_volume_sample_visible(pctx, &grid, records, depth, &vp, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample_visible");
+                if ((pst = mort_hip_volume_sample_visible(pctx, &grid, volume, depth, &vp, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample_visible");
             } else
-            if ((pst = mort_hip_volume_sample(pctx, &grid, records, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample");
+            if ((pst = mort_hip_volume_sample(pctx, &grid, volume, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample");
             mort_hip_shutdown(pctx);
         }
         if (cached) {
@@ -513,6 +612,7 @@ int main(int argc, char **argv) {
                 printf(", \"min_visibility\": "); print_f32(vp.min_visibility);
                 printf(", \"depth_subsamples\": %d, \"max_distance\": ", dp.subsamples); print_f32(dp.max_distance);
             }
+            print_refresh(&refresh);
             printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"probe_samples\": %d, \"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f}\n",
                    (int)grid.count[0], (int)grid.count[1], (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec);
             free(qstates); free(rgb); free(ends);
@@ -535,6 +635,7 @@ int main(int argc, char **argv) {
                 printf(", \"min_visibility\": "); print_f32(vp.min_visibility);
                 printf(", \"depth_subsamples\": %d, \"max_distance\": ", dp.subsamples); print_f32(dp.max_distance);
             }
+            print_refresh(&refresh);
             printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"samples\": %d, \"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f, \"sample_seconds\": %.6f}\n",
                    (int)grid.count[0], (int)grid.count[1], (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec, sample_sec);
         } else {
@@ -560,10 +661,11 @@ int main(int argc, char **argv) {
                 printf(", \"min_visibility\": "); print_f32(vp.min_visibility);
                 printf(", \"depth_subsamples\": %d, \"max_distance\": ", dp.subsamples); print_f32(dp.max_distance);
             }
+            print_refresh(&refresh);
             printf("}\n");
         }
         }
-        free(probes); free(states); free(sh); free(records); free(rays); free(hits); free(irr); free(depth);
+        free(probes); free(states); free(sh); free(records); free(records2); free(rays); free(hits); free(irr); free(depth);
         mort_world_free(&world);
         free(texels);
         return 0;
@@ -747,9 +849,10 @@ int main(int argc, char **argv) {
             if (!f || fread(hstates, sizeof *hstates, npx, f) != npx) { fprintf(stderr, "cannot read %zu states from %s\n", npx, sin); return EXIT_FAILURE; }
             fclose(f);
         } else if ((st = mort_hip_rng_seed_host(seed, W, H, hstates)) != MORT_OK) die(NULL, st, "mort_hip_rng_seed_host");
-        if (cache_render) bake_cache_volume(&cv, NULL, &world, &cam, seed, sh_d, sh_n, vis_s, threads, tree ? MORT_HOST_TREE : 0);
+        if (cache_render) bake_cache_volume(&cv, NULL, &world, &cam, seed, sh_d, sh_n, vis_s, threads, tree ? MORT_HOST_TREE : 0, &refresh);
         for (int f = 0; f < frames; f++) {
             if (f > 0) frame_input(&cam, keys, f, mouse_dx, mouse_dy);
+            if (f > 0 && cache_render && refresh.stride > 0) refresh_before_frame(&cv, NULL, &world, &cam, &refresh, sh_d, sh_n, f, threads, tree ? MORT_HOST_TREE : 0);
             if (cache_render) {
                 if ((st = mort_hip_render_cached_host(&world, &cam, hstates, threads, tree ? MORT_HOST_TREE : 0, &cv.p, cv.records, cv.depth, rgba, accum, NULL,
                                                       ends_px, &stats)) != MORT_OK) die(NULL, st, "mort_hip_render_cached_host");
@@ -801,11 +904,15 @@ int main(int argc, char **argv) {
             if ((st = mort_hip_view_create(ctx, &vp, &view)) != MORT_OK) die(ctx, st, "mort_hip_view_create");
         }
         if (cache_render) { /* the volume baked on this context; the view keeps its own device copies of the records and maps */
-            bake_cache_volume(&cv, ctx, &world, &cam, seed, sh_d, sh_n, vis_s, threads, 0);
+            bake_cache_volume(&cv, ctx, &world, &cam, seed, sh_d, sh_n, vis_s, threads, 0, &refresh);
             if ((st = mort_hip_view_set_cache_host(view, &cv.p, cv.records, cv.depth)) != MORT_OK) die(ctx, st, "mort_hip_view_set_cache_host");
         }
         for (int f = 0; f < frames; f++) {
             if (f > 0) frame_input(&cam, keys, f, mouse_dx, mouse_dy);
+            if (f > 0 && cache_render && refresh.stride > 0) { /* some probes once more; the view takes the records and keeps its history */
+                refresh_before_frame(&cv, ctx, &world, &cam, &refresh, sh_d, sh_n, f, threads, 0);
+                if ((st = mort_hip_view_update_cache_host(view, cv.records, cv.depth)) != MORT_OK) die(ctx, st, "mort_hip_view_update_cache_host");
+            }
             const double t0 = now_s();
             if (view && (temporal || cache_render || f == frames - 1)) { /* render, features, temporal step and filter on the device; the frame's uchar4
                                                           * comes back.  Without --temporal only the last frame is filtered or written:
@@ -934,6 +1041,7 @@ int main(int argc, char **argv) {
             printf(", \"min_visibility\": "); print_f32(cv.p.vis.min_visibility);
             printf(", \"depth_subsamples\": %d, \"max_distance\": ", cv.dp.subsamples); print_f32(cv.dp.max_distance);
         }
+        print_refresh(&refresh);
         printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"probe_samples\": %d, \"bake_seconds\": %.6f", (int)cv.p.grid.count[0], (int)cv.p.grid.count[1],
                (int)cv.p.grid.count[2], sh_d, sh_n, cv.bake_sec);
     }
@@ -954,6 +1062,6 @@ int main(int argc, char **argv) {
     }
     if (ctx) mort_hip_shutdown(ctx);
     mort_world_free(&world);
-    free(texels); free(rgba); free(accum); free(hstates); free(ends_px); free(cv.records); free(cv.depth);
+    free(texels); free(rgba); free(accum); free(hstates); free(ends_px); free(cv.records); free(cv.depth); free(cv.back); free(cv.states);
     return 0;
 }

@@ -62,6 +62,9 @@ bool mort_cached_volume_ok(int32_t cache_depth, uint32_t flags, const mort_volum
 void mort_cached_volume(VolumeArgs &v, const mort_volume_grid &grid, const void *records);
 void mort_cached_volume(VolumeVisArgs &v, const mort_volume_grid &grid, const mort_volume_vis_params &vis, const void *records, const void *depth);
 
+/* probe.hip: the context's device copy of the library's own set of D directions, for the volume refresh (refresh.hip) */
+int mort_probe_own_directions(mort_ctx *c, int D, hipStream_t s, const float **d_dirs);
+
 /* view.hip: mort_hip_shutdown frees the views still alive on the context */
 void mort_views_free(mort_ctx *c);
 

@@ -180,6 +180,8 @@ void launch_probes(const ProbeArgs &a, hipStream_t s) {
 
 } // namespace
 
+int mort_probe_own_directions(mort_ctx *c, int D, hipStream_t s, const float **d_dirs) { return own_directions(c, D, s, d_dirs); }
+
 extern "C" int mort_hip_probe_directions(int directions, float *dirs_out) {
     if (!dirs_out || !directions_ok(directions)) return MORT_ERR_INVALID;
     fibonacci_directions(directions, dirs_out);

@@ -292,20 +292,52 @@ int free_own_cache(mort_view *v) {
 }
 } // namespace
 
+namespace {
+/* device copies of a caller's host records and maps (depth may be null), for the _host forms of set_cache and update_cache */
+int upload_cache(mort_view *v, const mort_volume_grid &grid, const float *records, const float *depth, void **d_rec, void **d_dep, const char *what) {
+    mort_ctx *c = v->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t probes = (size_t)grid.count[0] * (size_t)grid.count[1] * (size_t)grid.count[2];
+    const size_t rb = probes * MORT_VOLUME_RECORD_FLOATS * sizeof(float), db = probes * MORT_DEPTH_FLOATS * sizeof(float);
+    *d_rec = *d_dep = nullptr;
+    hipError_t e = hipMalloc(d_rec, rb);
+    if (e == hipSuccess) e = hipMemcpy(*d_rec, records, rb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && depth) e = hipMalloc(d_dep, db);
+    if (e == hipSuccess && depth) e = hipMemcpy(*d_dep, depth, db, hipMemcpyHostToDevice);
+    return e == hipSuccess ? MORT_OK : e == hipErrorOutOfMemory ? ((void)hipGetLastError(), MORT_ERR_NOMEM) : hip_fail(c, e, what);
+}
+} // namespace
+
 extern "C" int mort_hip_view_set_cache_host(mort_view *v, const mort_cached_frame_params *p, const float *records, const float *depth) {
     if (!v || !p) return MORT_ERR_INVALID;
     if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, records, depth)) return MORT_ERR_INVALID;
-    mort_ctx *c = v->ctx;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t probes = (size_t)p->grid.count[0] * (size_t)p->grid.count[1] * (size_t)p->grid.count[2];
-    const size_t rb = probes * MORT_VOLUME_RECORD_FLOATS * sizeof(float), db = probes * MORT_DEPTH_FLOATS * sizeof(float);
     void *d_rec = nullptr, *d_dep = nullptr;
-    hipError_t e = hipMalloc(&d_rec, rb);
-    if (e == hipSuccess) e = hipMemcpy(d_rec, records, rb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && depth) e = hipMalloc(&d_dep, db);
-    if (e == hipSuccess && depth) e = hipMemcpy(d_dep, depth, db, hipMemcpyHostToDevice);
-    int st = e == hipSuccess ? MORT_OK : e == hipErrorOutOfMemory ? ((void)hipGetLastError(), MORT_ERR_NOMEM) : hip_fail(c, e, "mort_hip_view_set_cache_host");
+    int st = upload_cache(v, p->grid, records, depth, &d_rec, &d_dep, "mort_hip_view_set_cache_host");
     if (st == MORT_OK) st = mort_hip_view_set_cache(v, p, d_rec, d_dep); /* frees the copies of an earlier call */
+    if (st != MORT_OK) { (void)hipFree(d_rec); (void)hipFree(d_dep); return st; }
+    v->own_records = d_rec; v->own_depth = d_dep;
+    return MORT_OK;
+}
+
+/* new records and maps under the attached params; the history goes on */
+extern "C" int mort_hip_view_update_cache(mort_view *v, const void *d_records, const void *d_depth) {
+    if (!v || !v->cached) return MORT_ERR_INVALID;
+    const mort_cached_frame_params *p = &v->cache;
+    if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, d_records, d_depth)) return MORT_ERR_INVALID;
+    if (((uintptr_t)d_records & 15u) || ((uintptr_t)d_depth & 15u)) return MORT_ERR_INVALID;
+    const int st = free_own_cache(v); /* whatever is attached now replaces them */
+    if (st != MORT_OK) return st;
+    v->d_records = d_records; v->d_cache_depth = d_depth;
+    return MORT_OK;
+}
+
+extern "C" int mort_hip_view_update_cache_host(mort_view *v, const float *records, const float *depth) {
+    if (!v || !v->cached) return MORT_ERR_INVALID;
+    const mort_cached_frame_params *p = &v->cache;
+    if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, records, depth)) return MORT_ERR_INVALID;
+    void *d_rec = nullptr, *d_dep = nullptr;
+    int st = upload_cache(v, p->grid, records, depth, &d_rec, &d_dep, "mort_hip_view_update_cache_host");
+    if (st == MORT_OK) st = mort_hip_view_update_cache(v, d_rec, d_dep); /* frees the copies of an earlier call */
     if (st != MORT_OK) { (void)hipFree(d_rec); (void)hipFree(d_dep); return st; }
     v->own_records = d_rec; v->own_depth = d_dep;
     return MORT_OK;

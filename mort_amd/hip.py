@@ -44,6 +44,8 @@ EXPORTS = [
     "mort_hip_query_radiance_cached", "mort_hip_query_radiance_cached_device", "mort_hip_query_radiance_cached_host",
     "mort_hip_render_cached", "mort_hip_render_cached_device", "mort_hip_render_cached_host", "mort_hip_view_set_cache",
     "mort_hip_view_set_cache_host",
+    "mort_hip_volume_refresh", "mort_hip_volume_refresh_device", "mort_hip_volume_refresh_host", "mort_hip_probe_directions_round",
+    "mort_hip_view_update_cache", "mort_hip_view_update_cache_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -160,6 +162,23 @@ class CACHED_FRAME_PARAMS(C.Structure):
         self.cache_depth = cache_depth
         self.vis.normal_bias, self.vis.min_visibility = (vis.normal_bias, vis.min_visibility) if vis is not None else (0.0, 0.0)
         self.flags = CACHED_VISIBLE if vis is not None else 0
+
+
+class REFRESH_PARAMS(C.Structure):
+    """mort_refresh_params of include/mort_hip.h: the probes first, first + step, ... of cached.grid re-baked through the volume
+    (cached: CACHED_PARAMS, its path.samples the paths per direction) along `directions` directions and blended under `hysteresis`"""
+    _fields_ = [("cached", CACHED_PARAMS), ("directions", C.c_int32), ("hysteresis", C.c_float), ("first", C.c_uint32), ("step", C.c_uint32)]
+
+    def __init__(self, cached=None, directions=256, hysteresis=0.9, first=0, step=1):
+        super().__init__()
+        if cached is not None:
+            C.memmove(C.byref(self.cached), C.byref(cached), C.sizeof(CACHED_PARAMS))
+        self.directions, self.hysteresis, self.first, self.step = directions, hysteresis, first, step
+
+    def selected(self):
+        """how many probes first, first + step, ... the grid holds"""
+        P = self.cached.grid.probes
+        return (P - 1 - self.first) // self.step + 1 if self.step and self.first < P else 0
 
 
 class Partition(C.Structure):
@@ -370,6 +389,14 @@ def lib():
         L.mort_hip_render_cached_host.restype = C.c_int
         L.mort_hip_view_set_cache.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache.restype = C.c_int
         L.mort_hip_view_set_cache_host.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache_host.restype = C.c_int
+        xp = C.POINTER(REFRESH_PARAMS)
+        L.mort_hip_volume_refresh.argtypes = [ctx, xp, sz, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_volume_refresh.restype = C.c_int
+        L.mort_hip_volume_refresh_device.argtypes = [ctx, xp, sz, vp, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_volume_refresh_device.restype = C.c_int
+        L.mort_hip_volume_refresh_host.argtypes = [wd, xp, sz, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, dp]
+        L.mort_hip_volume_refresh_host.restype = C.c_int
+        L.mort_hip_probe_directions_round.argtypes = [C.c_int, C.c_uint32, vp]; L.mort_hip_probe_directions_round.restype = C.c_int
+        L.mort_hip_view_update_cache.argtypes = [view, vp, vp]; L.mort_hip_view_update_cache.restype = C.c_int
+        L.mort_hip_view_update_cache_host.argtypes = [view, vp, vp]; L.mort_hip_view_update_cache_host.restype = C.c_int
         _lib = L
     return _lib
 
@@ -698,6 +725,42 @@ class Context:
                                                       dptr(ends), stream, C.byref(st) if sync else None), "mort_hip_render_cached_device")
         return st.asdict() if sync else None
 
+    def volume_refresh(self, params, states, records_in, depth=None, records_out=None, ends=True, dirs=None, m=None):
+        """A volume refresh on the GPU (mort_hip_volume_refresh): params REFRESH_PARAMS; states the P * D 48-byte streams of the whole
+        grid, advanced IN PLACE for the selected probes; records_in float32 (P, 32), depth float32 (P, 200) with CACHED_VISIBLE and
+        None without; records_out a writeable float32 (P, 32) whose selected records are written in place, or None for a new array
+        of zeros; ends a writeable uint32 (P,) written in place, True for a new one, None for no counts; dirs as for probe_bake;
+        m the number of selected probes, None = as many as the grid holds.  dict(records, ends, seconds)."""
+        m, dirs, records_in, depth, records_out, ends = _refresh_arrays(params, states, records_in, depth, records_out, ends, dirs, m)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_volume_refresh(self._h, C.byref(params), m, _ptr(dirs), _ptr(states), _ptr(records_in), _ptr(depth),
+                                                _ptr(records_out), _ptr(ends), C.byref(sec)), "mort_hip_volume_refresh")
+        return dict(records=records_out, ends=ends, seconds=sec.value)
+
+    def volume_refresh_device(self, params, states, records_in, depth, records_out, ends=None, dirs=None, m=None, sync=False):
+        """The refresh on torch tensors on this context's device, on the current torch stream: states of at least 48 P D bytes,
+        records_in of 128 P and depth (or None) of 800 P bytes, records_out of at least 128 P and ends (or None) of at least 4 P
+        bytes, written from their heads, dirs None or float32 of 3 D elements.  Asynchronous unless sync (then returns the device
+        seconds) or torch runs on its legacy default stream."""
+        import torch
+        P, D = params.cached.grid.probes, params.directions
+        if records_in.device.type != "cuda":
+            raise ValueError("expected tensors on the GPU")
+        for t, size, exact in ((states, 48 * P * D, False), (records_in, 128 * P, True), (depth, 4 * DEPTH_FLOATS * P, True),
+                               (records_out, 128 * P, False), (ends, 4 * P, False), (dirs, 12 * D, True)):
+            if t is None:
+                continue
+            have = t.numel() * t.element_size()
+            if not t.is_contiguous() or t.device != records_in.device or (have != size if exact else have < size):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {records_in.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, records_in.device, sync)
+        dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._chk(lib().mort_hip_volume_refresh_device(self._h, C.byref(params), params.selected() if m is None else m, dptr(dirs), dptr(states),
+                                                       dptr(records_in), dptr(depth), dptr(records_out), dptr(ends), stream,
+                                                       C.byref(sec) if sync else None), "mort_hip_volume_refresh_device")
+        return sec.value if sync else None
+
     def probe_bake(self, params, probes, states, dirs=None):
         """SH9 light probes on the GPU (mort_hip_probe_bake): params PROBE_PARAMS, probes PROBE_DTYPE (n,) or float32 (n, 4) =
         position, time; states n * D 48-byte XORWOW streams, advanced IN PLACE; dirs None = the library's own set, else float32
@@ -905,6 +968,19 @@ class View:
         self.ctx._chk(lib().mort_hip_view_set_cache(self._handle(), C.byref(params) if params is not None else None, dptr(records), dptr(depth)),
                       "mort_hip_view_set_cache")
         self._cache = (records, depth) if params is not None else None
+
+    def update_cache(self, records, depth=None):
+        """New records and maps for the attached cache, under the same params (mort_hip_view_update_cache[_host]): torch tensors on
+        the GPU, kept alive by the view, or numpy arrays, which the view copies to the device.  The history is kept."""
+        if isinstance(records, np.ndarray):
+            records = np.ascontiguousarray(records, dtype=np.float32)
+            depth = np.ascontiguousarray(depth, dtype=np.float32) if depth is not None else None
+            self.ctx._chk(lib().mort_hip_view_update_cache_host(self._handle(), _ptr(records), _ptr(depth)), "mort_hip_view_update_cache_host")
+            self._cache = None
+            return
+        dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.ctx._chk(lib().mort_hip_view_update_cache(self._handle(), dptr(records), dptr(depth)), "mort_hip_view_update_cache")
+        self._cache = (records, depth)
 
     def frame(self, cam, mode=MODE_MEGA):
         """One frame, one host wait: dict(rgba (H, W, 4) u8, stats)."""
@@ -1331,6 +1407,52 @@ def query_radiance_cached_host(world, params, rays, states, records, depth=None,
     if rc != 0:
         raise MortHipError(rc, "mort_hip_query_radiance_cached_host")
     return dict(rgb=rgb, ends=ends, seconds=sec.value)
+
+
+def _refresh_arrays(params, states, records_in, depth, records_out, ends, dirs, m):
+    """the arrays of a volume refresh: inputs as contiguous float32, the outputs the caller's own (written in place) or new"""
+    sized = all(0 < c <= VOLUME_MAX_COUNT for c in params.cached.grid.count)
+    P = params.cached.grid.probes if sized else 0
+    records_in, depth = _cached_volume_arrays(params.cached, records_in, depth)
+    dirs = _probe_dirs(dirs, params.directions)
+    if states is not None and not (isinstance(states, np.ndarray) and states.flags.c_contiguous and states.flags.writeable):
+        raise ValueError("expected a contiguous writeable array of 48-byte streams")
+    if sized and states is not None and 0 < params.directions <= 4096 and states.nbytes != 48 * P * params.directions:
+        raise ValueError(f"expected {P * params.directions} 48-byte streams")
+    if records_out is None:
+        records_out = np.zeros((P, VOLUME_RECORD_FLOATS), dtype=np.float32)
+    elif not (isinstance(records_out, np.ndarray) and records_out.dtype == np.float32 and records_out.flags.c_contiguous and
+              records_out.flags.writeable and (not sized or records_out.size == VOLUME_RECORD_FLOATS * P)):
+        raise ValueError(f"expected a contiguous writeable float32 array of {P} records of 32 floats")
+    if ends is True:
+        ends = np.zeros(P, dtype=np.uint32)
+    elif ends is False:
+        ends = None
+    elif ends is not None and not (isinstance(ends, np.ndarray) and ends.dtype == np.uint32 and ends.flags.c_contiguous and ends.flags.writeable and
+                                   (not sized or ends.size == P)):
+        raise ValueError(f"expected a contiguous writeable uint32 array of {P} counts")
+    return (params.selected() if m is None else m), dirs, records_in, depth, records_out, ends
+
+
+def volume_refresh_host(world, params, states, records_in, depth=None, records_out=None, ends=True, dirs=None, m=None, tree=False, nthreads=1):
+    """The refresh as a host loop (mort_hip_volume_refresh_host), no GPU: arguments and result as Context.volume_refresh."""
+    m, dirs, records_in, depth, records_out, ends = _refresh_arrays(params, states, records_in, depth, records_out, ends, dirs, m)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_volume_refresh_host(world.ptr, C.byref(params), m, _ptr(dirs), _ptr(states), _ptr(records_in), _ptr(depth), nthreads,
+                                            HOST_TREE if tree else 0, _ptr(records_out), _ptr(ends), C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_volume_refresh_host")
+    return dict(records=records_out, ends=ends, seconds=sec.value)
+
+
+def probe_directions_round(D, round):
+    """The direction set of refresh round `round` (mort_hip_probe_directions_round, needs no GPU): round 0 is probe_directions(D), a
+    later round that set rotated; float32 (D, 3)."""
+    out = np.zeros((max(int(D), 0), 3), dtype=np.float32)
+    rc = lib().mort_hip_probe_directions_round(D, round, out.ctypes.data)
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_probe_directions_round")
+    return out
 
 
 def _probe_records(probes):
