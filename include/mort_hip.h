@@ -631,6 +631,51 @@ int mort_hip_query_radiance_cached_host(const mort_world *world, const mort_cach
                                         mort_rng_state *states, const float *records, const float *depth, int nthreads, int flags,
                                         float *rgb_out, uint32_t *ends_out, double *seconds);
 
+/* ---- direct-light cached radiance queries: a sampled light plus a volume of indirect light.  A 128-byte SH9
+ * record cannot hold the emitters' own light -- its shadows and the fall-off under a small emitter are lost -- so the volume keeps
+ * indirect light only and a path that ends in it adds one sampled shadow segment toward the light object.
+ *
+ * The indirect volume is a composition of two bakes, not a call of its own.  "Indirect" is the radiance arriving at a probe with
+ * the emission of directly seen emitters taken out; the background and every reflected bounce stay in.
+ *   sh_full  mort_hip_probe_bake* under the caller's mort_probe_params;
+ *   sh_emit  mort_hip_probe_bake* over the same probes and directions, from a COPY of the streams sh_full started from, under the
+ *            same params changed in three fields: rp.bounce_limit = 1, rp.background = 0, rp.samples = 1 (at limit 1 a path
+ *            returns its first hit's emission or 0);
+ *   sh_ind[i] = sh_full[i] - sh_emit[i], one fp32 subtraction per float; mort_hip_volume_pack* makes the records of it.
+ *
+ * The calls take mort_hip_query_radiance_cached*'s arguments under the same mort_cached_params -- no new flag bit -- and one more
+ * optional output, lit_out (n words or NULL): per ray, how many of its paths' shadow segments returned a non-zero emission.
+ * Everything is fp32, nothing contracted, every / correctly rounded.  The path is the cached query's, word for word, but for its
+ * step 2: the hit is Lambertian, iter >= K, the weight sum is > 0 and the path ends, with the final value per channel
+ *   final_c = ((albedo_c * E_c) * INV_PI) + direct_c,    direct formed in this order:
+ *   a. if params->path.light_obj_type == -1, or iter + 1 >= bounce_limit, there is no direct term: nothing is drawn, nothing is
+ *      added, and final_c is the cached query's to the bit;
+ *   b. dir = the light object's random direction from p, drawn from the ray's stream as the render's light sampling draws it;
+ *      pdf = the light object's pdf_value(p, dir);  cosine = dot(n, unit(dir)), n the hit's facing normal;
+ *      spdf = cosine < 0 ? 0 : cosine * INV_PI;
+ *   c. the shadow segment (p, dir, the ray's time) is searched as every path segment is: [0.001, inf), the solids, then the media
+ *      with their draws from the stream.  If it ends on a hit whose material tag is MORT_MAT_DIFFUSE_LIGHT, Le is the emission a
+ *      radiance query returns at that hit (front face only, the light's texture); otherwise -- a miss, a medium's scatter point,
+ *      any other material -- Le = 0.  No scatter is evaluated and nothing further is drawn; a miss does not return the
+ *      background, which is in the probes;
+ *   d. direct_c = ((albedo_c * spdf) * Le_c) / pdf, without a guard: a zero, infinite or NaN pdf gives what the division gives.
+ *      The ray's count in lit_out goes up by one when any Le_c != 0.
+ * The unwind, the sum over the samples and ends_out are the cached query's.  So
+ *   (i)   with no light object the call is mort_hip_query_radiance_cached* to the bit, streams included;
+ *   (ii)  with K >= bounce_limit, or with every weight 0, it is mort_hip_query_radiance* to the bit;
+ *   (iii) ends_out is the cached query's for the same inputs wherever the streams have not yet parted: the terminal hit ends the
+ *         path, and the streams differ only by the draws of (b) and (c).
+ * Checks, forms, `seconds`, n == 0, alignment and overlap as for the cached queries; lit_out is one more output. ---- */
+int mort_hip_query_radiance_cached_direct(mort_ctx *ctx, const mort_cached_params *params, size_t n, const mort_ray *rays, mort_rng_state *states,
+                                          const float *records, const float *depth /* or NULL */, float *rgb_out, uint32_t *ends_out /* n or NULL */,
+                                          uint32_t *lit_out /* n or NULL */, double *seconds);
+int mort_hip_query_radiance_cached_direct_device(mort_ctx *ctx, const mort_cached_params *params, size_t n, const void *d_rays, void *d_states,
+                                                 const void *d_records, const void *d_depth, void *d_rgb_out, void *d_ends_out, void *d_lit_out,
+                                                 void *stream, double *seconds);
+int mort_hip_query_radiance_cached_direct_host(const mort_world *world, const mort_cached_params *params, size_t n, const mort_ray *rays,
+                                               mort_rng_state *states, const float *records, const float *depth, int nthreads, int flags,
+                                               float *rgb_out, uint32_t *ends_out, uint32_t *lit_out, double *seconds);
+
 /* ---- cached frames: renders whose paths end in an irradiance volume.  Camera::render for every pixel, as
  * mort_hip_render runs it -- the pixel's stream from the context (or `states`), get_ray per stratum drawn from that stream, the flat
  * sample x bounce loop with one segment counted per search, the unwind, the pixel's finish and its uchar4, the stream stored back

@@ -105,6 +105,14 @@
  * refresh_stride and refresh_ends (the paths of the last full round that ended in the volume; 0 for R = 0).  Without --refresh
  * every accepted and refused combination and every output byte is what it was.
  *
+ * --cache-direct (with --sh-volume ... --cache-depth K and --probe or --radiance-out; excludes --cache-render and --refresh, whose
+ * paths do not have the direct terminal yet): the volume holds indirect light only and a path that ends in it adds one sampled shadow
+ * segment toward the scene's light object.  After the bake a second, emission-only bake runs over the same probes
+ * and directions from a copy of the streams the first one started from (bounce limit 1, black background, one path per direction),
+ * the coefficients are subtracted float by float, packed, and the query is mort_hip_query_radiance_cached_direct (or its _host
+ * form).  The JSON line gains cache_direct: 1 and lit (the paths whose shadow segment returned a non-zero emission), after ends.
+ * Without --cache-direct every accepted and refused combination and every output byte is what it was.
+ *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
  * RCCL (`--gather rccl`, the default: xGMI inside a node), or through a shared host mapping (`--gather shm`: for ranks
@@ -150,12 +158,14 @@ static int usage(void) {
            "[--out f.ppm] [--dump-f32 f.raw] [--states-in f] [--states-out f] [--earth image.jpg|.ppm] [--rtl] [--device K] [--keys WASD..] [--mouse dx,dy] "
            "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
            "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]] "
-           "[--cache-depth K] [--radiance-out FILE] [--cache-render] [--refresh R[,H[,KR[,S]]]]\n"
+           "[--cache-depth K] [--radiance-out FILE] [--cache-render] [--refresh R[,H[,KR[,S]]]] [--cache-direct]\n"
            "  --cache-depth K with --sh-volume: paths end in the volume from bounce K on; --probe X,Y[,N] prints one pixel's colour,\n"
            "  --radiance-out FILE writes a preview from pixel-centre rays (--spp paths each; no jitter, no lens), not a render,\n"
            "  --cache-render renders: the ordinary frame loop (--frames, --out, --temporal, --svgf, ...) over cached frames\n"
            "  --refresh R[,H[,KR[,S]]] with --sh-volume: R rounds re-bake every probe through the volume (hysteresis H, refresh depth KR);\n"
-           "  with --cache-render and S > 0 every S-th probe is refreshed again before each frame\n");
+           "  with --cache-render and S > 0 every S-th probe is refreshed again before each frame\n"
+           "  --cache-direct with --cache-depth and --probe or --radiance-out: the volume keeps indirect light only and a path that\n"
+           "  ends in it adds one sampled shadow ray toward the scene's light\n");
     return -1;
 }
 
@@ -367,6 +377,7 @@ int main(int argc, char **argv) {
     int cached = 0, cache_depth = 0;
     const char *rad_out = NULL;
     int cache_render = 0;
+    int cache_direct = 0;
     refresh_opts refresh;
     memset(&refresh, 0, sizeof refresh);
     refresh.h = 0.9f;
@@ -426,6 +437,7 @@ int main(int argc, char **argv) {
         else if (ARG("--cache-depth")) { cached = 1; if (sscanf(argv[++i], "%d", &cache_depth) != 1) { fprintf(stderr, "--cache-depth K\n"); return -1; } }
         else if (ARG("--radiance-out")) rad_out = argv[++i];
         else if (strcmp(argv[i], "--cache-render") == 0) cache_render = 1;
+        else if (strcmp(argv[i], "--cache-direct") == 0) cache_direct = 1;
         else if (ARG("--refresh")) {
             refresh.on = 1;
             if (sscanf(argv[++i], "%d,%f,%d,%d", &refresh.rounds, &refresh.h, &refresh.depth, &refresh.stride) < 1) { fprintf(stderr, "--refresh R[,H[,KR[,S]]]\n"); return -1; }
@@ -447,6 +459,8 @@ int main(int argc, char **argv) {
     if (cached && !sh_volume) { fprintf(stderr, "--cache-depth needs --sh-volume\n"); return -1; }
     if (rad_out && !cached) { fprintf(stderr, "--radiance-out needs --cache-depth\n"); return -1; }
     if (cached && (cache_depth < 0 || cache_depth > MORT_MAX_BOUNCE_LIMIT)) { fprintf(stderr, "--cache-depth: K in 0..%d\n", MORT_MAX_BOUNCE_LIMIT); return -1; }
+    if (cache_direct && !cached) { fprintf(stderr, "--cache-direct needs --cache-depth\n"); return -1; }
+    if (cache_direct && (cache_render || refresh.on)) { fprintf(stderr, "--cache-direct excludes --cache-render and --refresh\n"); return -1; }
     if (cache_render && (!sh_volume || !cached)) { fprintf(stderr, "--cache-render needs --sh-volume and --cache-depth\n"); return -1; }
     if (cache_render && (probe || rad_out || pick || irr_out)) { fprintf(stderr, "--cache-render excludes --probe, --radiance-out, --pick and --irradiance-out\n"); return -1; }
     if (cache_render && (gpus > 1 || mode != MORT_MODE_MEGA)) { fprintf(stderr, "--cache-render is a single-GPU option of the default mode and of --mode host\n"); return -1; }
@@ -535,6 +549,21 @@ int main(int argc, char **argv) {
         mort_rng_state *qstates = NULL;
         float *rgb = NULL;
         uint32_t *ends = NULL;
+        /* --cache-direct: the emission-only bake's parameters, the streams the bake starts from, its coefficients, the lit counts */
+        mort_probe_params pe = pp;
+        pe.rp.bounce_limit = 1; pe.rp.samples = 1;
+        pe.rp.background[0] = pe.rp.background[1] = pe.rp.background[2] = 0.0f;
+        mort_rng_state *states_e = NULL;
+        float *sh_e = NULL;
+        uint32_t *lit = NULL;
+        double emit_sec = 0;
+        if (cache_direct) {
+            states_e = (mort_rng_state *)malloc(probes_n * (size_t)sh_d * sizeof *states_e);
+            sh_e = (float *)malloc(probes_n * MORT_SH9_FLOATS * sizeof *sh_e);
+            lit = (uint32_t *)malloc(nq * sizeof *lit);
+            if (!states_e || !sh_e || !lit) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+            memcpy(states_e, states, probes_n * (size_t)sh_d * sizeof *states_e);
+        }
         if (cached) {
             mort_rng_state *pixels = (mort_rng_state *)malloc(npx * sizeof *pixels); /* the run's pixel streams */
             qstates = (mort_rng_state *)malloc(nq * sizeof *qstates);
@@ -553,11 +582,18 @@ int main(int argc, char **argv) {
         if (host_mode) {
             const int fl = tree ? MORT_HOST_TREE : 0;
             if ((pst = mort_hip_probe_bake_host(&world, &pp, probes_n, probes, NULL, states, threads, fl, sh, &bake_sec)) != MORT_OK) die(NULL, pst, "mort_hip_probe_bake_host");
+            if (cache_direct) { /* the volume keeps indirect light: the full bake minus the emission-only bake, float by float */
+                if ((pst = mort_hip_probe_bake_host(&world, &pe, probes_n, probes, NULL, states_e, threads, fl, sh_e, &emit_sec)) != MORT_OK) die(NULL, pst, "mort_hip_probe_bake_host");
+                for (size_t i = 0; i < probes_n * MORT_SH9_FLOATS; i++) sh[i] = sh[i] - sh_e[i];
+                bake_sec += emit_sec;
+            }
             if ((pst = mort_hip_volume_pack_host(probes_n, sh, NULL, threads, records, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_volume_pack_host");
             if (!cached && (pst = mort_hip_query_closest_host(&world, nq, rays, NULL, threads, fl, hits, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_closest_host");
             if (visibility && (pst = mort_hip_probe_depth_bake_host(&world, &dp, probes_n, probes, threads, fl, depth, NULL)) != MORT_OK) die(NULL, pst, "mort_hip_probe_depth_bake_host");
             if (refresh.on) volume = refresh_all(NULL, &world, &cam, &refresh, &grid, cp.flags, &vp, sh_d, sh_n, states, records, records2, depth, threads, fl);
-            if (cached) {
+            if (cache_direct) {
+                if ((pst = mort_hip_query_radiance_cached_direct_host(&world, &cp, nq, rays, qstates, volume, depth, threads, fl, rgb, ends, lit, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_radiance_cached_direct_host");
+            } else if (cached) {
                 if ((pst = mort_hip_query_radiance_cached_host(&world, &cp, nq, rays, qstates, volume, depth, threads, fl, rgb, ends, &sec)) != MORT_OK) die(NULL, pst, "mort_hip_query_radiance_cached_host");
             } else if (visibility) {
                 if ((pst = mort_hip_volume_sample_visible_host(&grid, volume, depth, &vp, nq, hits, sizeof *hits, threads, irr, &sample_sec)) != MORT_OK) die(NULL, pst, "mort_hip_volume_sample_visible_host");
@@ -568,11 +604,18 @@ int main(int argc, char **argv) {
             if ((pst = mort_hip_init(device, &pctx)) != MORT_OK) die(NULL, pst, "mort_hip_init");
             if ((pst = mort_hip_upload_world(pctx, &world)) != MORT_OK) die(pctx, pst, "mort_hip_upload_world");
             if ((pst = mort_hip_probe_bake(pctx, &pp, probes_n, probes, NULL, states, sh, &bake_sec)) != MORT_OK) die(pctx, pst, "mort_hip_probe_bake");
+            if (cache_direct) {
+                if ((pst = mort_hip_probe_bake(pctx, &pe, probes_n, probes, NULL, states_e, sh_e, &emit_sec)) != MORT_OK) die(pctx, pst, "mort_hip_probe_bake");
+                for (size_t i = 0; i < probes_n * MORT_SH9_FLOATS; i++) sh[i] = sh[i] - sh_e[i];
+                bake_sec += emit_sec;
+            }
             if ((pst = mort_hip_volume_pack(pctx, probes_n, sh, NULL, records, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_volume_pack");
             if (!cached && (pst = mort_hip_query_closest(pctx, nq, rays, NULL, hits, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_closest");
             if (visibility && (pst = mort_hip_probe_depth_bake(pctx, &dp, probes_n, probes, depth, NULL)) != MORT_OK) die(pctx, pst, "mort_hip_probe_depth_bake");
             if (refresh.on) volume = refresh_all(pctx, &world, &cam, &refresh, &grid, cp.flags, &vp, sh_d, sh_n, states, records, records2, depth, threads, 0);
-            if (cached) {
+            if (cache_direct) {
+                if ((pst = mort_hip_query_radiance_cached_direct(pctx, &cp, nq, rays, qstates, volume, depth, rgb, ends, lit, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_radiance_cached_direct");
+            } else if (cached) {
                 if ((pst = mort_hip_query_radiance_cached(pctx, &cp, nq, rays, qstates, volume, depth, rgb, ends, &sec)) != MORT_OK) die(pctx, pst, "mort_hip_query_radiance_cached");
             } else if (visibility) {
                 if ((pst = mort_hip_volume_sample_visible(pctx, &grid, volume, depth, &vp, nq, hits, sizeof *hits, irr, &sample_sec)) != MORT_OK) die(pctx, pst, "mort_hip_volume_sample_visible");
@@ -587,6 +630,7 @@ int main(int argc, char **argv) {
                 printf(", \"time\": "); print_f32(rays[0].time);
                 print_v3("rgb", rgb);
                 printf(", \"cache_depth\": %d, \"ends\": %u", cache_depth, (unsigned)ends[0]);
+                if (cache_direct) printf(", \"cache_direct\": 1, \"lit\": %u", (unsigned)lit[0]);
             } else {
                 uint8_t *img = (uint8_t *)malloc(npx * 4);
                 if (!img) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
@@ -606,6 +650,11 @@ int main(int argc, char **argv) {
                 free(img);
                 printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"radiance_out\": \"%s\", \"samples\": %d, \"cache_depth\": %d, \"ends\": %llu", scene, W, H,
                        rad_out, cp.path.samples, cache_depth, ended);
+                if (cache_direct) {
+                    unsigned long long lit_paths = 0;
+                    for (size_t i = 0; i < npx; i++) lit_paths += lit[i];
+                    printf(", \"cache_direct\": 1, \"lit\": %llu", lit_paths);
+                }
             }
             if (visibility) {
                 printf(", \"normal_bias\": "); print_f32(vp.normal_bias);
@@ -615,7 +664,7 @@ int main(int argc, char **argv) {
             print_refresh(&refresh);
             printf(", \"probes\": [%d, %d, %d], \"directions\": %d, \"probe_samples\": %d, \"mode\": \"%s\", \"seconds\": %.6f, \"bake_seconds\": %.6f}\n",
                    (int)grid.count[0], (int)grid.count[1], (int)grid.count[2], sh_d, sh_n, host_mode ? "host" : "mega", sec, bake_sec);
-            free(qstates); free(rgb); free(ends);
+            free(qstates); free(rgb); free(ends); free(states_e); free(sh_e); free(lit);
         } else {
         for (size_t i = 0; i < nq; i++) /* a miss is an all-zero record: its sample means nothing */
             if (!(hits[i].flags & MORT_HIT_HIT)) irr[4 * i] = irr[4 * i + 1] = irr[4 * i + 2] = irr[4 * i + 3] = 0.0f;

@@ -1,7 +1,8 @@
 /*
  * query_common.h -- host scaffolding that the ray queries (query.hip), the radiance queries (radiance.hip) and the cached radiance
- * queries (cached.hip) share: the one workgroup shape and its limits, the alignment the _device forms ask for, and the launch
- * arguments over the context's scene.  The per-ray bodies are in dev_query.h, dev_radiance.h and dev_cached.h.
+ * queries (cached.hip, cached_direct.hip) share: the one workgroup shape and its limits, the alignment the _device forms ask for, and
+ * the launch arguments over the context's scene.  The per-ray bodies are in dev_query.h, dev_radiance.h, dev_cached.h and
+ * dev_cached_direct.h.
  */
 #ifndef MORT_QUERY_COMMON_H
 #define MORT_QUERY_COMMON_H

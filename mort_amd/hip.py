@@ -46,6 +46,7 @@ EXPORTS = [
     "mort_hip_view_set_cache_host",
     "mort_hip_volume_refresh", "mort_hip_volume_refresh_device", "mort_hip_volume_refresh_host", "mort_hip_probe_directions_round",
     "mort_hip_view_update_cache", "mort_hip_view_update_cache_host",
+    "mort_hip_query_radiance_cached_direct", "mort_hip_query_radiance_cached_direct_device", "mort_hip_query_radiance_cached_direct_host",
 ]
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
@@ -380,6 +381,12 @@ def lib():
         L.mort_hip_query_radiance_cached_device.restype = C.c_int
         L.mort_hip_query_radiance_cached_host.argtypes = [wd, cp, sz, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, dp]
         L.mort_hip_query_radiance_cached_host.restype = C.c_int
+        L.mort_hip_query_radiance_cached_direct.argtypes = [ctx, cp, sz, vp, vp, vp, vp, vp, vp, vp, dp]
+        L.mort_hip_query_radiance_cached_direct.restype = C.c_int
+        L.mort_hip_query_radiance_cached_direct_device.argtypes = [ctx, cp, sz, vp, vp, vp, vp, vp, vp, vp, vp, dp]
+        L.mort_hip_query_radiance_cached_direct_device.restype = C.c_int
+        L.mort_hip_query_radiance_cached_direct_host.argtypes = [wd, cp, sz, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, dp]
+        L.mort_hip_query_radiance_cached_direct_host.restype = C.c_int
         fp = C.POINTER(CACHED_FRAME_PARAMS)
         L.mort_hip_render_cached.argtypes = [ctx, C.POINTER(S.Camera), fp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
         L.mort_hip_render_cached.restype = C.c_int
@@ -689,6 +696,41 @@ class Context:
                                                               dptr(rgb), dptr(ends), stream, C.byref(sec) if sync else None),
                   "mort_hip_query_radiance_cached_device")
         return sec.value if sync else None
+
+    def query_radiance_cached_direct(self, params, rays, states, records, depth=None, want_ends=True, want_lit=True):
+        """The direct-light cached radiance query on the GPU (mort_hip_query_radiance_cached_direct): query_radiance_cached's
+        arguments over records of INDIRECT light (probe_bake_indirect); a path that ends in the volume adds one sampled shadow
+        segment toward params.path's light object.  query_radiance_cached's dict plus lit uint32 (n,) or None: the paths of a ray
+        whose shadow segment returned a non-zero emission."""
+        rays, st8, records, depth, rgb, ends = _cached_arrays(params, rays, states, records, depth, want_ends)
+        lit = np.zeros(rays.shape[0], dtype=np.uint32) if want_lit else None
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_query_radiance_cached_direct(self._h, C.byref(params), rays.shape[0], rays.ctypes.data, _ptr(st8), _ptr(records),
+                                                              _ptr(depth), rgb.ctypes.data, _ptr(ends), _ptr(lit), C.byref(sec)),
+                  "mort_hip_query_radiance_cached_direct")
+        return dict(rgb=rgb, ends=ends, lit=lit, seconds=sec.value)
+
+    def query_radiance_cached_direct_device(self, params, rays, states, records, depth, rgb, ends=None, lit=None, sync=False):
+        """The direct-light cached radiance query on torch tensors: query_radiance_cached_device's arguments and lit, None or 4 n
+        bytes."""
+        import torch
+        n = _check_query_tensors(torch, rays, ((states, 48), (rgb, 12), (ends, 4), (lit, 4)))
+        for t, size in ((records, 128 * params.grid.probes), (depth, 4 * DEPTH_FLOATS * params.grid.probes)):
+            if t is not None and (not t.is_contiguous() or t.numel() * t.element_size() != size or t.device != rays.device):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {rays.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, rays.device, sync)
+        dptr = lambda t: t.data_ptr() if t is not None else None
+        self._chk(lib().mort_hip_query_radiance_cached_direct_device(self._h, C.byref(params), n, rays.data_ptr(), dptr(states), dptr(records),
+                                                                     dptr(depth), dptr(rgb), dptr(ends), dptr(lit), stream,
+                                                                     C.byref(sec) if sync else None),
+                  "mort_hip_query_radiance_cached_direct_device")
+        return sec.value if sync else None
+
+    def probe_bake_indirect(self, params, probes, states, dirs=None):
+        """The three bakes of an indirect-light volume on the GPU (probe_bake_indirect_host has the composition): dict(sh_full,
+        sh_emit, sh_ind float32 (n, 9, 3), seconds of both bakes); states are advanced IN PLACE by the full bake."""
+        return _bake_indirect(lambda pp, st: self.probe_bake(pp, probes, st, dirs), params, states)
 
     def render_cached(self, cam, params, records, depth=None, want_accum=True, want_segments=False, want_ends=True):
         """A cached frame on the GPU (mort_hip_render_cached): Context.render in MODE_MEGA whose paths end in the volume.  params
@@ -1409,6 +1451,20 @@ def query_radiance_cached_host(world, params, rays, states, records, depth=None,
     return dict(rgb=rgb, ends=ends, seconds=sec.value)
 
 
+def query_radiance_cached_direct_host(world, params, rays, states, records, depth=None, want_ends=True, want_lit=True, tree=False, nthreads=1):
+    """The direct-light cached radiance query as a host loop (mort_hip_query_radiance_cached_direct_host), no GPU: arguments and
+    result as Context.query_radiance_cached_direct."""
+    rays, st8, records, depth, rgb, ends = _cached_arrays(params, rays, states, records, depth, want_ends)
+    lit = np.zeros(rays.shape[0], dtype=np.uint32) if want_lit else None
+    sec = C.c_double(0)
+    rc = lib().mort_hip_query_radiance_cached_direct_host(world.ptr, C.byref(params), rays.shape[0], rays.ctypes.data, _ptr(st8), _ptr(records),
+                                                          _ptr(depth), nthreads, HOST_TREE if tree else 0, rgb.ctypes.data, _ptr(ends), _ptr(lit),
+                                                          C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_query_radiance_cached_direct_host")
+    return dict(rgb=rgb, ends=ends, lit=lit, seconds=sec.value)
+
+
 def _refresh_arrays(params, states, records_in, depth, records_out, ends, dirs, m):
     """the arrays of a volume refresh: inputs as contiguous float32, the outputs the caller's own (written in place) or new"""
     sized = all(0 < c <= VOLUME_MAX_COUNT for c in params.cached.grid.count)
@@ -1504,6 +1560,37 @@ def probe_bake_host(world, params, probes, states, dirs=None, tree=False, nthrea
     if rc != 0:
         raise MortHipError(rc, "mort_hip_probe_bake_host")
     return dict(sh=sh, seconds=sec.value)
+
+
+def emission_probe_params(params):
+    """params (PROBE_PARAMS) as the emission-only bake of an indirect volume takes them: bounce limit 1, a black background, one
+    path per direction -- at limit 1 a path returns its first hit's emission or 0"""
+    p = PROBE_PARAMS.from_buffer_copy(params)
+    p.rp.bounce_limit = 1
+    p.rp.samples = 1
+    for k in range(3):
+        p.rp.background[k] = 0.0
+    return p
+
+
+def _bake_indirect(bake, params, states):
+    """bake(params, states) -> probe_bake's dict, run twice: the full bake on the caller's streams, the emission-only bake on a copy
+    of the streams the full bake started from; sh_ind = sh_full - sh_emit, one float32 subtraction per float"""
+    start = np.array(states, copy=True)
+    full = bake(params, states)
+    emit = bake(emission_probe_params(params), start)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ind = (full["sh"] - emit["sh"]).astype(np.float32)
+    return dict(sh_full=full["sh"], sh_emit=emit["sh"], sh_ind=ind, seconds=full["seconds"] + emit["seconds"])
+
+
+def probe_bake_indirect_host(world, params, probes, states, dirs=None, tree=False, nthreads=1):
+    """The bakes of an indirect-light volume as host loops, no GPU.  "Indirect" is the radiance arriving at a probe with the
+    emission of directly seen emitters taken out; the background and every reflected bounce stay in.  No new kernel: sh_full is
+    probe_bake_host under params; sh_emit is probe_bake_host over the same probes and directions, from a copy of the streams sh_full
+    started from, under emission_probe_params(params); sh_ind = sh_full - sh_emit.  dict(sh_full, sh_emit, sh_ind float32
+    (n, 9, 3), seconds); states are advanced IN PLACE by the full bake."""
+    return _bake_indirect(lambda pp, st: probe_bake_host(world, pp, probes, st, dirs, tree=tree, nthreads=nthreads), params, states)
 
 
 def sh9_irradiance(sh, normal):
