@@ -370,7 +370,7 @@ extern "C" int mort_hip_debug_bvh_lds_levels(const mort_world *w, int *out) {
     const uint32_t levels = (uint32_t)(o.own4_stack > 1 ? o.own4_stack : 1) + MORT_BVH_TSTACK_SPARE;
     const int shapes[3] = {1024, 768, 256};
     out[0] = (int)im.fb.size();
-    for (int k = 0; k < 3; k++) { uint32_t a = 0, b = 0; out[1 + k] = state_lds_levels((uint32_t)im.fb.size(), shapes[k], levels, 1024u, a, b); }
+    for (int k = 0; k < 3; k++) { uint32_t a = 0, b = 0; out[1 + k] = state_lds_levels((uint32_t)im.fb.size(), shapes[k], levels, 1024u, 1, a, b); }
     return MORT_OK;
 }
 

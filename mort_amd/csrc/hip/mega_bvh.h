@@ -45,6 +45,11 @@
  *  - Hit record rebuilt only for the winner; sphere uv (acosf/atan2f) only when
  *    the material's texture reads it.
  *
+ *  - Bounce stack: one 16-byte entry per STORED level (a dielectric level is an identity and takes no index).  The newest entries live in
+ *    LDS as a ring of stack_lds_depth slots per lane; a push onto a full ring first moves the oldest of them to the HBM buffer.  The unwind
+ *    goes newest first: it requests the newest HBM entries, combines the ring's entries, two LDS reads per wait, while those loads run, and
+ *    keeps MORT_BVH_UNWIND_P loads in flight through the HBM entries (DESIGN.md 4.1 l).
+ *
  *  - Leaf step: sphere::hit's square root and its divisions by the ray's `a` in the compiler's own instruction sequences minus the steps that are
  *    identities for ordinary values (range scaling, fix-up, class check), one reciprocal per segment for all of them (dev_math.h sqrt_ord, DivBy;
  *    sphere_hit_root_fast below).  Guarded: whatever lies outside the range takes the plain operators.  178 -> 143 vector instructions per step.
@@ -65,7 +70,7 @@ struct FastArgs {
     unsigned int *next_q; /* work counter, zeroed before launch */
     int tiles_x, tiles_total;
     uint32_t off_stack;   /* LDS offset of the per-lane bounce stacks: [depth][thread] float4 */
-    int stack_lds_depth;  /* entries per lane kept in LDS; deeper entries spill to private memory */
+    int stack_lds_depth;  /* bounce-stack entries per lane kept in LDS (mega_bvh_kernel: its ring, at least 1); the others go to `deep` */
     const unsigned *tile_order; /* tiles by decreasing cost, or null = row-major */
     int gen_tiles;              /* tiles per generation of the slot -> pixel map (below); 0 = plain order */
     int spread_shift;           /* log2 of the pixels a wave takes from one tile (6 = whole tiles ... 0 = single pixels) */
@@ -76,7 +81,8 @@ struct FastArgs {
      * covers a VIRTUAL image of local_rows * sub rows: virtual row = row * sub + s_j; r.states / vaccum are indexed by virtual pixel */
     int sub;                    /* 0, or sqrt_spp in sub-stream launches */
     float *vaccum;              /* sub-stream launches: per virtual pixel, the unscaled colour sum of its stratum row (3 floats) */
-    float4 *deep;               /* bounce-stack levels >= stack_lds_depth: [level - stack_lds_depth][lane of the launch] (HBM, coalesced per wave) */
+    float4 *deep;               /* bounce-stack entries outside the LDS part: [entry][lane of the launch] (HBM, coalesced per wave).  mega_gen_kernel: bounce level -
+                                 * stack_lds_depth; mega_bvh_kernel: stored entry n, once n + stack_lds_depth newer ones exist */
     /* priority pixels (mega_gen.hip): the pixels of the first prio_tiles tiles of the cost order are handed out prio_lanes per fetch from
      * their own cursor (next_q[1]), so that every wave holds at most a few of the frame's longest chains, and flagged: their wave runs
      * the state THEY are in next (PixelFetch.prio).  0 = none */
@@ -570,8 +576,8 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
     uint32_t node = 0;     /* T: own-tree node; L: leaf record */
     unsigned short *spa = ts_base; /* pending children: next free entry of the lane's traversal stack */
     int flags = 0;          /* FL_TIE / FL_REF | FL_SIGNS */
-    /* bounce-stack levels below the LDS part: [level - DL][lane of the launch] in HBM, one coalesced 1 KB row per wave and level, touched
-     * only by paths deeper than the LDS part (a private array is scratch memory sized for the deepest path in every lane).
+    /* bounce-stack entries older than the LDS ring: [entry][lane of the launch] in HBM, one coalesced 1 KB row per wave and entry, touched
+     * only by paths that store more entries than the ring holds (a private array is scratch memory sized for the deepest path in every lane).
      * Addressed as GLOBAL memory, never through a generic pointer: a pointer read from the argument block is generic to the compiler, the
      * stack store and the unwind then use FLAT instructions (and the unwind one flat_load for the LDS and the HBM levels alike), and a FLAT
      * access that may be in flight turns every later wait for an LDS read into s_waitcnt lgkmcnt(0), as FLAT and LDS results return in no
@@ -579,11 +585,24 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
      * use (measured on Scene 10) */
     DeepPtr stack_deep = (DeepPtr)BU_P(L.deep) + ((size_t)blockIdx.x * BLOCK + threadIdx.x);
     const size_t deep_stride = (size_t)gridDim.x * BLOCK;
-    /* bit i set: bounce level i is a dielectric scatter, whose entry (k = (1,1,1), 1/pdf = 1) unwinds as
-     * final = 0 + 1*((1,1,1)*final) = 0 + final exactly -- such levels are neither stored nor loaded */
-    unsigned long long ident_mask = 0ull;
-    float4 *stack_lds = (float4 *)(lds + BU_U(L.off_stack));
+    /* The bounce stack is indexed by STORED entries.  A dielectric scatter's entry (k = (1,1,1), 1/pdf = 1) unwinds as
+     * final = 0 + 1*((1,1,1)*final) = 0 + final exactly: such a level is neither stored nor loaded and takes no index.
+     * The newest DL entries live in LDS as a ring, [slot][thread] float4.  Pushing entry n >= DL first moves the slot's old content, entry
+     * n - DL, to stack_deep[n - DL]: an unwind, which goes newest first, starts in LDS whatever the path's depth, with its HBM entries
+     * already requested (MORT_BVH_UNWIND_P, below).  The launch keeps DL >= 1 (state_setup).
+     * nst, one register: stored entries << 8 | the ring's next free slot (0 .. DL - 1 <= 11) << 1 | (the path's deepest level so far is an
+     * identity: all the unwind's -0 rule needs).  The slot wraps by a compare, no division.  As a pointer of its own, like the traversal
+     * stack's, the cursor costs the 1024-thread kernel two more spilled registers, and a stepping pointer into stack_deep four spilled scalar
+     * ones (its stride times 16, hoisted): hence the packed slot and a multiply per HBM access. */
+    int nst = 0;
     const int DL = BU_I(L.stack_lds_depth);
+    float4 *const stack_lds = (float4 *)(lds + BU_U(L.off_stack));
+#define RING_AT(k) stack_lds[(k) * BLOCK + threadIdx.x]
+/* HBM entries requested ahead of their use in the unwind: 0 = each one loaded where it is consumed (the ring alone), 2, 3 (measured: DESIGN.md 4.7) */
+#ifndef MORT_BVH_UNWIND_P
+#define MORT_BVH_UNWIND_P 2
+#endif
+    static_assert(MORT_BVH_UNWIND_P == 0 || MORT_BVH_UNWIND_P == 2 || MORT_BVH_UNWIND_P == 3, "MORT_BVH_UNWIND_P");
 #ifdef MORT_PROFILE_STATES
     unsigned long long *const counters_p = fap->r.counters;
     unsigned long long prof[6] = {0, 0, 0, 0, 0, 0}; /* steps/lanes for T, L, S (wave-uniform) */
@@ -595,7 +614,11 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
     unsigned long long pt0 = __builtin_readcyclecounter(), pt1;
     const unsigned long long prof_r0 = __builtin_amdgcn_s_memrealtime();
 #define PROF(i, lanes) do { prof[2 * (i)] += 1; prof[2 * (i) + 1] += (unsigned long long)(lanes); } while (0)
-    unsigned long long profb[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; /* S branches: steps entered, lanes: metal, dielectric, lambertian, finish, get_ray, unwind iterations */
+    unsigned long long profb[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; /* S branches: steps entered, lanes: metal, dielectric, lambertian, finish, get_ray */
+    /* the unwind's levels: per lane and shade step (uw_l from the ring, uw_h from HBM), summed over the wave's lanes and steps in prof_uw[0 / 1];
+     * prof_uw[2]: the step's deepest lane (the one the wave waits for), summed over the steps */
+    int uw_l = 0, uw_h = 0;
+    unsigned long long prof_uw[3] = {0, 0, 0};
 #ifdef MORT_PROFILE_FINE /* cycles of the parts of the shade step instead of the branch counts (whose atomics distort the step's time) */
 #define PROFB(i) do { } while (0)
     unsigned long long proff[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; /* verify, hit record, metal, dielectric, lambert texture, lambert scatter, light, stack store */
@@ -813,6 +836,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                             reflected = vadd(vunit(reflected), vscale(m.fuzz, random_unit_vector(rng)));
                             ray.o = p; ray.d = reflected;
                             e.kx = 1.0f * m.r; e.ky = 1.0f * m.g; e.kz = 1.0f * m.b; e.rp = 1.0f;
+                            nst &= ~1;
                             PROFF(2);
                         } else if (mtype == MORT_MAT_DIELECTRIC) { /* materials.cuh:107-130 */
                 REGION("S:dielectric");
@@ -830,7 +854,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                                 direction = refract(unit_direction, normal, refraction_ratio);
                             ray.o = p; ray.d = direction;
                             e.kx = 1.0f; e.ky = 1.0f; e.kz = 1.0f; e.rp = 1.0f;
-                            ident_mask |= (1ull << iter);
+                            nst |= 1; /* an identity level */
                             PROFF(3);
                         } else if (mtype == MORT_MAT_LAMBERTIAN || mtype == MORT_MAT_ISOTROPIC) {
                 REGION("S:lambertian");
@@ -877,6 +901,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                             ray.o = p; ray.d = dir; ray.tm = ray_time0;
                             e.kx = scattering_pdf * attenuation.x; e.ky = scattering_pdf * attenuation.y; e.kz = scattering_pdf * attenuation.z;
                             e.rp = 1 / mat_pdf;
+                            nst &= ~1;
                             PROFF(5);
                         } else { /* diffuse_light or unknown tag: no scatter (materials.cuh:151-163) */
                 REGION("S:light");
@@ -892,10 +917,17 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                         }
                 REGION("S:stackstore");
                         if (kind == K_SHADE) {
-                            if (!((ident_mask >> iter) & 1ull)) {
+                            if (!(nst & 1)) {
                                 float4 e4; e4.x = e.kx; e4.y = e.ky; e4.z = e.kz; e4.w = e.rp;
-                                if (iter < DL) stack_lds[iter * BLOCK + threadIdx.x] = e4;
-                                else stack_deep[(size_t)(iter - DL) * deep_stride] = DeepEntry{e4.x, e4.y, e4.z, e4.w};
+                                const int n = nst >> 8;
+                                int ring = (nst >> 1) & 15;
+                                if (n >= DL) { /* the slot holds entry n - DL, the oldest of the ring: to HBM */
+                                    const float4 old = RING_AT(ring);
+                                    stack_deep[(size_t)(n - DL) * deep_stride] = DeepEntry{old.x, old.y, old.z, old.w};
+                                }
+                                RING_AT(ring) = e4;
+                                ring = ring + 1 == DL ? 0 : ring + 1;
+                                nst = ((n + 1) << 8) | (ring << 1);
                             }
                             iter++;
                             if (iter >= bounce_limit) { final_value = mk(0, 0, 0); kind = K_FINISH; } /* camera.cuh:161-163 */
@@ -909,21 +941,65 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                     /* an identity (dielectric) level is final = 0 + final: it only turns -0 into +0, and every level
                      * leaves a value without -0, so only an identity level that comes FIRST (deepest) can matter;
                      * the loop visits the stored levels alone, deepest first */
-                    if (iter > 0) {
-                        unsigned long long todo = ~ident_mask & (iter >= 64 ? ~0ull : ((1ull << iter) - 1ull));
-                        if ((ident_mask >> (iter - 1)) & 1ull) final_value = vadd(mk(0, 0, 0), final_value);
-                        while (todo != 0ull) {
-                            const int lvl = 63 - __builtin_clzll(todo);
-                            todo &= ~(1ull << lvl);
-                            StackEntry e;
-                            if (lvl < DL) { const float4 e4 = stack_lds[lvl * BLOCK + threadIdx.x]; e.kx = e4.x; e.ky = e4.y; e.kz = e4.z; e.rp = e4.w; }
-                            else { const DeepEntry e4 = stack_deep[(size_t)(lvl - DL) * deep_stride]; e.kx = e4.x; e.ky = e4.y; e.kz = e4.z; e.rp = e4.w; }
-                            const V3 t = vmul(mk(e.kx, e.ky, e.kz), final_value);
-                            final_value = vadd(mk(0, 0, 0), vscale(e.rp, t));
+                    if (nst != 0) { /* some level exists (iter > 0); after a path nst is 0, and an empty ring may start at any slot */
+#define UNWIND_LEVEL(v) do { const V3 t_ = vmul(mk((v).x, (v).y, (v).z), final_value); final_value = vadd(mk(0, 0, 0), vscale((v).w, t_)); } while (0)
+/* the same for the lanes where `c` holds, as selects: a branch inside the loop costs a pair of scalar registers the kernel does not have */
+#define UNWIND_LEVEL_IF(c, v) do { const V3 t_ = vmul(mk((v).x, (v).y, (v).z), final_value); const V3 f_ = vadd(mk(0, 0, 0), vscale((v).w, t_)); \
+        final_value.x = (c) ? f_.x : final_value.x; final_value.y = (c) ? f_.y : final_value.y; final_value.z = (c) ? f_.z : final_value.z; } while (0)
+                        if (nst & 1) final_value = vadd(mk(0, 0, 0), final_value);
+                        const int n = nst >> 8;
+                        int ring = (nst >> 1) & 15;
+                        int nd = n > DL ? n - DL : 0; /* entries 0 .. nd - 1 are in HBM, the newer n - nd in the ring */
+                        int nr = n - nd;
+                        int di = nd; /* the next entry to request is di - 1 */
+#ifdef MORT_PROFILE_STATES
+                        uw_l = nr; uw_h = nd;
+#endif
+#if MORT_BVH_UNWIND_P > 0
+                        /* the newest HBM entries, requested before the ring is read: they arrive while the ring's entries are combined */
+                        DeepEntry q0 = DeepEntry{0, 0, 0, 0}, q1 = q0;
+                        if (nd > 0) { di--; q0 = stack_deep[(size_t)di * deep_stride]; }
+                        if (nd > 1) { di--; q1 = stack_deep[(size_t)di * deep_stride]; }
+#if MORT_BVH_UNWIND_P > 2
+                        DeepEntry q2 = q0;
+                        if (nd > 2) { di--; q2 = stack_deep[(size_t)di * deep_stride]; }
+#endif
+#endif
+                        /* the ring, newest first, two reads per wait (a lane with one entry left reads a slot it does not use) */
+                        while (nr > 0) {
+                            const int r1 = (ring == 0 ? DL : ring) - 1;
+                            const int r2 = (r1 == 0 ? DL : r1) - 1;
+                            const float4 a = RING_AT(r1), b = RING_AT(r2);
+                            ring = nr > 1 ? r2 : r1;
+                            UNWIND_LEVEL(a);
+                            UNWIND_LEVEL_IF(nr > 1, b);
+                            nr -= 2;
                         }
+                        /* the HBM entries, newest first */
+#if MORT_BVH_UNWIND_P == 0
+                        while (nd > 0) { nd--; const DeepEntry v = stack_deep[(size_t)nd * deep_stride]; UNWIND_LEVEL(v); }
+                        (void)di;
+#else
+                        /* every entry consumed requests the one MORT_BVH_UNWIND_P places further on into its own registers: no copies, so each wait is for one load */
+                        while (nd > 0) {
+                            UNWIND_LEVEL(q0);
+                            if (nd > MORT_BVH_UNWIND_P) { di--; q0 = stack_deep[(size_t)di * deep_stride]; }
+                            nd--;
+                            UNWIND_LEVEL_IF(nd > 0, q1);
+                            if (nd > MORT_BVH_UNWIND_P) { di--; q1 = stack_deep[(size_t)di * deep_stride]; }
+                            nd--;
+#if MORT_BVH_UNWIND_P > 2
+                            UNWIND_LEVEL_IF(nd > 0, q2);
+                            if (nd > MORT_BVH_UNWIND_P) { di--; q2 = stack_deep[(size_t)di * deep_stride]; }
+                            nd--;
+#endif
+                        }
+#endif
+#undef UNWIND_LEVEL
+#undef UNWIND_LEVEL_IF
                         iter = 0;
+                        nst = 0;
                     }
-                    ident_mask = 0ull;
                     pixel_color = vadd(pixel_color, final_value);
                     s_ij++;
                     bool more; /* samples left in this work item (SUB: one stratum row) */
@@ -995,6 +1071,15 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
                 for (int off = 32; off > 0; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)key, off); key = o < key ? o : key; }
                 leader = (key == 0xffffffffu) ? -1 : __builtin_amdgcn_readfirstlane((int)(key & 63u));
             }
+#ifdef MORT_PROFILE_STATES
+            {
+                int sl = uw_l, sh = uw_h, mx = uw_l + uw_h;
+                for (int off = 32; off > 0; off >>= 1) { sl += __shfl_xor(sl, off); sh += __shfl_xor(sh, off); const int o = __shfl_xor(mx, off); mx = o > mx ? o : mx; }
+                prof_uw[0] += (unsigned long long)__builtin_amdgcn_readfirstlane(sl); prof_uw[1] += (unsigned long long)__builtin_amdgcn_readfirstlane(sh);
+                prof_uw[2] += (unsigned long long)__builtin_amdgcn_readfirstlane(mx);
+                uw_l = 0; uw_h = 0;
+            }
+#endif
             PROFS(7);
             PROFC(2);
         }
@@ -1006,6 +1091,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
 #endif
         for (int k = 0; k < 6; k++) atomicAdd(&counters_p[4 + k], prof[k]);
         atomicAdd(&counters_p[30], prof_truns);
+        atomicAdd(&counters_p[28], prof_uw[0]); atomicAdd(&counters_p[29], prof_uw[1]); atomicAdd(&counters_p[31], prof_uw[2]);
         for (int k = 0; k < 4; k++) atomicAdd(&counters_p[10 + k], profc[k]);
         for (int k = 4; k < 8; k++) atomicAdd(&counters_p[14 + k - 4], profc[k]);
         /* MORT_WAVE_LINES=1: one record per wave (same columns as mega_gen.hip's, the M columns empty) */
@@ -1013,6 +1099,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (DRAIN && BLOCK < 7
             unsigned long long *w = fap->wave_log + 16 * ((size_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6));
             w[0] = blockIdx.x; w[1] = threadIdx.x >> 6; w[2] = __builtin_amdgcn_s_memrealtime() - prof_r0;
             w[3] = prof[0]; w[4] = prof[2]; w[5] = 0; w[6] = prof[4]; w[7] = profc[0]; w[8] = profc[1]; w[9] = 0; w[10] = profc[2]; w[11] = profc[3];
+            w[12] = prof_uw[0]; w[13] = prof_uw[1]; w[14] = prof_uw[2]; w[15] = profc[5]; /* unwind levels: ring, HBM, deepest lane per step; cycles of the finish part */
         }
         (void)profb;
 #endif

@@ -199,15 +199,15 @@ static void fast_args_base(const mort_ctx *c, const mort_camera *cam, const Rend
 }
 
 /* LDS, grid and HBM scratch of a launch of `kern` in FB-thread groups.  LDS: the image (fa.hot_bytes) | traversal stacks
- * [tstack_levels][FB] u16 | as many bounce-stack levels [dl][FB] float4 as fit next to them (world_images.h state_lds_levels), at most 12 and dl_cap, with as many
+ * [tstack_levels][FB] u16 | as many bounce-stack levels [dl][FB] float4 as fit next to them (world_images.h state_lds_levels), at least dl_min, at most 12 and dl_cap, with as many
  * groups per CU as keep 12 waves per CU (fewer when their LDS does not fit 160 KB) and at most per_cu_cap.  The levels below dl
  * go to c->d_deep; MORT_WAVE_LINES (profile builds) sizes the per-wave log. */
-static int state_setup(mort_ctx *c, const mort_camera *cam, FastArgs &fa, const void *kern, int FB, uint32_t tstack_levels, int dl_cap,
+static int state_setup(mort_ctx *c, const mort_camera *cam, FastArgs &fa, const void *kern, int FB, uint32_t tstack_levels, int dl_min, int dl_cap,
                        int per_cu_cap, const char *too_big, hipStream_t s, size_t &lds_bytes, int &grid) {
     uint32_t static_lds = 1024; /* the kernel's own __shared__ objects come out of the same 160 KB */
     { hipFuncAttributes fattr; if (hipFuncGetAttributes(&fattr, kern) == hipSuccess) static_lds = (uint32_t)((fattr.sharedSizeBytes + 1023) & ~(size_t)1023); }
     uint32_t tstack_off = 0, stack_off = 0;
-    int dl = state_lds_levels(fa.hot_bytes, FB, tstack_levels, static_lds, tstack_off, stack_off);
+    int dl = state_lds_levels(fa.hot_bytes, FB, tstack_levels, static_lds, dl_min, tstack_off, stack_off);
     fa.off_tstack = tstack_off;
     if (dl < 0) { c->last_error = too_big; return MORT_ERR_CAPACITY; }
     if (dl > dl_cap) dl = dl_cap;
@@ -302,7 +302,7 @@ static int launch_bvh(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, 
     /* traversal stacks: the world's own four-wide bound (at most MORT_OWN4_STACK) */
     size_t lds_bytes = 0;
     int grid = 0;
-    int st = state_setup(c, cam, fa, (const void *)kern, FB, (uint32_t)c->own4_stack + MORT_BVH_TSTACK_SPARE, 12, per_cu_cap, "BVH image does not fit one CU's LDS", s, lds_bytes, grid);
+    int st = state_setup(c, cam, fa, (const void *)kern, FB, (uint32_t)c->own4_stack + MORT_BVH_TSTACK_SPARE, 1, 12, per_cu_cap, "BVH image does not fit one CU's LDS", s, lds_bytes, grid);
     if (st != MORT_OK) return st;
     st = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, chain_bound, sub, timed, s, [&](const FastArgs &pa) {
         hipError_t e_ = hipFuncSetAttribute((const void *)kern_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
@@ -359,7 +359,7 @@ static int launch_gen(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, 
     if (knob_int(std::getenv("MORT_GEN_DL"), dl_cap) && dl_cap < 0) dl_cap = 0; /* a negative count would shrink the LDS below the traversal stacks */
     size_t lds_bytes = 0;
     int grid = 0;
-    int st = state_setup(c, cam, fa, (const void *)kern, FB, MORT_OWN_STACK, dl_cap, INT_MAX, "unified-tree image does not fit one CU's LDS", s, lds_bytes, grid);
+    int st = state_setup(c, cam, fa, (const void *)kern, FB, MORT_OWN_STACK, 0, dl_cap, INT_MAX, "unified-tree image does not fit one CU's LDS", s, lds_bytes, grid);
     if (st != MORT_OK) return st;
     st = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, false, sub, timed, s, [&](const FastArgs &pa) {
         GenArgs pg = ga;
@@ -479,11 +479,15 @@ static void print_profile(const mort_ctx *c, RenderFamily fam, const unsigned lo
                      (double)cnt[18] / (double)cnt[8], (double)cnt[19] / (double)cnt[8], (double)cnt[20] / (double)cnt[8], (double)cnt[21] / (double)cnt[8],
                      (double)cnt[22] / (double)cnt[8], (double)cnt[23] / (double)cnt[8], (double)cnt[24] / (double)cnt[8]);
 #else
-        const char *bn[6] = {"metal", "dielectric", "lambertian", "finish", "get_ray", "unwind iteration"};
-        for (int k = 0; k < 6; k++)
+        const char *bn[5] = {"metal", "dielectric", "lambertian", "finish", "get_ray"};
+        for (int k = 0; k < 5; k++)
             std::fprintf(stderr, "[S branch] %-16s entered in %5.1f%% of S steps (x%.2f), %4.1f lanes when entered\n", bn[k],
                          100.0 * (double)cnt[18 + 2 * k] / (double)cnt[8], (double)cnt[18 + 2 * k] / (double)cnt[8],
                          cnt[18 + 2 * k] ? (double)cnt[19 + 2 * k] / (double)cnt[18 + 2 * k] : 0.0);
+        /* mega_bvh_kernel: cnt[28 / 29] unwind levels read from LDS / from HBM (lane-levels), cnt[31] the deepest lane's levels summed over the S steps */
+        std::fprintf(stderr, "[S branch] unwind iteration: %.2f levels from LDS + %.2f from HBM per S step (%.1f %% from HBM), the step's deepest lane unwinds %.2f\n",
+                     (double)cnt[28] / (double)cnt[8], (double)cnt[29] / (double)cnt[8], cnt[28] + cnt[29] ? 100.0 * (double)cnt[29] / (double)(cnt[28] + cnt[29]) : 0.0,
+                     (double)cnt[31] / (double)cnt[8]);
 #endif
         std::fprintf(stderr, "[S parts, cycles/step] shade %.0f  finish %.0f  newpix %.0f  newsample+setup %.0f\n", (double)cnt[14] / (double)cnt[8],
                      (double)cnt[15] / (double)cnt[8], (double)cnt[16] / (double)cnt[8], (double)cnt[17] / (double)cnt[8]);

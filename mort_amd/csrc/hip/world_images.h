@@ -91,15 +91,17 @@ static inline void build_gen_image(const mortc::Compiled &o, GenImage &gi) {
 }
 
 /* the bounce-stack levels (at most 12) that fit in LDS beside an image of hot_bytes and the traversal stacks, in FB-thread groups, with
- * as many groups per CU as keep 12 waves per CU (fewer when their LDS does not fit 160 KB); -1: the image and stacks alone do not fit */
-static inline int state_lds_levels(uint32_t hot_bytes, int FB, uint32_t tstack_levels, uint32_t static_lds, uint32_t &tstack_off, uint32_t &stack_off) {
+ * as many groups per CU as keep 12 waves per CU (fewer when their LDS does not fit 160 KB, or leaves fewer than min_levels levels:
+ * mega_bvh_kernel's ring needs one); -1: the image and stacks alone, with min_levels levels, do not fit */
+static inline int state_lds_levels(uint32_t hot_bytes, int FB, uint32_t tstack_levels, uint32_t static_lds, int min_levels, uint32_t &tstack_off, uint32_t &stack_off) {
     tstack_off = (hot_bytes + 15u) & ~15u;
     stack_off = tstack_off + tstack_levels * (uint32_t)FB * 2u;
     int groups_per_cu = FB >= 768 ? 1 : 768 / FB;
-    while (groups_per_cu > 1 && (long long)(stack_off + static_lds) * groups_per_cu > 160ll * 1024) groups_per_cu--;
+    while (groups_per_cu > 1 && (long long)(stack_off + static_lds + (uint32_t)min_levels * (uint32_t)FB * 16u) * groups_per_cu > 160ll * 1024) groups_per_cu--;
     const long long room = (160ll * 1024 - (long long)static_lds * groups_per_cu) / groups_per_cu - (long long)stack_off;
     if (room < 0) return -1;
     const int dl = (int)(room / ((long long)FB * 16));
+    if (dl < min_levels) return -1;
     return dl > 12 ? 12 : dl;
 }
 

@@ -33,3 +33,5 @@ if len(a):
         cyc = b[:, 7:12].sum()
         print(f"{name:18s}: end {b[:,2].mean()*1e-5:7.1f} ms  S steps/wave {b[:,6].mean():8.0f}  per S step: T {b[:,3].sum()/Ssteps:5.1f} L {b[:,4].sum()/Ssteps:4.2f} M {b[:,5].sum()/Ssteps:4.2f} steps; cycles per S-round {cyc/Ssteps:8.0f} "
               f"(T {b[:,7].sum()/Ssteps:6.0f} L {b[:,8].sum()/Ssteps:6.0f} M {b[:,9].sum()/Ssteps:6.0f} S {b[:,10].sum()/Ssteps:6.0f} sched {b[:,11].sum()/Ssteps:6.0f}); us per round {(b[:,2]*1e-2).sum()/Ssteps:6.1f}")
+        if b[:, 12:16].any():  # mega_bvh_kernel: the unwind's levels and the finish part of the S step
+            print(f"{'':18s}  unwind per S step: {b[:,12].sum()/Ssteps:5.2f} levels from LDS + {b[:,13].sum()/Ssteps:5.2f} from HBM, deepest lane {b[:,14].sum()/Ssteps:5.2f} levels; finish part {b[:,15].sum()/Ssteps:6.0f} cycles")
