@@ -807,6 +807,36 @@ int mort_hip_local_rows(const mort_ctx *ctx, int height);
 /* Global row index of local row `local_row`. */
 int mort_hip_global_row(const mort_ctx *ctx, int local_row);
 
+/* ---- diagnostics of the tile scheduler (DESIGN.md 5 "Reading the scheduler back"): what decides when and where a pixel is
+ * rendered never reaches the pixel, so the tests read it here.  Nothing in this section launches or changes a render kernel. */
+#define MORT_TILE_COUNTERS 96
+typedef struct mort_tile_state {
+    int32_t ordered;      /* 1: the launch was ordered by the cost order (0: sub-stream launch, MORT_NO_TILE_ORDER, tiles < 4 * grid, a family without one) */
+    int32_t probed;       /* 1: the launch ran the one-sample cost probe first */
+    int32_t tiles, tiles_x, grid, block;
+    int32_t key_sum;      /* 1: MORT_TILE_KEY=sum */
+    int32_t spread_shift, gen_tiles;
+    int32_t heavy[4];     /* heavy waves of the launch: mod, num, cap, percent */
+    int32_t has_head;     /* 1: heavy waves were on, `head` and `frame_total` are the launch's */
+    uint32_t head;        /* tiles in the head of the order (tile_sort.hip heavy_count_kernel) */
+    uint32_t pad_;
+    uint64_t frame_total[MORT_TILE_COUNTERS]; /* the saved counters as heavy_count_kernel read them */
+} mort_tile_state;
+MORT_SA(sizeof(mort_tile_state) == 64 + 8 * MORT_TILE_COUNTERS, "tile state layout");
+/* The last render launch of ctx, after waiting for its stream.  keys / order (what the launch was ordered by) and cost (what it left
+ * for the next one) receive out->tiles words each when the launch was ordered and cap >= out->tiles; any of them may be NULL. */
+int mort_hip_debug_tile_state(mort_ctx *ctx, mort_tile_state *out, uint32_t *keys, uint32_t *order, uint32_t *cost, size_t cap);
+/* The scheduler's helper kernels on a caller's arrays, through the functions the render calls (host arrays in and out):
+ * the descending stable argsort of n costs, */
+int mort_hip_debug_tile_sort(int device, const uint32_t *cost, size_t n, uint32_t *keys_out, uint32_t *order_out);
+/* the size of the heavy-wave head for n sorted keys (counters: MORT_TILE_COUNTERS words or NULL), */
+int mort_hip_debug_heavy_count(int device, const uint32_t *keys, size_t n, uint32_t percent, uint32_t max_r, const uint64_t *counters,
+                               uint64_t lanes, uint32_t *head_out);
+/* and the frame gather's de-interleave of nranks tiles of packed rows, *tile_px pixels apart (the stride mort_hip_render_gather uses;
+ * written whenever tile_px is not NULL, and alone when gathered and frame are NULL), into the W x H frame.  No RCCL is involved. */
+int mort_hip_debug_deinterleave(int device, const uint8_t *gathered, int width, int height, int nranks, int rows_per_block,
+                                uint8_t *frame_out, size_t *tile_px);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,38 @@ __global__ void __launch_bounds__(256) deinterleave_kernel(const uchar4 *gathere
     frame[i] = gathered[(size_t)r * tile_stride_px + (size_t)ly * (size_t)width + (size_t)x];
 }
 
+/* pixels between two ranks' tiles in `gathered`: every rank's packed rows fit (the rank with the most blocks, all of them whole) */
+static size_t gather_tile_px(int width, int height, int nranks, int rpb) {
+    const size_t max_rows = (size_t)(((height + rpb - 1) / rpb + nranks - 1) / nranks) * (size_t)rpb;
+    return max_rows * (size_t)width;
+}
+
+/* diagnostic: deinterleave_kernel over a caller's `gathered` (nranks tiles, gather_tile_px apart) on `device`, without RCCL or a
+ * communicator -- the N > 1 index arithmetic on one GPU.  Every index the kernel forms lies below nranks * gather_tile_px. */
+extern "C" int mort_hip_debug_deinterleave(int device, const uint8_t *gathered, int width, int height, int nranks, int rows_per_block,
+                                           uint8_t *frame_out, size_t *tile_px) {
+    if (width <= 0 || height <= 0 || nranks < 1 || rows_per_block < 1 || (size_t)width * (size_t)height > ((size_t)1 << 28)) return MORT_ERR_INVALID;
+    const size_t stride = gather_tile_px(width, height, nranks, rows_per_block), npx = (size_t)width * (size_t)height;
+    if (tile_px) *tile_px = stride;
+    if (!gathered && !frame_out && tile_px) return MORT_OK;
+    if (!gathered || !frame_out) return MORT_ERR_INVALID;
+    int caller_device = -1;
+    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+    if (hipSetDevice(device) != hipSuccess) return MORT_ERR_NO_DEVICE;
+    uchar4 *d_g = nullptr, *d_f = nullptr;
+    int st = MORT_OK;
+    if (hipMalloc((void **)&d_g, stride * (size_t)nranks * 4) != hipSuccess || hipMalloc((void **)&d_f, npx * 4) != hipSuccess) st = MORT_ERR_NOMEM;
+    if (st == MORT_OK && hipMemcpy(d_g, gathered, stride * (size_t)nranks * 4, hipMemcpyHostToDevice) != hipSuccess) st = MORT_ERR_HIP;
+    if (st == MORT_OK) {
+        hipLaunchKernelGGL(deinterleave_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, nullptr, (const uchar4 *)d_g, d_f, width, height, nranks, rows_per_block, stride);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(frame_out, d_f, npx * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MORT_ERR_HIP;
+    }
+    if (d_g) (void)hipFree(d_g);
+    if (d_f) (void)hipFree(d_f);
+    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
+    return st;
+}
+
 extern "C" int mort_hip_comm_id(void *id) {
     if (!id) return MORT_ERR_INVALID;
     if (!rccl().ok) return MORT_ERR_UNSUPPORTED;
@@ -113,8 +145,7 @@ extern "C" int mort_hip_render_gather(mort_ctx *c, const mort_camera *cam, int m
     if (R == 0 && !rgba_out) return MORT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     const int lr = local_rows_for(c->part, H);
-    const size_t max_rows = (size_t)(((H + rpb - 1) / rpb + N - 1) / N) * (size_t)rpb; /* every rank's tile fits */
-    const size_t tile_px = max_rows * (size_t)W;
+    const size_t tile_px = gather_tile_px(W, H, N, rpb); /* every rank's tile fits */
     /* ---- every allocation first ---- */
     if (c->rgba_cap < tile_px * 4) {
         if (c->d_rgba) { hipFree(c->d_rgba); c->d_rgba = nullptr; c->rgba_cap = 0; }

@@ -1,5 +1,6 @@
 /*
- * debug.hip -- the diagnostics behind mort_amd/hip.py's debug_* calls (none is in include/mort_hip.h).  Most are host only:
+ * debug.hip -- the diagnostics behind mort_amd/hip.py's debug_* calls (only the tile scheduler's, at the end, are in
+ * include/mort_hip.h: they read a context's last launch back and drive tile_sort.hip's kernels, and add no kernel).  Most are host only:
  * they compile a world and report what world_images.h decides from it, or run the kernels' DEV bodies on the CPU.  Seven
  * launch small kernels of their own: exact_forms_kernel, f2i_all_kernel and f2i_list_kernel put the device's short forms
  * beside its plain operators, math_kernel runs the math layer on a caller's inputs, light_kernel the light sampling on a caller's
@@ -16,6 +17,7 @@
 #include "mega_bvh.h"
 #include "scene_blob.h"
 #include "mort_ctx.h"
+#include "mort_internal.h"
 #include "world_images.h"
 #include "dev_radiance.h"
 #include "query_common.h"
@@ -1007,4 +1009,78 @@ extern "C" int mort_hip_debug_random_float_device(int device, unsigned long long
     if (d_out) (void)hipFree(d_out);
     if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device); /* the caller's current device, as it was */
     return st;
+}
+
+/* ---- the tile scheduler read back (include/mort_hip.h; DESIGN.md 5 "Reading the scheduler back") ---- */
+
+/* the last render launch's tile order as the host recorded it (mort_ctx::TileLaunch) and as the device holds it: the keys and the
+ * order stay in their buffers until the next ordered launch sorts again, the costs are what the frame's pixel_write left */
+extern "C" int mort_hip_debug_tile_state(mort_ctx *c, mort_tile_state *out, uint32_t *keys, uint32_t *order, uint32_t *cost, size_t cap) {
+    if (!c || !out) return MORT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, quiesce(c));
+    const mort_ctx::TileLaunch &t = c->tile_launch;
+    std::memset(out, 0, sizeof *out);
+    out->ordered = t.ordered; out->probed = t.probed;
+    out->tiles = t.tiles; out->tiles_x = t.tiles_x; out->grid = t.grid; out->block = t.block;
+    out->key_sum = t.key_sum; out->spread_shift = t.spread_shift; out->gen_tiles = t.gen_tiles;
+    for (int k = 0; k < 4; k++) out->heavy[k] = t.heavy[k];
+    out->has_head = t.has_head;
+    if (t.has_head && c->d_prio_count) {
+        HIPCHK(c, hipMemcpy(&out->head, c->d_prio_count, sizeof out->head, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out->frame_total, c->d_prio_count + 4 + 2 * MORT_TILE_COUNTERS, sizeof out->frame_total, hipMemcpyDeviceToHost));
+    }
+    if (!t.ordered || t.tiles <= 0 || cap < (size_t)t.tiles || c->tile_cap < (size_t)t.tiles) return MORT_OK;
+    const size_t bytes = (size_t)t.tiles * sizeof(uint32_t);
+    if (keys) HIPCHK(c, hipMemcpy(keys, c->d_tile_keys, bytes, hipMemcpyDeviceToHost));
+    if (order) HIPCHK(c, hipMemcpy(order, c->d_tile_order, bytes, hipMemcpyDeviceToHost));
+    if (cost) HIPCHK(c, hipMemcpy(cost, c->d_tile_cost, bytes, hipMemcpyDeviceToHost));
+    return MORT_OK;
+}
+
+/* device buffers of a helper-kernel driver: freed when it returns */
+namespace {
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess; }
+    bool up(const void *src, size_t bytes) { return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess; }
+    bool down(void *dst, size_t bytes) const { return hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+};
+struct OnDevice { /* the caller's current device, as it was */
+    int caller = -1, device;
+    bool ok;
+    explicit OnDevice(int d) : device(d) { if (hipGetDevice(&caller) != hipSuccess) caller = -1; ok = hipSetDevice(d) == hipSuccess; }
+    ~OnDevice() { if (caller >= 0 && caller != device) (void)hipSetDevice(caller); }
+};
+}
+
+/* mort_tile_sort_desc (tile_sort.hip) as prepare_tile_order calls it, on a caller's costs */
+extern "C" int mort_hip_debug_tile_sort(int device, const uint32_t *cost, size_t n, uint32_t *keys_out, uint32_t *order_out) {
+    if (!cost || !keys_out || !order_out || n < 1 || n > ((size_t)1 << 24)) return MORT_ERR_INVALID;
+    OnDevice dev(device);
+    if (!dev.ok) return MORT_ERR_NO_DEVICE;
+    DevBuf d_cost, d_keys, d_iota, d_order, d_tmp;
+    const size_t bytes = n * sizeof(uint32_t), tmp_bytes = mort_tile_sort_temp_bytes((int)n);
+    if (!d_cost.alloc(bytes) || !d_keys.alloc(bytes) || !d_iota.alloc(bytes) || !d_order.alloc(bytes) || !d_tmp.alloc(tmp_bytes)) return MORT_ERR_NOMEM;
+    if (!d_cost.up(cost, bytes)) return MORT_ERR_HIP;
+    if (mort_tile_sort_desc((const unsigned *)d_cost.p, (unsigned *)d_keys.p, (unsigned *)d_iota.p, (unsigned *)d_order.p, d_tmp.p, tmp_bytes, (int)n, nullptr) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess || !d_keys.down(keys_out, bytes) || !d_order.down(order_out, bytes)) return MORT_ERR_HIP;
+    return MORT_OK;
+}
+
+/* mort_tile_heavy_count (tile_sort.hip) as prepare_tile_order calls it, on a caller's sorted keys and saved counters */
+extern "C" int mort_hip_debug_heavy_count(int device, const uint32_t *keys, size_t n, uint32_t percent, uint32_t max_r, const uint64_t *counters,
+                                          uint64_t lanes, uint32_t *head_out) {
+    if (!keys || !head_out || n < 1 || n > ((size_t)1 << 24)) return MORT_ERR_INVALID;
+    OnDevice dev(device);
+    if (!dev.ok) return MORT_ERR_NO_DEVICE;
+    DevBuf d_keys, d_cnt, d_out;
+    const size_t bytes = n * sizeof(uint32_t), cnt_bytes = MORT_TILE_COUNTERS * sizeof(uint64_t);
+    const uint32_t unwritten = 0xffffffffu; /* the kernel always writes the word: this value never comes back */
+    if (!d_keys.alloc(bytes) || !d_out.alloc(sizeof(uint32_t)) || (counters && !d_cnt.alloc(cnt_bytes))) return MORT_ERR_NOMEM;
+    if (!d_keys.up(keys, bytes) || !d_out.up(&unwritten, sizeof unwritten) || (counters && !d_cnt.up(counters, cnt_bytes))) return MORT_ERR_HIP;
+    if (mort_tile_heavy_count((const unsigned *)d_keys.p, (int)n, percent, max_r, (const unsigned long long *)d_cnt.p, (unsigned long long)lanes, (unsigned *)d_out.p, nullptr) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess || !d_out.down(head_out, sizeof(uint32_t))) return MORT_ERR_HIP;
+    return MORT_OK;
 }

@@ -74,6 +74,8 @@ struct mort_ctx {
     /* unified-tree megakernel (mega_gen.hip): its LDS image and launch constants */
     void *d_gen = nullptr;
     unsigned *d_prio_count = nullptr; int heavy_percent = 50; /* heavy waves: device word with the number of head tiles; its threshold */
+    /* d_prio_count: head word (16 bytes) | the 96 counters heavy_count_kernel reads | a copy of them as it read them (mort_hip_debug_tile_state) */
+    static constexpr size_t prio_count_bytes = 16 + 2 * 96 * sizeof(unsigned long long);
     uint32_t gen_bytes = 0;
     GenArgs gen{};
     bool gen_ok = false;
@@ -90,6 +92,13 @@ struct mort_ctx {
     unsigned *d_tile_keys = nullptr, *d_tile_iota = nullptr; /* device argsort scratch (tile_sort.hip) */
     void *d_sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
+    /* what the last render launch decided about its tile order, for mort_hip_debug_tile_state (debug.hip): host stores of
+     * render_device_impl (reset, tiles), launch_bvh / launch_gen (grid, block, heavy) and prepare_tile_order (the rest) */
+    struct TileLaunch {
+        int ordered = 0, probed = 0, tiles = 0, tiles_x = 0, grid = 0, block = 0, key_sum = 0, spread_shift = 0, gen_tiles = 0;
+        int heavy[4] = {0, 0, 0, 0}; /* mod, num, cap, percent */
+        int has_head = 0;            /* heavy_count_kernel ran for this launch: d_prio_count[0] and the saved counters are its */
+    } tile_launch;
     hipStream_t last_stream = nullptr; /* stream of the most recent render launch (may be the caller's) */
     /* wavefront mode work buffers */
     void *d_wf = nullptr;

@@ -132,8 +132,8 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
         c->cost_key = 0;
     }
     if (fa.heavy_mod > 0 && !c->d_prio_count) {
-        HIPCHK(c, hipMalloc((void **)&c->d_prio_count, 16 + 96 * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->d_prio_count, 0, 16 + 96 * sizeof(unsigned long long), s));
+        HIPCHK(c, hipMalloc((void **)&c->d_prio_count, mort_ctx::prio_count_bytes));
+        HIPCHK(c, hipMemsetAsync(c->d_prio_count, 0, mort_ctx::prio_count_bytes, s));
     }
     const char *tk = std::getenv("MORT_TILE_KEY");
     const int key_sum = (tk && std::strcmp(tk, "sum") == 0) ? 1 : 0;
@@ -162,6 +162,7 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
         if (c->d_prio_count) HIPCHK(c, hipMemcpyAsync(c->d_prio_count + 4, c->d_counters, 96 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s)); /* the probe's counters (pixel_write<true> adds its segments to the per-workgroup slots), beside its tile costs */
         HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 96 * sizeof(unsigned long long), s)); /* probe totals and work cursor */
         c->cost_key = key;
+        c->tile_launch.probed = 1;
     }
     /* order = argsort(cost, descending, equal costs by index), on the device and on this stream */
     HIPCHK(c, mort_tile_sort_desc(c->d_tile_cost, c->d_tile_keys, c->d_tile_iota, c->d_tile_order, c->d_sort_tmp, c->sort_tmp_bytes, tiles, s));
@@ -172,6 +173,9 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
         HIPCHK(c, mort_tile_heavy_count(c->d_tile_keys, tiles, (unsigned)c->heavy_percent, (unsigned)(tiles / 2 > 0 ? tiles / 2 : 1),
                                         (const unsigned long long *)(c->d_prio_count + 4), (unsigned long long)grid * (unsigned long long)FB, c->d_prio_count, s));
         fa.prio_dev = c->d_prio_count;
+        /* diagnostic: the counters as the kernel above read them (launch_gen overwrites them after the frame) */
+        HIPCHK(c, hipMemcpyAsync(c->d_prio_count + 4 + 192, c->d_prio_count + 4, 96 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        c->tile_launch.has_head = 1;
     }
     HIPCHK(c, hipMemsetAsync(c->d_tile_cost, 0, (size_t)tiles * sizeof(unsigned), s));
     fa.tile_order = c->d_tile_order; fa.tile_cost = c->d_tile_cost;
@@ -180,6 +184,7 @@ static int prepare_tile_order(mort_ctx *c, const mort_camera *cam, const RenderA
     fa.spread_shift = chain_bound ? 0 : 6; /* measured: whole tiles while lanes refill several times, single pixels otherwise */
     knob_int(std::getenv("MORT_SPREAD_SHIFT"), fa.spread_shift);
     if (fa.spread_shift >= 6 || fa.spread_shift < 0) fa.gen_tiles = 0;
+    c->tile_launch.ordered = 1; c->tile_launch.key_sum = key_sum; c->tile_launch.spread_shift = fa.spread_shift; c->tile_launch.gen_tiles = fa.gen_tiles;
     if (timed) HIPCHK(c, hipEventRecord(c->ev0, s)); /* time the frame itself; ordering upkeep is reported by wall-clock benches */
     return MORT_OK;
 }
@@ -304,6 +309,7 @@ static int launch_bvh(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, 
     int grid = 0;
     int st = state_setup(c, cam, fa, (const void *)kern, FB, (uint32_t)c->own4_stack + MORT_BVH_TSTACK_SPARE, 1, 12, per_cu_cap, "BVH image does not fit one CU's LDS", s, lds_bytes, grid);
     if (st != MORT_OK) return st;
+    c->tile_launch.grid = grid; c->tile_launch.block = FB;
     st = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, chain_bound, sub, timed, s, [&](const FastArgs &pa) {
         hipError_t e_ = hipFuncSetAttribute((const void *)kern_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e_ != hipSuccess) return e_;
@@ -361,6 +367,8 @@ static int launch_gen(mort_ctx *c, const mort_camera *cam, const RenderArgs &a, 
     int grid = 0;
     int st = state_setup(c, cam, fa, (const void *)kern, FB, MORT_OWN_STACK, 0, dl_cap, INT_MAX, "unified-tree image does not fit one CU's LDS", s, lds_bytes, grid);
     if (st != MORT_OK) return st;
+    c->tile_launch.grid = grid; c->tile_launch.block = FB;
+    c->tile_launch.heavy[0] = fa.heavy_mod; c->tile_launch.heavy[1] = fa.heavy_num; c->tile_launch.heavy[2] = fa.heavy_cap; c->tile_launch.heavy[3] = c->heavy_percent;
     st = prepare_tile_order(c, cam, a, fa, tiles, grid, FB, false, sub, timed, s, [&](const FastArgs &pa) {
         GenArgs pg = ga;
         pg.f = pa;
@@ -566,6 +574,8 @@ static int render_device_impl(mort_ctx *c, const mort_camera *cam, int mode, voi
     const bool sub = mode == MORT_MODE_THROUGHPUT;
     const int tiles = ((W + 7) / 8) * (((sub ? a.local_rows * cam->sqrt_spp : a.local_rows) + 7) / 8);
     if (sub && (st = mort_ensure_substates(c, W, H, cam->sqrt_spp, s)) != MORT_OK) return st;
+    c->tile_launch = mort_ctx::TileLaunch(); /* this launch's, whatever family renders it (mort_hip_debug_tile_state) */
+    c->tile_launch.tiles = tiles; c->tile_launch.tiles_x = (W + 7) / 8;
     if (stats) HIPCHK(c, hipEventRecord(c->ev0, s));
     /* a rank that owns no rows launches nothing (and reports mega_kernel) */
     if (tiles > 0) {

@@ -47,7 +47,9 @@ EXPORTS = [
     "mort_hip_volume_refresh", "mort_hip_volume_refresh_device", "mort_hip_volume_refresh_host", "mort_hip_probe_directions_round",
     "mort_hip_view_update_cache", "mort_hip_view_update_cache_host",
     "mort_hip_query_radiance_cached_direct", "mort_hip_query_radiance_cached_direct_device", "mort_hip_query_radiance_cached_direct_host",
+    "mort_hip_debug_tile_state", "mort_hip_debug_tile_sort", "mort_hip_debug_heavy_count", "mort_hip_debug_deinterleave",
 ]
+TILE_COUNTERS = 96
 TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
 # mort_hip_view_read: name -> (MORT_VIEW_* code, floats per pixel)
@@ -273,6 +275,17 @@ class ViewStats(C.Structure):
         return d
 
 
+class TileState(C.Structure):
+    """mort_tile_state: the last render launch's tile order as the host recorded it (Context.tile_state)"""
+    _fields_ = [("ordered", C.c_int32), ("probed", C.c_int32), ("tiles", C.c_int32), ("tiles_x", C.c_int32), ("grid", C.c_int32),
+                ("block", C.c_int32), ("key_sum", C.c_int32), ("spread_shift", C.c_int32), ("gen_tiles", C.c_int32),
+                ("heavy", C.c_int32 * 4), ("has_head", C.c_int32), ("head", C.c_uint32), ("pad_", C.c_uint32),
+                ("frame_total", C.c_uint64 * TILE_COUNTERS)]
+
+
+assert C.sizeof(TileState) == 64 + 8 * TILE_COUNTERS
+
+
 class MortHipError(RuntimeError):
     def __init__(self, status, what, detail=""):
         self.status = status
@@ -404,6 +417,12 @@ def lib():
         L.mort_hip_probe_directions_round.argtypes = [C.c_int, C.c_uint32, vp]; L.mort_hip_probe_directions_round.restype = C.c_int
         L.mort_hip_view_update_cache.argtypes = [view, vp, vp]; L.mort_hip_view_update_cache.restype = C.c_int
         L.mort_hip_view_update_cache_host.argtypes = [view, vp, vp]; L.mort_hip_view_update_cache_host.restype = C.c_int
+        L.mort_hip_debug_tile_state.argtypes = [ctx, C.POINTER(TileState), vp, vp, vp, sz]; L.mort_hip_debug_tile_state.restype = C.c_int
+        L.mort_hip_debug_tile_sort.argtypes = [C.c_int, vp, sz, vp, vp]; L.mort_hip_debug_tile_sort.restype = C.c_int
+        L.mort_hip_debug_heavy_count.argtypes = [C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint32)]
+        L.mort_hip_debug_heavy_count.restype = C.c_int
+        L.mort_hip_debug_deinterleave.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_size_t)]
+        L.mort_hip_debug_deinterleave.restype = C.c_int
         _lib = L
     return _lib
 
@@ -478,6 +497,25 @@ class Context:
                                         accum.ctypes.data if accum is not None else None,
                                         seg.ctypes.data if seg is not None else None, C.byref(st)), "mort_hip_render")
         return dict(rgba=rgba, accum=accum, segments_px=seg, stats=st.asdict())
+
+    def tile_state(self):
+        """The tile scheduler's state of this context's last render launch (mort_hip_debug_tile_state), after waiting for its stream:
+        the scalars of mort_tile_state, heavy = (mod, num, cap, percent), head and frame_total (the 96 saved counters heavy_count_kernel
+        read) or None when heavy waves were off, and -- None unless ordered -- keys and order (what the launch was ordered by) and cost
+        (what it left for the next launch), uint32 arrays of `tiles` words."""
+        ts = TileState()
+        self._chk(lib().mort_hip_debug_tile_state(self._h, C.byref(ts), None, None, None, 0), "mort_hip_debug_tile_state")
+        out = {k: int(getattr(ts, k)) for k in ("ordered", "probed", "tiles", "tiles_x", "grid", "block", "key_sum", "spread_shift", "gen_tiles")}
+        out["heavy"] = tuple(int(v) for v in ts.heavy)
+        out["head"] = int(ts.head) if ts.has_head else None
+        out["frame_total"] = np.array(ts.frame_total, dtype=np.uint64) if ts.has_head else None
+        out["keys"] = out["order"] = out["cost"] = None
+        if ts.ordered and ts.tiles > 0:
+            keys, order, cost = (np.full(ts.tiles, 0xdeadbeef, dtype=np.uint32) for _ in range(3))
+            self._chk(lib().mort_hip_debug_tile_state(self._h, C.byref(ts), keys.ctypes.data, order.ctypes.data, cost.ctypes.data, ts.tiles),
+                      "mort_hip_debug_tile_state")
+            out["keys"], out["order"], out["cost"] = keys, order, cost
+        return out
 
     def render_device(self, cam, d_rgba, d_accum=0, stream=0, mode=MODE_MEGA, sync=True):
         """Render into caller-owned device buffers (packed owned rows); d_* are raw device addresses."""
@@ -1348,6 +1386,52 @@ def debug_random_float_device(device=0):
     if st != 0:
         raise MortHipError(st, "mort_hip_debug_random_float_device")
     return dict(differ=out[0], lowest=out[1], visited=out[2])
+
+
+def debug_tile_sort(cost, device=0):
+    """mort_hip_debug_tile_sort: the render's device argsort (tile_sort.hip mort_tile_sort_desc) of n uint32 costs -- (keys, order)."""
+    cost = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+    keys, order = np.full(cost.size, 0xdeadbeef, np.uint32), np.full(cost.size, 0xdeadbeef, np.uint32)
+    st = lib().mort_hip_debug_tile_sort(device, cost.ctypes.data, cost.size, keys.ctypes.data, order.ctypes.data)
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_tile_sort")
+    return keys, order
+
+
+def debug_heavy_count(keys, percent, max_r, counters, lanes, device=0):
+    """mort_hip_debug_heavy_count: the heavy-wave head heavy_count_kernel decides from n sorted keys, the threshold `percent`, the cap
+    max_r, the 96 saved counters (None: no counters) and the launch's lane count."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    if counters is not None:
+        counters = np.ascontiguousarray(counters, dtype=np.uint64).reshape(-1)
+        assert counters.size == TILE_COUNTERS
+    head = C.c_uint32(0)
+    st = lib().mort_hip_debug_heavy_count(device, keys.ctypes.data, keys.size, percent, max_r,
+                                          counters.ctypes.data if counters is not None else None, lanes, C.byref(head))
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_heavy_count")
+    return int(head.value)
+
+
+def debug_gather_stride(width, height, nranks, rows_per_block):
+    """pixels between two ranks' tiles in the frame gather's buffer (comm_rccl.hip gather_tile_px); host only"""
+    px = C.c_size_t(0)
+    st = lib().mort_hip_debug_deinterleave(0, None, width, height, nranks, rows_per_block, None, C.byref(px))
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_deinterleave")
+    return int(px.value)
+
+
+def debug_deinterleave(gathered, width, height, nranks, rows_per_block, device=0):
+    """mort_hip_debug_deinterleave: the frame gather's de-interleave kernel over `gathered` (uint8, nranks * stride * 4 bytes with
+    stride = debug_gather_stride(...)) -- the (height, width, 4) uint8 frame."""
+    gathered = np.ascontiguousarray(gathered, dtype=np.uint8).reshape(-1)
+    assert gathered.size == nranks * debug_gather_stride(width, height, nranks, rows_per_block) * 4
+    frame = np.zeros((height, width, 4), dtype=np.uint8)
+    st = lib().mort_hip_debug_deinterleave(device, gathered.ctypes.data, width, height, nranks, rows_per_block, frame.ctypes.data, None)
+    if st != 0:
+        raise MortHipError(st, "mort_hip_debug_deinterleave")
+    return frame
 
 
 def _query_rays(rays):

@@ -12,7 +12,8 @@ accumulators, per-pixel segment counts, final RNG words, and the totals `segment
    values are not all zero;
  - a glass shell around Lambertian spheres: paths whose deepest level is an identity, at the limit too;
  - a second frame on one context, a two-way partition, and the first frame after an upload, which runs the one-sample cost probe (the
-   kernel's PROBE variant) before it: the probe's tile costs order the frame and cannot be read back, what is checked is the frame after it;
+   kernel's PROBE variant) before it: the probe's tile costs order the frame and are read back through Context.tile_state(), and the
+   frame after it is checked as every frame is;
  - MODE_THROUGHPUT (the SUB variant) against its own reference, the oracle's arithmetic on the sub-streams (test_gpu_throughput.py)."""
 import ctypes as C
 
@@ -20,6 +21,7 @@ import numpy as np
 import pytest
 
 from mort_amd import host, hip, structs as S
+from tests import tile_ref
 from tests.test_gpu_throughput import expected_substream, render_tp
 from tests.worlds import custom_bvh_world, set_view
 
@@ -188,7 +190,21 @@ def test_first_frame_after_the_probe_and_second_frame(gpu_ctx, oracle, monkeypat
         _REF["frame2"] = oracle.render(world, cam, states=r1["states"].copy(), nthreads=8)
     r2 = _REF["frame2"]
     _same(_render(gpu_ctx, oracle, world, cam), r1)
+    # the PROBE variant's own result: the tile costs the first frame was ordered by (Context.tile_state) are the oracle's one-sample
+    # frame's from the same streams
+    if "probe" not in _REF:
+        cam1 = type(cam).from_buffer_copy(cam)
+        cam1.samples_per_pixel, cam1.sqrt_spp, cam1.recip_sqrt_spp, cam1.pixel_samples_scale = 1, 1, 1.0, 1.0
+        _REF["probe"] = oracle.render(world, cam1, nthreads=8, want_accum=False)
+    ts = gpu_ctx.tile_state()
+    assert (ts["ordered"], ts["probed"], ts["block"]) == (1, 1, block)
+    probe_cost = np.zeros(ts["tiles"], np.uint32)
+    probe_cost[ts["order"]] = ts["keys"]
+    assert (np.sort(ts["order"]) == np.arange(ts["tiles"])).all()
+    assert (probe_cost == tile_ref.tile_costs(_REF["probe"]["segments_px"], cam.image_width)).all(), "the probe's tile costs"
+    assert (ts["cost"] == tile_ref.tile_costs(r1["segments_px"], cam.image_width)).all(), "the first frame's tile costs"
     _same(_render(gpu_ctx, oracle, world, cam, seed=False), r2)
+    assert gpu_ctx.tile_state()["probed"] == 0
 
 
 @pytest.mark.parametrize("block", [1024, 256])
