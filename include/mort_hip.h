@@ -312,6 +312,7 @@ typedef struct mort_view_stats {
 #define MORT_VIEW_DEPTH 6     /* [1] */
 #define MORT_VIEW_HISTORY 7   /* [MORT_TEMPORAL_HISTORY_FLOATS] the history the last frame wrote, three float4 planes; needs temporal */
 #define MORT_VIEW_ENDS 8      /* [1, uint32] the last cached frame's paths per pixel that ended in the volume; needs a cache attached */
+#define MORT_VIEW_LIT 9       /* [1, uint32] of those, the paths whose shadow segment saw light; needs a DIRECT cache attached (4.23) */
 /* the three stages' own defaults; temporal 1, filter SVGF; width = height = 0 */
 int mort_hip_view_defaults(mort_view_params *p);
 /* MORT_OK or MORT_ERR_INVALID: sizes > 0, temporal 0 / 1, a known filter, and the stages' own checks of the parameters in use
@@ -721,6 +722,48 @@ int mort_hip_view_set_cache(mort_view *v, const mort_cached_frame_params *params
 /* the same for a caller without device buffers (the CLI): records and depth (or NULL) are host arrays, which the view copies into
  * device buffers of its own; those live until the next attach or detach by either form, or the view's end */
 int mort_hip_view_set_cache_host(mort_view *v, const mort_cached_frame_params *params, const float *records, const float *depth);
+
+/* ---- direct-light cached frames: cached frames over a volume of INDIRECT light whose paths add one sampled shadow segment toward
+ * the light object where they end.  The calls take mort_hip_render_cached*'s arguments under the same
+ * mort_cached_frame_params -- no new flag bit -- and one more optional output, lit_px_out / d_lit (one uint32 per pixel, or NULL):
+ * how many of the pixel's paths had a shadow segment that returned a non-zero emission.  The volume is composed as for the
+ * direct-light cached queries above (sh_full - sh_emit).
+ *
+ * A direct cached frame is a cached frame word for word, except at the hit where a path ends in the volume.  There steps (a)-(d)
+ * of the direct-light cached queries apply, bound to the frame so:
+ *   - the light object is cam->light_obj_type / cam->light_obj_idx, the bounce limit and the background are the camera's;
+ *   - the shadow segment's time is the sample's ray time, the time get_ray gave that sample's ray;
+ *   - the draws of (b) and (c) come from the pixel's stream, after the path's own draws and before the next sample's get_ray;
+ *   - rule (a): with no light object, or when iter + 1 >= bounce_limit, nothing is drawn and nothing is added;
+ *   - the shadow segment's search counts as a segment ("one segment counted per search"): in segments_px_out, in stats.segments
+ *     and, through its draws, in stats.rng_draws;
+ *   - ends counts a path once, however its terminal went; per pixel lit <= ends <= sqrt_spp^2.
+ * So
+ *   (i)   with cam->light_obj_type == -1 the call is mort_hip_render_cached* to the bit: uchar4, accumulators, per-pixel segments,
+ *         ends, final streams, stats.segments and stats.rng_draws; lit is all 0;
+ *   (ii)  with K >= cam->bounce_limit, or with every weight 0, it is mort_hip_render(..., MORT_MODE_MEGA, ...) to the bit;
+ *   (iii) with cam->bounce_limit == K + 1 every terminal takes rule (a) and the frame is the cached frame to the bit.
+ * Checks, forms, alignment, overlap, the partition's refusal (MORT_ERR_UNSUPPORTED), the asynchronous form and the deferred stats
+ * are the cached frame's; lit is one more output among those that must not overlap, 16-byte aligned in the _device form.
+ * mort_stats as the cached frame fills it: algorithmic_hbm_bytes the cached frame's plus 4 B per pixel when lit is written,
+ * kernel_name cached_frame_direct_kernel<TREE, VISIBLE>; the host loop's name says "cached frame, direct". ---- */
+int mort_hip_render_cached_direct(mort_ctx *ctx, const mort_camera *cam, const mort_cached_frame_params *params, const float *records,
+                                  const float *depth /* or NULL */, uint8_t *rgba_out, float *accum_out /* or NULL */,
+                                  uint32_t *segments_px_out /* or NULL */, uint32_t *ends_px_out /* or NULL */, uint32_t *lit_px_out /* or NULL */,
+                                  mort_stats *stats);
+int mort_hip_render_cached_direct_device(mort_ctx *ctx, const mort_camera *cam, const mort_cached_frame_params *params, const void *d_records,
+                                         const void *d_depth, void *d_rgba, void *d_accum /* or NULL */, void *d_ends /* or NULL */,
+                                         void *d_lit /* or NULL */, void *stream, mort_stats *stats);
+int mort_hip_render_cached_direct_host(const mort_world *world, const mort_camera *cam, mort_rng_state *states, int nthreads, int flags,
+                                       const mort_cached_frame_params *params, const float *records, const float *depth, uint8_t *rgba_out,
+                                       float *accum_out, uint32_t *segments_px_out, uint32_t *ends_px_out, uint32_t *lit_px_out,
+                                       mort_stats *stats);
+/* mort_hip_view_set_cache* with the view's frames run as direct cached frames: the same checks, the history forgotten the same
+ * way.  Attaching by either family replaces what the other attached; NULL params detaches.  mort_hip_view_update_cache* works
+ * unchanged on such a view: the params and the direct-ness stay, the history is kept.  mort_hip_view_read(MORT_VIEW_LIT) gives
+ * the last frame's lit counts, kept beside the ends; it is MORT_ERR_INVALID unless a direct cache is attached. */
+int mort_hip_view_set_cache_direct(mort_view *v, const mort_cached_frame_params *params, const void *d_records, const void *d_depth);
+int mort_hip_view_set_cache_direct_host(mort_view *v, const mort_cached_frame_params *params, const float *records, const float *depth);
 
 /* ---- volume refresh: probes re-baked through the volume and blended into their records.  The producer that uses
  * the cache: a probe's rays are traced as cached paths that end in the volume as it stands, projected as the bake projects them,

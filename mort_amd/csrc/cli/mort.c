@@ -113,6 +113,16 @@
  * form).  The JSON line gains cache_direct: 1 and lit (the paths whose shadow segment returned a non-zero emission), after ends.
  * Without --cache-direct every accepted and refused combination and every output byte is what it was.
  *
+ * --cache-render-direct (with --sh-volume ... --cache-depth K, --visibility optional; excludes --cache-render, --cache-direct,
+ * --refresh, --probe, --radiance-out, --pick and --irradiance-out; one GPU in the default mode, or --mode host): --cache-render with
+ * direct cached frames in the cached frames' place.  The volume is composed as --cache-direct composes it (the bake
+ * minus an emission-only bake from a copy of its streams), then the frame loop runs as under --cache-render: on a GPU through a view
+ * with the direct cache attached (mort_hip_view_set_cache_direct_host), under --mode host through mort_hip_render_cached_direct_host.
+ * The JSON line is --cache-render's plus cache_direct: 1 and lit (the last frame's paths whose shadow segment returned a non-zero
+ * emission), after ends.  --refresh is refused: a refresh through plain cached paths would put the emitters' light back into a
+ * volume that is to hold indirect light only.  Without --cache-render-direct every accepted and refused combination and every
+ * output byte is what it was.
+ *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
  * RCCL (`--gather rccl`, the default: xGMI inside a node), or through a shared host mapping (`--gather shm`: for ranks
@@ -159,13 +169,16 @@ static int usage(void) {
            "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
            "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]] "
            "[--cache-depth K] [--radiance-out FILE] [--cache-render] [--refresh R[,H[,KR[,S]]]] [--cache-direct]\n"
+           "            [--cache-render-direct]\n"
            "  --cache-depth K with --sh-volume: paths end in the volume from bounce K on; --probe X,Y[,N] prints one pixel's colour,\n"
            "  --radiance-out FILE writes a preview from pixel-centre rays (--spp paths each; no jitter, no lens), not a render,\n"
            "  --cache-render renders: the ordinary frame loop (--frames, --out, --temporal, --svgf, ...) over cached frames\n"
            "  --refresh R[,H[,KR[,S]]] with --sh-volume: R rounds re-bake every probe through the volume (hysteresis H, refresh depth KR);\n"
            "  with --cache-render and S > 0 every S-th probe is refreshed again before each frame\n"
            "  --cache-direct with --cache-depth and --probe or --radiance-out: the volume keeps indirect light only and a path that\n"
-           "  ends in it adds one sampled shadow ray toward the scene's light\n");
+           "  ends in it adds one sampled shadow ray toward the scene's light\n"
+           "  --cache-render-direct with --sh-volume and --cache-depth: --cache-render over that indirect-only volume, the frames'\n"
+           "  paths adding the sampled shadow ray where they end; excludes --cache-render, --cache-direct and --refresh\n");
     return -1;
 }
 
@@ -296,7 +309,8 @@ typedef struct {
     mort_rng_state *states;
 } cache_volume;
 static void bake_cache_volume(cache_volume *v, mort_ctx *ctx /* NULL: the host forms */, const mort_world *world, const mort_camera *cam,
-                              unsigned long long seed, int sh_d, int sh_n, int vis_s, int threads, int host_flags, refresh_opts *ro) {
+                              unsigned long long seed, int sh_d, int sh_n, int vis_s, int threads, int host_flags, refresh_opts *ro,
+                              int direct /* --cache-render-direct: indirect light only, as --cache-direct composes it */) {
     const mort_volume_grid *g = &v->p.grid;
     const int visible = (v->p.flags & MORT_CACHED_VISIBLE) != 0;
     const size_t n = v->probes = (size_t)g->count[0] * (size_t)g->count[1] * (size_t)g->count[2];
@@ -316,12 +330,32 @@ static void bake_cache_volume(cache_volume *v, mort_ctx *ctx /* NULL: the host f
     int st;
     if ((st = mort_hip_volume_probes(g, probes)) != MORT_OK) die(NULL, st, "mort_hip_volume_probes");
     if ((st = mort_hip_rng_seed_host(seed, (int)(n * (size_t)sh_d), 1, states)) != MORT_OK) die(NULL, st, "mort_hip_rng_seed_host");
+    if (direct) { /* the full bake minus the emission-only bake (bounce limit 1, black background, one path) from a copy of the streams */
+        mort_probe_params pe = pp;
+        pe.rp.bounce_limit = 1; pe.rp.samples = 1;
+        pe.rp.background[0] = pe.rp.background[1] = pe.rp.background[2] = 0.0f;
+        mort_rng_state *states_e = (mort_rng_state *)malloc(n * (size_t)sh_d * sizeof *states_e);
+        float *sh_e = (float *)malloc(n * MORT_SH9_FLOATS * sizeof *sh_e);
+        if (!states_e || !sh_e) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+        memcpy(states_e, states, n * (size_t)sh_d * sizeof *states_e);
+        double emit_sec = 0;
+        if (!ctx) {
+            if ((st = mort_hip_probe_bake_host(world, &pp, n, probes, NULL, states, threads, host_flags, sh, &v->bake_sec)) != MORT_OK) die(NULL, st, "mort_hip_probe_bake_host");
+            if ((st = mort_hip_probe_bake_host(world, &pe, n, probes, NULL, states_e, threads, host_flags, sh_e, &emit_sec)) != MORT_OK) die(NULL, st, "mort_hip_probe_bake_host");
+        } else {
+            if ((st = mort_hip_probe_bake(ctx, &pp, n, probes, NULL, states, sh, &v->bake_sec)) != MORT_OK) die(ctx, st, "mort_hip_probe_bake");
+            if ((st = mort_hip_probe_bake(ctx, &pe, n, probes, NULL, states_e, sh_e, &emit_sec)) != MORT_OK) die(ctx, st, "mort_hip_probe_bake");
+        }
+        for (size_t i = 0; i < n * MORT_SH9_FLOATS; i++) sh[i] = sh[i] - sh_e[i];
+        v->bake_sec += emit_sec;
+        free(states_e); free(sh_e);
+    }
     if (!ctx) {
-        if ((st = mort_hip_probe_bake_host(world, &pp, n, probes, NULL, states, threads, host_flags, sh, &v->bake_sec)) != MORT_OK) die(NULL, st, "mort_hip_probe_bake_host");
+        if (!direct && (st = mort_hip_probe_bake_host(world, &pp, n, probes, NULL, states, threads, host_flags, sh, &v->bake_sec)) != MORT_OK) die(NULL, st, "mort_hip_probe_bake_host");
         if ((st = mort_hip_volume_pack_host(n, sh, NULL, threads, v->records, NULL)) != MORT_OK) die(NULL, st, "mort_hip_volume_pack_host");
         if (visible && (st = mort_hip_probe_depth_bake_host(world, &v->dp, n, probes, threads, host_flags, v->depth, NULL)) != MORT_OK) die(NULL, st, "mort_hip_probe_depth_bake_host");
     } else {
-        if ((st = mort_hip_probe_bake(ctx, &pp, n, probes, NULL, states, sh, &v->bake_sec)) != MORT_OK) die(ctx, st, "mort_hip_probe_bake");
+        if (!direct && (st = mort_hip_probe_bake(ctx, &pp, n, probes, NULL, states, sh, &v->bake_sec)) != MORT_OK) die(ctx, st, "mort_hip_probe_bake");
         if ((st = mort_hip_volume_pack(ctx, n, sh, NULL, v->records, NULL)) != MORT_OK) die(ctx, st, "mort_hip_volume_pack");
         if (visible && (st = mort_hip_probe_depth_bake(ctx, &v->dp, n, probes, v->depth, NULL)) != MORT_OK) die(ctx, st, "mort_hip_probe_depth_bake");
     }
@@ -378,6 +412,7 @@ int main(int argc, char **argv) {
     const char *rad_out = NULL;
     int cache_render = 0;
     int cache_direct = 0;
+    int cache_render_direct = 0; /* --cache-render-direct: sets cache_render too, once its own refusals are through */
     refresh_opts refresh;
     memset(&refresh, 0, sizeof refresh);
     refresh.h = 0.9f;
@@ -438,6 +473,7 @@ int main(int argc, char **argv) {
         else if (ARG("--radiance-out")) rad_out = argv[++i];
         else if (strcmp(argv[i], "--cache-render") == 0) cache_render = 1;
         else if (strcmp(argv[i], "--cache-direct") == 0) cache_direct = 1;
+        else if (strcmp(argv[i], "--cache-render-direct") == 0) cache_render_direct = 1;
         else if (ARG("--refresh")) {
             refresh.on = 1;
             if (sscanf(argv[++i], "%d,%f,%d,%d", &refresh.rounds, &refresh.h, &refresh.depth, &refresh.stride) < 1) { fprintf(stderr, "--refresh R[,H[,KR[,S]]]\n"); return -1; }
@@ -459,6 +495,17 @@ int main(int argc, char **argv) {
     if (cached && !sh_volume) { fprintf(stderr, "--cache-depth needs --sh-volume\n"); return -1; }
     if (rad_out && !cached) { fprintf(stderr, "--radiance-out needs --cache-depth\n"); return -1; }
     if (cached && (cache_depth < 0 || cache_depth > MORT_MAX_BOUNCE_LIMIT)) { fprintf(stderr, "--cache-depth: K in 0..%d\n", MORT_MAX_BOUNCE_LIMIT); return -1; }
+    if (cache_render_direct) {
+        if (cache_render || cache_direct) { fprintf(stderr, "--cache-render-direct excludes --cache-render and --cache-direct\n"); return -1; }
+        if (!sh_volume || !cached) { fprintf(stderr, "--cache-render-direct needs --sh-volume and --cache-depth\n"); return -1; }
+        if (probe || rad_out || pick || irr_out) { fprintf(stderr, "--cache-render-direct excludes --probe, --radiance-out, --pick and --irradiance-out\n"); return -1; }
+        if (gpus > 1 || mode != MORT_MODE_MEGA) { fprintf(stderr, "--cache-render-direct is a single-GPU option of the default mode and of --mode host\n"); return -1; }
+        if (refresh.on) {
+            fprintf(stderr, "--cache-render-direct excludes --refresh: a refresh through plain cached paths would put the emitters' light back into the indirect volume\n");
+            return -1;
+        }
+        cache_render = 1; /* from here on: --cache-render with another volume and another frame call */
+    }
     if (cache_direct && !cached) { fprintf(stderr, "--cache-direct needs --cache-depth\n"); return -1; }
     if (cache_direct && (cache_render || refresh.on)) { fprintf(stderr, "--cache-direct excludes --cache-render and --refresh\n"); return -1; }
     if (cache_render && (!sh_volume || !cached)) { fprintf(stderr, "--cache-render needs --sh-volume and --cache-depth\n"); return -1; }
@@ -854,13 +901,14 @@ int main(int argc, char **argv) {
 
     cache_volume cv; /* --cache-render */
     memset(&cv, 0, sizeof cv);
-    uint32_t *ends_px = NULL;
+    uint32_t *ends_px = NULL, *lit_px = NULL;
     if (cache_render) {
         cv.p.cache_depth = cache_depth; cv.p.flags = visibility ? MORT_CACHED_VISIBLE : 0u;
         cv.p.vis.normal_bias = vis_bias; cv.p.vis.min_visibility = vis_min;
         if (volume_grid(vol_box, vol_n, &cv.p.grid) != 0) return -1;
         ends_px = calloc(npx, sizeof *ends_px);
-        if (!ends_px) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
+        lit_px = cache_render_direct ? calloc(npx, sizeof *lit_px) : NULL;
+        if (!ends_px || (cache_render_direct && !lit_px)) { fprintf(stderr, "out of memory\n"); return EXIT_FAILURE; }
     }
 
     uint8_t *rgba = calloc(npx, 4);
@@ -898,11 +946,14 @@ int main(int argc, char **argv) {
             if (!f || fread(hstates, sizeof *hstates, npx, f) != npx) { fprintf(stderr, "cannot read %zu states from %s\n", npx, sin); return EXIT_FAILURE; }
             fclose(f);
         } else if ((st = mort_hip_rng_seed_host(seed, W, H, hstates)) != MORT_OK) die(NULL, st, "mort_hip_rng_seed_host");
-        if (cache_render) bake_cache_volume(&cv, NULL, &world, &cam, seed, sh_d, sh_n, vis_s, threads, tree ? MORT_HOST_TREE : 0, &refresh);
+        if (cache_render) bake_cache_volume(&cv, NULL, &world, &cam, seed, sh_d, sh_n, vis_s, threads, tree ? MORT_HOST_TREE : 0, &refresh, cache_render_direct);
         for (int f = 0; f < frames; f++) {
             if (f > 0) frame_input(&cam, keys, f, mouse_dx, mouse_dy);
             if (f > 0 && cache_render && refresh.stride > 0) refresh_before_frame(&cv, NULL, &world, &cam, &refresh, sh_d, sh_n, f, threads, tree ? MORT_HOST_TREE : 0);
-            if (cache_render) {
+            if (cache_render_direct) {
+                if ((st = mort_hip_render_cached_direct_host(&world, &cam, hstates, threads, tree ? MORT_HOST_TREE : 0, &cv.p, cv.records, cv.depth, rgba, accum,
+                                                             NULL, ends_px, lit_px, &stats)) != MORT_OK) die(NULL, st, "mort_hip_render_cached_direct_host");
+            } else if (cache_render) {
                 if ((st = mort_hip_render_cached_host(&world, &cam, hstates, threads, tree ? MORT_HOST_TREE : 0, &cv.p, cv.records, cv.depth, rgba, accum, NULL,
                                                       ends_px, &stats)) != MORT_OK) die(NULL, st, "mort_hip_render_cached_host");
             } else
@@ -953,7 +1004,10 @@ int main(int argc, char **argv) {
             if ((st = mort_hip_view_create(ctx, &vp, &view)) != MORT_OK) die(ctx, st, "mort_hip_view_create");
         }
         if (cache_render) { /* the volume baked on this context; the view keeps its own device copies of the records and maps */
-            bake_cache_volume(&cv, ctx, &world, &cam, seed, sh_d, sh_n, vis_s, threads, 0, &refresh);
+            bake_cache_volume(&cv, ctx, &world, &cam, seed, sh_d, sh_n, vis_s, threads, 0, &refresh, cache_render_direct);
+            if (cache_render_direct) {
+                if ((st = mort_hip_view_set_cache_direct_host(view, &cv.p, cv.records, cv.depth)) != MORT_OK) die(ctx, st, "mort_hip_view_set_cache_direct_host");
+            } else
             if ((st = mort_hip_view_set_cache_host(view, &cv.p, cv.records, cv.depth)) != MORT_OK) die(ctx, st, "mort_hip_view_set_cache_host");
         }
         for (int f = 0; f < frames; f++) {
@@ -991,6 +1045,7 @@ int main(int argc, char **argv) {
         }
         if (view) { /* what the files need of the last frame */
             if (cache_render && (st = mort_hip_view_read(view, MORT_VIEW_ENDS, ends_px)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
+            if (cache_render_direct && (st = mort_hip_view_read(view, MORT_VIEW_LIT, lit_px)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
             if (dump && (st = mort_hip_view_read(view, MORT_VIEW_RAW_ACCUM, accum)) != MORT_OK) die(ctx, st, "mort_hip_view_read");
             if (feat_out) {
                 alb = malloc(npx * 3 * sizeof(float)); nrm = malloc(npx * 3 * sizeof(float)); dep = malloc(npx * sizeof(float));
@@ -1085,6 +1140,11 @@ int main(int argc, char **argv) {
         unsigned long long ended = 0;
         for (size_t i = 0; i < npx; i++) ended += ends_px[i];
         printf(", \"cache_depth\": %d, \"ends\": %llu", cache_depth, ended);
+        if (cache_render_direct) { /* of those, the paths whose shadow segment returned a non-zero emission */
+            unsigned long long lit_paths = 0;
+            for (size_t i = 0; i < npx; i++) lit_paths += lit_px[i];
+            printf(", \"cache_direct\": 1, \"lit\": %llu", lit_paths);
+        }
         if (visibility) {
             printf(", \"normal_bias\": "); print_f32(cv.p.vis.normal_bias);
             printf(", \"min_visibility\": "); print_f32(cv.p.vis.min_visibility);

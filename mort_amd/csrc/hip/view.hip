@@ -54,6 +54,9 @@ struct mort_view {
     mort_cached_frame_params cache{};
     const void *d_records = nullptr, *d_cache_depth = nullptr;
     uint32_t *d_ends = nullptr; /* per pixel, the last frame's paths that ended in the volume (allocated when a cache is first attached) */
+    /* mort_hip_view_set_cache_direct: the frames are direct cached frames */
+    bool direct = false;
+    uint32_t *d_lit = nullptr; /* per pixel, the last frame's ended paths whose shadow segment saw light (allocated with the first direct cache) */
     void *own_records = nullptr, *own_depth = nullptr; /* mort_hip_view_set_cache_host: the view's own copies of the caller's host arrays */
 
     float *albedo() const { return d_feat; }
@@ -73,6 +76,7 @@ bool same_feature_camera(const mort_camera &a, const mort_camera &b) {
 void free_buffers(mort_view *v) {
     (void)hipFree(v->d_rgba); (void)hipFree(v->d_accum); (void)hipFree(v->d_feat); (void)hipFree(v->d_hist[0]); (void)hipFree(v->d_hist[1]);
     (void)hipFree(v->d_tacc); (void)hipFree(v->d_var); (void)hipFree(v->d_facc); (void)hipFree(v->d_out); (void)hipFree(v->d_ends);
+    (void)hipFree(v->d_lit);
     (void)hipFree(v->own_records); (void)hipFree(v->own_depth);
     if (v->h_out) (void)hipHostFree(v->h_out);
     for (hipEvent_t e : v->ev) if (e) (void)hipEventDestroy(e);
@@ -114,6 +118,9 @@ int view_frame(mort_view *v, const mort_camera *cam, int mode, void *d_dst, uint
     int st;
     if (!v->cached) st = mort_hip_render_device(c, cam, mode, v->d_rgba, v->d_accum, s, timed ? &local : nullptr);
     else if (mode != MORT_MODE_MEGA) st = MORT_ERR_UNSUPPORTED;
+    else if (v->direct)
+        st = mort_hip_render_cached_direct_device(c, cam, &v->cache, v->d_records, v->d_cache_depth, v->d_rgba, v->d_accum, v->d_ends, v->d_lit, s,
+                                                  timed ? &local : nullptr);
     else st = mort_hip_render_cached_device(c, cam, &v->cache, v->d_records, v->d_cache_depth, v->d_rgba, v->d_accum, v->d_ends, s, timed ? &local : nullptr);
     c->defer_stats = false;
     if (st != MORT_OK) {
@@ -308,15 +315,27 @@ int upload_cache(mort_view *v, const mort_volume_grid &grid, const float *record
 }
 } // namespace
 
-extern "C" int mort_hip_view_set_cache_host(mort_view *v, const mort_cached_frame_params *p, const float *records, const float *depth) {
+namespace {
+int set_cache_impl(mort_view *v, const mort_cached_frame_params *p, const void *d_records, const void *d_depth, bool direct);
+
+int set_cache_host_impl(mort_view *v, const mort_cached_frame_params *p, const float *records, const float *depth, bool direct, const char *what) {
     if (!v || !p) return MORT_ERR_INVALID;
     if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, records, depth)) return MORT_ERR_INVALID;
     void *d_rec = nullptr, *d_dep = nullptr;
-    int st = upload_cache(v, p->grid, records, depth, &d_rec, &d_dep, "mort_hip_view_set_cache_host");
-    if (st == MORT_OK) st = mort_hip_view_set_cache(v, p, d_rec, d_dep); /* frees the copies of an earlier call */
+    int st = upload_cache(v, p->grid, records, depth, &d_rec, &d_dep, what);
+    if (st == MORT_OK) st = set_cache_impl(v, p, d_rec, d_dep, direct); /* frees the copies of an earlier call */
     if (st != MORT_OK) { (void)hipFree(d_rec); (void)hipFree(d_dep); return st; }
     v->own_records = d_rec; v->own_depth = d_dep;
     return MORT_OK;
+}
+} // namespace
+
+extern "C" int mort_hip_view_set_cache_host(mort_view *v, const mort_cached_frame_params *p, const float *records, const float *depth) {
+    return set_cache_host_impl(v, p, records, depth, false, "mort_hip_view_set_cache_host");
+}
+
+extern "C" int mort_hip_view_set_cache_direct_host(mort_view *v, const mort_cached_frame_params *p, const float *records, const float *depth) {
+    return set_cache_host_impl(v, p, records, depth, true, "mort_hip_view_set_cache_direct_host");
 }
 
 /* new records and maps under the attached params; the history goes on */
@@ -343,26 +362,44 @@ extern "C" int mort_hip_view_update_cache_host(mort_view *v, const float *record
     return MORT_OK;
 }
 
-extern "C" int mort_hip_view_set_cache(mort_view *v, const mort_cached_frame_params *p, const void *d_records, const void *d_depth) {
+namespace {
+/* one more per-pixel count of the view's, allocated when first wanted */
+int ensure_counts(mort_view *v, uint32_t **d) {
+    if (*d) return MORT_OK;
+    mort_ctx *c = v->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    const hipError_t e = hipMalloc((void **)d, v->npx * sizeof(uint32_t));
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return MORT_ERR_NOMEM; }
+    HIPCHK(c, e);
+    return MORT_OK;
+}
+
+int set_cache_impl(mort_view *v, const mort_cached_frame_params *p, const void *d_records, const void *d_depth, bool direct) {
     if (!v) return MORT_ERR_INVALID;
-    if (p) { /* what mort_hip_render_cached_device will ask of them at every frame */
+    if (p) { /* what mort_hip_render_cached[_direct]_device will ask of them at every frame */
         if (!mort_cached_volume_ok(p->cache_depth, p->flags, &p->grid, &p->vis, d_records, d_depth)) return MORT_ERR_INVALID;
         if (((uintptr_t)d_records & 15u) || ((uintptr_t)d_depth & 15u)) return MORT_ERR_INVALID;
-        if (!v->d_ends) {
-            mort_ctx *c = v->ctx;
-            HIPCHK(c, hipSetDevice(c->device));
-            const hipError_t e = hipMalloc((void **)&v->d_ends, v->npx * sizeof(uint32_t));
-            if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return MORT_ERR_NOMEM; }
-            HIPCHK(c, e);
-        }
+        int st = ensure_counts(v, &v->d_ends);
+        if (st == MORT_OK && direct) st = ensure_counts(v, &v->d_lit);
+        if (st != MORT_OK) return st;
     }
     const int st = free_own_cache(v); /* whatever is attached now replaces them */
     if (st != MORT_OK) return st;
     if (p) v->cache = *p;
     v->cached = p != nullptr;
+    v->direct = v->cached && direct;
     v->d_records = p ? d_records : nullptr; v->d_cache_depth = p ? d_depth : nullptr;
     v->frame = 0; /* another estimator: its history does not continue */
     return MORT_OK;
+}
+} // namespace
+
+extern "C" int mort_hip_view_set_cache(mort_view *v, const mort_cached_frame_params *p, const void *d_records, const void *d_depth) {
+    return set_cache_impl(v, p, d_records, d_depth, false);
+}
+
+extern "C" int mort_hip_view_set_cache_direct(mort_view *v, const mort_cached_frame_params *p, const void *d_records, const void *d_depth) {
+    return set_cache_impl(v, p, d_records, d_depth, true);
 }
 
 extern "C" int mort_hip_view_frame_device(mort_view *v, const mort_camera *cam, int mode, void *d_rgba_out, void *stream, mort_view_stats *stats) {
@@ -384,7 +421,7 @@ extern "C" int mort_hip_view_read(mort_view *v, int what, void *host_out) {
     if (!v || !host_out || !v->have_frame) return MORT_ERR_INVALID;
     mort_ctx *c = v->ctx;
     const size_t npx = v->npx;
-    const void *src = nullptr; /* 32-bit words: floats, but for MORT_VIEW_ENDS */
+    const void *src = nullptr; /* 32-bit words: floats, but for MORT_VIEW_ENDS and MORT_VIEW_LIT */
     size_t floats = 0;
     switch (what) {
     case MORT_VIEW_RAW_ACCUM: src = v->d_accum; floats = 3 * npx; break;
@@ -395,6 +432,7 @@ extern "C" int mort_hip_view_read(mort_view *v, int what, void *host_out) {
     case MORT_VIEW_NORMAL: src = v->normal(); floats = 3 * npx; break;
     case MORT_VIEW_DEPTH: src = v->depth(); floats = npx; break;
     case MORT_VIEW_ENDS: src = v->cached ? v->d_ends : nullptr; floats = npx; break;
+    case MORT_VIEW_LIT: src = v->direct ? v->d_lit : nullptr; floats = npx; break;
     case MORT_VIEW_HISTORY: src = v->p.temporal ? v->d_hist[v->hist_cur] : (const void *)nullptr; floats = MORT_TEMPORAL_HISTORY_FLOATS * npx; break;
     default: return MORT_ERR_INVALID;
     }

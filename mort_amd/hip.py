@@ -47,6 +47,8 @@ EXPORTS = [
     "mort_hip_volume_refresh", "mort_hip_volume_refresh_device", "mort_hip_volume_refresh_host", "mort_hip_probe_directions_round",
     "mort_hip_view_update_cache", "mort_hip_view_update_cache_host",
     "mort_hip_query_radiance_cached_direct", "mort_hip_query_radiance_cached_direct_device", "mort_hip_query_radiance_cached_direct_host",
+    "mort_hip_render_cached_direct", "mort_hip_render_cached_direct_device", "mort_hip_render_cached_direct_host",
+    "mort_hip_view_set_cache_direct", "mort_hip_view_set_cache_direct_host",
     "mort_hip_debug_tile_state", "mort_hip_debug_tile_sort", "mort_hip_debug_heavy_count", "mort_hip_debug_deinterleave",
 ]
 TILE_COUNTERS = 96
@@ -54,7 +56,7 @@ TEMPORAL_HISTORY_FLOATS = 12
 FILTER_NONE, FILTER_DENOISE, FILTER_SVGF = 0, 1, 2
 # mort_hip_view_read: name -> (MORT_VIEW_* code, floats per pixel)
 VIEW_BUFFERS = {"raw_accum": (0, 3), "accum": (1, 3), "filtered": (2, 3), "variance": (3, 1), "albedo": (4, 3), "normal": (5, 3),
-                "depth": (6, 1), "history": (7, TEMPORAL_HISTORY_FLOATS), "ends": (8, 1)}
+                "depth": (6, 1), "history": (7, TEMPORAL_HISTORY_FLOATS), "ends": (8, 1), "lit": (9, 1)}
 HOST_TREE = 1
 # ray queries (mort_ray, mort_hit of include/mort_hip.h)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("dir", "<f4", (3,)), ("time", "<f4"), ("t_max", "<f4")])
@@ -407,6 +409,15 @@ def lib():
         L.mort_hip_render_cached_device.restype = C.c_int
         L.mort_hip_render_cached_host.argtypes = [wd, C.POINTER(S.Camera), vp, C.c_int, C.c_int, fp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
         L.mort_hip_render_cached_host.restype = C.c_int
+        L.mort_hip_render_cached_direct.argtypes = [ctx, C.POINTER(S.Camera), fp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.mort_hip_render_cached_direct.restype = C.c_int
+        L.mort_hip_render_cached_direct_device.argtypes = [ctx, C.POINTER(S.Camera), fp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.mort_hip_render_cached_direct_device.restype = C.c_int
+        L.mort_hip_render_cached_direct_host.argtypes = [wd, C.POINTER(S.Camera), vp, C.c_int, C.c_int, fp, vp, vp, vp, vp, vp, vp, vp,
+                                                         C.POINTER(Stats)]
+        L.mort_hip_render_cached_direct_host.restype = C.c_int
+        L.mort_hip_view_set_cache_direct.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache_direct.restype = C.c_int
+        L.mort_hip_view_set_cache_direct_host.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache_direct_host.restype = C.c_int
         L.mort_hip_view_set_cache.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache.restype = C.c_int
         L.mort_hip_view_set_cache_host.argtypes = [view, fp, vp, vp]; L.mort_hip_view_set_cache_host.restype = C.c_int
         xp = C.POINTER(REFRESH_PARAMS)
@@ -805,6 +816,42 @@ class Context:
                                                       dptr(ends), stream, C.byref(st) if sync else None), "mort_hip_render_cached_device")
         return st.asdict() if sync else None
 
+    def render_cached_direct(self, cam, params, records, depth=None, want_accum=True, want_segments=False, want_ends=True, want_lit=True):
+        """A direct-light cached frame on the GPU (mort_hip_render_cached_direct): render_cached over a volume of indirect light
+        whose paths add one shadow segment toward cam's light object where they end.  render_cached's dict plus lit_px uint32 (H, W)
+        or None: the paths of a pixel whose shadow segment returned a non-zero emission."""
+        W, H = cam.image_width, cam.image_height
+        records, depth = _cached_volume_arrays(params, records, depth)
+        rgba = np.zeros((H, W, 4), dtype=np.uint8)
+        accum = np.zeros((H, W, 3), dtype=np.float32) if want_accum else None
+        seg = np.zeros((H, W), dtype=np.uint32) if want_segments else None
+        ends = np.zeros((H, W), dtype=np.uint32) if want_ends else None
+        lit = np.zeros((H, W), dtype=np.uint32) if want_lit else None
+        st = Stats()
+        self._chk(lib().mort_hip_render_cached_direct(self._h, C.byref(cam), C.byref(params), _ptr(records), _ptr(depth), rgba.ctypes.data,
+                                                      _ptr(accum), _ptr(seg), _ptr(ends), _ptr(lit), C.byref(st)), "mort_hip_render_cached_direct")
+        return dict(rgba=rgba, accum=accum, segments_px=seg, ends_px=ends, lit_px=lit, stats=st.asdict())
+
+    def render_cached_direct_device(self, cam, params, records, depth, rgba, accum=None, ends=None, lit=None, sync=False):
+        """The direct-light cached frame on torch tensors, on the current torch stream: render_cached_device's arguments and lit (or
+        None) of at least 4 bytes per pixel, written from its head.  Asynchronous (returns None) unless sync (then returns the stats)."""
+        import torch
+        npx = cam.image_width * cam.image_height
+        for t, size, exact in ((records, 128 * params.grid.probes, True), (depth, 4 * DEPTH_FLOATS * params.grid.probes, True),
+                               (rgba, 4 * npx, False), (accum, 12 * npx, False), (ends, 4 * npx, False), (lit, 4 * npx, False)):
+            if t is None:
+                continue
+            have = t.numel() * t.element_size()
+            if not t.is_contiguous() or t.device != rgba.device or (have != size if exact else have < size):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {rgba.device}")
+        stream, sync = _torch_stream(torch, rgba.device, sync)
+        dptr = lambda t: t.data_ptr() if t is not None else None
+        st = Stats()
+        self._chk(lib().mort_hip_render_cached_direct_device(self._h, C.byref(cam), C.byref(params), dptr(records), dptr(depth), dptr(rgba),
+                                                             dptr(accum), dptr(ends), dptr(lit), stream, C.byref(st) if sync else None),
+                  "mort_hip_render_cached_direct_device")
+        return st.asdict() if sync else None
+
     def volume_refresh(self, params, states, records_in, depth=None, records_out=None, ends=True, dirs=None, m=None):
         """A volume refresh on the GPU (mort_hip_volume_refresh): params REFRESH_PARAMS; states the P * D 48-byte streams of the whole
         grid, advanced IN PLACE for the selected probes; records_in float32 (P, 32), depth float32 (P, 200) with CACHED_VISIBLE and
@@ -1034,19 +1081,20 @@ class View:
         """Forget the history: the next frame starts over.  RNG states are not touched."""
         self.ctx._chk(lib().mort_hip_view_reset(self._handle()), "mort_hip_view_reset")
 
-    def set_cache(self, params=None, records=None, depth=None):
+    def set_cache(self, params=None, records=None, depth=None, direct=False):
         """The view's frames become cached frames: params CACHED_FRAME_PARAMS; records and depth (or None) either torch tensors on
         the GPU as for Context.render_cached_device, kept alive by the view (mort_hip_view_set_cache), or numpy arrays, which the
-        view copies to the device (mort_hip_view_set_cache_host).  params None detaches the cache.  Either way the history is
-        forgotten, as by reset()."""
+        view copies to the device (mort_hip_view_set_cache_host).  direct: direct-light cached frames over a volume of indirect
+        light (mort_hip_view_set_cache_direct[_host]), after which read("lit") works.  params None detaches the cache.  Either way
+        the history is forgotten, as by reset()."""
+        name = "mort_hip_view_set_cache_direct" if direct else "mort_hip_view_set_cache"
         if params is not None and isinstance(records, np.ndarray):
             records, depth = _cached_volume_arrays(params, records, depth)
-            self.ctx._chk(lib().mort_hip_view_set_cache_host(self._handle(), C.byref(params), _ptr(records), _ptr(depth)), "mort_hip_view_set_cache_host")
+            self.ctx._chk(getattr(lib(), name + "_host")(self._handle(), C.byref(params), _ptr(records), _ptr(depth)), name + "_host")
             self._cache = None
             return
         dptr = lambda t: t.data_ptr() if t is not None else None
-        self.ctx._chk(lib().mort_hip_view_set_cache(self._handle(), C.byref(params) if params is not None else None, dptr(records), dptr(depth)),
-                      "mort_hip_view_set_cache")
+        self.ctx._chk(getattr(lib(), name)(self._handle(), C.byref(params) if params is not None else None, dptr(records), dptr(depth)), name)
         self._cache = (records, depth) if params is not None else None
 
     def update_cache(self, records, depth=None):
@@ -1083,12 +1131,12 @@ class View:
 
     def read(self, name):
         """One buffer of the last frame as a numpy array (VIEW_BUFFERS): raw_accum / accum / filtered / albedo / normal (H, W, 3),
-        variance / depth (H, W), history (3, H, W, 4); "ends" (uint32 (H, W)) with a cache attached."""
+        variance / depth (H, W), history (3, H, W, 4); "ends" (uint32 (H, W)) with a cache attached, "lit" (the same) with a direct one."""
         code, ch = VIEW_BUFFERS[name]
         shape = (3, self.height, self.width, 4) if name == "history" else (self.height, self.width, ch) if ch > 1 else (self.height, self.width)
         out = np.zeros(shape, dtype=np.float32)
         self.ctx._chk(lib().mort_hip_view_read(self._handle(), code, out.ctypes.data), f"mort_hip_view_read({name})")
-        return out.view(np.uint32) if name == "ends" else out  # MORT_VIEW_ENDS holds counts
+        return out.view(np.uint32) if name in ("ends", "lit") else out  # MORT_VIEW_ENDS and MORT_VIEW_LIT hold counts
 
 
 def seed_states_host(seed, width, height, dtype=None):
@@ -1149,6 +1197,28 @@ def render_cached_host(world, cam, params, records, depth=None, states=None, see
     if rc != 0:
         raise MortHipError(rc, "mort_hip_render_cached_host")
     return dict(rgba=rgba, accum=accum, segments_px=seg, ends_px=ends, stats=stt.asdict(), states=st8)
+
+
+def render_cached_direct_host(world, cam, params, records, depth=None, states=None, seed=S.DEFAULT_SEED, nthreads=1, tree=False, want_accum=True,
+                              want_segments=True, want_ends=True, want_lit=True):
+    """The direct-light cached frame as a host loop (mort_hip_render_cached_direct_host), no GPU: render_cached_host's arguments and
+    dict with Context.render_cached_direct's lit_px."""
+    W, H = cam.image_width, cam.image_height
+    st8 = seed_states_host(seed, W, H) if states is None else np.ascontiguousarray(states).view(np.uint8).reshape(-1).copy()
+    assert st8.nbytes == W * H * 48
+    records, depth = _cached_volume_arrays(params, records, depth)
+    rgba = np.zeros((H, W, 4), dtype=np.uint8)
+    accum = np.zeros((H, W, 3), dtype=np.float32) if want_accum else None
+    seg = np.zeros((H, W), dtype=np.uint32) if want_segments else None
+    ends = np.zeros((H, W), dtype=np.uint32) if want_ends else None
+    lit = np.zeros((H, W), dtype=np.uint32) if want_lit else None
+    stt = Stats()
+    rc = lib().mort_hip_render_cached_direct_host(world.ptr, C.byref(cam), st8.ctypes.data, nthreads, HOST_TREE if tree else 0, C.byref(params),
+                                                  _ptr(records), _ptr(depth), rgba.ctypes.data, _ptr(accum), _ptr(seg), _ptr(ends), _ptr(lit),
+                                                  C.byref(stt))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_render_cached_direct_host")
+    return dict(rgba=rgba, accum=accum, segments_px=seg, ends_px=ends, lit_px=lit, stats=stt.asdict(), states=st8)
 
 
 def debug_own_tree(world):
