@@ -837,6 +837,47 @@ int mort_hip_volume_refresh_host(const mort_world *world, const mort_refresh_par
                                  const float *records_in, const float *depth, int nthreads, int flags, float *records_out, uint32_t *ends_out,
                                  double *seconds);
 int mort_hip_probe_directions_round(int directions, uint32_t round, float *dirs_out /* 3 D */);
+
+/* ---- direct-light volume refresh: the volume refresh for a volume of INDIRECT light.  "Indirect" is the
+ * direct-light cached queries' definition: the radiance arriving at a probe with the emission of directly seen emitters taken out;
+ * the background and every reflected bounce stay in.  The calls take mort_hip_volume_refresh*'s arguments under the same
+ * mort_refresh_params -- no new flag bit -- and one more optional output after ends_out, lit_out / d_lit_out (P words or NULL,
+ * written for the selected probes only): how many of the probe's D samples paths had a shadow segment that returned a non-zero
+ * emission.  A copied (masked) probe writes 0.
+ *
+ * A direct refresh is the volume refresh above with two changes to its step 3; steps 1, 2, 4, 5 and 6, the checks and their order,
+ * the forms, `seconds`, MORT_HOST_TREE, the stream layout, the selection and the copy rule are unchanged:
+ *   3'. the paths are the direct-light cached query's (its rules (a)-(d)) over records_in and depth, word for word: a path that
+ *       ends in the volume has the value ((albedo E) INV_PI) + ((albedo spdf) Le) / pdf, and the shadow segment counts and draws as
+ *       it does there;
+ *   E.  a path whose PRIMARY segment ends in the shade step's non-scattering branch (iteration 0, not a shadow segment, the hit a
+ *       diffuse light or a material the shade step does not know) has the value (0, 0, 0) instead of what the shade step returned.
+ *       Nothing else changes: the search, the shade step and every draw are made as before, so the streams equal those of the
+ *       direct-light cached query on the same rays.  Emission met after a path-traced bounce stays in: it is reflected light.
+ * So
+ *   (A) in a world without an emitter, or called with light_obj_type == -1 where no primary ray meets an emitter, records, streams
+ *       and ends equal mort_hip_volume_refresh* to the bit and lit is 0;
+ *   (B) per path, with "the primary hit emits" read from mort_hip_query_radiance* at bounce limit 1 and a black background on a
+ *       copy of the streams, and the path's value v from mort_hip_query_radiance_cached_direct* at one sample on the carried
+ *       streams, the direction's sum is the sum of (emits ? 0 : v) in path order; projection and blend as above give the records
+ *       to the bit, and the streams and both counts are the query's;
+ *   (C) with hysteresis 0, K >= bounce_limit, one sample and records_in = mort_hip_volume_pack(zeros, weight > 0), the 27 floats
+ *       equal mort_hip_probe_bake_indirect*'s sh_ind on the same probes, directions and streams up to the rounding of two fp32
+ *       summations (the bake subtracts two sums, the refresh sums the differences), and the streams equal the full bake's to the bit;
+ *   (D) a masked probe is copied, none of its streams moves, and both of its counts are 0;
+ *   (E) the selected records never depend on the unselected bytes of records_out.
+ * Per probe lit <= ends <= D samples.  lit_out is an output for the overlap checks: it must not overlap an input or another
+ * output, and the _device form wants it 16-byte aligned.  The host-buffer form sends records_out up as well. ---- */
+int mort_hip_volume_refresh_direct(mort_ctx *ctx, const mort_refresh_params *params, size_t m, const float *dirs /* 3 D or NULL */,
+                                   mort_rng_state *states /* P D */, const float *records_in, const float *depth /* or NULL */,
+                                   float *records_out, uint32_t *ends_out /* P or NULL */, uint32_t *lit_out /* P or NULL */, double *seconds);
+int mort_hip_volume_refresh_direct_device(mort_ctx *ctx, const mort_refresh_params *params, size_t m, const void *d_dirs /* or NULL */,
+                                          void *d_states, const void *d_records_in, const void *d_depth, void *d_records_out, void *d_ends_out,
+                                          void *d_lit_out, void *stream, double *seconds);
+int mort_hip_volume_refresh_direct_host(const mort_world *world, const mort_refresh_params *params, size_t m, const float *dirs,
+                                        mort_rng_state *states, const float *records_in, const float *depth, int nthreads, int flags,
+                                        float *records_out, uint32_t *ends_out, uint32_t *lit_out, double *seconds);
+
 /* new records (and maps) for a view that has a cache attached: the params stay, the checks are mort_hip_view_set_cache's, the
  * presence of depth must match the attached flag, and a view without a cache is MORT_ERR_INVALID.  The history is KEPT: set_cache
  * forgets it because the estimator changes; a refreshed volume is the same estimator with a better cache.  The caller runs the

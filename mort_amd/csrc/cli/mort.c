@@ -106,7 +106,7 @@
  * every accepted and refused combination and every output byte is what it was.
  *
  * --cache-direct (with --sh-volume ... --cache-depth K and --probe or --radiance-out; excludes --cache-render and --refresh, whose
- * paths do not have the direct terminal yet): the volume holds indirect light only and a path that ends in it adds one sampled shadow
+ * paths do not have the direct terminal: --refresh-direct is the refresh for this volume): the volume holds indirect light only and a path that ends in it adds one sampled shadow
  * segment toward the scene's light object.  After the bake a second, emission-only bake runs over the same probes
  * and directions from a copy of the streams the first one started from (bounce limit 1, black background, one path per direction),
  * the coefficients are subtracted float by float, packed, and the query is mort_hip_query_radiance_cached_direct (or its _host
@@ -120,8 +120,18 @@
  * with the direct cache attached (mort_hip_view_set_cache_direct_host), under --mode host through mort_hip_render_cached_direct_host.
  * The JSON line is --cache-render's plus cache_direct: 1 and lit (the last frame's paths whose shadow segment returned a non-zero
  * emission), after ends.  --refresh is refused: a refresh through plain cached paths would put the emitters' light back into a
- * volume that is to hold indirect light only.  Without --cache-render-direct every accepted and refused combination and every
+ * volume that is to hold indirect light only; --refresh-direct is the refresh for this volume.  Without --cache-render-direct every accepted and refused combination and every
  * output byte is what it was.
+ *
+ * --refresh-direct R[,H[,KR[,S]]] (with --cache-direct or --cache-render-direct only; --refresh's grammar and defaults): --refresh
+ * for the indirect-only volume of those two options, through mort_hip_volume_refresh_direct (or its _host form).
+ * The rounds run over the indirect records (the full bake minus the emission-only bake); the full bake's streams are carried on, the
+ * direction sets are rotated and the records ping-pong as under --refresh.  With --cache-direct S must be 0; with
+ * --cache-render-direct and S > 0 every S-th probe is refreshed before each frame f >= 1 with the set of round R + f, and the view
+ * takes the records by mort_hip_view_update_cache_host.  It is refused with --refresh, with --cache-render and without a direct
+ * option; --refresh beside the direct options stays refused.  The JSON line gains --refresh's fields, then refresh_direct: 1 and
+ * refresh_lit (the paths of the last full round whose shadow segment returned a non-zero emission).  Without --refresh-direct every
+ * accepted and refused combination and every output byte is what it was.
  *
  * --gpus N: N - 1 ranks are forked BEFORE any HIP call (a process that has initialised the GPU must not fork or exec);
  * rank r renders row blocks r, r + N, ... on device r (or --devices) and the packed rows are gathered to rank 0 -- over
@@ -169,7 +179,7 @@ static int usage(void) {
            "[--denoise] [--features-out PREFIX] [--temporal] [--variance-out F] [--svgf] [--pick X,Y] [--probe X,Y[,N]] [--sh-probe X,Y,Z[,D[,N]]] "
            "[--sh-volume X0,Y0,Z0,X1,Y1,Z1,NX,NY,NZ[,D[,N]]] [--irradiance-out FILE] [--visibility BIAS[,MINVIS[,S]]] "
            "[--cache-depth K] [--radiance-out FILE] [--cache-render] [--refresh R[,H[,KR[,S]]]] [--cache-direct]\n"
-           "            [--cache-render-direct]\n"
+           "            [--cache-render-direct] [--refresh-direct R[,H[,KR[,S]]]]\n"
            "  --cache-depth K with --sh-volume: paths end in the volume from bounce K on; --probe X,Y[,N] prints one pixel's colour,\n"
            "  --radiance-out FILE writes a preview from pixel-centre rays (--spp paths each; no jitter, no lens), not a render,\n"
            "  --cache-render renders: the ordinary frame loop (--frames, --out, --temporal, --svgf, ...) over cached frames\n"
@@ -178,7 +188,10 @@ static int usage(void) {
            "  --cache-direct with --cache-depth and --probe or --radiance-out: the volume keeps indirect light only and a path that\n"
            "  ends in it adds one sampled shadow ray toward the scene's light\n"
            "  --cache-render-direct with --sh-volume and --cache-depth: --cache-render over that indirect-only volume, the frames'\n"
-           "  paths adding the sampled shadow ray where they end; excludes --cache-render, --cache-direct and --refresh\n");
+           "  paths adding the sampled shadow ray where they end; excludes --cache-render, --cache-direct and --refresh\n"
+           "  --refresh-direct R[,H[,KR[,S]]] with --cache-direct or --cache-render-direct: --refresh for their indirect-only volume,\n"
+           "  the probes' paths adding the shadow ray and leaving out the emitters a probe sees directly; S > 0 only with\n"
+           "  --cache-render-direct\n");
     return -1;
 }
 
@@ -251,14 +264,16 @@ typedef struct {
     int on, rounds, depth, stride;
     float h;
     unsigned long long ends; /* the paths of the last full round that ended in the volume */
+    int direct;              /* --refresh-direct: the direct refresh in the refresh's place */
+    unsigned long long lit;  /* direct: of those paths, the ones whose shadow segment returned a non-zero emission */
 } refresh_opts;
 
 /* one round over the probes first, first + step, ... with the direction set of round `round`: from `in` into `out`, the streams
- * carried on; ctx NULL: the host form.  *ends_sum (or NULL): the selected probes' counts */
+ * carried on; ctx NULL: the host form.  *ends_sum, *lit_sum (or NULL): the selected probes' counts (lit: of a direct refresh) */
 static void refresh_round(mort_ctx *ctx, const mort_world *world, const mort_camera *cam, const refresh_opts *ro, const mort_volume_grid *grid,
                           uint32_t flags, const mort_volume_vis_params *vis, int sh_d, int sh_n, uint32_t round, uint32_t first, uint32_t step,
                           mort_rng_state *states, const float *in, const float *depth, float *out, int threads, int host_flags,
-                          unsigned long long *ends_sum) {
+                          unsigned long long *ends_sum, unsigned long long *lit_sum) {
     const size_t n = (size_t)grid->count[0] * (size_t)grid->count[1] * (size_t)grid->count[2];
     const size_t m = first < n ? (n - 1 - first) / step + 1 : 0;
     mort_refresh_params rp;
@@ -269,14 +284,20 @@ static void refresh_round(mort_ctx *ctx, const mort_world *world, const mort_cam
     rp.directions = sh_d; rp.hysteresis = ro->h; rp.first = first; rp.step = step;
     float *dirs = (float *)malloc(3 * (size_t)sh_d * sizeof *dirs);
     uint32_t *ends = (uint32_t *)calloc(n, sizeof *ends);
-    if (!dirs || !ends) { fprintf(stderr, "out of memory\n"); fail_exit(); }
+    uint32_t *lit = ro->direct ? (uint32_t *)calloc(n, sizeof *lit) : NULL;
+    if (!dirs || !ends || (ro->direct && !lit)) { fprintf(stderr, "out of memory\n"); fail_exit(); }
     int st;
     if ((st = mort_hip_probe_directions_round(sh_d, round, dirs)) != MORT_OK) die(NULL, st, "mort_hip_probe_directions_round");
-    if (!ctx) {
+    if (ro->direct) {
+        if (!ctx) {
+            if ((st = mort_hip_volume_refresh_direct_host(world, &rp, m, dirs, states, in, depth, threads, host_flags, out, ends, lit, NULL)) != MORT_OK) die(NULL, st, "mort_hip_volume_refresh_direct_host");
+        } else if ((st = mort_hip_volume_refresh_direct(ctx, &rp, m, dirs, states, in, depth, out, ends, lit, NULL)) != MORT_OK) die(ctx, st, "mort_hip_volume_refresh_direct");
+        if (lit_sum) { *lit_sum = 0; for (size_t i = 0; i < m; i++) *lit_sum += lit[first + i * step]; }
+    } else if (!ctx) {
         if ((st = mort_hip_volume_refresh_host(world, &rp, m, dirs, states, in, depth, threads, host_flags, out, ends, NULL)) != MORT_OK) die(NULL, st, "mort_hip_volume_refresh_host");
     } else if ((st = mort_hip_volume_refresh(ctx, &rp, m, dirs, states, in, depth, out, ends, NULL)) != MORT_OK) die(ctx, st, "mort_hip_volume_refresh");
     if (ends_sum) { *ends_sum = 0; for (size_t i = 0; i < m; i++) *ends_sum += ends[first + i * step]; }
-    free(dirs); free(ends);
+    free(dirs); free(ends); free(lit);
 }
 
 /* rounds 1 .. R over every probe; the records ping-pong between `a` (the bake's) and `b`: returns the one that holds the last round's */
@@ -284,7 +305,7 @@ static float *refresh_all(mort_ctx *ctx, const mort_world *world, const mort_cam
                           const mort_volume_vis_params *vis, int sh_d, int sh_n, mort_rng_state *states, float *a, float *b, const float *depth,
                           int threads, int host_flags) {
     for (int r = 1; r <= ro->rounds; r++) {
-        refresh_round(ctx, world, cam, ro, grid, flags, vis, sh_d, sh_n, (uint32_t)r, 0, 1, states, a, depth, b, threads, host_flags, &ro->ends);
+        refresh_round(ctx, world, cam, ro, grid, flags, vis, sh_d, sh_n, (uint32_t)r, 0, 1, states, a, depth, b, threads, host_flags, &ro->ends, &ro->lit);
         float *t = a; a = b; b = t;
     }
     return a;
@@ -294,6 +315,7 @@ static void print_refresh(const refresh_opts *ro) {
     if (!ro->on) return;
     printf(", \"refresh_rounds\": %d, \"hysteresis\": ", ro->rounds); print_f32(ro->h);
     printf(", \"refresh_depth\": %d, \"refresh_stride\": %d, \"refresh_ends\": %llu", ro->depth, ro->stride, ro->ends);
+    if (ro->direct) printf(", \"refresh_direct\": 1, \"refresh_lit\": %llu", ro->lit);
 }
 
 /* --cache-render: the volume a cached frame ends its paths in, baked as the no-render uses of --sh-volume bake it (D directions, N
@@ -375,7 +397,7 @@ static void refresh_before_frame(cache_volume *v, mort_ctx *ctx, const mort_worl
                                  int sh_n, int f, int threads, int host_flags) {
     memcpy(v->back, v->records, v->probes * MORT_VOLUME_RECORD_FLOATS * sizeof(float));
     refresh_round(ctx, world, cam, ro, &v->p.grid, v->p.flags, &v->p.vis, sh_d, sh_n, (uint32_t)(ro->rounds + f), (uint32_t)(f % ro->stride),
-                  (uint32_t)ro->stride, v->states, v->records, v->depth, v->back, threads, host_flags, NULL);
+                  (uint32_t)ro->stride, v->states, v->records, v->depth, v->back, threads, host_flags, NULL, NULL);
     float *t = v->records; v->records = v->back; v->back = t;
 }
 
@@ -413,9 +435,10 @@ int main(int argc, char **argv) {
     int cache_render = 0;
     int cache_direct = 0;
     int cache_render_direct = 0; /* --cache-render-direct: sets cache_render too, once its own refusals are through */
-    refresh_opts refresh;
+    refresh_opts refresh, refresh_direct; /* --refresh-direct: takes --refresh's place once both options' refusals are through */
     memset(&refresh, 0, sizeof refresh);
     refresh.h = 0.9f;
+    refresh_direct = refresh;
     for (int i = 2; i < argc; i++) {
 #define ARG(name) (strcmp(argv[i], name) == 0 && i + 1 < argc)
         if (ARG("--width")) width = atoi(argv[++i]);
@@ -474,6 +497,10 @@ int main(int argc, char **argv) {
         else if (strcmp(argv[i], "--cache-render") == 0) cache_render = 1;
         else if (strcmp(argv[i], "--cache-direct") == 0) cache_direct = 1;
         else if (strcmp(argv[i], "--cache-render-direct") == 0) cache_render_direct = 1;
+        else if (ARG("--refresh-direct")) {
+            refresh_direct.on = refresh_direct.direct = 1;
+            if (sscanf(argv[++i], "%d,%f,%d,%d", &refresh_direct.rounds, &refresh_direct.h, &refresh_direct.depth, &refresh_direct.stride) < 1) { fprintf(stderr, "--refresh-direct R[,H[,KR[,S]]]\n"); return -1; }
+        }
         else if (ARG("--refresh")) {
             refresh.on = 1;
             if (sscanf(argv[++i], "%d,%f,%d,%d", &refresh.rounds, &refresh.h, &refresh.depth, &refresh.stride) < 1) { fprintf(stderr, "--refresh R[,H[,KR[,S]]]\n"); return -1; }
@@ -495,6 +522,15 @@ int main(int argc, char **argv) {
     if (cached && !sh_volume) { fprintf(stderr, "--cache-depth needs --sh-volume\n"); return -1; }
     if (rad_out && !cached) { fprintf(stderr, "--radiance-out needs --cache-depth\n"); return -1; }
     if (cached && (cache_depth < 0 || cache_depth > MORT_MAX_BOUNCE_LIMIT)) { fprintf(stderr, "--cache-depth: K in 0..%d\n", MORT_MAX_BOUNCE_LIMIT); return -1; }
+    if (refresh_direct.on) {
+        if (refresh.on) { fprintf(stderr, "--refresh-direct excludes --refresh: the one is for an indirect-only volume, the other for a full one\n"); return -1; }
+        if (cache_render) { fprintf(stderr, "--refresh-direct excludes --cache-render: its volume holds the emitters' light, --refresh is the option for it\n"); return -1; }
+        if (!cache_direct && !cache_render_direct) { fprintf(stderr, "--refresh-direct needs --cache-direct or --cache-render-direct\n"); return -1; }
+        if (refresh_direct.rounds < 0 || refresh_direct.rounds > 65535 || !(refresh_direct.h >= 0.0f) || !(refresh_direct.h < 1.0f) || refresh_direct.depth < 0 ||
+            refresh_direct.depth > MORT_MAX_BOUNCE_LIMIT || refresh_direct.stride < 0 || (refresh_direct.stride > 0 && !cache_render_direct)) {
+            fprintf(stderr, "--refresh-direct: R in 0..65535, H in [0, 1), KR in 0..%d, S >= 0 and S > 0 only with --cache-render-direct\n", MORT_MAX_BOUNCE_LIMIT); return -1;
+        }
+    }
     if (cache_render_direct) {
         if (cache_render || cache_direct) { fprintf(stderr, "--cache-render-direct excludes --cache-render and --cache-direct\n"); return -1; }
         if (!sh_volume || !cached) { fprintf(stderr, "--cache-render-direct needs --sh-volume and --cache-depth\n"); return -1; }
@@ -527,6 +563,7 @@ int main(int argc, char **argv) {
                        refresh.depth > MORT_MAX_BOUNCE_LIMIT || refresh.stride < 0 || (refresh.stride > 0 && !cache_render))) {
         fprintf(stderr, "--refresh: R in 0..65535, H in [0, 1), KR in 0..%d, S >= 0 and S > 0 only with --cache-render\n", MORT_MAX_BOUNCE_LIMIT); return -1;
     }
+    if (refresh_direct.on) refresh = refresh_direct; /* from here on: --refresh with another refresh call */
     if (n_devices && n_devices != gpus) { fprintf(stderr, "--devices needs %d entries\n", gpus); return -1; }
 
     mort_world world;

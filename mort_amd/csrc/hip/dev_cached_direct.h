@@ -69,8 +69,10 @@ DEV V3 direct_emission(const DScene &sc, const Ray &ray, const Best &best) {
     return lambert_color_rec(sc, sc.dlight[DREF_IDX(rec.mat)], rec);
 }
 
-/* cached_paths with the direct terminal; ends: the paths that ended in the volume, lit: those of them whose shadow segment saw light */
-template <bool TREE, bool VISIBLE>
+/* cached_paths with the direct terminal; ends: the paths that ended in the volume, lit: those of them whose shadow segment saw light.
+ * PRIMARY_DARK (the direct refresh's rule E): a path whose primary segment ends in the shade step's non-scattering
+ * branch has the value 0 -- the search, the shade step and every draw are made as without it */
+template <bool TREE, bool VISIBLE, bool PRIMARY_DARK = false>
 DEV V3 cached_direct_paths(const CachedArgs<VISIBLE> &c, const Ray ray0, Rng &rng, unsigned short *walk, int walk_stride, float4 *lds_stack,
                            int lds_levels, int lds_stride, uint32_t &ends, uint32_t &lit) {
     const RadianceArgs &a = c.r;
@@ -118,8 +120,11 @@ DEV V3 cached_direct_paths(const CachedArgs<VISIBLE> &c, const Ray ray0, Rng &rn
                     }
                 } else {
                     const ShadeOut so = shade_hit(sc, a.light_type, a.light_idx, ray, ray_time0, best, rng);
-                    if (so.done) { final_value = so.final_value; done = true; }
-                    else {
+                    if (so.done) {
+                        final_value = so.final_value;
+                        if constexpr (PRIMARY_DARK) { if (iter == 0) final_value = mk(0, 0, 0); }
+                        done = true;
+                    } else {
                         if (so.ident) ident_mask |= (1ull << iter);
                         else if (iter < lds_levels) { float4 e4; e4.x = so.e.kx; e4.y = so.e.ky; e4.z = so.e.kz; e4.w = so.e.rp; lds_stack[iter * lds_stride] = e4; }
                         else stack[iter] = so.e;

@@ -49,6 +49,7 @@ EXPORTS = [
     "mort_hip_query_radiance_cached_direct", "mort_hip_query_radiance_cached_direct_device", "mort_hip_query_radiance_cached_direct_host",
     "mort_hip_render_cached_direct", "mort_hip_render_cached_direct_device", "mort_hip_render_cached_direct_host",
     "mort_hip_view_set_cache_direct", "mort_hip_view_set_cache_direct_host",
+    "mort_hip_volume_refresh_direct", "mort_hip_volume_refresh_direct_device", "mort_hip_volume_refresh_direct_host",
     "mort_hip_debug_tile_state", "mort_hip_debug_tile_sort", "mort_hip_debug_heavy_count", "mort_hip_debug_deinterleave",
 ]
 TILE_COUNTERS = 96
@@ -425,6 +426,11 @@ def lib():
         L.mort_hip_volume_refresh_device.argtypes = [ctx, xp, sz, vp, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_volume_refresh_device.restype = C.c_int
         L.mort_hip_volume_refresh_host.argtypes = [wd, xp, sz, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, dp]
         L.mort_hip_volume_refresh_host.restype = C.c_int
+        L.mort_hip_volume_refresh_direct.argtypes = [ctx, xp, sz, vp, vp, vp, vp, vp, vp, vp, dp]; L.mort_hip_volume_refresh_direct.restype = C.c_int
+        L.mort_hip_volume_refresh_direct_device.argtypes = [ctx, xp, sz, vp, vp, vp, vp, vp, vp, vp, vp, dp]
+        L.mort_hip_volume_refresh_direct_device.restype = C.c_int
+        L.mort_hip_volume_refresh_direct_host.argtypes = [wd, xp, sz, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, dp]
+        L.mort_hip_volume_refresh_direct_host.restype = C.c_int
         L.mort_hip_probe_directions_round.argtypes = [C.c_int, C.c_uint32, vp]; L.mort_hip_probe_directions_round.restype = C.c_int
         L.mort_hip_view_update_cache.argtypes = [view, vp, vp]; L.mort_hip_view_update_cache.restype = C.c_int
         L.mort_hip_view_update_cache_host.argtypes = [view, vp, vp]; L.mort_hip_view_update_cache_host.restype = C.c_int
@@ -886,6 +892,39 @@ class Context:
         self._chk(lib().mort_hip_volume_refresh_device(self._h, C.byref(params), params.selected() if m is None else m, dptr(dirs), dptr(states),
                                                        dptr(records_in), dptr(depth), dptr(records_out), dptr(ends), stream,
                                                        C.byref(sec) if sync else None), "mort_hip_volume_refresh_device")
+        return sec.value if sync else None
+
+    def volume_refresh_direct(self, params, states, records_in, depth=None, records_out=None, ends=True, lit=True, dirs=None, m=None):
+        """A direct-light volume refresh on the GPU (mort_hip_volume_refresh_direct): Context.volume_refresh over records of
+        INDIRECT light, the paths the direct cached query's and a primary hit on an emitter counted as 0; lit as ends: a writeable
+        uint32 (P,) written in place, True for a new one, None for no counts.  dict(records, ends, lit, seconds)."""
+        m, dirs, records_in, depth, records_out, ends = _refresh_arrays(params, states, records_in, depth, records_out, ends, dirs, m)
+        lit = _refresh_counts(params, lit)
+        sec = C.c_double(0)
+        self._chk(lib().mort_hip_volume_refresh_direct(self._h, C.byref(params), m, _ptr(dirs), _ptr(states), _ptr(records_in), _ptr(depth),
+                                                       _ptr(records_out), _ptr(ends), _ptr(lit), C.byref(sec)), "mort_hip_volume_refresh_direct")
+        return dict(records=records_out, ends=ends, lit=lit, seconds=sec.value)
+
+    def volume_refresh_direct_device(self, params, states, records_in, depth, records_out, ends=None, lit=None, dirs=None, m=None, sync=False):
+        """The direct refresh on torch tensors, as volume_refresh_device: lit (or None) of at least 4 P bytes, written from its head."""
+        import torch
+        P, D = params.cached.grid.probes, params.directions
+        if records_in.device.type != "cuda":
+            raise ValueError("expected tensors on the GPU")
+        for t, size, exact in ((states, 48 * P * D, False), (records_in, 128 * P, True), (depth, 4 * DEPTH_FLOATS * P, True),
+                               (records_out, 128 * P, False), (ends, 4 * P, False), (lit, 4 * P, False), (dirs, 12 * D, True)):
+            if t is None:
+                continue
+            have = t.numel() * t.element_size()
+            if not t.is_contiguous() or t.device != records_in.device or (have != size if exact else have < size):
+                raise ValueError(f"expected a contiguous tensor of {size} bytes on {records_in.device}")
+        sec = C.c_double(0)
+        stream, sync = _torch_stream(torch, records_in.device, sync)
+        dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._chk(lib().mort_hip_volume_refresh_direct_device(self._h, C.byref(params), params.selected() if m is None else m, dptr(dirs),
+                                                              dptr(states), dptr(records_in), dptr(depth), dptr(records_out), dptr(ends),
+                                                              dptr(lit), stream, C.byref(sec) if sync else None),
+                  "mort_hip_volume_refresh_direct_device")
         return sec.value if sync else None
 
     def probe_bake(self, params, probes, states, dirs=None):
@@ -1653,6 +1692,34 @@ def volume_refresh_host(world, params, states, records_in, depth=None, records_o
     if rc != 0:
         raise MortHipError(rc, "mort_hip_volume_refresh_host")
     return dict(records=records_out, ends=ends, seconds=sec.value)
+
+
+def _refresh_counts(params, counts):
+    """one more count array of a refresh, by _refresh_arrays' rule for ends"""
+    sized = all(0 < c <= VOLUME_MAX_COUNT for c in params.cached.grid.count)
+    P = params.cached.grid.probes if sized else 0
+    if counts is True:
+        return np.zeros(P, dtype=np.uint32)
+    if counts is False or counts is None:
+        return None
+    if not (isinstance(counts, np.ndarray) and counts.dtype == np.uint32 and counts.flags.c_contiguous and counts.flags.writeable and
+            (not sized or counts.size == P)):
+        raise ValueError(f"expected a contiguous writeable uint32 array of {P} counts")
+    return counts
+
+
+def volume_refresh_direct_host(world, params, states, records_in, depth=None, records_out=None, ends=True, lit=True, dirs=None, m=None,
+                               tree=False, nthreads=1):
+    """The direct refresh as a host loop (mort_hip_volume_refresh_direct_host), no GPU: arguments and result as
+    Context.volume_refresh_direct."""
+    m, dirs, records_in, depth, records_out, ends = _refresh_arrays(params, states, records_in, depth, records_out, ends, dirs, m)
+    lit = _refresh_counts(params, lit)
+    sec = C.c_double(0)
+    rc = lib().mort_hip_volume_refresh_direct_host(world.ptr, C.byref(params), m, _ptr(dirs), _ptr(states), _ptr(records_in), _ptr(depth),
+                                                   nthreads, HOST_TREE if tree else 0, _ptr(records_out), _ptr(ends), _ptr(lit), C.byref(sec))
+    if rc != 0:
+        raise MortHipError(rc, "mort_hip_volume_refresh_direct_host")
+    return dict(records=records_out, ends=ends, lit=lit, seconds=sec.value)
 
 
 def probe_directions_round(D, round):
