@@ -44,6 +44,40 @@ def _some_streams(n):
     return np.ascontiguousarray(np.resize(base, n))
 
 
+def media_in_scan_order(world):
+    """[(medium, path)] for every constant medium world::hit reaches, in the order it reaches them (world.cuh:122-168: translates,
+    rotate_ys, media, lists, each table's entries without `skip`); path: the (type, index) of the transforms around the medium,
+    outermost first.  A medium bounded by a medium is not followed."""
+    o = world.c.objs
+    found = []
+    if world.c.bvh_mode:  # world::hit returns after the BVHs
+        return found
+
+    def walk(t, i, path):
+        if t == S.OBJ_TRANSLATE and 0 <= i < o.num_translates:
+            walk(o.host_translate[i].obj_type, o.host_translate[i].obj_idx, path + [(t, i)])
+        elif t == S.OBJ_ROTATE_Y and 0 <= i < o.num_rotate_y:
+            walk(o.host_rotate_y[i].obj_type, o.host_rotate_y[i].obj_idx, path + [(t, i)])
+        elif t == S.OBJ_CONSTANT_MEDIUM and 0 <= i < o.num_constant_medium:
+            found.append((i, path))
+        elif t == S.OBJ_HITTABLE_LIST and 0 <= i < o.num_hittable_list:
+            lst = o.host_hittable_list[i]
+            for k in range(lst.num_objs):
+                walk(lst.obj_types[k], lst.obj_idxs[k], path)
+
+    for i in range(o.num_translates):
+        if not o.host_translate[i].skip:
+            walk(S.OBJ_TRANSLATE, i, [])
+    for i in range(o.num_rotate_y):
+        if not o.host_rotate_y[i].skip:
+            walk(S.OBJ_ROTATE_Y, i, [])
+    found += [(i, []) for i in range(o.num_constant_medium) if not o.host_constant_medium[i].skip]
+    for i in range(o.num_hittable_list):
+        if not o.host_hittable_list[i].skip:
+            walk(S.OBJ_HITTABLE_LIST, i, [])
+    return found
+
+
 def oracle_features(world, cam, nthreads=16):
     """dict(albedo (H, W, 3), normal (H, W, 3), depth (H, W)) float32 as the contract defines them, plus what the tests assert
     their cases on: kind (H, W) of MISS / SOLID / MEDIUM, mat_type, front_face, t, and started_inside (H, W) = the number of
@@ -56,17 +90,20 @@ def oracle_features(world, cam, nthreads=16):
     d = rays[:, 3:6]
     inf = F(np.inf)
 
-    # solids: world::hit with every constant medium passed over, so no random number is drawn
-    media = [i for i in range(o.num_constant_medium) if not o.host_constant_medium[i].skip]
+    # solids: world::hit with every constant medium passed over, so no random number is drawn.  A medium the scan reaches through a
+    # transform or a list has no skip flag that counts, so each medium's boundary reference is set to a tag hitDispatch does not
+    # know for the call: constant_medium::hit then returns at its first boundary test, before it draws
+    media = media_in_scan_order(world)
     streams = _some_streams(n)
     before = streams.copy()
+    bounds = [(o.host_constant_medium[i].obj_type, o.host_constant_medium[i].obj_idx) for i in range(o.num_constant_medium)]
     try:
-        for i in media:
-            o.host_constant_medium[i].skip = True
+        for i in range(o.num_constant_medium):
+            o.host_constant_medium[i].obj_type = 0
         rec, hit = O.world_hit_batch(world, rays, T_MIN, inf, states=streams, nthreads=nthreads)
     finally:
-        for i in media:
-            o.host_constant_medium[i].skip = False
+        for i, (bt, bi) in enumerate(bounds):
+            o.host_constant_medium[i].obj_type = bt
     assert streams.tobytes() == before.tobytes(), "the solid pass drew a random number"
 
     kind = np.where(hit, SOLID, MISS).astype(np.int32)
@@ -85,12 +122,22 @@ def oracle_features(world, cam, nthreads=16):
         inv = F(1) / dlen
         minus_unit = -(inv[:, None] * d)
         assert minus_unit.dtype == F
-    for i in media:
+    for i, path in media:
         cm = o.host_constant_medium[i]
-        r1, h1 = O.object_hit_batch(world, cm.obj_type, cm.obj_idx, rays, -inf, inf, nthreads=nthreads)
-        t1 = r1["t"]
-        lo2 = (t1.astype(np.float64) + 0.0001).astype(F)
-        r2, h2 = O.object_hit_batch(world, cm.obj_type, cm.obj_idx, rays, np.where(h1, lo2, inf), inf, nthreads=nthreads)
+        # a medium under transforms: the outermost is dispatched on with the innermost holding the boundary in the medium's place, so
+        # the ray reaches the boundary through the oracle's own translate::hit / rotate_y::hit (t is the same in every frame)
+        entry = path[0] if path else (cm.obj_type, cm.obj_idx)
+        holder = (o.host_translate if path[-1][0] == S.OBJ_TRANSLATE else o.host_rotate_y)[path[-1][1]] if path else None
+        try:
+            if holder is not None:
+                holder.obj_type, holder.obj_idx = cm.obj_type, cm.obj_idx
+            r1, h1 = O.object_hit_batch(world, entry[0], entry[1], rays, -inf, inf, nthreads=nthreads)
+            t1 = r1["t"]
+            lo2 = (t1.astype(np.float64) + 0.0001).astype(F)
+            r2, h2 = O.object_hit_batch(world, entry[0], entry[1], rays, np.where(h1, lo2, inf), inf, nthreads=nthreads)
+        finally:
+            if holder is not None:
+                holder.obj_type, holder.obj_idx = S.OBJ_CONSTANT_MEDIUM, i
         both = h1 & h2
         grazed += h1 & ~h2  # no second boundary hit beyond t1 + 0.0001
         inside = both & (t1 < T_MIN)  # the ray starts inside this medium: it does not enter it, so it is no first hit

@@ -16,6 +16,8 @@
    tests/ref_lib.py), renders for REF_PIN_CASES (two frames each: uchar4 image, fp32 accumulators, XORWOW words), and of
    the world bytes the reference's BVH builder leaves for REF_PIN_BVH.  Needs the reference; skipped (existing file
    kept) when it is absent.  The GPU kernels and the oracle are compared with these where the reference is absent.
+5. medium_pin.npz -- the same digests for the constant-medium worlds of tests/medium_worlds.py (density and boundary edges), two
+   frames each.  Needs the reference like (4).
 
 The reference ships no golden data of its own.  (3) pins the oracle against its own regressions; (4) records
 the reference's own arithmetic, so the oracle and the kernels stay pinned to it where the reference is absent (what
@@ -89,6 +91,27 @@ def make_ref_pin():
         assert R.lib().mort_ref_add_bvh(w.ptr, li, False, 0) == 0
         out["bvh_" + name] = np.array([digest(np.frombuffer(world_object_bytes(w), np.uint8))])
     np.savez_compressed(os.path.join(HERE, "ref_pin.npz"), **out)
+
+
+MEDIUM_PIN_FRAMES = 2
+
+
+def make_medium_pin():
+    """5. medium_pin.npz -- as (4), for the worlds of tests/medium_worlds.py from their own cameras"""
+    from tests import medium_worlds as MW
+    from tests import ref_lib as R
+    if not R.ensure_built():
+        print("reference absent: keeping existing medium_pin fixture")
+        return
+    out = {}
+    for name in MW.NAMES:
+        world, cam = MW.world(name), MW.camera(name)
+        st = R.seed_states(69420, cam.image_width, cam.image_height)
+        for f in range(MEDIUM_PIN_FRAMES):
+            r = R.render(world, cam, states=st)
+            out[f"{name}_f{f}"] = np.array([digest(r["rgba"]), digest(r["accum"]), digest(state_words(r["states"]))])
+        print(name, cam.image_width, cam.image_height)
+    np.savez_compressed(os.path.join(HERE, "medium_pin.npz"), **out)
 
 
 def make_earth():
@@ -176,3 +199,4 @@ if __name__ == "__main__":
     make_damaged()
     make_oracle()
     make_ref_pin()
+    make_medium_pin()
